@@ -3,6 +3,10 @@
 ring phases are not all reachable, frozen per-step scalars, mid-episode restarts, the full-size C2 instance of the
 headline."""
 import ctypes as C
+import json
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -460,3 +464,31 @@ def test_a_request_for_the_deleted_bf16_split_passes_is_an_error(pkg, monkeypatc
         p.run(6)
     monkeypatch.setenv("PDEC_SPLIT", "0")
     p.close()
+
+
+def test_bench_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    """`bench.py --steps K --dump-outputs DIR`: exactly K timed steps, in one block, ms_per_step = that block / K; the arrays
+    of the last timed step land in DIR as float32 / float64 .npy files, and a second run with the same arguments computes
+    the same arrays"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "7", "--warmup", "3", "--batch", "64",
+                            "--no-cpu-baseline", "--no-variants", "--dump-outputs", str(out)], env=env, capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert d["steps"] == 7 and d["repeats"] == 1 and len(d["repeat_ms_per_step"]) == 1
+        assert abs(d["ms_per_step"] - d["repeat_ms_per_step"][0]) < 1e-5 and d["checks"]["finite"]
+        names = set(d["dump_outputs"]["arrays"])
+        assert {p.name for p in out.iterdir()} == {n + ".npy" for n in names}
+        assert {"y", "state", "action", "reward", "terminal", "actor_params", "critic_params", "losses"} <= names
+        arrs = {n: np.load(out / f"{n}.npy") for n in names}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 10 ** 6
+        assert arrs["y"].shape == (64, 256) and arrs["action"].size == 64 * 64 and np.isfinite(arrs["critic_params"]).all()
+        dumps.append(arrs)
+    for n, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][n]), n

@@ -91,6 +91,26 @@ def test_bench_self_launches_its_ranks():
     assert d["n_gpus"] == 2 and d["n_ranks_observed"] == 2 and d["self_launched"] is True
 
 
+def test_bench_dump_outputs_stays_in_budget_with_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs writes every array as <name>.npy in float32 / float64; what does not fit its share of the
+    budget is written as a seeded sample of its elements -- the same positions in every run -- and the files stay within it"""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 400_000)
+    rng = np.random.default_rng(5)
+    arrays = {"big": rng.standard_normal((64, 4096)), "wide": rng.standard_normal(300_000).astype(np.float32),
+              "small": np.arange(10, dtype=np.int32), "losses": np.array([0.5, 1.5])}
+    recs = [bench.dump_outputs(str(tmp_path / d), arrays) for d in ("a", "b")]
+    assert recs[0]["arrays"] == recs[1]["arrays"]
+    back = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert {k: v.dtype for k, v in back.items()} == {"big": np.float64, "wide": np.float32, "small": np.float32, "losses": np.float64}
+    assert np.array_equal(back["small"], np.arange(10)) and np.array_equal(back["losses"], arrays["losses"])
+    assert sum(v.nbytes for v in back.values()) <= 400_000
+    m = recs[0]["arrays"]["big"]["sampled_elements"]
+    assert 0 < m < arrays["big"].size and back["big"].shape == (m,) and recs[0]["arrays"]["big"]["shape"] == [64, 4096]
+    assert np.isin(back["big"], arrays["big"]).all() and np.array_equal(back["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert "sampled_elements" in recs[0]["arrays"]["wide"] and "sampled_elements" not in recs[0]["arrays"]["small"]
+
+
 def test_product_does_not_import_oracle():
     """the product path must not route through the oracle or any CPU fallback"""
     pdir = os.path.join(ROOT, "distributedconvrl-pde-control_amd")
@@ -234,15 +254,11 @@ def test_fluid_setup_box_tables_reproduce_dense_kernels(pkg):
 
 
 def test_read_hook_matches_committed_golden(pkg):
-    """checkpoint.read_hook on the reference's own saves/hook.jld2 (row F3) reproduces the committed fixture;
-    runs only where the reference tree is mounted (the build container)."""
-    import os
+    """checkpoint.read_hook on the reference's own saves/hook.jld2 (row F3; committed as tests/golden/ks22_hook.jld2)
+    reproduces the committed fixture."""
     import numpy as np
-    import pytest
-    ref = "/root/reference/scripts/KS/KS22/saves/hook.jld2"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not mounted")
-    from util import load_golden
+    from util import GOLD, load_golden
+    ref = os.path.join(GOLD, "ks22_hook.jld2")
     g = load_golden("ks22_hook.npz")
     h = pkg.checkpoint.read_hook(ref)
     for a, b in zip(h["best"], (g["best_W1"], g["best_b1"], g["best_W2"], g["best_b2"])):
@@ -282,14 +298,14 @@ def test_jld2_writer_roundtrip_and_checksums(pkg, tmp_path):
     assert set(back) == set(arrs)
     for k, a in arrs.items():
         assert back[k].dtype == a.dtype and np.array_equal(back[k], a), k
-    ref = "/root/reference/scripts/KS/KS22/saves/hook.jld2"
-    if os.path.exists(ref):                  # the reader's view of a reference dataset header == what the writer emits
-        fr = jl.JLD2File(ref)
-        o = next(o for o in (fr.objs[k] for k in fr.order) if o.cls == 1 and o.size == 4 and o.dims == (1, 6))
-        w = jl.JLD2File(path)
-        mine = next(o for o in w.objs.values() if o.dims == (1, 6))
-        for (ta, pa, sa), (tb, pb, sb_) in zip(o.msgs[:3], mine.msgs[:3]):
-            assert ta == tb and fr.buf[pa:pa + sa] == w.buf[pb:pb + sb_]
+    from util import GOLD
+    # the reader's view of a reference dataset header (saves/hook.jld2 of KS22) == what the writer emits
+    fr = jl.JLD2File(os.path.join(GOLD, "ks22_hook.jld2"))
+    o = next(o for o in (fr.objs[k] for k in fr.order) if o.cls == 1 and o.size == 4 and o.dims == (1, 6))
+    w = jl.JLD2File(path)
+    mine = next(o for o in w.objs.values() if o.dims == (1, 6))
+    for (ta, pa, sa), (tb, pb, sb_) in zip(o.msgs[:3], mine.msgs[:3]):
+        assert ta == tb and fr.buf[pa:pa + sa] == w.buf[pb:pb + sb_]
 
 
 def test_optional_featurize_branches_are_refused_or_restated(pkg):
