@@ -1175,19 +1175,116 @@ struct SmallSampling {     // != null: draw the slots in the kernel (pdec_ddpg_u
   int stride;
 };
 
-static int ddpg_update_small_impl(pdec_handle hA, pdec_handle hC, pdec_handle hAt, pdec_handle hCt, const void* state_trace,
-                                  const void* action_trace, const void* reward_trace, const void* terminal_trace,
-                                  const int32_t* idx_s, const int32_t* idx_rt, const int32_t* idx_sn, int loops, int Bu,
-                                  double gamma, double rho, int quirk, double eta_actor, double eta_critic,
-                                  void* losses_dev, const SmallSampling* smp) {
+// Every kernel instantiation pdec_ddpg_update_small(_rng) can launch.  small_plan() picks one; the launch site and
+// pdec_debug_small_update_kernel both go through it, so the query reports exactly what a call would launch.
+enum SmallKernelId {
+  SK_GENERIC,
+  SK_S2F_2_1_3,       // ddpg_small2f_kernel<2, 1, 3, true, 3>
+  SK_S2_2_1_3,        // ddpg_small2_kernel<2, 1, 3, true>
+  SK_S2_13_12_3_OS5,  // ddpg_small2_kernel<13, 12, 3, true, 5>
+  SK_S2_10_9_3_OS4,   // ddpg_small2_kernel<10, 9, 3, true, 4>
+  SK_S2_13_12_3,      // ddpg_small2_kernel<13, 12, 3, true>
+  SK_S2_10_9_3,       // ddpg_small2_kernel<10, 9, 3, true>
+  SK_S2_4_3_4,        // ddpg_small2_kernel<4, 3, S2_BU, false>
+  SK_S2_10_9_4,
+  SK_S2_13_12_4,
+  SK_S2_16_15_4,
+};
+static const char* const small_kernel_names[] = {
+    "ddpg_small_kernel",
+    "ddpg_small2f_kernel<2,1,3,1,3>",
+    "ddpg_small2_kernel<2,1,3,1>",
+    "ddpg_small2_kernel<13,12,3,1,5>",
+    "ddpg_small2_kernel<10,9,3,1,4>",
+    "ddpg_small2_kernel<13,12,3,1>",
+    "ddpg_small2_kernel<10,9,3,1>",
+    "ddpg_small2_kernel<4,3,4,0>",
+    "ddpg_small2_kernel<10,9,4,0>",
+    "ddpg_small2_kernel<13,12,4,0>",
+    "ddpg_small2_kernel<16,15,4,0>",
+};
+
+struct SmallPlan {
+  SmallKernelId id;
+  int threads;              // block size
+  size_t lds;               // dynamic LDS bytes of the launch (slot table included)
+  int smp_lds;              // float offset of the slot table
+  int lds_params;           // generic kernel: the learner state staged in LDS
+  int maxw;                 // generic kernel: widest layer
+};
+
+// the kernel a call launches, its block and its dynamic LDS -- or the error the call raises.  Reads the env switches
+// PDEC_SMALL_GENERIC / PDEC_SMALL_OWN / PDEC_SMALL_SPLIT per call (the identity tests switch them).
+static int small_plan(const Mlp* A, const Mlp* C, int loops, int Bu, float rho, bool sampling, SmallPlan* pl) {
+  PDEC_REQUIRE(loops >= 1 && Bu >= 1 && Bu <= 16, "pdec_ddpg_update_small: needs 1 <= Bu <= 16 (got %d)", Bu);
+  PDEC_REQUIRE(A->L <= SM_MAXL && C->L <= SM_MAXL, "small update: at most %d layers", SM_MAXL);
+  const int ns = A->dims[0];
+  int maxw = 1;
+  for (int l = 0; l <= A->L; ++l) maxw = std::max(maxw, A->dims[l]);
+  for (int l = 0; l <= C->L; ++l) maxw = std::max(maxw, C->dims[l]);
+  pl->maxw = maxw;
+  size_t lds = ((size_t)(A->L + 1 + C->L + 1 + 2) * maxw * Bu + 3 * Bu + 4) * 4;
+  PDEC_REQUIRE(lds <= 160 * 1024, "pdec_ddpg_update_small: layers too wide for the in-LDS activations (%zu B)", lds);
+  const size_t lds_state = (size_t)5 * (((A->nparams + 3) & ~3) + ((C->nparams + 3) & ~3)) * 4;
+  pl->lds_params = lds + lds_state <= 150 * 1024;
+  if (pl->lds_params) lds += lds_state;
+  const size_t tab_floats = sampling ? (size_t)3 * loops * Bu : 0;
+  if (small2_ok(A, C, Bu) && (size_t)loops * (2 * ns + 3) * Bu * 4 <= 120 * 1024) {
+    const int nC = C->dims[1], nA = A->dims[1];
+    // the actor's ADAM state one parameter per lane of wave 0 (template OS slots) for the shipped moving-target shapes
+    const char* noown = getenv("PDEC_SMALL_OWN");
+    const int nown = (ns + 2) * nA;
+    int os = 0;
+    if (Bu == 3 && nA <= 64 && !(noown && noown[0] == '0')) {
+      if (ns == 12 && nown <= 64 * 5) os = 5;             // Keller-Segel10_16: 14 x 20 parameters
+      else if (ns == 9 && nown <= 64 * 4) os = 4;         // Fluid: 11 x 18
+    }
+    const size_t lds2f = (size_t)loops * (2 * ns + 3) * Bu + (size_t)2 * S2_NW * S2_ROW + (size_t)3 * 64 * os;   // + exchange buffers (+ owner rows)
+    // frozen targets (the KS experiments' regime): the critic and the actor updates as two chains side by side (ddpg_small2f_kernel).
+    // Only the exact KS instantiation (ns 1, batch 3, 129 - 192 critic units: KS22 / KS200 / KS500): there every guard folds at compile time and the
+    // backend fuses multiplies and adds the same way in both kernels, which is what makes them agree bit for bit; the bounded
+    // instantiations differ in the last place of the actor's gradient (a product fused into one kernel's sum and not the other's).
+    const char* nosplit = getenv("PDEC_SMALL_SPLIT");
+    const int nwc = (nC + 63) / 64;
+    if (rho == 1.0f && Bu == 3 && ns == 1 && 3 * nA + 1 <= 64 && nwc == 3 && !(nosplit && nosplit[0] == '0')) {
+      const int ncol = loops * Bu;
+      const size_t ldsf = (size_t)loops * (2 * ns + 3) * Bu + (size_t)2 * S2_NW * S2_ROW + (size_t)ncol * (2 + S2_NW) +
+                          (size_t)2 * ((2 + 2) * nwc * 64 + 4);
+      if ((ldsf + tab_floats) * 4 <= 150 * 1024) {
+        pl->id = SK_S2F_2_1_3; pl->threads = (nwc + 1) * 64; pl->smp_lds = (int)ldsf; pl->lds = (ldsf + tab_floats) * 4;
+        return PDEC_OK;
+      }
+    }
+    // the slot table sits behind the register kernel's LDS: it must fit in the workgroup's 160 KB, or the call takes the
+    // generic kernel (which refuses cleanly when nothing fits)
+    if ((lds2f + tab_floats) * 4 <= 160 * 1024) {
+      pl->threads = (std::max(nC, nA) + 63) / 64 * 64;
+      pl->smp_lds = (int)lds2f;
+      pl->lds = (lds2f + tab_floats) * 4;
+      if (Bu == 3 && ns == 1) pl->id = SK_S2_2_1_3;                      // KS22 / KS200 / KS500
+      else if (Bu == 3 && ns == 12 && os == 5) pl->id = SK_S2_13_12_3_OS5;
+      else if (Bu == 3 && ns == 9 && os == 4) pl->id = SK_S2_10_9_3_OS4;
+      else if (Bu == 3 && ns == 12) pl->id = SK_S2_13_12_3;              // Keller-Segel10_16
+      else if (Bu == 3 && ns == 9) pl->id = SK_S2_10_9_3;                // Fluid
+      else if (ns <= 3) pl->id = SK_S2_4_3_4;
+      else if (ns <= 9) pl->id = SK_S2_10_9_4;
+      else if (ns <= 12) pl->id = SK_S2_13_12_4;
+      else pl->id = SK_S2_16_15_4;
+      return PDEC_OK;
+    }
+  }
+  PDEC_REQUIRE(lds + tab_floats * 4 <= 160 * 1024, "pdec_ddpg_update_small: the slot table does not fit beside the learner state in LDS");
+  pl->id = SK_GENERIC; pl->threads = SM_THREADS; pl->smp_lds = (int)(lds / 4); pl->lds = lds + tab_floats * 4;
+  return PDEC_OK;
+}
+
+// the shape checks of a small update on the four networks
+static int small_nets(pdec_handle hA, pdec_handle hC, pdec_handle hAt, pdec_handle hCt, Mlp** pA, Mlp** pC, Mlp** pAt, Mlp** pCt) {
   Mlp* A = lookup_as<Mlp>(hA, Kind::Mlp);
   Mlp* C = lookup_as<Mlp>(hC, Kind::Mlp);
   Mlp* At = lookup_as<Mlp>(hAt, Kind::Mlp);
   Mlp* Ct = lookup_as<Mlp>(hCt, Kind::Mlp);
   if (!A || !C || !At || !Ct) { set_error("pdec_ddpg_update_small: bad network handle"); return PDEC_E_HANDLE; }
-  PDEC_REQUIRE(state_trace && action_trace && reward_trace && terminal_trace && (smp || (idx_s && idx_rt && idx_sn)),
-               "pdec_ddpg_update_small: null argument");
-  PDEC_REQUIRE(loops >= 1 && Bu >= 1 && Bu <= 16, "pdec_ddpg_update_small: needs 1 <= Bu <= 16 (got %d)", Bu);
   PDEC_REQUIRE(A->dtype == PDEC_F32 && C->dtype == PDEC_F32 && At->dtype == PDEC_F32 && Ct->dtype == PDEC_F32,
                "pdec_ddpg_update_small: fp32 networks only (the reference's network dtype)");
   PDEC_REQUIRE(At->dims == A->dims && Ct->dims == C->dims, "ddpg: target networks must have the behaviour networks' shapes");
@@ -1195,28 +1292,43 @@ static int ddpg_update_small_impl(pdec_handle hA, pdec_handle hC, pdec_handle hA
   PDEC_REQUIRE(C->dims[0] == ns + na && C->dims[C->L] == 1, "ddpg: critic must map ns+na -> 1");
   PDEC_REQUIRE(A->stream == C->stream && At->stream == C->stream && Ct->stream == C->stream,
                "pdec_ddpg_update_small: the four networks must share one stream");
-  SmallArgs g{};
+  *pA = A; *pC = C; *pAt = At; *pCt = Ct;
+  return PDEC_OK;
+}
+
+// once per instantiation: allow the dynamic LDS of the launch (the register kernels ask for up to 160 KB)
+template <class K>
+static int small_lds_attr(K kern, size_t lds, size_t* done) {
+  if (*done < lds) {
+    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    *done = lds;
+  }
+  return PDEC_OK;
+}
+
+static int ddpg_update_small_impl(pdec_handle hA, pdec_handle hC, pdec_handle hAt, pdec_handle hCt, const void* state_trace,
+                                  const void* action_trace, const void* reward_trace, const void* terminal_trace,
+                                  const int32_t* idx_s, const int32_t* idx_rt, const int32_t* idx_sn, int loops, int Bu,
+                                  double gamma, double rho, int quirk, double eta_actor, double eta_critic,
+                                  void* losses_dev, const SmallSampling* smp) {
+  Mlp *A, *C, *At, *Ct;
   int rc;
+  if ((rc = small_nets(hA, hC, hAt, hCt, &A, &C, &At, &Ct))) return rc;
+  PDEC_REQUIRE(state_trace && action_trace && reward_trace && terminal_trace && (smp || (idx_s && idx_rt && idx_sn)),
+               "pdec_ddpg_update_small: null argument");
+  SmallPlan pl{};
+  if ((rc = small_plan(A, C, loops, Bu, (float)rho, smp != nullptr, &pl))) return rc;
+  const int ns = A->dims[0], na = A->dims[A->L];
+  SmallArgs g{};
   if ((rc = fill_net(g.A, A, At)) || (rc = fill_net(g.C, C, Ct))) return rc;
-  int maxw = 1;
-  for (int l = 0; l <= A->L; ++l) maxw = std::max(maxw, A->dims[l]);
-  for (int l = 0; l <= C->L; ++l) maxw = std::max(maxw, C->dims[l]);
-  g.maxw = maxw;
-  size_t lds = ((size_t)(A->L + 1 + C->L + 1 + 2) * maxw * Bu + 3 * Bu + 4) * 4;
-  PDEC_REQUIRE(lds <= 160 * 1024, "pdec_ddpg_update_small: layers too wide for the in-LDS activations (%zu B)", lds);
-  const size_t lds_state = (size_t)5 * (((A->nparams + 3) & ~3) + ((C->nparams + 3) & ~3)) * 4;
-  g.lds_params = lds + lds_state <= 150 * 1024;
-  if (g.lds_params) lds += lds_state;
+  g.maxw = pl.maxw;
+  g.lds_params = pl.lds_params;
   g.state = (const float*)state_trace; g.action = (const float*)action_trace;
   g.reward = (const float*)reward_trace; g.terminal = (const float*)terminal_trace;
   g.i_s = idx_s; g.i_rt = idx_rt; g.i_sn = idx_sn;
   g.loops = loops; g.Bu = Bu; g.ns = ns; g.na = na; g.quirk = quirk;
   g.gamma = (float)gamma; g.rho = (float)rho;      // Float32 in the reference (y = 0.99f0, p = 0.995f0)
   g.eta_a = eta_actor; g.eta_c = eta_critic; g.b1 = 0.9; g.b2 = 0.999; g.eps = 1e-8;
-  if ((rc = bp_begin(A, g.b1, g.b2, &g.bpA)) || (rc = bp_begin(C, g.b1, g.b2, &g.bpC))) return rc;
-  g.losses = (float*)losses_dev;
-  g.halt = C->halt;
-  const size_t tab_floats = smp ? (size_t)3 * loops * Bu : 0;
   if (smp) {
     const int64_t hi = smp->n_valid - smp->stride;           // inds in 1:length(t)-number_actuators (src/PDEagent.jl:318)
     PDEC_REQUIRE(hi >= 1 && hi < ((int64_t)1 << 32) && smp->capacity >= 1 && smp->stride >= 0,
@@ -1226,71 +1338,58 @@ static int ddpg_update_small_impl(pdec_handle hA, pdec_handle hC, pdec_handle hA
     g.smp_base = smp->n_rt > smp->capacity ? smp->n_rt - smp->capacity : 0;      // logical index of the oldest entry
     g.smp_cap = (int)smp->capacity; g.smp_cap1 = (int)(smp->capacity + smp->stride); g.smp_stride = smp->stride;
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ddpg_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 160 * 1024));
-    attr_set = true;
-  }
-  if (small2_ok(A, C, Bu) && (size_t)loops * (2 * ns + 3) * Bu * 4 <= 120 * 1024) {
+  g.smp_lds = pl.smp_lds;
+  if ((rc = bp_begin(A, g.b1, g.b2, &g.bpA)) || (rc = bp_begin(C, g.b1, g.b2, &g.bpC))) return rc;
+  g.losses = (float*)losses_dev;
+  g.halt = C->halt;
+  static size_t attr[sizeof(small_kernel_names) / sizeof(small_kernel_names[0])] = {};
+  ProfScope ps(C, "ddpg_small");
+  if (pl.id == SK_GENERIC) {
+    if ((rc = small_lds_attr(ddpg_small_kernel, 160 * 1024, &attr[SK_GENERIC]))) return rc;
+    hipLaunchKernelGGL(ddpg_small_kernel, dim3(1), dim3(SM_THREADS), pl.lds, C->stream, g);
+  } else {
     Small2Args a2{};
     a2.g = g;
     a2.g.lds_params = 0;
     a2.nC = C->dims[1]; a2.nA = A->dims[1];
-    const int nt = (std::max(a2.nC, a2.nA) + 63) / 64 * 64;
-    // the actor's ADAM state one parameter per lane of wave 0 (template OS slots) for the shipped moving-target shapes
-    const char* noown = getenv("PDEC_SMALL_OWN");          // (read per launch: the identity test switches it)
-    const int nown = (ns + 2) * a2.nA;
-    int os = 0;
-    if (Bu == 3 && a2.nA <= 64 && !(noown && noown[0] == '0')) {
-      if (ns == 12 && nown <= 64 * 5) os = 5;             // Keller-Segel10_16: 14 x 20 parameters
-      else if (ns == 9 && nown <= 64 * 4) os = 4;         // Fluid: 11 x 18
+#define S2_LAUNCH(ID, ...)                                                                                             \
+  case ID:                                                                                                             \
+    if ((rc = small_lds_attr(__VA_ARGS__, pl.lds, &attr[ID]))) return rc;                                              \
+    hipLaunchKernelGGL((__VA_ARGS__), dim3(1), dim3(pl.threads), pl.lds, C->stream, a2);                               \
+    break;
+    switch (pl.id) {
+      S2_LAUNCH(SK_S2F_2_1_3, ddpg_small2f_kernel<2, 1, 3, true, 3>)
+      S2_LAUNCH(SK_S2_2_1_3, ddpg_small2_kernel<2, 1, 3, true>)
+      S2_LAUNCH(SK_S2_13_12_3_OS5, ddpg_small2_kernel<13, 12, 3, true, 5>)
+      S2_LAUNCH(SK_S2_10_9_3_OS4, ddpg_small2_kernel<10, 9, 3, true, 4>)
+      S2_LAUNCH(SK_S2_13_12_3, ddpg_small2_kernel<13, 12, 3, true>)
+      S2_LAUNCH(SK_S2_10_9_3, ddpg_small2_kernel<10, 9, 3, true>)
+      S2_LAUNCH(SK_S2_4_3_4, ddpg_small2_kernel<4, 3, S2_BU, false>)
+      S2_LAUNCH(SK_S2_10_9_4, ddpg_small2_kernel<10, 9, S2_BU, false>)
+      S2_LAUNCH(SK_S2_13_12_4, ddpg_small2_kernel<13, 12, S2_BU, false>)
+      S2_LAUNCH(SK_S2_16_15_4, ddpg_small2_kernel<16, 15, S2_BU, false>)
+      default: set_error("pdec_ddpg_update_small: no kernel for plan %d", (int)pl.id); return PDEC_E_INVALID;
     }
-    const size_t lds2f = (size_t)loops * (2 * ns + 3) * Bu + (size_t)2 * S2_NW * S2_ROW + (size_t)3 * 64 * os;   // + exchange buffers (+ owner rows)
-    a2.g.smp_lds = (int)lds2f;
-    const size_t lds2 = (lds2f + tab_floats) * 4;
-    ProfScope ps(C, "ddpg_small");
-    // frozen targets (the KS experiments' regime): the critic and the actor updates as two chains side by side (ddpg_small2f_kernel).
-    // Only the exact KS instantiation (ns 1, batch 3, 129 - 192 critic units: KS22 / KS200 / KS500): there every guard folds at compile time and the
-    // backend fuses multiplies and adds the same way in both kernels, which is what makes them agree bit for bit; the bounded
-    // instantiations differ in the last place of the actor's gradient (a product fused into one kernel's sum and not the other's).
-    const char* nosplit = getenv("PDEC_SMALL_SPLIT");      // (read per launch: the identity test switches it)
-    const int nwc = (a2.nC + 63) / 64;
-    if (a2.g.rho == 1.0f && Bu == 3 && ns == 1 && 3 * a2.nA + 1 <= 64 && nwc == 3 && !(nosplit && nosplit[0] == '0')) {
-      const int ntf = (nwc + 1) * 64, ncol = loops * Bu;
-      const size_t ldsf = (size_t)loops * (2 * ns + 3) * Bu + (size_t)2 * S2_NW * S2_ROW + (size_t)ncol * (2 + S2_NW) +
-                          (size_t)2 * ((2 + 2) * nwc * 64 + 4);
-      if ((ldsf + tab_floats) * 4 <= 150 * 1024) {
-        a2.g.smp_lds = (int)ldsf;
-        hipLaunchKernelGGL((ddpg_small2f_kernel<2, 1, 3, true, 3>), dim3(1), dim3(ntf), (ldsf + tab_floats) * 4, C->stream, a2);
-        PDEC_HIP(hipGetLastError());
-        bp_done(A);
-        bp_done(C);
-        A->fw_dirty = C->fw_dirty = At->fw_dirty = Ct->fw_dirty = true;
-        return PDEC_OK;
-      }
-    }
-#define S2_LAUNCH(KC, KA, BUT, EX) hipLaunchKernelGGL((ddpg_small2_kernel<KC, KA, BUT, EX>), dim3(1), dim3(nt), lds2, C->stream, a2)
-    if (Bu == 3 && ns == 1) S2_LAUNCH(2, 1, 3, true);            // KS22 / KS200 / KS500
-    else if (Bu == 3 && ns == 12 && os == 5) hipLaunchKernelGGL((ddpg_small2_kernel<13, 12, 3, true, 5>), dim3(1), dim3(nt), lds2, C->stream, a2);
-    else if (Bu == 3 && ns == 9 && os == 4) hipLaunchKernelGGL((ddpg_small2_kernel<10, 9, 3, true, 4>), dim3(1), dim3(nt), lds2, C->stream, a2);
-    else if (Bu == 3 && ns == 12) S2_LAUNCH(13, 12, 3, true);    // Keller-Segel10_16
-    else if (Bu == 3 && ns == 9) S2_LAUNCH(10, 9, 3, true);      // Fluid
-    else if (ns <= 3) S2_LAUNCH(4, 3, S2_BU, false);
-    else if (ns <= 9) S2_LAUNCH(10, 9, S2_BU, false);
-    else if (ns <= 12) S2_LAUNCH(13, 12, S2_BU, false);
-    else S2_LAUNCH(16, 15, S2_BU, false);
 #undef S2_LAUNCH
-  } else {
-    g.smp_lds = (int)(lds / 4);
-    PDEC_REQUIRE(lds + tab_floats * 4 <= 160 * 1024, "pdec_ddpg_update_small: the slot table does not fit beside the learner state in LDS");
-    ProfScope ps(C, "ddpg_small");
-    hipLaunchKernelGGL(ddpg_small_kernel, dim3(1), dim3(SM_THREADS), lds + tab_floats * 4, C->stream, g);
   }
   PDEC_HIP(hipGetLastError());
   bp_done(A);
   bp_done(C);
   A->fw_dirty = C->fw_dirty = At->fw_dirty = Ct->fw_dirty = true;
+  return PDEC_OK;
+}
+
+extern "C" int pdec_debug_small_update_kernel(pdec_handle hA, pdec_handle hC, pdec_handle hAt, pdec_handle hCt, int loops, int Bu,
+                                              double rho, int sampling, char* name, int name_len, int64_t* lds_bytes) {
+  Mlp *A, *C, *At, *Ct;
+  int rc;
+  PDEC_REQUIRE(name && name_len > 0 && lds_bytes, "pdec_debug_small_update_kernel: null argument");
+  if ((rc = small_nets(hA, hC, hAt, hCt, &A, &C, &At, &Ct))) return rc;
+  SmallPlan pl{};
+  if ((rc = small_plan(A, C, loops, Bu, (float)rho, sampling != 0, &pl))) return rc;
+  if (pl.id == SK_GENERIC) snprintf(name, name_len, "ddpg_small_kernel/lds_params=%d", pl.lds_params);
+  else snprintf(name, name_len, "%s", small_kernel_names[pl.id]);
+  *lds_bytes = (int64_t)pl.lds;
   return PDEC_OK;
 }
 

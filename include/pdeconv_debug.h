@@ -33,6 +33,14 @@ int pdec_debug_kseg2d_probe(pdec_handle env, int nb, int reps, int iters, double
  * small-message collective on a box with one GPU.  The loop is bounded by the counter AND by an iteration cap. */
 int pdec_debug_spin_us(void* hip_stream, double us);
 
+/* Unit-test entry (no reference counterpart): the kernel pdec_ddpg_update_small (sampling = 0) / pdec_ddpg_update_small_rng
+ * (sampling != 0) would launch for these four networks, `loops`, `Bu` and `rho`, with the env switches as they are now --
+ * launches nothing.  Writes the instantiation's name (e.g. "ddpg_small2f_kernel<2,1,3,1,3>", "ddpg_small_kernel/lds_params=0")
+ * to name[name_len] and the dynamic LDS bytes of the launch, slot table included, to *lds_bytes; or returns the error the call
+ * would return. */
+int pdec_debug_small_update_kernel(pdec_handle actor, pdec_handle critic, pdec_handle target_actor, pdec_handle target_critic,
+                                   int loops, int Bu, double rho, int sampling, char* name, int name_len, int64_t* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,373 @@
+"""Every kernel of the small DDPG update (pdec_ddpg_update_small / _rng, csrc/mlp_small.hip) against the fp64 oracle.
+
+Each case names the instantiation it must reach and asserts it through pdec_debug_small_update_kernel; together the cases
+reach every name the dispatch can return (test_cases_reach_every_kernel_of_the_dispatch).  Per case:
+  A. one update from a fresh ADAM state: gradients (through m), v, ADAM step, Polyak, beta powers, losses vs fp64;
+  B. the same for an update that starts from a state three real launches old (teacher forced: small_update_ref.py);
+  C. a 20-loop launch at eta = 0: m, v, beta powers and targets in closed form over the 20 fp64 minibatch gradients;
+  D. one launch of L loops == L launches of one loop, bit for bit;
+  E. in-kernel slot sampling == the host slots of oracle.rng.sample_slots, bit for bit, on a wrapped buffer.
+The LDS limits on `loops` are pinned through the query on both sides (with and without the slot table), with real launches
+at the largest legal `loops` of the register kernel and the first one past it."""
+import ctypes as C_
+import os
+import re
+import zlib
+
+import numpy as np
+import pytest
+
+from small_update_ref import B1, B2, Snap, check_launch, minibatches
+from util import to_dev
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+GAMMA, ETA_A, ETA_C = 0.99, 5e-4, 1e-3
+S2F = "ddpg_small2f_kernel<2,1,3,1,3>"
+S2KS = "ddpg_small2_kernel<2,1,3,1>"
+GEN1, GEN0 = "ddpg_small_kernel/lds_params=1", "ddpg_small_kernel/lds_params=0"
+
+# id: (ns, na, actor hidden, critic hidden, 3 layers, Bu, rho, kernel)
+CASES = {
+    "ks22_frozen": (1, 1, 6, 140, False, 3, 1.0, S2F),
+    "ks_a21_c129_frozen": (1, 1, 21, 129, False, 3, 1.0, S2F),
+    "ks_c192_frozen": (1, 1, 6, 192, False, 3, 1.0, S2F),
+    "ks22_moving": (1, 1, 6, 140, False, 3, 0.995, S2KS),
+    "ks_a21_c129_moving": (1, 1, 21, 129, False, 3, 0.995, S2KS),
+    "ks_c192_moving": (1, 1, 6, 192, False, 3, 0.995, S2KS),
+    "ks_c128_frozen": (1, 1, 6, 128, False, 3, 1.0, S2KS),
+    "ks_c193_frozen": (1, 1, 6, 193, False, 3, 1.0, S2KS),
+    "ks_a22_frozen": (1, 1, 22, 140, False, 3, 1.0, S2KS),
+    "ks_c512_frozen": (1, 1, 6, 512, False, 3, 1.0, S2KS),
+    "kseg_owner_lanes": (12, 1, 20, 340, False, 3, 0.995, "ddpg_small2_kernel<13,12,3,1,5>"),
+    "fluid_owner_lanes": (9, 1, 18, 340, False, 3, 0.995, "ddpg_small2_kernel<10,9,3,1,4>"),
+    "kseg_frozen_owner_lanes": (12, 1, 20, 340, False, 3, 1.0, "ddpg_small2_kernel<13,12,3,1,5>"),
+    "kseg_wide_actor": (12, 1, 40, 340, False, 3, 0.995, "ddpg_small2_kernel<13,12,3,1>"),
+    "fluid_wide_actor": (9, 1, 40, 340, False, 3, 1.0, "ddpg_small2_kernel<10,9,3,1>"),
+    "ns1_bu4": (1, 1, 6, 140, False, 4, 0.995, "ddpg_small2_kernel<4,3,4,0>"),
+    "ns2_bu1_w64_65": (2, 1, 64, 65, False, 1, 1.0, "ddpg_small2_kernel<4,3,4,0>"),
+    "ns3_bu2": (3, 1, 16, 64, False, 2, 0.995, "ddpg_small2_kernel<4,3,4,0>"),
+    "ns4_bu3": (4, 1, 30, 80, False, 3, 0.995, "ddpg_small2_kernel<10,9,4,0>"),
+    "ns9_bu4_w65_64": (9, 1, 65, 64, False, 4, 1.0, "ddpg_small2_kernel<10,9,4,0>"),
+    "ns10_bu1": (10, 1, 20, 100, False, 1, 0.995, "ddpg_small2_kernel<13,12,4,0>"),
+    "ns12_bu2": (12, 1, 24, 200, False, 2, 1.0, "ddpg_small2_kernel<13,12,4,0>"),
+    "ns13_bu3": (13, 1, 20, 100, False, 3, 0.995, "ddpg_small2_kernel<16,15,4,0>"),
+    "ns15_bu4": (15, 1, 25, 500, False, 4, 1.0, "ddpg_small2_kernel<16,15,4,0>"),
+    "three_layer_small": (3, 1, 16, 16, True, 3, 0.995, GEN1),
+    "three_layer_c2": (3, 1, 16, 140, True, 3, 1.0, GEN0),
+    "global_na8": (8, 8, 48, 100, False, 3, 0.995, GEN1),
+    "ns16_bu5": (16, 1, 20, 60, False, 5, 0.995, GEN1),
+    "ks_bu16": (1, 1, 6, 140, False, 16, 1.0, GEN1),
+    "wide_critic_bu5": (1, 1, 6, 900, False, 5, 0.995, GEN0),
+}
+
+
+class Rig:
+    """four networks, replay traces and a losses buffer on the device"""
+
+    def __init__(self, pkg, case, seed=0, n=400, stride=1):
+        from oracle import nn
+        ns, na, ha, hc, three, Bu, rho, self.expected = CASES[case]
+        self.case = case
+        self.pkg, self.L, self.Bu, self.rho, self.ns, self.na = pkg, pkg._lib, Bu, rho, ns, na
+        rng = np.random.default_rng(zlib.crc32(case.encode()) % 1000 + seed)
+        self.da = [ns, ha, ha, na] if three else [ns, ha, na]
+        self.aa = [nn.RELU, nn.RELU, nn.TANH] if three else [nn.RELU, nn.TANH]
+        self.dc = [ns + na, hc, hc, 1] if three else [ns + na, hc, 1]
+        self.ac = [nn.RELU, nn.RELU, nn.IDENT] if three else [nn.RELU, nn.IDENT]
+        code = {nn.RELU: "relu", nn.TANH: "tanh", nn.IDENT: None}
+
+        def params(d):
+            P = nn.glorot_uniform(rng, d, np.float64)
+            for i in range(1, len(P), 2):
+                P[i] = rng.standard_normal(P[i].shape) * 0.1
+            return P
+        PA, PC = params(self.da), params(self.dc)
+        PAt = [p + rng.standard_normal(p.shape) * 0.02 for p in PA]     # targets apart from the behaviour networks
+        PCt = [p + rng.standard_normal(p.shape) * 0.02 for p in PC]
+        self.nets = [pkg.HipMLP(d, [code[a] for a in acts], P, dtype=torch.float32, max_cols=16)
+                     for d, acts, P in ((self.da, self.aa, PA), (self.dc, self.ac, PC), (self.da, self.aa, PAt),
+                                        (self.dc, self.ac, PCt))]
+        # traces: n + stride state rows (the trajectory's capacity + stride), n reward / terminal rows
+        self.n, self.stride = n, stride
+        self.S = rng.standard_normal((n + stride, ns)).astype(np.float32)
+        self.Aa = rng.uniform(-1, 1, (n + stride, na)).astype(np.float32)
+        self.R = -rng.uniform(0, 1, n).astype(np.float32)
+        self.T = (rng.uniform(0, 1, n) < 0.25).astype(np.float32)
+        self.dev = [to_dev(x, torch.float32) for x in (self.S, self.Aa, self.R, self.T)]
+        self.losses = torch.full((2,), float("nan"), dtype=torch.float32, device="cuda:0")
+        self.rng = rng
+        self._keep = []
+
+    def slots(self, loops):
+        s = np.stack([self.rng.integers(0, self.n + self.stride, (loops, self.Bu)), self.rng.integers(0, self.n, (loops, self.Bu)),
+                      self.rng.integers(0, self.n + self.stride, (loops, self.Bu))]).astype(np.int32)
+        s[1, 0, 0] = self.rng.choice(np.flatnonzero(self.T))      # a terminal flag in the first minibatch
+        return s
+
+    def kernel(self, loops, sampling=False):
+        """(kernel name, dynamic LDS bytes) the call would launch, or (None, error text)"""
+        A, C, At, Ct = self.nets
+        buf, lds = C_.create_string_buffer(128), C_.c_int64(-1)
+        rc = self.L.load().pdec_debug_small_update_kernel(A.handle, C.handle, At.handle, Ct.handle, loops, self.Bu, self.rho,
+                                                          int(sampling), buf, 128, C_.byref(lds))
+        if rc != 0:
+            return None, self.L.load().pdec_last_error().decode()
+        return buf.value.decode(), lds.value
+
+    def launch(self, slots, quirk, eta_a=ETA_A, eta_c=ETA_C):
+        A, C, At, Ct = self.nets
+        d = torch.as_tensor(np.ascontiguousarray(slots, dtype=np.int32), device="cuda:0")
+        torch.cuda.synchronize()                 # (the slots and traces are written on torch's stream)
+        self._keep.append(d)
+        L = self.L
+        L.check(A.lib.pdec_ddpg_update_small(A.handle, C.handle, At.handle, Ct.handle, *(L.ptr(x) for x in self.dev),
+                                             C_.c_void_p(d[0].data_ptr()), C_.c_void_p(d[1].data_ptr()),
+                                             C_.c_void_p(d[2].data_ptr()), int(slots.shape[1]), self.Bu, GAMMA, self.rho,
+                                             quirk, eta_a, eta_c, L.ptr(self.losses)))
+
+    def launch_rng(self, loops, quirk, seed, offset, n_rt, eta_a=ETA_A, eta_c=ETA_C):
+        A, C, At, Ct = self.nets
+        L = self.L
+        torch.cuda.synchronize()
+        L.check(A.lib.pdec_ddpg_update_small_rng(A.handle, C.handle, At.handle, Ct.handle, *(L.ptr(x) for x in self.dev),
+                                                 loops, self.Bu, seed, offset, self.n + self.stride, n_rt, self.n, self.stride,
+                                                 GAMMA, self.rho, quirk, eta_a, eta_c, L.ptr(self.losses)))
+
+    def snap(self):
+        torch.cuda.synchronize()
+        A, C, At, Ct = self.nets
+
+        def adam(net):
+            m = np.empty(net.num_params, np.float32)
+            v = np.empty_like(m)
+            bp = (C_.c_double * 2)()
+            self.L.check(net.lib.pdec_adam_get_state(net.handle, m.ctypes.data_as(C_.c_void_p), v.ctypes.data_as(C_.c_void_p), bp))
+            b = np.array([bp[0], bp[1]]) if bp[0] >= 0 else np.array([B1, B2])      # (not initialised: the first step's)
+            return net._unflatten(m), net._unflatten(v), b
+        mA, vA, bpA = adam(A)
+        mC, vC, bpC = adam(C)
+        lv = self.losses.cpu().numpy()
+        return Snap(A.params(), C.params(), At.params(), Ct.params(), mA, vA, mC, vC, bpA, bpC, (float(lv[0]), float(lv[1])))
+
+    def check(self, before, after, slots, quirk, eta_a=ETA_A, eta_c=ETA_C):
+        mbs = minibatches(self.S, self.Aa, self.R, self.T, slots)
+        return check_launch(before, after, mbs, self.aa, self.ac, GAMMA, self.rho, quirk, eta_a, eta_c)
+
+    def close(self):
+        for n in self.nets:
+            n.close()
+
+
+def _same(a, b):
+    """bit equality of two snapshots"""
+    for f in ("A", "C", "At", "Ct", "mA", "vA", "mC", "vC"):
+        for x, y in zip(getattr(a, f), getattr(b, f)):
+            if not np.array_equal(x, y):
+                return f
+    if not (np.array_equal(a.bpA, b.bpA) and np.array_equal(a.bpC, b.bpC)):
+        return "beta powers"
+    if not np.array_equal(np.array(a.losses, np.float32), np.array(b.losses, np.float32)):
+        return "losses"
+    return None
+
+
+@pytest.fixture
+def rig(pkg, request):
+    r = Rig(pkg, request.param)
+    yield r
+    r.close()
+
+
+def _reach(rig, loops, sampling=False):
+    name, lds = rig.kernel(loops, sampling)
+    assert name == rig.expected, (name, lds)
+    assert 0 < lds <= 160 * 1024
+
+
+@pytest.mark.parametrize("rig", list(CASES), indirect=True)
+@pytest.mark.parametrize("quirk", [1, 0])
+def test_first_and_continued_update_against_fp64(rig, quirk):
+    """A + B: one update from a fresh ADAM state, then one from a state three launches of five real updates old"""
+    _reach(rig, 1)
+    _reach(rig, 5)
+    s = rig.slots(1)
+    before = rig.snap()
+    rig.launch(s, quirk)
+    errs = rig.check(before, rig.snap(), s, quirk)
+    assert not errs, ("first update", errs)
+    for _ in range(3):
+        rig.launch(rig.slots(5), quirk)
+    s = rig.slots(1)
+    before = rig.snap()
+    assert before.bpA[0] == pytest.approx(B1 ** 17, rel=1e-14) and before.bpC[1] == pytest.approx(B2 ** 17, rel=1e-14)
+    rig.launch(s, quirk)
+    errs = rig.check(before, rig.snap(), s, quirk)
+    assert not errs, ("continued update", errs)
+
+
+@pytest.mark.parametrize("rig", list(CASES), indirect=True)
+def test_twenty_loops_at_zero_learning_rate_closed_form(rig):
+    """C: eta = 0 keeps the parameters, so after 20 loops m, v, the beta powers and the targets are closed forms over the 20
+    per-minibatch fp64 gradients (v keeps 0.999^20 of the first minibatch: every loop's slots count)"""
+    quirk = zlib.crc32(rig.expected.encode()) & 1
+    rig.launch(rig.slots(3), quirk)               # a started ADAM state
+    _reach(rig, 20)
+    s = rig.slots(20)
+    before = rig.snap()
+    rig.launch(s, quirk, 0.0, 0.0)
+    errs = rig.check(before, rig.snap(), s, quirk, 0.0, 0.0)
+    assert not errs, errs
+
+
+@pytest.mark.parametrize("rig", list(CASES), indirect=True)
+def test_one_launch_of_many_loops_equals_launches_of_one(rig, pkg):
+    """D: one launch of 7 loops == 7 launches of one loop, bit for bit (parameters, moments, beta powers, last losses): pins
+    what the single-update checks cannot -- the split kernel's actor update i - 1 beside critic update i, its TD targets
+    computed up front, the loop-to-loop hand-over of the state held in registers / LDS"""
+    twin = Rig(pkg, rig.case)
+    try:
+        s = rig.slots(7)
+        _reach(rig, 7)
+        _reach(twin, 1)
+        rig.launch(s, 1)
+        for k in range(7):
+            twin.launch(s[:, k:k + 1], 1)
+        diff = _same(rig.snap(), twin.snap())
+        assert diff is None, diff
+    finally:
+        twin.close()
+
+
+def _sampling_pair(pkg, rig, loops, eta=(ETA_A, ETA_C), twin_env=None, monkeypatch=None):
+    """the rng launch on `rig` vs the host-slot launch on a twin from the same state (the twin's env switches `twin_env`
+    set for its launch only); returns (the first field that differs or None, state before, state after, slots)"""
+    from oracle import rng as orng
+    quirk, seed, off, n_rt = 0, 777, 5, rig.n + 123          # n_rt > capacity: the buffer has wrapped
+    twin = Rig(pkg, rig.case)
+    try:
+        slots = orng.sample_slots(seed, off, loops * rig.Bu, rig.n + rig.stride, n_rt, rig.n, rig.stride)
+        slots = slots.reshape(3, loops, rig.Bu)
+        assert (slots[0] != slots[1]).any()      # the state rows and the reward rows of a wrapped buffer differ
+        name, _ = rig.kernel(loops, sampling=True)
+        before = rig.snap()
+        rig.launch_rng(loops, quirk, seed, off, n_rt, *eta)
+        for k, v in (twin_env or {}).items():
+            monkeypatch.setenv(k, v)
+        assert twin.kernel(loops)[0] == name
+        twin.launch(slots, quirk, *eta)
+        for k in twin_env or {}:
+            monkeypatch.delenv(k)
+        after = rig.snap()
+        return _same(after, twin.snap()), before, after, slots
+    finally:
+        twin.close()
+
+
+@pytest.mark.parametrize("rig", list(CASES), indirect=True)
+def test_in_kernel_sampling_equals_host_slots(rig, pkg):
+    """E: pdec_ddpg_update_small_rng == pdec_ddpg_update_small fed with oracle.rng.sample_slots of the same Philox stream,
+    bit for bit, on a wrapped buffer, for the kernel of every case"""
+    _reach(rig, 20, sampling=True)
+    assert _sampling_pair(pkg, rig, 20)[0] is None
+
+
+def _kernel_names_of_the_dispatch():
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                            "distributedconvrl-pde-control_amd", "csrc", "mlp_small.hip")).read()
+    table = re.search(r"small_kernel_names\[\] = \{(.*?)\};", src, re.S).group(1)
+    names = re.findall(r'"([^"]+)"', table)
+    assert names[0] == "ddpg_small_kernel"
+    return {n for n in names[1:]} | {GEN0, GEN1}
+
+
+def test_cases_reach_every_kernel_of_the_dispatch(pkg):
+    """the kernels the cases reach (each asserted through the query in every test above) are all the dispatch can return:
+    a new branch without a case fails here"""
+    reached = set()
+    for case in CASES:
+        r = Rig(pkg, case)
+        try:
+            name, lds = r.kernel(1)
+            assert name == r.expected, (case, name, lds)
+            reached.add(name)
+        finally:
+            r.close()
+    assert reached == _kernel_names_of_the_dispatch()
+
+
+# LDS limits on `loops`, derived from ddpg_update_small_impl's budgets (floats; 150 KB for the split kernel, 160 KB otherwise):
+#   split (KS22: ns 1, Bu 3, 3 critic waves): 15 L trace + 128 exchange + 30 L target columns + 1544 published rows
+#     (+ 9 L slot table) <= 38 400  ->  L <= 816 (host slots), L <= 680 (in-kernel sampling)
+#   register kernel: trace (2 ns + 3) Bu L <= 30 720 (120 KB), and trace + 128 (+ 3 Bu L slot table) <= 40 960:
+#     ns 1, Bu 3: L <= 2048 (host slots), L <= 1701 (sampling); ns 1, Bu 4: L <= 1536, L <= 1276
+#   past them the generic kernel (its learner state staged in LDS: lds_params=1)
+# (case, sampling, last L of the first kernel, its kernel, kernel at L + 1)
+LIMITS = [
+    ("ks22_frozen", False, 816, S2F, S2KS),
+    ("ks22_frozen", True, 680, S2F, S2KS),
+    ("ks22_frozen", False, 2048, S2KS, GEN1),
+    ("ks22_frozen", True, 1701, S2KS, GEN1),
+    ("ks22_moving", False, 2048, S2KS, GEN1),
+    ("ks22_moving", True, 1701, S2KS, GEN1),
+    ("ns1_bu4", False, 1536, "ddpg_small2_kernel<4,3,4,0>", GEN1),
+    ("ns1_bu4", True, 1276, "ddpg_small2_kernel<4,3,4,0>", GEN1),
+]
+
+
+@pytest.mark.parametrize("case,sampling,last,k0,k1", LIMITS)
+def test_lds_limits_on_loops(pkg, case, sampling, last, k0, k1):
+    """both sides of every LDS limit on `loops` through the query, with and without the slot table"""
+    r = Rig(pkg, case)
+    try:
+        n0, lds0 = r.kernel(last, sampling)
+        n1, lds1 = r.kernel(last + 1, sampling)
+        assert (n0, n1) == (k0, k1), (lds0, lds1)
+        assert lds0 <= (150 if k0 == S2F else 160) * 1024 and lds1 <= 160 * 1024
+    finally:
+        r.close()
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("case,last", [("ks22_frozen", 680), ("ks22_frozen", 1701), ("ns1_bu4", 1276)])
+@pytest.mark.parametrize("side", [0, 1])
+def test_launches_on_both_sides_of_an_lds_limit(pkg, case, last, side, monkeypatch):
+    """a real in-kernel-sampling launch at the largest `loops` of a kernel and at the first past it: closed form at
+    eta = 0 (C) over the slots of oracle.rng.sample_slots, and == the host-slot launch (E), the host-slot twin forced onto
+    the same kernel where the slot table alone moved the sampling launch on (PDEC_SMALL_SPLIT=0 / PDEC_SMALL_GENERIC)"""
+    loops = last + side
+    r = Rig(pkg, case)
+    try:
+        name, lds = r.kernel(loops, True)
+        host = r.kernel(loops)[0]
+        assert lds <= 160 * 1024 and (name == host) == (side == 0), (name, host)
+        env = None
+        if name != host:
+            env = {"PDEC_SMALL_SPLIT": "0"} if host == S2F else {"PDEC_SMALL_GENERIC": "1"}
+        diff, before, after, slots = _sampling_pair(pkg, r, loops, (0.0, 0.0), env, monkeypatch)
+        assert diff is None, diff
+        errs = r.check(before, after, slots, 0, 0.0, 0.0)
+        assert not errs, errs
+    finally:
+        r.close()
+
+
+SWEEP_SHAPES = [c for c in CASES if not c.startswith(("ks_c", "ks_a"))] + ["ks_c128_frozen", "ks_a21_c129_frozen"]
+
+
+def test_query_sweep_never_asks_for_more_lds_than_a_workgroup_has(pkg):
+    """loops = 1 ... 2100 for every case's shape, with and without the slot table: every call either launches with
+    <= 160 KB of dynamic LDS or refuses with an error (nothing launches here)"""
+    for case in SWEEP_SHAPES:
+        r = Rig(pkg, case)
+        try:
+            for sampling in (False, True):
+                for loops in range(1, 2101):
+                    name, lds = r.kernel(loops, sampling)
+                    if name is None:
+                        assert "does not fit" in lds or "too wide" in lds, (case, loops, lds)
+                    else:
+                        assert lds <= (150 if name == S2F else 160) * 1024, (case, sampling, loops, name, lds)
+        finally:
+            r.close()
