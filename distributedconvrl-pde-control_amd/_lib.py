@@ -115,6 +115,7 @@ SIGNATURES = {
 # include/pdeconv_debug.h: unit-test / measurement entry points (tests/, bench.py, tools/), not part of the drop-in surface
 DEBUG_SIGNATURES = {
     "pdec_debug_wave_fft": [_vp, _vp, _i, _i, _i],
+    "pdec_debug_wave_fft_f32": [_vp, _vp, _i, _i, _i],
     "pdec_debug_critic_stamps": [Handle, _i, _pd],
     "pdec_debug_kseg2d_probe": [Handle, _i, _i, _i, _pd],
     "pdec_debug_spin_us": [_vp, _d],

@@ -1,4 +1,4 @@
-// fluid.hip -- batched 2-D pseudo-spectral vorticity environment for gfx950 (fp64).
+// fluid.hip -- batched 2-D pseudo-spectral vorticity environment for gfx950 (fp64; fp32 on the same kernels).
 //
 // Restates (from scratch, batched over independent trajectories):
 //   rk4(f, p, dt)            src/fluid_rk4.jl:122-132      classical RK4, forcing frozen over the step
@@ -29,6 +29,8 @@
 // Lx = Ly) as in every shipped script.  "fast axis" = y, "slow axis" = x.
 #include "env.hpp"
 #include "wave_fft.hpp"
+
+#include <type_traits>
 
 namespace pdec {
 
@@ -501,20 +503,20 @@ __global__ __launch_bounds__(256) void fluid_actuate_kernel(int n, int A, int BH
 
 // the spectral part of K1w for one work item: from the two spectrum lines in LDS (Lj: line j0, Lm: its mirror j1) the
 // packed inverse transforms of the carried line t and -- nhalf = 2 -- of its mirror line s_mirror
-template <int E, int Q, int LB>
-__device__ __forceinline__ void fluid_k1w_body(const FluidDev<double>& d, const C2<double>* Lj, const C2<double>* Lm, int j0, int j1,
-                                               int t, int s_mirror, int nhalf, C2<double>* __restrict__ W, int b,
-                                               WaveFftD<E, Q, LB>& f, int l, const double* __restrict__ kt) {
-  typedef WaveFftD<E, Q, LB> F;
-  typedef C2<double> Z;
+template <class T, int E, int Q, int LB>
+__device__ __forceinline__ void fluid_k1w_body(const FluidDev<T>& d, const C2<T>* Lj, const C2<T>* Lm, int j0, int j1,
+                                               int t, int s_mirror, int nhalf, C2<T>* __restrict__ W, int b,
+                                               WaveFft<T, E, Q, LB>& f, int l, const T* __restrict__ kt) {
+  typedef WaveFft<T, E, Q, LB> F;
+  typedef C2<T> Z;
   const int n = d.n, p = d.p;
-  const Z zero = mk<double>(0, 0);
+  const Z zero = mk<T>(0, 0);
 #pragma unroll 1
   for (int half = 0; half < nhalf; ++half) {
     const Z* La = half ? Lm : Lj;     // the line's own spectrum / its mirror's
     const Z* Lb = half ? Lj : Lm;
     const int j = half ? j1 : j0, jm = half ? j0 : j1, s = half ? s_mirror : t;
-    const double kj = j >= 0 ? kt[j] : 0.0, kjm = jm >= 0 ? kt[jm] : 0.0;
+    const T kj = j >= 0 ? kt[j] : (T)0, kjm = jm >= 0 ? kt[jm] : (T)0;
 #pragma unroll 1
     for (int fld = 0; fld < 2; ++fld) {
       Z a[F::R];
@@ -526,25 +528,25 @@ __device__ __forceinline__ void fluid_k1w_body(const FluidDev<double>& d, const 
         // psihat = omghat ./ k^2, the vorticity gradients do not)
         const bool va = j >= 0 && i >= 0, vm = jm >= 0 && im >= 0;
         Z oa = zero, om_ = zero;
-        double ki = 0.0, kim = 0.0;
+        T ki = 0, kim = 0;
         if (va) { oa = La[i]; ki = kt[i]; }
         if (vm) { om_ = Lb[im]; kim = kt[im]; }
         if (fld == 0) {   // Z1 = Herm(u) + i Herm(v),  u = i ky psi, v = -i kx psi
           // one reciprocal serves the four quotients of the pair (k^2 of a mode and of its mirror are the same number;
           // omghat * (1 / k^2) instead of omghat / k^2: <= 1 ulp from the reference's quotient)
-          const double k2 = va ? kj * kj + ki * ki : kjm * kjm + kim * kim;
-          const double r = 1.0 / k2;
-          const Z pa = (va && !(i == 0 && j == 0)) ? mk<double>(oa.x * r, oa.y * r) : zero;
-          const Z pm = (vm && !(im == 0 && jm == 0)) ? mk<double>(om_.x * r, om_.y * r) : zero;
-          const Z au = mk<double>(-ki * pa.y, ki * pa.x), av = mk<double>(kj * pa.y, -kj * pa.x);
-          const Z mu = mk<double>(-kim * pm.y, kim * pm.x), mv = mk<double>(kjm * pm.y, -kjm * pm.x);
-          const Z hu = mk<double>(0.5 * (au.x + mu.x), 0.5 * (au.y - mu.y)), hv = mk<double>(0.5 * (av.x + mv.x), 0.5 * (av.y - mv.y));
-          a[jj] = mk<double>(hu.x - hv.y, hu.y + hv.x);
+          const T k2 = va ? kj * kj + ki * ki : kjm * kjm + kim * kim;
+          const T r = (T)1 / k2;
+          const Z pa = (va && !(i == 0 && j == 0)) ? mk<T>(oa.x * r, oa.y * r) : zero;
+          const Z pm = (vm && !(im == 0 && jm == 0)) ? mk<T>(om_.x * r, om_.y * r) : zero;
+          const Z au = mk<T>(-ki * pa.y, ki * pa.x), av = mk<T>(kj * pa.y, -kj * pa.x);
+          const Z mu = mk<T>(-kim * pm.y, kim * pm.x), mv = mk<T>(kjm * pm.y, -kjm * pm.x);
+          const Z hu = mk<T>((T)0.5 * (au.x + mu.x), (T)0.5 * (au.y - mu.y)), hv = mk<T>((T)0.5 * (av.x + mv.x), (T)0.5 * (av.y - mv.y));
+          a[jj] = mk<T>(hu.x - hv.y, hu.y + hv.x);
         } else {          // Z2 = Herm(wx) + i Herm(wy),  wx = i kx omg, wy = i ky omg
-          const Z ax = mk<double>(-kj * oa.y, kj * oa.x), ay = mk<double>(-ki * oa.y, ki * oa.x);
-          const Z mx = mk<double>(-kjm * om_.y, kjm * om_.x), my = mk<double>(-kim * om_.y, kim * om_.x);
-          const Z hx = mk<double>(0.5 * (ax.x + mx.x), 0.5 * (ax.y - mx.y)), hy = mk<double>(0.5 * (ay.x + my.x), 0.5 * (ay.y - my.y));
-          a[jj] = mk<double>(hx.x - hy.y, hx.y + hy.x);
+          const Z ax = mk<T>(-kj * oa.y, kj * oa.x), ay = mk<T>(-ki * oa.y, ki * oa.x);
+          const Z mx = mk<T>(-kjm * om_.y, kjm * om_.x), my = mk<T>(-kim * om_.y, kim * om_.x);
+          const Z hx = mk<T>((T)0.5 * (ax.x + mx.x), (T)0.5 * (ax.y - mx.y)), hy = mk<T>((T)0.5 * (ay.x + my.x), (T)0.5 * (ay.y - my.y));
+          a[jj] = mk<T>(hx.x - hy.y, hx.y + hy.x);
         }
       }
       f.inverse(a);
@@ -567,11 +569,11 @@ __device__ __forceinline__ void fluid_k1w_body(const FluidDev<double>& d, const 
 }
 
 // K1w: one wave per PAIR of carried lines (a line and its mirror, see below).  LDS: per wave the two spectrum lines j and mirror(j) (2 n complex).
-template <int E, int Q, int LB>
-__global__ __launch_bounds__(256) void fluid_k1w_kernel(FluidDev<double> d, const C2<double>* __restrict__ omg,
-                                                        C2<double>* __restrict__ W, int pair) {
-  typedef WaveFftD<E, Q, LB> F;
-  typedef C2<double> Z;
+template <class T, int E, int Q, int LB>
+__global__ __launch_bounds__(256) void fluid_k1w_kernel(FluidDev<T> d, const C2<T>* __restrict__ omg,
+                                                        C2<T>* __restrict__ W, int pair) {
+  typedef WaveFft<T, E, Q, LB> F;
+  typedef C2<T> Z;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   // a "line slot" is a wave (LB = 6) or a half wave (LB = 5: two lines per wave); l = position inside the line
   const int lane = threadIdx.x & 63, l = lane & (F::LANES - 1), slot = (threadIdx.x >> 6) * F::LPW + (lane >> LB);
@@ -580,7 +582,7 @@ __global__ __launch_bounds__(256) void fluid_k1w_kernel(FluidDev<double> d, cons
   Z* Lm = Lj + n;
   // the wavenumber table in LDS (round 4): the spectral part reads k of every mode and of its mirror -- 48 dependent global
   // loads per wave item, each with its own wait, in the middle of the fp64 arithmetic
-  double* kt = reinterpret_cast<double*>(smem_raw + (size_t)4 * F::LPW * 2 * n * sizeof(Z));
+  T* kt = reinterpret_cast<T*>(smem_raw + (size_t)4 * F::LPW * 2 * n * sizeof(Z));
   for (int i = threadIdx.x; i < n; i += 256) kt[i] = d.k[i];
   __syncthreads();
   // work item t = carried line t (jp = t <= n/2) TOGETHER WITH its mirror line (jp' = p - t): both need exactly the
@@ -593,26 +595,26 @@ __global__ __launch_bounds__(256) void fluid_k1w_kernel(FluidDev<double> d, cons
   const int jp = fl_line_jp(t, n, p, d.nl), jpm = (p - jp) % p;
   const int s_mirror = fl_line_of(jpm, n, p, d.nl);
   const int j0 = fl_unpad(jp, n, p), j1 = fl_unpad(jpm, n, p);
-  const Z zero = mk<double>(0, 0);
+  // (a literal zero, not a named one: the named object was given a stack slot -- a dead scratch store per wave)
   for (int i = l; i < n; i += F::LANES) {
-    Lj[i] = j0 >= 0 ? omg[((size_t)b * n + j0) * n + i] : zero;
-    Lm[i] = j1 >= 0 ? omg[((size_t)b * n + j1) * n + i] : zero;
+    Lj[i] = j0 >= 0 ? omg[((size_t)b * n + j0) * n + i] : mk<T>(0, 0);
+    Lm[i] = j1 >= 0 ? omg[((size_t)b * n + j1) * n + i] : mk<T>(0, 0);
   }
   __builtin_amdgcn_wave_barrier();
   F f;
   f.init(d.twp, lane);
   const int nhalf = (pair && s_mirror >= 0 && s_mirror != t) ? 2 : 1;
-  fluid_k1w_body<E, Q, LB>(d, Lj, Lm, j0, j1, t, s_mirror, nhalf, W, b, f, l, kt);
+  fluid_k1w_body<T, E, Q, LB>(d, Lj, Lm, j0, j1, t, s_mirror, nhalf, W, b, f, l, kt);
 }
 
 // K2w: TC columns per workgroup, one wave per column.  LDS: the [TC][p] column tile (transposition + permuted access).
 // TC = 4 keeps the tile at 48 KB so that several workgroups share a CU and one's global loads / stores overlap the
 // others' transforms (with TC = 8 a CU holds a single workgroup and load -> transform -> store serialise).
-template <int E, int Q, int TC, int LB>
-__global__ __launch_bounds__(64 * TC >> (6 - LB)) void fluid_k2w_kernel(FluidDev<double> d, const C2<double>* __restrict__ W,
-                                                            C2<double>* __restrict__ W2) {
-  typedef WaveFftD<E, Q, LB> F;
-  typedef C2<double> Z;
+template <class T, int E, int Q, int TC, int LB>
+__global__ __launch_bounds__(64 * TC >> (6 - LB)) void fluid_k2w_kernel(FluidDev<T> d, const C2<T>* __restrict__ W,
+                                                            C2<T>* __restrict__ W2) {
+  typedef WaveFft<T, E, Q, LB> F;
+  typedef C2<T> Z;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   Z* tile = reinterpret_cast<Z*>(smem_raw);
   constexpr int NT = 64 * TC / F::LPW;                      // one line slot (wave or half wave) per column
@@ -627,14 +629,14 @@ __global__ __launch_bounds__(64 * TC >> (6 - LB)) void fluid_k2w_kernel(FluidDev
     const int t = idx % TC, jp = idx / TC;
     const int s = fl_line_of(jp, n, p, d.nl), ip = ip0 + t;
     if (s >= 0 && ip < p) return W[(((size_t)b * 2 + fld) * d.nl + s) * p + ip];
-    return mk<double>(0, 0);
+    return mk<T>(0, 0);
   };
   for (int idx = tid; idx < TC * p; idx += NT) tile[(idx % TC) * LS + idx / TC] = tile_src(0, idx);
   Z pre[NPF];                                               // field 1 is fetched while field 0 is transformed
 #pragma unroll
   for (int u = 0; u < NPF; ++u) {
     const int idx = tid + u * NT;
-    pre[u] = idx < TC * p ? tile_src(1, idx) : mk<double>(0, 0);
+    pre[u] = idx < TC * p ? tile_src(1, idx) : mk<T>(0, 0);
   }
   __syncthreads();
 #pragma unroll
@@ -652,7 +654,7 @@ __global__ __launch_bounds__(64 * TC >> (6 - LB)) void fluid_k2w_kernel(FluidDev
   f.inverse(a);
   // -(u wx + v wy), both ifft scalings; forward transform of the real product (one column per wave)
 #pragma unroll
-  for (int jj = 0; jj < F::R; ++jj) a[jj] = mk<double>(-(r0[jj].x * a[jj].x + r0[jj].y * a[jj].y) * d.inv2, 0.0);
+  for (int jj = 0; jj < F::R; ++jj) a[jj] = mk<T>(-(r0[jj].x * a[jj].x + r0[jj].y * a[jj].y) * d.inv2, (T)0);
   f.forward(a);
   __syncthreads();
 #pragma unroll
@@ -685,18 +687,39 @@ __device__ __forceinline__ void k2p_lds_barrier() { asm volatile("s_waitcnt lgkm
 template <int N>
 __device__ __forceinline__ void k2p_wait_but() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-// NPW: DMA pieces per wave and field = ceil(ceil(nl / 8) / 8); NSU: output elements per thread = n * 8 / 512
-template <int E, int Q, int NPW, int NSU>
-__global__ __launch_bounds__(512) void fluid_k2p_kernel(FluidDev<double> d, const C2<double>* __restrict__ W,
-                                                        C2<double>* __restrict__ W2, int ntiles) {
-  typedef WaveFftD<E, Q, 6, true> F;      // radix-Q twiddles from an LDS table: the kernel sits near the 256-VGPR limit of 2 waves / SIMD
-  typedef C2<double> Z;
-  constexpr int TC = 8;
+// K2p's tile geometry for an element of ZB bytes (16: complex double, 8: complex float), in ONE place.  A tile is TC = 8
+// columns (one wave per column); a DMA piece is what one 16-byte-per-lane wave instruction moves, 1 KiB: LPL lanes per tile line,
+// EPL elements per lane, LPP lines.  fp64: 8 lanes x 1 element, 8 lines; fp32: 4 lanes x 2 adjacent columns, 16 lines.
+// The column swizzle acts on the lane slot (a column pair in fp32): slot ^ ((line >> 2) & (LPL - 1)).
+template <int ZB>
+struct K2pGeom {
+  static constexpr int TC = 8, EPL = 16 / ZB, LPL = TC / EPL, LPL_SH = EPL == 1 ? 3 : 2, LPP = 64 / LPL, PIECE = 64 * EPL;   // PIECE: elements
+  static __host__ __device__ int npieces(int nl) { return (nl + LPP - 1) / LPP; }
+  static __host__ __device__ int npw(int nl) { return (npieces(nl) + 7) / 8; }                    // DMA pieces per wave and field
+  static __host__ __device__ int nsu(int n) { return n * TC / 512; }                             // output elements per thread
+  // LDS element of (line sl, column col) in the field region
+  static __device__ __forceinline__ int at(int sl, int col) {
+    return sl * TC + EPL * ((col / EPL) ^ ((sl >> 2) & (LPL - 1))) + col % EPL;
+  }
+  // vmcnt waits: behind the DMA of the next tile's field 0 a thread issues exactly its NSU output stores (one store instruction
+  // per element: the elements of a thread lie 64 rows apart, nothing to merge); nothing is issued behind field 1's DMA
+  template <int NSU>
+  static constexpr int wait_f0_next() { return NSU; }
+};
+
+// NPW: DMA pieces per wave and field (K2pGeom::npw); NSU: output elements per thread (K2pGeom::nsu)
+template <class T, int E, int Q, int NPW, int NSU>
+__global__ __launch_bounds__(512) void fluid_k2p_kernel(FluidDev<T> d, const C2<T>* __restrict__ W,
+                                                        C2<T>* __restrict__ W2, int ntiles) {
+  typedef WaveFft<T, E, Q, 6, true> F;    // radix-Q twiddles from an LDS table: the kernel sits near the 256-VGPR limit of 2 waves / SIMD
+  typedef C2<T> Z;
+  typedef K2pGeom<(int)sizeof(Z)> G;
+  constexpr int TC = G::TC;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = d.n, p = d.p, nl = d.nl;
-  const int npieces = (nl + 7) / 8;
+  const int npieces = G::npieces(nl);
   Z* R = reinterpret_cast<Z*>(smem_raw);
-  Z* S = R + (size_t)npieces * 64;        // [n][8]
+  Z* S = R + (size_t)npieces * G::PIECE;  // [n][8]
   Z* WQ = S + (size_t)n * TC;             // [(Q - 1) E][64]
   const int tiles_per_b = p / TC;
   F f;
@@ -706,7 +729,7 @@ __global__ __launch_bounds__(512) void fluid_k2p_kernel(FluidDev<double> d, cons
   // operations per slot against a 768-point transform) instead of held in registers
   auto src_of = [&](int jj) -> int {
     const int sl = fl_line_of(f.mode_index(jj), n, p, nl);
-    return sl >= 0 ? sl * TC + (wv ^ ((sl >> 2) & 7)) : -1;
+    return sl >= 0 ? G::at(sl, wv) : -1;
   };
   // the transform's twiddles are ordinary global loads: they must have landed BEFORE the first DMA is issued -- the compiler
   // waits vmcnt(0) at the first use of a global load, which would drain every prefetch in flight behind it
@@ -719,32 +742,39 @@ __global__ __launch_bounds__(512) void fluid_k2p_kernel(FluidDev<double> d, cons
     const char* base = reinterpret_cast<const char*>(W + ((size_t)b * 2 + fld) * nl * p + (size_t)(ip0 >> 3) * nl * 8);      // wave-uniform
 #pragma unroll
     for (int j = 0; j < NPW; ++j) {
-      // piece c: lines 8c .. 8c+7; this lane's element (recomputed per issue: kept in registers the offsets spill, and a
-      // scratch reload is a vector-memory load whose wait drains the DMA queue)
+      // piece c: lines LPP c .. LPP c + LPP - 1; this lane's 16 bytes (recomputed per issue: kept in registers the offsets spill,
+      // and a scratch reload is a vector-memory load whose wait drains the DMA queue).  LDS receives the lanes in order, so lane
+      // slot s of a line holds the columns of slot s ^ swizzle -- what G::at() reads back.
       int c = wv + 8 * j;
       c = c < npieces ? c : npieces - 1;
-      int sl = c * 8 + (lv >> 3);
+      int sl = c * G::LPP + (lv >> G::LPL_SH);
       sl = sl < nl ? sl : nl - 1;                        // rows past nl - 1 of the last piece: never read
-      const unsigned off = (unsigned)(sl * 8 + ((lv & 7) ^ ((sl >> 2) & 7))) * (unsigned)sizeof(Z);
+      const unsigned off = (unsigned)(sl * TC + G::EPL * ((lv & (G::LPL - 1)) ^ ((sl >> 2) & (G::LPL - 1)))) * (unsigned)sizeof(Z);
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + off),
-                                       (__attribute__((address_space(3))) void*)(R + (size_t)c * 64), 16, 0, 0);
+                                       (__attribute__((address_space(3))) void*)(R + (size_t)c * G::PIECE), 16, 0, 0);
     }
   };
   int tile = blockIdx.x;
   if (tile >= ntiles) return;
   dma_tile(0, tile);
-  const Z zero = mk<double>(0, 0);
+  // the pad() zero: a named object in fp64 (the form built and measured there); in fp32 the named one was given a stack slot,
+  // and a scratch access is a vector-memory operation whose wait would drain the DMA queue -- a literal there
+  [[maybe_unused]] const Z zero = mk<T>(0, 0);
   bool first = true;
   for (; tile < ntiles; tile += gridDim.x) {
     const int next = tile + gridDim.x;
     const bool more = next < ntiles;
     Z r0[F::R], a[F::R];
     // ---- field 0 has landed: behind its DMA only the NSU stores of the previous tile were issued
-    if (first) k2p_wait_but<0>(); else k2p_wait_but<NSU>();
+    if (first) k2p_wait_but<0>(); else k2p_wait_but<G::template wait_f0_next<NSU>()>();
     first = false;
     k2p_lds_barrier();
 #pragma unroll
-    for (int jj = 0; jj < F::R; ++jj) { const int si = src_of(jj); r0[jj] = si >= 0 ? R[si] : zero; }
+    for (int jj = 0; jj < F::R; ++jj) {
+      const int si = src_of(jj);
+      if constexpr (sizeof(T) == 8) r0[jj] = si >= 0 ? R[si] : zero;
+      else r0[jj] = si >= 0 ? R[si] : mk<T>(0, 0);
+    }
     k2p_lds_barrier();                                   // every wave has read field 0
     dma_tile(1, tile);
     f.inverse(r0);
@@ -752,13 +782,17 @@ __global__ __launch_bounds__(512) void fluid_k2p_kernel(FluidDev<double> d, cons
     k2p_wait_but<0>();
     k2p_lds_barrier();
 #pragma unroll
-    for (int jj = 0; jj < F::R; ++jj) { const int si = src_of(jj); a[jj] = si >= 0 ? R[si] : zero; }
+    for (int jj = 0; jj < F::R; ++jj) {
+      const int si = src_of(jj);
+      if constexpr (sizeof(T) == 8) a[jj] = si >= 0 ? R[si] : zero;
+      else a[jj] = si >= 0 ? R[si] : mk<T>(0, 0);
+    }
     k2p_lds_barrier();                                   // every wave has read field 1
     if (more) dma_tile(0, next);
     f.inverse(a);
     // ---- -(u wx + v wy), both ifft scalings; forward transform of the real product (one column per wave)
 #pragma unroll
-    for (int jj = 0; jj < F::R; ++jj) a[jj] = mk<double>(-(r0[jj].x * a[jj].x + r0[jj].y * a[jj].y) * d.inv2, 0.0);
+    for (int jj = 0; jj < F::R; ++jj) a[jj] = mk<T>(-(r0[jj].x * a[jj].x + r0[jj].y * a[jj].y) * d.inv2, (T)0);
     f.forward(a);
     // ---- chop() along x: kept modes of my column into S (S was last read two barriers ago), then whole-line stores.
     // (Round 6, measured: the stores issued in the middle of the NEXT tile by all waves, or at its start by waves 4 - 7 only while
@@ -780,13 +814,13 @@ __global__ __launch_bounds__(512) void fluid_k2p_kernel(FluidDev<double> d, cons
 }
 
 // K3w: one wave per kept line j.  LDS: per wave one n-complex line (digit-reversed -> natural for coalesced global access).
-template <int E, int Q, int LB>
-__global__ __launch_bounds__(256) void fluid_k3w_kernel(FluidDev<double> d, const C2<double>* __restrict__ W2,
-                                                        const C2<double>* omg_s, const C2<double>* __restrict__ phat,
-                                                        const C2<double>* f0, C2<double>* acc, C2<double>* out, int mode,
-                                                        double ca, double cb) {
-  typedef WaveFftD<E, Q, LB> F;
-  typedef C2<double> Z;
+template <class T, int E, int Q, int LB>
+__global__ __launch_bounds__(256) void fluid_k3w_kernel(FluidDev<T> d, const C2<T>* __restrict__ W2,
+                                                        const C2<T>* omg_s, const C2<T>* __restrict__ phat,
+                                                        const C2<T>* f0, C2<T>* acc, C2<T>* out, int mode,
+                                                        T ca, T cb) {
+  typedef WaveFft<T, E, Q, LB> F;
+  typedef C2<T> Z;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int lane = threadIdx.x & 63, l = lane & (F::LANES - 1), slot = (threadIdx.x >> 6) * F::LPW + (lane >> LB);
   const int n = d.n, p = d.p;
@@ -806,24 +840,24 @@ __global__ __launch_bounds__(256) void fluid_k3w_kernel(FluidDev<double> d, cons
     if (i >= 0) Ln[i] = a[jj];
   }
   __builtin_amdgcn_wave_barrier();
-  const double kj = d.k[j];
+  const T kj = d.k[j];
   for (int i = l; i < n; i += F::LANES) {
     const size_t off = ((size_t)b * n + j) * n + i;
-    const double ki = d.k[i], lin = -d.nu * (kj * kj + ki * ki);
+    const T ki = d.k[i], lin = -d.nu * (kj * kj + ki * ki);
     const Z o = omg_s[off], nlv = Ln[i], ph = phat[off];
-    const Z k = mk<double>(lin * o.x + d.scale_out * nlv.x + ph.x, lin * o.y + d.scale_out * nlv.y + ph.y);
+    const Z k = mk<T>(lin * o.x + d.scale_out * nlv.x + ph.x, lin * o.y + d.scale_out * nlv.y + ph.y);
     if (mode == 0) {
       out[off] = k;
     } else if (mode == 4) {
       const Z ac = acc[off];
-      out[off] = mk<double>(ac.x + cb * k.x, ac.y + cb * k.y);
+      out[off] = mk<T>(ac.x + cb * k.x, ac.y + cb * k.y);
     } else {
       const Z fv = f0[off];
-      out[off] = mk<double>(fv.x + ca * k.x, fv.y + ca * k.y);
-      if (mode == 1) acc[off] = mk<double>(fv.x + cb * k.x, fv.y + cb * k.y);
+      out[off] = mk<T>(fv.x + ca * k.x, fv.y + ca * k.y);
+      if (mode == 1) acc[off] = mk<T>(fv.x + cb * k.x, fv.y + cb * k.y);
       else {
         const Z ac = acc[off];
-        acc[off] = mk<double>(ac.x + cb * k.x, ac.y + cb * k.y);
+        acc[off] = mk<T>(ac.x + cb * k.x, ac.y + cb * k.y);
       }
     }
   }
@@ -835,13 +869,13 @@ __global__ __launch_bounds__(256) void fluid_k3w_kernel(FluidDev<double> d, cons
 // W2, chop, linear term + forcing, stage update; `out` / `acc` to HBM as K3w does), keeps the two new spectrum lines in
 // LDS and runs the K1w body from there.  Saves the re-read of the stage value (4 MB per trajectory and RHS at n = 512)
 // and one launch per RHS.  mode 1 / 2 / 4 as in K3w (mode 0, the bare RHS, has no successor).  Pair items only (n >= 256).
-template <int E, int Q, int LB>
-__global__ __launch_bounds__(256) void fluid_k31w_kernel(FluidDev<double> d, const C2<double>* __restrict__ W2,
-                                                         const C2<double>* omg_s, const C2<double>* __restrict__ phat,
-                                                         const C2<double>* f0, C2<double>* acc, C2<double>* out, int mode,
-                                                         double ca, double cb, C2<double>* __restrict__ W) {
-  typedef WaveFftD<E, Q, LB> F;
-  typedef C2<double> Z;
+template <class T, int E, int Q, int LB>
+__global__ __launch_bounds__(256) void fluid_k31w_kernel(FluidDev<T> d, const C2<T>* __restrict__ W2,
+                                                         const C2<T>* omg_s, const C2<T>* __restrict__ phat,
+                                                         const C2<T>* f0, C2<T>* acc, C2<T>* out, int mode,
+                                                         T ca, T cb, C2<T>* __restrict__ W) {
+  typedef WaveFft<T, E, Q, LB> F;
+  typedef C2<T> Z;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int lane = threadIdx.x & 63, l = lane & (F::LANES - 1), slot = (threadIdx.x >> 6) * F::LPW + (lane >> LB);
   const int n = d.n, p = d.p;
@@ -852,7 +886,7 @@ __global__ __launch_bounds__(256) void fluid_k31w_kernel(FluidDev<double> d, con
   const int jp = fl_line_jp(t, n, p, d.nl), jpm = (p - jp) % p;
   const int s_mirror = fl_line_of(jpm, n, p, d.nl);
   const int j0 = fl_unpad(jp, n, p), j1 = fl_unpad(jpm, n, p);
-  const Z zero = mk<double>(0, 0);
+  const Z zero = mk<T>(0, 0);
   F f;
   f.init(d.twp, lane);
   // ---- K3 for the kept lines j0 and (if it is another line) j1
@@ -876,23 +910,23 @@ __global__ __launch_bounds__(256) void fluid_k31w_kernel(FluidDev<double> d, con
       if (i >= 0) Ln[i] = a[jj];
     }
     __builtin_amdgcn_wave_barrier();
-    const double kj = d.k[j];
+    const T kj = d.k[j];
     for (int i = l; i < n; i += F::LANES) {
       const size_t off = ((size_t)b * n + j) * n + i;
-      const double ki = d.k[i], lin = -d.nu * (kj * kj + ki * ki);
+      const T ki = d.k[i], lin = -d.nu * (kj * kj + ki * ki);
       const Z o = omg_s[off], nlv = Ln[i], ph = phat[off];
-      const Z k = mk<double>(lin * o.x + d.scale_out * nlv.x + ph.x, lin * o.y + d.scale_out * nlv.y + ph.y);
+      const Z k = mk<T>(lin * o.x + d.scale_out * nlv.x + ph.x, lin * o.y + d.scale_out * nlv.y + ph.y);
       Z nv;
       if (mode == 4) {
         const Z ac = acc[off];
-        nv = mk<double>(ac.x + cb * k.x, ac.y + cb * k.y);
+        nv = mk<T>(ac.x + cb * k.x, ac.y + cb * k.y);
       } else {
         const Z fv = f0[off];
-        nv = mk<double>(fv.x + ca * k.x, fv.y + ca * k.y);
-        if (mode == 1) acc[off] = mk<double>(fv.x + cb * k.x, fv.y + cb * k.y);
+        nv = mk<T>(fv.x + ca * k.x, fv.y + ca * k.y);
+        if (mode == 1) acc[off] = mk<T>(fv.x + cb * k.x, fv.y + cb * k.y);
         else {
           const Z ac = acc[off];
-          acc[off] = mk<double>(ac.x + cb * k.x, ac.y + cb * k.y);
+          acc[off] = mk<T>(ac.x + cb * k.x, ac.y + cb * k.y);
         }
       }
       out[off] = nv;
@@ -903,22 +937,22 @@ __global__ __launch_bounds__(256) void fluid_k31w_kernel(FluidDev<double> d, con
   // ---- K1 of the next right-hand side from the two lines
   const Z* Lmm = (j1 == j0) ? Lj : Lm;              // line 0 is its own mirror
   const int nhalf = (s_mirror >= 0 && s_mirror != t) ? 2 : 1;
-  fluid_k1w_body<E, Q, LB>(d, Lj, Lmm, j0, j1, t, s_mirror, nhalf, W, b, f, l, d.k);
+  fluid_k1w_body<T, E, Q, LB>(d, Lj, Lmm, j0, j1, t, s_mirror, nhalf, W, b, f, l, d.k);
 }
 
 // ------------------------------------------------------------------ wave FFT unit-test entry (pdec_debug_wave_fft)
-template <int E, int Q, int LB>
-__global__ __launch_bounds__(256) void wave_fft_debug_kernel(const C2<double>* __restrict__ in, C2<double>* __restrict__ out,
-                                                            const C2<double>* __restrict__ tw, int nlines, int sgn) {
-  typedef WaveFftD<E, Q, LB> F;
+template <class T, int E, int Q, int LB>
+__global__ __launch_bounds__(256) void wave_fft_debug_kernel(const C2<T>* __restrict__ in, C2<T>* __restrict__ out,
+                                                            const C2<T>* __restrict__ tw, int nlines, int sgn) {
+  typedef WaveFft<T, E, Q, LB> F;
   const int lane = threadIdx.x & 63, l = lane & (F::LANES - 1);
   const int line = (blockIdx.x * 4 + (threadIdx.x >> 6)) * F::LPW + (lane >> LB);
   if (line >= nlines) return;
   F f;
   f.init(tw, lane);
-  C2<double> a[F::R];
-  const C2<double>* x = in + (size_t)line * F::N;
-  C2<double>* y = out + (size_t)line * F::N;
+  C2<T> a[F::R];
+  const C2<T>* x = in + (size_t)line * F::N;
+  C2<T>* y = out + (size_t)line * F::N;
   if (sgn < 0) {
 #pragma unroll
     for (int j = 0; j < F::R; ++j) a[j] = x[l + F::LANES * j];
@@ -1001,23 +1035,28 @@ struct FluidEnv : Env {
 // does the persistent x-pass (fluid_k2p_kernel) serve this environment?  Decided once: K1 writes W in the layout K2 reads.
 static bool k2p_eligible(const FluidEnv& E) {
   static const char* env = getenv("PDEC_FLUID_K2P");
-  const int npw = ((E.nl + 7) / 8 + 7) / 8, nsu = E.n * 8 / 512;
+  const bool f32 = E.cfg.dtype == PDEC_F32;
+  const int npw = f32 ? K2pGeom<8>::npw(E.nl) : K2pGeom<16>::npw(E.nl), nsu = K2pGeom<16>::nsu(E.n);
   const bool want = env ? env[0] == '1' : E.n >= 256;
   const bool wave64 = E.wave_E != 0 && E.wave_LB == 6;        // the one-line-per-wave plans (wave-FFT kernels K1w / K2p / K3w)
-  return want && wave64 && E.p % 8 == 0 && E.cfg.ifpad && E.n * 8 % 512 == 0 && ((npw == 9 && nsu == 8) || (npw == 5 && nsu == 4));
+  // instantiated (fluid_k2_launch): n = 512 (nl = 513: 9 DMA pieces per wave in fp64, 5 in fp32; 8 output elements per thread)
+  // and n = 256 (nl = 257: 5 / 3 pieces; 4 elements)
+  const bool built = f32 ? ((npw == 5 && nsu == 8) || (npw == 3 && nsu == 4)) : ((npw == 9 && nsu == 8) || (npw == 5 && nsu == 4));
+  return want && wave64 && E.p % 8 == 0 && E.cfg.ifpad && E.n * 8 % 512 == 0 && built;
 }
 
-static FluidDev<double> fluid_dev(const FluidEnv& E) {
-  FluidDev<double> d;
+template <class T>
+static FluidDev<T> fluid_dev(const FluidEnv& E) {
+  FluidDev<T> d;
   d.wtile = k2p_eligible(E) ? 1 : 0;
   d.B = E.cfg.B; d.n = E.n; d.p = E.p; d.nl = E.nl; d.TL = E.TL; d.TLn = E.TLn;
   d.LS = E.p + 2; d.LSn = E.n + 2;
-  d.nu = E.cfg.nu;
+  d.nu = (T)E.cfg.nu;
   const double inv = 1.0 / ((double)E.p * E.p);
-  d.inv2 = inv * inv;
-  d.scale_out = E.cfg.ifpad ? 1.5 * 1.5 : 1.0;        // src/fluid_rk4.jl:176
-  d.invn2 = 1.0 / ((double)E.n * E.n);
-  d.k = E.k.as<double>(); d.twp = E.twp.as<C2<double>>(); d.twn = E.twn.as<C2<double>>();
+  d.inv2 = (T)(inv * inv);                            // (scalars: computed in fp64, rounded once)
+  d.scale_out = (T)(E.cfg.ifpad ? 1.5 * 1.5 : 1.0);   // src/fluid_rk4.jl:176
+  d.invn2 = (T)(1.0 / ((double)E.n * E.n));
+  d.k = E.k.as<T>(); d.twp = E.twp.as<C2<T>>(); d.twn = E.twn.as<C2<T>>();
   d.plp = E.plp; d.pln = E.pln;
   return d;
 }
@@ -1034,28 +1073,32 @@ static int set_lds(K kern, size_t bytes) {
   return PDEC_OK;
 }
 
+template <class T>
 static int fluid_set_attrs(const FluidEnv& E) {
   int rc;
-  if ((rc = set_lds(fluid_k1_kernel<double>, E.lds_p))) return rc;
-  if ((rc = set_lds(fluid_k2_kernel<double>, E.lds_p))) return rc;
-  if ((rc = set_lds(fluid_k3_kernel<double>, E.lds_p))) return rc;
-  if ((rc = set_lds(fluid_fft_fast_kernel<double, +1, false>, E.lds_n))) return rc;
-  if ((rc = set_lds(fluid_fft_fast_kernel<double, -1, true>, E.lds_n))) return rc;
-  if ((rc = set_lds(fluid_fft_slow_kernel<double, +1, true>, E.lds_n))) return rc;
-  if ((rc = set_lds(fluid_fft_slow_kernel<double, -1, false>, E.lds_n))) return rc;
+  if ((rc = set_lds(fluid_k1_kernel<T>, E.lds_p))) return rc;
+  if ((rc = set_lds(fluid_k2_kernel<T>, E.lds_p))) return rc;
+  if ((rc = set_lds(fluid_k3_kernel<T>, E.lds_p))) return rc;
+  if ((rc = set_lds(fluid_fft_fast_kernel<T, +1, false>, E.lds_n))) return rc;
+  if ((rc = set_lds(fluid_fft_fast_kernel<T, -1, true>, E.lds_n))) return rc;
+  if ((rc = set_lds(fluid_fft_slow_kernel<T, +1, true>, E.lds_n))) return rc;
+  if ((rc = set_lds(fluid_fft_slow_kernel<T, -1, false>, E.lds_n))) return rc;
   return PDEC_OK;
 }
 
 // K2 of the wave path: the persistent pipelined form (fluid_k2p_kernel) where it is built -- one line per wave, p a multiple of 8,
 // the DMA piece count instantiated -- else the tile form.  PDEC_FLUID_K2P=0 / 1 forces the choice.
-template <int E, int Q, int LB>
-static int fluid_k2_launch(FluidEnv& Ev, const FluidDev<double>& d) {
-  typedef C2<double> Z;
+#ifndef FL_K2P_WPC32
+#define FL_K2P_WPC32 2      // fp32 K2p: at most this many workgroups per CU, where registers and LDS allow (fp64: one, 134 KB of LDS)
+#endif
+template <class T, int E, int Q, int LB>
+static int fluid_k2_launch(FluidEnv& Ev, const FluidDev<T>& d) {
+  typedef C2<T> Z;
   const int B = Ev.cfg.B, p = Ev.p;
-  constexpr int LPW = 64 >> LB;
+  constexpr int LPW = 64 >> LB, TC = FL_K2_TC;   // (fp32 too: measured 8 columns, 131 -> 4 columns, 152-156 env-steps/s at C5's shape)
   if constexpr (LB == 6) {
-    const int npw = ((Ev.nl + 7) / 8 + 7) / 8;
-    // instantiated: n = 512 (nl = 513 -> 9 DMA pieces per wave, 8 output elements per thread) and n = 256 (257 -> 5, 4)
+    typedef K2pGeom<(int)sizeof(Z)> G;
+    const int npw = G::npw(Ev.nl);
     if (d.wtile) {
       static int ncu = 0;
       if (!ncu) {
@@ -1066,96 +1109,108 @@ static int fluid_k2_launch(FluidEnv& Ev, const FluidDev<double>& d) {
         ncu = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
       }
       const int ntiles = B * (p / 8);
-      const size_t lds = ((size_t)((Ev.nl + 7) / 8) * 64 + (size_t)Ev.n * 8 + (size_t)(Q > 1 ? (Q - 1) * E : 1) * 64) * 16;
-      const int grid = ntiles < ncu ? ntiles : ncu;
+      const size_t lds = ((size_t)G::npieces(Ev.nl) * G::PIECE + (size_t)Ev.n * G::TC + (size_t)(Q > 1 ? (Q - 1) * E : 1) * 64) * sizeof(Z);
 #define PDEC_K2P(NPW, NSU)                                                                                                     \
   {                                                                                                                            \
     static bool attr = false;                                                                                                  \
+    static int wpc = 1;                                                                                                        \
     if (!attr) {                                                                                                               \
-      PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k2p_kernel<E, Q, NPW, NSU>),                            \
+      PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k2p_kernel<T, E, Q, NPW, NSU>),                         \
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                                   \
+      if (!std::is_same<T, double>::value) {   /* fp32: as many resident workgroups per CU as registers and LDS allow, <= 2 */ \
+        int nb = 1;                                                                                                            \
+        PDEC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fluid_k2p_kernel<T, E, Q, NPW, NSU>, 512, lds));           \
+        wpc = nb < 1 ? 1 : (nb < FL_K2P_WPC32 ? nb : FL_K2P_WPC32);                                                            \
+      }                                                                                                                        \
       attr = true;                                                                                                             \
     }                                                                                                                          \
-    hipLaunchKernelGGL((fluid_k2p_kernel<E, Q, NPW, NSU>), dim3(grid), dim3(512), lds, Ev.stream, d, Ev.W.as<Z>(),             \
+    const int grid = ntiles < ncu * wpc ? ntiles : ncu * wpc;                                                                  \
+    hipLaunchKernelGGL((fluid_k2p_kernel<T, E, Q, NPW, NSU>), dim3(grid), dim3(512), lds, Ev.stream, d, Ev.W.as<Z>(),          \
                        Ev.W2.as<Z>(), ntiles);                                                                                 \
   }
-      if (npw == 9) PDEC_K2P(9, 8) else PDEC_K2P(5, 4)
+      if constexpr (std::is_same<T, double>::value) {
+        if (npw == 9) PDEC_K2P(9, 8) else PDEC_K2P(5, 4)
+      } else {
+        if (npw == 5) PDEC_K2P(5, 8) else PDEC_K2P(3, 4)
+      }
 #undef PDEC_K2P
       return PDEC_OK;
     }
   }
-  hipLaunchKernelGGL((fluid_k2w_kernel<E, Q, FL_K2_TC, LB>), dim3((p + FL_K2_TC - 1) / FL_K2_TC, B), dim3(64 * FL_K2_TC / LPW),
-                     (size_t)FL_K2_TC * (p + 1) * 16, Ev.stream, d, Ev.W.as<Z>(), Ev.W2.as<Z>());
+  hipLaunchKernelGGL((fluid_k2w_kernel<T, E, Q, TC, LB>), dim3((p + TC - 1) / TC, B), dim3(64 * TC / LPW),
+                     (size_t)TC * (p + 1) * sizeof(Z), Ev.stream, d, Ev.W.as<Z>(), Ev.W2.as<Z>());
   return PDEC_OK;
 }
 
 // one rhs evaluation fused with an RK4 stage update (mode as in fluid_k3_kernel)
-template <int E, int Q, int LB>
-static int fluid_rhs_launch_wave(FluidEnv& Ev, const FluidDev<double>& d, const void* omg_s, const void* phat, const void* f0,
+template <class T, int E, int Q, int LB>
+static int fluid_rhs_launch_wave(FluidEnv& Ev, const FluidDev<T>& d, const void* omg_s, const void* phat, const void* f0,
                                  void* acc, void* out, int mode, double ca, double cb) {
-  typedef C2<double> Z;
+  typedef C2<T> Z;
+  constexpr int TC = FL_K2_TC;
   const int B = Ev.cfg.B, n = Ev.n;
   constexpr int LPW = 64 >> LB, LPB = 4 * LPW;               // line slots per wave / per 256-thread workgroup
   static bool attr = false;
   if (!attr) {
-    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k1w_kernel<E, Q, LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k2w_kernel<E, Q, FL_K2_TC, LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k3w_kernel<E, Q, LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k1w_kernel<T, E, Q, LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k2w_kernel<T, E, Q, TC, LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k3w_kernel<T, E, Q, LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr = true;
   }
   const int pair = n >= 256 ? 1 : 0;      // a line and its mirror per wave (K1w) once there are enough lines to fill the chip
   {
     ProfScope ps(&Ev, "fluid_k1", true);
     for (int r = 0; r < ps.reps; ++r)
-      hipLaunchKernelGGL((fluid_k1w_kernel<E, Q, LB>), dim3(((pair ? n / 2 + 1 : Ev.nl) + LPB - 1) / LPB, B), dim3(256),
-                         (size_t)LPB * 2 * n * 16 + (size_t)n * 8, Ev.stream, d, (const Z*)omg_s, Ev.W.as<Z>(), pair);
+      hipLaunchKernelGGL((fluid_k1w_kernel<T, E, Q, LB>), dim3(((pair ? n / 2 + 1 : Ev.nl) + LPB - 1) / LPB, B), dim3(256),
+                         (size_t)LPB * 2 * n * sizeof(Z) + (size_t)n * sizeof(T), Ev.stream, d, (const Z*)omg_s, Ev.W.as<Z>(), pair);
   }
   {
     ProfScope ps(&Ev, "fluid_k2", true);
     for (int r = 0; r < ps.reps; ++r) {
-      const int rc = fluid_k2_launch<E, Q, LB>(Ev, d);
+      const int rc = fluid_k2_launch<T, E, Q, LB>(Ev, d);
       if (rc) return rc;
     }
   }
   {
     ProfScope ps(&Ev, "fluid_k3", mode == 0);
     for (int r = 0; r < ps.reps; ++r)
-      hipLaunchKernelGGL((fluid_k3w_kernel<E, Q, LB>), dim3((n + LPB - 1) / LPB, B), dim3(256), (size_t)LPB * n * 16, Ev.stream, d,
-                         Ev.W2.as<Z>(), (const Z*)omg_s, (const Z*)phat, (const Z*)f0, (Z*)acc, (Z*)out, mode, ca, cb);
+      hipLaunchKernelGGL((fluid_k3w_kernel<T, E, Q, LB>), dim3((n + LPB - 1) / LPB, B), dim3(256), (size_t)LPB * n * sizeof(Z), Ev.stream, d,
+                         Ev.W2.as<Z>(), (const Z*)omg_s, (const Z*)phat, (const Z*)f0, (Z*)acc, (Z*)out, mode, (T)ca, (T)cb);
   }
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
 }
 
+template <class T>
 static int fluid_rhs_launch(FluidEnv& E, const void* omg_s, const void* phat, const void* f0, void* acc, void* out,
                             int mode, double ca, double cb) {
-  typedef C2<double> Z;
-  const FluidDev<double> d = fluid_dev(E);
+  typedef C2<T> Z;
+  const FluidDev<T> d = fluid_dev<T>(E);
   const int B = E.cfg.B;
-  if (E.wave_E == 4 && E.wave_Q == 3) return fluid_rhs_launch_wave<4, 3, 6>(E, d, omg_s, phat, f0, acc, out, mode, ca, cb);
-  if (E.wave_E == 4 && E.wave_Q == 2) return fluid_rhs_launch_wave<4, 2, 6>(E, d, omg_s, phat, f0, acc, out, mode, ca, cb);
-  if (E.wave_E == 4 && E.wave_Q == 1) return fluid_rhs_launch_wave<4, 1, 6>(E, d, omg_s, phat, f0, acc, out, mode, ca, cb);
-  if (E.wave_E == 2 && E.wave_Q == 3 && E.wave_LB == 6) return fluid_rhs_launch_wave<2, 3, 6>(E, d, omg_s, phat, f0, acc, out, mode, ca, cb);
-  if (E.wave_E == 2 && E.wave_Q == 1 && E.wave_LB == 6) return fluid_rhs_launch_wave<2, 1, 6>(E, d, omg_s, phat, f0, acc, out, mode, ca, cb);
-  if (E.wave_E == 2 && E.wave_Q == 3 && E.wave_LB == 5) return fluid_rhs_launch_wave<2, 3, 5>(E, d, omg_s, phat, f0, acc, out, mode, ca, cb);
-  if (E.wave_E == 2 && E.wave_Q == 1 && E.wave_LB == 5) return fluid_rhs_launch_wave<2, 1, 5>(E, d, omg_s, phat, f0, acc, out, mode, ca, cb);
+  if (E.wave_E == 4 && E.wave_Q == 3) return fluid_rhs_launch_wave<T, 4, 3, 6>(E, d, omg_s, phat, f0, acc, out, mode, ca, cb);
+  if (E.wave_E == 4 && E.wave_Q == 2) return fluid_rhs_launch_wave<T, 4, 2, 6>(E, d, omg_s, phat, f0, acc, out, mode, ca, cb);
+  if (E.wave_E == 4 && E.wave_Q == 1) return fluid_rhs_launch_wave<T, 4, 1, 6>(E, d, omg_s, phat, f0, acc, out, mode, ca, cb);
+  if (E.wave_E == 2 && E.wave_Q == 3 && E.wave_LB == 6) return fluid_rhs_launch_wave<T, 2, 3, 6>(E, d, omg_s, phat, f0, acc, out, mode, ca, cb);
+  if (E.wave_E == 2 && E.wave_Q == 1 && E.wave_LB == 6) return fluid_rhs_launch_wave<T, 2, 1, 6>(E, d, omg_s, phat, f0, acc, out, mode, ca, cb);
+  if (E.wave_E == 2 && E.wave_Q == 3 && E.wave_LB == 5) return fluid_rhs_launch_wave<T, 2, 3, 5>(E, d, omg_s, phat, f0, acc, out, mode, ca, cb);
+  if (E.wave_E == 2 && E.wave_Q == 1 && E.wave_LB == 5) return fluid_rhs_launch_wave<T, 2, 1, 5>(E, d, omg_s, phat, f0, acc, out, mode, ca, cb);
   {
     ProfScope ps(&E, "fluid_k1", true);
     for (int r = 0; r < ps.reps; ++r)
-      hipLaunchKernelGGL(fluid_k1_kernel<double>, dim3((E.nl + E.TL - 1) / E.TL, B), dim3(FL_NTH), E.lds_p, E.stream, d,
+      hipLaunchKernelGGL(fluid_k1_kernel<T>, dim3((E.nl + E.TL - 1) / E.TL, B), dim3(FL_NTH), E.lds_p, E.stream, d,
                          (const Z*)omg_s, E.W.as<Z>());
   }
   {
     ProfScope ps(&E, "fluid_k2", true);
     for (int r = 0; r < ps.reps; ++r)
-      hipLaunchKernelGGL(fluid_k2_kernel<double>, dim3((E.p + E.TL - 1) / E.TL, B), dim3(FL_NTH), E.lds_p, E.stream, d,
+      hipLaunchKernelGGL(fluid_k2_kernel<T>, dim3((E.p + E.TL - 1) / E.TL, B), dim3(FL_NTH), E.lds_p, E.stream, d,
                          E.W.as<Z>(), E.W2.as<Z>());
   }
   {
     ProfScope ps(&E, "fluid_k3", mode == 0);
     for (int r = 0; r < ps.reps; ++r)
-      hipLaunchKernelGGL(fluid_k3_kernel<double>, dim3((E.n + E.TL - 1) / E.TL, B), dim3(FL_NTH), E.lds_p, E.stream, d,
-                         E.W2.as<Z>(), (const Z*)omg_s, (const Z*)phat, (const Z*)f0, (Z*)acc, (Z*)out, mode, ca, cb);
+      hipLaunchKernelGGL(fluid_k3_kernel<T>, dim3((E.n + E.TL - 1) / E.TL, B), dim3(FL_NTH), E.lds_p, E.stream, d,
+                         E.W2.as<Z>(), (const Z*)omg_s, (const Z*)phat, (const Z*)f0, (Z*)acc, (Z*)out, mode, (T)ca, (T)cb);
   }
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
@@ -1164,35 +1219,36 @@ static int fluid_rhs_launch(FluidEnv& E, const void* omg_s, const void* phat, co
 // do_step (FluidSetup.jl:163-172): K sub-steps of rk4 (src/fluid_rk4.jl:122-132), in place on f
 // RK4 sub-steps with K3 of every stage fused with K1 of the next right-hand side (fluid_k31w_kernel): K1 once, then
 // K2 + K31 per stage, a plain K3 at the very end.  Wave-transform path with line pairs (n >= 256).
-template <int E, int Q, int LB>
-static int fluid_integrate_wave(FluidEnv& Ev, const FluidDev<double>& d, void* f, const void* phat) {
-  typedef C2<double> Z;
+template <class T, int E, int Q, int LB>
+static int fluid_integrate_wave(FluidEnv& Ev, const FluidDev<T>& d, void* f, const void* phat) {
+  typedef C2<T> Z;
+  constexpr int TC = FL_K2_TC;
   const int B = Ev.cfg.B, n = Ev.n;
   constexpr int LPW = 64 >> LB, LPB = 4 * LPW;
   static bool attr = false;
   if (!attr) {
-    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k1w_kernel<E, Q, LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k2w_kernel<E, Q, FL_K2_TC, LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k3w_kernel<E, Q, LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k31w_kernel<E, Q, LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k1w_kernel<T, E, Q, LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k2w_kernel<T, E, Q, TC, LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k3w_kernel<T, E, Q, LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fluid_k31w_kernel<T, E, Q, LB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr = true;
   }
   const double h = Ev.cfg.dt / Ev.cfg.K;
   Z *fs = Ev.fs.as<Z>(), *acc = Ev.acc.as<Z>(), *fz = (Z*)f;
   const dim3 gpair((n / 2 + 1 + LPB - 1) / LPB, B);
-  const size_t lds2 = (size_t)LPB * 2 * n * 16;
+  const size_t lds2 = (size_t)LPB * 2 * n * sizeof(Z);
   auto k2 = [&]() {
     ProfScope ps(&Ev, "fluid_k2");
-    (void)fluid_k2_launch<E, Q, LB>(Ev, d);
+    (void)fluid_k2_launch<T, E, Q, LB>(Ev, d);
   };
   auto k31 = [&](const Z* omg_s, Z* out, int mode, double ca, double cb) {
     ProfScope ps(&Ev, "fluid_k31");
-    hipLaunchKernelGGL((fluid_k31w_kernel<E, Q, LB>), gpair, dim3(256), lds2, Ev.stream, d, Ev.W2.as<Z>(), omg_s, (const Z*)phat,
-                       (const Z*)fz, acc, out, mode, ca, cb, Ev.W.as<Z>());
+    hipLaunchKernelGGL((fluid_k31w_kernel<T, E, Q, LB>), gpair, dim3(256), lds2, Ev.stream, d, Ev.W2.as<Z>(), omg_s, (const Z*)phat,
+                       (const Z*)fz, acc, out, mode, (T)ca, (T)cb, Ev.W.as<Z>());
   };
   {
     ProfScope ps(&Ev, "fluid_k1");
-    hipLaunchKernelGGL((fluid_k1w_kernel<E, Q, LB>), gpair, dim3(256), lds2 + (size_t)n * 8, Ev.stream, d, (const Z*)fz, Ev.W.as<Z>(), 1);
+    hipLaunchKernelGGL((fluid_k1w_kernel<T, E, Q, LB>), gpair, dim3(256), lds2 + (size_t)n * sizeof(T), Ev.stream, d, (const Z*)fz, Ev.W.as<Z>(), 1);
   }
   for (int it = 0; it < Ev.cfg.K; ++it) {
     k2(); k31(fz, fs, 1, 0.5 * h, h / 6.0);
@@ -1203,8 +1259,8 @@ static int fluid_integrate_wave(FluidEnv& Ev, const FluidDev<double>& d, void* f
       k31(fs, fz, 4, 0.0, h / 6.0);
     } else {
       ProfScope ps(&Ev, "fluid_k3");
-      hipLaunchKernelGGL((fluid_k3w_kernel<E, Q, LB>), dim3((n + LPB - 1) / LPB, B), dim3(256), (size_t)LPB * n * 16, Ev.stream, d,
-                         Ev.W2.as<Z>(), (const Z*)fs, (const Z*)phat, (const Z*)fz, acc, fz, 4, 0.0, h / 6.0);
+      hipLaunchKernelGGL((fluid_k3w_kernel<T, E, Q, LB>), dim3((n + LPB - 1) / LPB, B), dim3(256), (size_t)LPB * n * sizeof(Z), Ev.stream, d,
+                         Ev.W2.as<Z>(), (const Z*)fs, (const Z*)phat, (const Z*)fz, acc, fz, 4, (T)0, (T)(h / 6.0));
     }
   }
   PDEC_HIP(hipGetLastError());
@@ -1214,135 +1270,171 @@ static int fluid_integrate_wave(FluidEnv& Ev, const FluidDev<double>& d, void* f
 // (A HIP graph of the whole sub-step loop -- 8 K = 320 kernel nodes at the reference's own shape, one trajectory on the 128^2
 // grid -- was measured and dropped: 232 against 260 env-steps/s eager.  That loop is not launch-bound: its kernels run
 // 17-48 workgroups of ~10 us each on 256 CUs, HISTORY.md.)
+template <class T>
 static int fluid_integrate(FluidEnv& E, void* f, const void* phat) {
   // measured (B = 16): n = 256: 650 -> 701 env-steps/s fused; n = 512: 76.6 -> 74.5 (the fused waves run six transforms
   // each and the stage's streaming phase no longer overlaps other waves' transforms) -> fused below 512 only
   static const char* fuse_env = getenv("PDEC_FLUID_FUSE");     // 1 / 0 force it on / off
   const bool fuse = fuse_env ? fuse_env[0] == '1' : (E.n >= 256 && E.n < 512);
   if (fuse && E.n >= 256) {
-    const FluidDev<double> d = fluid_dev(E);
-    if (E.wave_E == 4 && E.wave_Q == 3) return fluid_integrate_wave<4, 3, 6>(E, d, f, phat);
-    if (E.wave_E == 4 && E.wave_Q == 2) return fluid_integrate_wave<4, 2, 6>(E, d, f, phat);
-    if (E.wave_E == 4 && E.wave_Q == 1) return fluid_integrate_wave<4, 1, 6>(E, d, f, phat);
-    if (E.wave_E == 2 && E.wave_Q == 3 && E.wave_LB == 6) return fluid_integrate_wave<2, 3, 6>(E, d, f, phat);
-    if (E.wave_E == 2 && E.wave_Q == 1 && E.wave_LB == 6) return fluid_integrate_wave<2, 1, 6>(E, d, f, phat);
+    const FluidDev<T> d = fluid_dev<T>(E);
+    if (E.wave_E == 4 && E.wave_Q == 3) return fluid_integrate_wave<T, 4, 3, 6>(E, d, f, phat);
+    if (E.wave_E == 4 && E.wave_Q == 2) return fluid_integrate_wave<T, 4, 2, 6>(E, d, f, phat);
+    if (E.wave_E == 4 && E.wave_Q == 1) return fluid_integrate_wave<T, 4, 1, 6>(E, d, f, phat);
+    if (E.wave_E == 2 && E.wave_Q == 3 && E.wave_LB == 6) return fluid_integrate_wave<T, 2, 3, 6>(E, d, f, phat);
+    if (E.wave_E == 2 && E.wave_Q == 1 && E.wave_LB == 6) return fluid_integrate_wave<T, 2, 1, 6>(E, d, f, phat);
   }
   const double h = E.cfg.dt / E.cfg.K;
   void *fs = E.fs.p, *acc = E.acc.p;
   int rc;
   for (int it = 0; it < E.cfg.K; ++it) {
-    if ((rc = fluid_rhs_launch(E, f, phat, f, acc, fs, 1, 0.5 * h, h / 6.0))) return rc;
-    if ((rc = fluid_rhs_launch(E, fs, phat, f, acc, fs, 2, 0.5 * h, h / 3.0))) return rc;
-    if ((rc = fluid_rhs_launch(E, fs, phat, f, acc, fs, 2, h, h / 3.0))) return rc;
-    if ((rc = fluid_rhs_launch(E, fs, phat, f, acc, f, 4, 0.0, h / 6.0))) return rc;
+    if ((rc = fluid_rhs_launch<T>(E, f, phat, f, acc, fs, 1, 0.5 * h, h / 6.0))) return rc;
+    if ((rc = fluid_rhs_launch<T>(E, fs, phat, f, acc, fs, 2, 0.5 * h, h / 3.0))) return rc;
+    if ((rc = fluid_rhs_launch<T>(E, fs, phat, f, acc, fs, 2, h, h / 3.0))) return rc;
+    if ((rc = fluid_rhs_launch<T>(E, fs, phat, f, acc, f, 4, 0.0, h / 6.0))) return rc;
   }
   return PDEC_OK;
 }
 
 // yreal = real(ifft(y))
+template <class T>
 static int fluid_to_physical(FluidEnv& E, const void* y) {
-  typedef C2<double> Z;
-  const FluidDev<double> d = fluid_dev(E);
+  typedef C2<T> Z;
+  const FluidDev<T> d = fluid_dev<T>(E);
   const int B = E.cfg.B, gt = (E.n + E.TLn - 1) / E.TLn;
   ProfScope ps(&E, "fluid_ifft2");
-  hipLaunchKernelGGL((fluid_fft_fast_kernel<double, +1, false>), dim3(gt, B), dim3(FL_NTH), E.lds_n, E.stream, d, y,
+  hipLaunchKernelGGL((fluid_fft_fast_kernel<T, +1, false>), dim3(gt, B), dim3(FL_NTH), E.lds_n, E.stream, d, y,
                      E.tmpc.as<Z>());
-  hipLaunchKernelGGL((fluid_fft_slow_kernel<double, +1, true>), dim3(gt, B), dim3(FL_NTH), E.lds_n, E.stream, d,
+  hipLaunchKernelGGL((fluid_fft_slow_kernel<T, +1, true>), dim3(gt, B), dim3(FL_NTH), E.lds_n, E.stream, d,
                      E.tmpc.as<Z>(), E.yreal.p, d.invn2);
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
 }
 
+template <class T>
 static int fluid_dots(FluidEnv& E, const void* y) {
-  int rc = fluid_to_physical(E, y);
+  int rc = fluid_to_physical<T>(E, y);
   if (rc) return rc;
   const pdec_env_cfg& c = E.cfg;
   ProfScope ps(&E, "fluid_dots");
-  hipLaunchKernelGGL(fluid_dots_kernel<double>, dim3((c.S + 3) / 4, c.B), dim3(256), 0, E.stream, E.n, c.S, E.BH, E.BW,
-                     E.sbox.as<double>(), E.sorg.as<int>(), E.yreal.as<double>(), E.dots.as<double>());
+  hipLaunchKernelGGL(fluid_dots_kernel<T>, dim3((c.S + 3) / 4, c.B), dim3(256), 0, E.stream, E.n, c.S, E.BH, E.BW,
+                     E.sbox.as<T>(), E.sorg.as<int>(), E.yreal.as<T>(), E.dots.as<T>());
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
 }
 
-static FeatArgs<double> feat_args(const FluidEnv& E) {
+template <class T>
+static FeatArgs<T> feat_args(const FluidEnv& E) {
   const pdec_env_cfg& c = E.cfg;
-  FeatArgs<double> g;
+  FeatArgs<T> g;
   g.S = c.S; g.A = c.A; g.spa = c.sensors_per_axis; g.window = c.window;
   g.ns = env_ns(c); g.check_max = c.check_max_value;
   g.mem = c.memory_size; g.na = env_na(c);
-  g.sensor_scale = c.sensor_scale; g.r_in_scale = c.reward_in_scale; g.r_power = c.reward_power;
-  g.r_denom = c.reward_denom; g.a_pun = c.action_punish; g.da_pun = c.delta_action_punish; g.max_value = c.max_value;
+  g.sensor_scale = (T)c.sensor_scale; g.r_in_scale = (T)c.reward_in_scale; g.r_power = (T)c.reward_power;
+  g.r_denom = (T)c.reward_denom; g.a_pun = (T)c.action_punish; g.da_pun = (T)c.delta_action_punish; g.max_value = (T)c.max_value;
   g.a2s = E.a2s_d.as<int>();
   return g;
 }
 
+template <class T>
 static int fluid_feat_launch(FluidEnv& E, const void* action, const void* action_prev, const void* state_prev,
                              void* state_out, void* reward_out, int32_t* done) {
   ProfScope ps(&E, "fluid_feat");
-  hipLaunchKernelGGL(fluid_feat_kernel<double>, dim3(E.cfg.B), dim3(256), 0, E.stream, feat_args(E), E.dots.as<double>(),
-                     (const double*)action, (const double*)action_prev, (const double*)state_prev, (double*)state_out,
-                     (double*)reward_out, done);
+  hipLaunchKernelGGL(fluid_feat_kernel<T>, dim3(E.cfg.B), dim3(256), 0, E.stream, feat_args<T>(E), E.dots.as<T>(),
+                     (const T*)action, (const T*)action_prev, (const T*)state_prev, (T*)state_out,
+                     (T*)reward_out, done);
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
 }
 
 static FluidEnv& as_fluid(Env& E) { return static_cast<FluidEnv&>(E); }
+static bool is_f32(const FluidEnv& E) { return E.cfg.dtype == PDEC_F32; }
 
-int fluid_actuate(Env& E0, const void* action, void* p_out) {
-  typedef C2<double> Z;
-  FluidEnv& E = as_fluid(E0);
+template <class T>
+static int fluid_actuate_t(FluidEnv& E, const void* action, void* p_out) {
+  typedef C2<T> Z;
   const pdec_env_cfg& c = E.cfg;
-  const FluidDev<double> d = fluid_dev(E);
+  const FluidDev<T> d = fluid_dev<T>(E);
   const int gt = (E.n + E.TLn - 1) / E.TLn;
   ProfScope ps(&E, "fluid_actuate");
-  hipLaunchKernelGGL(fluid_actuate_kernel<double>, dim3(E.nb1 * E.nb1, c.B), dim3(256), 0, E.stream, E.n, c.A, E.BH, E.BW,
-                     E.nb1, E.abox.as<double>(), E.aorg.as<int>(), E.blkptr.as<int>(), E.blkidx.as<int>(),
-                     (const double*)action, env_na(c), c.agent_power, E.yreal.as<double>());
-  hipLaunchKernelGGL((fluid_fft_fast_kernel<double, -1, true>), dim3(gt, c.B), dim3(FL_NTH), E.lds_n, E.stream, d,
+  hipLaunchKernelGGL(fluid_actuate_kernel<T>, dim3(E.nb1 * E.nb1, c.B), dim3(256), 0, E.stream, E.n, c.A, E.BH, E.BW,
+                     E.nb1, E.abox.as<T>(), E.aorg.as<int>(), E.blkptr.as<int>(), E.blkidx.as<int>(),
+                     (const T*)action, env_na(c), (T)c.agent_power, E.yreal.as<T>());
+  hipLaunchKernelGGL((fluid_fft_fast_kernel<T, -1, true>), dim3(gt, c.B), dim3(FL_NTH), E.lds_n, E.stream, d,
                      E.yreal.p, E.tmpc.as<Z>());
-  hipLaunchKernelGGL((fluid_fft_slow_kernel<double, -1, false>), dim3(gt, c.B), dim3(FL_NTH), E.lds_n, E.stream, d,
-                     E.tmpc.as<Z>(), p_out, 1.0);
+  hipLaunchKernelGGL((fluid_fft_slow_kernel<T, -1, false>), dim3(gt, c.B), dim3(FL_NTH), E.lds_n, E.stream, d,
+                     E.tmpc.as<Z>(), p_out, (T)1);
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
 }
 
+int fluid_actuate(Env& E0, const void* action, void* p_out) {
+  FluidEnv& E = as_fluid(E0);
+  return is_f32(E) ? fluid_actuate_t<float>(E, action, p_out) : fluid_actuate_t<double>(E, action, p_out);
+}
+
 int fluid_featurize(Env& E0, const void* y, const void* state_prev, void* state_out, const void* action) {
   FluidEnv& E = as_fluid(E0);
-  int rc = fluid_dots(E, y);
+  int rc = is_f32(E) ? fluid_dots<float>(E, y) : fluid_dots<double>(E, y);
   if (rc) return rc;
-  return fluid_feat_launch(E, action, nullptr, state_prev, state_out, nullptr, nullptr);   // (action: the memory rows only)
+  // (action: the memory rows only)
+  if (is_f32(E)) return fluid_feat_launch<float>(E, action, nullptr, state_prev, state_out, nullptr, nullptr);
+  return fluid_feat_launch<double>(E, action, nullptr, state_prev, state_out, nullptr, nullptr);
 }
 
 int fluid_reward(Env& E0, const void* y, const void* action, const void* action_prev, void* r_out) {
   FluidEnv& E = as_fluid(E0);
-  int rc = fluid_dots(E, y);
+  int rc = is_f32(E) ? fluid_dots<float>(E, y) : fluid_dots<double>(E, y);
   if (rc) return rc;
-  return fluid_feat_launch(E, action, action_prev, nullptr, nullptr, r_out, nullptr);
+  if (is_f32(E)) return fluid_feat_launch<float>(E, action, action_prev, nullptr, nullptr, r_out, nullptr);
+  return fluid_feat_launch<double>(E, action, action_prev, nullptr, nullptr, r_out, nullptr);
 }
 
 int fluid_rhs_eval(Env& E0, const void* y, const void* p, void* out) {
   FluidEnv& E = as_fluid(E0);
-  return fluid_rhs_launch(E, y, p, nullptr, nullptr, out, 0, 0.0, 0.0);
+  if (is_f32(E)) return fluid_rhs_launch<float>(E, y, p, nullptr, nullptr, out, 0, 0.0, 0.0);
+  return fluid_rhs_launch<double>(E, y, p, nullptr, nullptr, out, 0, 0.0, 0.0);
 }
 
+template <class T>
 static int fluid_done_y(FluidEnv& E, const void* y, int32_t* done) {
-  hipLaunchKernelGGL(fluid_maxabs_kernel<double>, dim3(E.cfg.B), dim3(256), 0, E.stream, E.n * E.n, E.cfg.max_value,
-                     (const C2<double>*)y, done);
+  hipLaunchKernelGGL(fluid_maxabs_kernel<T>, dim3(E.cfg.B), dim3(256), 0, E.stream, E.n * E.n, (T)E.cfg.max_value,
+                     (const C2<T>*)y, done);
   PDEC_HIP(hipGetLastError());
+  return PDEC_OK;
+}
+
+template <class T>
+static int fluid_pde_step_t(FluidEnv& E, const void* y_in, const void* p, void* y_out, int32_t* done) {
+  const size_t bytes = (size_t)E.cfg.B * E.n * E.n * sizeof(C2<T>);
+  if (y_out != y_in) PDEC_HIP(hipMemcpyAsync(y_out, y_in, bytes, hipMemcpyDeviceToDevice, E.stream));
+  int rc = fluid_integrate<T>(E, y_out, p);
+  if (rc) return rc;
+  if (done) {
+    if (E.cfg.check_max_value == 1) return fluid_done_y<T>(E, y_out, done);
+    PDEC_HIP(hipMemsetAsync(done, 0, sizeof(int32_t) * E.cfg.B, E.stream));
+  }
   return PDEC_OK;
 }
 
 int fluid_pde_step(Env& E0, const void* y_in, const void* p, void* y_out, int32_t* done) {
   FluidEnv& E = as_fluid(E0);
-  const size_t bytes = (size_t)E.cfg.B * E.n * E.n * 16;
-  if (y_out != y_in) PDEC_HIP(hipMemcpyAsync(y_out, y_in, bytes, hipMemcpyDeviceToDevice, E.stream));
-  int rc = fluid_integrate(E, y_out, p);
-  if (rc) return rc;
-  if (done) {
-    if (E.cfg.check_max_value == 1) return fluid_done_y(E, y_out, done);
-    PDEC_HIP(hipMemsetAsync(done, 0, sizeof(int32_t) * E.cfg.B, E.stream));
+  return is_f32(E) ? fluid_pde_step_t<float>(E, y_in, p, y_out, done) : fluid_pde_step_t<double>(E, y_in, p, y_out, done);
+}
+
+template <class T>
+static int fluid_env_step_t(FluidEnv& E, const void* y_in, const void* action, const void* action_prev, const void* state_prev,
+                            void* y_out, void* p_out, void* state_out, void* reward_out, int32_t* done) {
+  void* ph = p_out ? p_out : E.phat.p;
+  int rc;
+  if ((rc = fluid_actuate_t<T>(E, action, ph))) return rc;                              // src/PDEenv.jl:199
+  if ((rc = fluid_pde_step_t<T>(E, y_in, ph, y_out, nullptr))) return rc;               // :216-218
+  if ((rc = fluid_dots<T>(E, y_out))) return rc;
+  if (done && E.cfg.check_max_value != 2) {
+    if (E.cfg.check_max_value == 1) { if ((rc = fluid_done_y<T>(E, y_out, done))) return rc; }
+    else PDEC_HIP(hipMemsetAsync(done, 0, sizeof(int32_t) * E.cfg.B, E.stream));
   }
-  return PDEC_OK;
+  return fluid_feat_launch<T>(E, action, action_prev, state_prev, state_out, reward_out, done);   // :220-222
 }
 
 int fluid_env_step(Env& E0, const void* y_in, const void* action, const void* action_prev, const void* state_prev,
@@ -1352,6 +1444,7 @@ int fluid_env_step(Env& E0, const void* y_in, const void* action, const void* ac
     // the parts of the batch side by side: every argument is batch-major, so a part is a pointer offset.  (Per-kernel
     // timing passes, pdec_prof_enable, take the whole batch on one stream.)
     const size_t nn = (size_t)E.n * E.n, A = E.cfg.A, ns = (size_t)env_ns(E.cfg), na = (size_t)env_na(E.cfg);
+    const size_t ts = dtype_size(E.cfg.dtype);          // bytes of a real; a spectrum element is two
     auto off = [](const void* p, size_t bytes) -> const void* { return p ? (const char*)p + bytes : nullptr; };
     auto offm = [](void* p, size_t bytes) -> void* { return p ? (char*)p + bytes : nullptr; };
     {
@@ -1368,10 +1461,10 @@ int fluid_env_step(Env& E0, const void* y_in, const void* action, const void* ac
     for (int hh = 0; hh < E.nparts; ++hh) {
       FluidEnv& H = *E.half[hh];
       H.stream = hh == 0 ? E.stream : E.ps.st[hh];
-      H.term_out = E.term_out ? (char*)E.term_out + (size_t)b0 * A * 8 : nullptr;
-      const int rc = fluid_env_step(H, off(y_in, b0 * nn * 16), off(action, b0 * A * na * 8), off(action_prev, b0 * A * na * 8),
-                                    off(state_prev, b0 * A * ns * 8), offm(y_out, b0 * nn * 16), offm(p_out, b0 * nn * 16),
-                                    offm(state_out, b0 * A * ns * 8), offm(reward_out, b0 * A * 8), done ? done + b0 : nullptr);
+      H.term_out = E.term_out ? (char*)E.term_out + (size_t)b0 * A * ts : nullptr;
+      const int rc = fluid_env_step(H, off(y_in, b0 * nn * 2 * ts), off(action, b0 * A * na * ts), off(action_prev, b0 * A * na * ts),
+                                    off(state_prev, b0 * A * ns * ts), offm(y_out, b0 * nn * 2 * ts), offm(p_out, b0 * nn * 2 * ts),
+                                    offm(state_out, b0 * A * ns * ts), offm(reward_out, b0 * A * ts), done ? done + b0 : nullptr);
       if (rc) { rc_part = rc; break; }              // (the part streams are joined below on this path too)
       b0 += H.cfg.B;
     }
@@ -1380,16 +1473,8 @@ int fluid_env_step(Env& E0, const void* y_in, const void* action, const void* ac
     PDEC_HIP(ej);
     return PDEC_OK;
   }
-  void* ph = p_out ? p_out : E.phat.p;
-  int rc;
-  if ((rc = fluid_actuate(E, action, ph))) return rc;                                   // src/PDEenv.jl:199
-  if ((rc = fluid_pde_step(E, y_in, ph, y_out, nullptr))) return rc;                    // :216-218
-  if ((rc = fluid_dots(E, y_out))) return rc;
-  if (done && E.cfg.check_max_value != 2) {
-    if (E.cfg.check_max_value == 1) { if ((rc = fluid_done_y(E, y_out, done))) return rc; }
-    else PDEC_HIP(hipMemsetAsync(done, 0, sizeof(int32_t) * E.cfg.B, E.stream));
-  }
-  return fluid_feat_launch(E, action, action_prev, state_prev, state_out, reward_out, done);   // :220-222
+  if (is_f32(E)) return fluid_env_step_t<float>(E, y_in, action, action_prev, state_prev, y_out, p_out, state_out, reward_out, done);
+  return fluid_env_step_t<double>(E, y_in, action, action_prev, state_prev, y_out, p_out, state_out, reward_out, done);
 }
 
 }  // namespace pdec
@@ -1400,7 +1485,8 @@ static int fluid_make(std::unique_ptr<FluidEnv>& out, const pdec_env_cfg& c, int
                       const int32_t* sensor_origin, const double* actuator_boxes, const int32_t* actuator_origin,
                       const int32_t* a2s) {
   PDEC_REQUIRE(c.pde_kind == PDEC_PDE_FLUID_RK4, "pdec_fluid_env_create: pde_kind must be PDEC_PDE_FLUID_RK4");
-  PDEC_REQUIRE(c.dtype == PDEC_F64, "the fluid path computes in fp64 (ComplexF64 in the reference)");
+  PDEC_REQUIRE(c.dtype == PDEC_F64 || c.dtype == PDEC_F32, "pdec_fluid_env_create: bad dtype %d (ComplexF64 in the reference; "
+               "ComplexF32 also served)", c.dtype);
   const int n = c.N;
   PDEC_REQUIRE(c.B >= 1 && n >= 8 && n % 4 == 0 && c.K >= 1, "pdec_fluid_env_create: bad sizes B=%d N=%d K=%d", c.B, n, c.K);
   PDEC_REQUIRE(c.S >= 1 && c.A >= 1 && c.sensors_per_axis >= 1 && c.sensors_per_axis * c.sensors_per_axis == c.S,
@@ -1440,19 +1526,21 @@ static int fluid_make(std::unique_ptr<FluidEnv>& out, const pdec_env_cfg& c, int
   E->TL = pick_tile(E->p);
   E->TLn = pick_tile(n);
   PDEC_REQUIRE(E->TL >= 2, "internal: tile too small");
-  E->lds_p = ((size_t)2 * E->TL * (E->p + 2) + E->p) * 16;
-  E->lds_n = ((size_t)2 * E->TLn * (n + 2) + n) * 16;
+  const size_t ts = dtype_size(c.dtype), zs = 2 * ts;     // bytes of a real / of a complex element
+  E->lds_p = ((size_t)2 * E->TL * (E->p + 2) + E->p) * zs;
+  E->lds_n = ((size_t)2 * E->TLn * (n + 2) + n) * zs;
   PDEC_REQUIRE(E->lds_p <= 160 * 1024 && E->lds_n <= 160 * 1024, "fluid kernels need too much LDS");
   std::vector<double> k(n), twp(2 * (size_t)E->p), twn(2 * (size_t)n);
   for (int i = 0; i < n; ++i) k[i] = (i <= n / 2 ? i : i - n) / c.Lx * 2 * M_PI;     // FluidSetup.jl:106
   for (int m = 0; m < E->p; ++m) { twp[2 * m] = cos(2 * M_PI * m / E->p); twp[2 * m + 1] = -sin(2 * M_PI * m / E->p); }
   for (int m = 0; m < n; ++m) { twn[2 * m] = cos(2 * M_PI * m / n); twn[2 * m + 1] = -sin(2 * M_PI * m / n); }
   int rc;
-  if ((rc = upload_converted(E->k, k.data(), n, PDEC_F64))) return rc;
-  if ((rc = upload_converted(E->twp, twp.data(), twp.size(), PDEC_F64))) return rc;
-  if ((rc = upload_converted(E->twn, twn.data(), twn.size(), PDEC_F64))) return rc;
-  if ((rc = upload_converted(E->sbox, sensor_boxes, (size_t)c.S * BH * BW, PDEC_F64))) return rc;
-  if ((rc = upload_converted(E->abox, actuator_boxes, (size_t)c.A * BH * BW, PDEC_F64))) return rc;
+  // (wavenumbers, twiddles and box tables: computed in fp64 and rounded once to the environment's dtype)
+  if ((rc = upload_converted(E->k, k.data(), n, c.dtype))) return rc;
+  if ((rc = upload_converted(E->twp, twp.data(), twp.size(), c.dtype))) return rc;
+  if ((rc = upload_converted(E->twn, twn.data(), twn.size(), c.dtype))) return rc;
+  if ((rc = upload_converted(E->sbox, sensor_boxes, (size_t)c.S * BH * BW, c.dtype))) return rc;
+  if ((rc = upload_converted(E->abox, actuator_boxes, (size_t)c.A * BH * BW, c.dtype))) return rc;
   auto up_i = [](DevBuf& b, const int32_t* src, size_t cnt) -> int {
     PDEC_HIP(b.alloc(sizeof(int32_t) * (cnt ? cnt : 1)));
     if (cnt) PDEC_HIP(hipMemcpy(b.p, src, sizeof(int32_t) * cnt, hipMemcpyHostToDevice));
@@ -1481,15 +1569,15 @@ static int fluid_make(std::unique_ptr<FluidEnv>& out, const pdec_env_cfg& c, int
   if ((rc = up_i(E->blkptr, ptr.data(), ptr.size()))) return rc;
   if ((rc = up_i(E->blkidx, idx.data(), idx.size()))) return rc;
   const size_t nn = (size_t)n * n, Bz = c.B;
-  PDEC_HIP(E->W.alloc(Bz * 2 * E->nl * E->p * 16));
-  PDEC_HIP(E->W2.alloc(Bz * n * E->p * 16));
-  PDEC_HIP(E->fs.alloc(Bz * nn * 16));
-  PDEC_HIP(E->acc.alloc(Bz * nn * 16));
-  PDEC_HIP(E->tmpc.alloc(Bz * nn * 16));
-  PDEC_HIP(E->phat.alloc(Bz * nn * 16));
-  PDEC_HIP(E->yreal.alloc(Bz * nn * 8));
-  PDEC_HIP(E->dots.alloc(Bz * c.S * 8));
-  if ((rc = fluid_set_attrs(*E))) return rc;
+  PDEC_HIP(E->W.alloc(Bz * 2 * E->nl * E->p * zs));
+  PDEC_HIP(E->W2.alloc(Bz * n * E->p * zs));
+  PDEC_HIP(E->fs.alloc(Bz * nn * zs));
+  PDEC_HIP(E->acc.alloc(Bz * nn * zs));
+  PDEC_HIP(E->tmpc.alloc(Bz * nn * zs));
+  PDEC_HIP(E->phat.alloc(Bz * nn * zs));
+  PDEC_HIP(E->yreal.alloc(Bz * nn * ts));
+  PDEC_HIP(E->dots.alloc(Bz * c.S * ts));
+  if ((rc = (c.dtype == PDEC_F32 ? fluid_set_attrs<float>(*E) : fluid_set_attrs<double>(*E)))) return rc;
   out = std::move(E);
   return PDEC_OK;
 }
@@ -1522,19 +1610,21 @@ extern "C" int pdec_fluid_env_create(pdec_handle* h, const pdec_env_cfg* cfg, in
   return PDEC_OK;
 }
 
-// Unit-test entry for the register-resident wave FFT (wave_fft.hpp): nlines lines of `len` complex doubles, natural
-// order in and out, unnormalised forward (sgn < 0) or inverse (sgn > 0).  len in {64, 128, 192, 256, 384, 512, 768}.
-extern "C" int pdec_debug_wave_fft(const void* in_dev, void* out_dev, int len, int nlines, int sgn) {
-  PDEC_REQUIRE(in_dev && out_dev && nlines >= 1, "pdec_debug_wave_fft: null/empty");
+// Unit-test entries for the register-resident wave FFT (wave_fft.hpp): nlines lines of `len` complex doubles
+// (pdec_debug_wave_fft) or complex floats (pdec_debug_wave_fft_f32), natural order in and out, unnormalised forward (sgn < 0)
+// or inverse (sgn > 0).  len in {64, 128, 192, 256, 384, 512, 768}.  Twiddles computed in fp64, rounded once.
+template <class T>
+static int debug_wave_fft(const char* name, const void* in_dev, void* out_dev, int len, int nlines, int sgn) {
+  PDEC_REQUIRE(in_dev && out_dev && nlines >= 1, "%s: null/empty", name);
   std::vector<double> tw(2 * (size_t)len);
   for (int m = 0; m < len; ++m) { tw[2 * m] = cos(2 * M_PI * m / len); tw[2 * m + 1] = -sin(2 * M_PI * m / len); }
   DevBuf d;
-  int rc = upload_converted(d, tw.data(), tw.size(), PDEC_F64);
+  int rc = upload_converted(d, tw.data(), tw.size(), std::is_same<T, float>::value ? PDEC_F32 : PDEC_F64);
   if (rc) return rc;
   const dim3 block(256);
-  typedef const C2<double>* CI;
-  typedef C2<double>* CO;
-#define WFD(E, Q, LB) hipLaunchKernelGGL((wave_fft_debug_kernel<E, Q, LB>), dim3((nlines + 4 * (64 >> LB) - 1) / (4 * (64 >> LB))), block, 0, 0, (CI)in_dev, (CO)out_dev, d.as<C2<double>>(), nlines, sgn)
+  typedef const C2<T>* CI;
+  typedef C2<T>* CO;
+#define WFD(E, Q, LB) hipLaunchKernelGGL((wave_fft_debug_kernel<T, E, Q, LB>), dim3((nlines + 4 * (64 >> LB) - 1) / (4 * (64 >> LB))), block, 0, 0, (CI)in_dev, (CO)out_dev, d.as<C2<T>>(), nlines, sgn)
   if (len == 768) WFD(4, 3, 6);
   else if (len == 512) WFD(4, 2, 6);
   else if (len == 256) WFD(4, 1, 6);
@@ -1542,10 +1632,44 @@ extern "C" int pdec_debug_wave_fft(const void* in_dev, void* out_dev, int len, i
   else if (len == 128) WFD(2, 1, 6);
   else if (len == 192) WFD(2, 3, 5);
   else if (len == 64) WFD(2, 1, 5);
-  else { set_error("pdec_debug_wave_fft: unsupported length %d", len); return PDEC_E_INVALID; }
+  else { set_error("%s: unsupported length %d", name, len); return PDEC_E_INVALID; }
 #undef WFD
   PDEC_HIP(hipGetLastError());
   PDEC_HIP(hipDeviceSynchronize());
+  return PDEC_OK;
+}
+extern "C" int pdec_debug_wave_fft(const void* in_dev, void* out_dev, int len, int nlines, int sgn) {
+  return debug_wave_fft<double>("pdec_debug_wave_fft", in_dev, out_dev, len, nlines, sgn);
+}
+extern "C" int pdec_debug_wave_fft_f32(const void* in_dev, void* out_dev, int len, int nlines, int sgn) {
+  return debug_wave_fft<float>("pdec_debug_wave_fft_f32", in_dev, out_dev, len, nlines, sgn);
+}
+
+// the vortex table in the environment's dtype (fp32: rounded once from the caller's doubles), the initialiser, the 2-D FFT
+template <class T>
+static int fluid_ic_t(FluidEnv& E, const double* vortices, int nv, void* y_out) {
+  typedef C2<T> Z;
+  const pdec_env_cfg& c = E.cfg;
+  const size_t cnt = (size_t)c.B * nv * 4, vb = cnt * sizeof(T);
+  std::vector<T> vt;
+  const void* src = vortices;
+  if (!std::is_same<T, double>::value) {
+    vt.assign(vortices, vortices + cnt);
+    src = vt.data();
+  }
+  if (E.icv.bytes < vb) PDEC_HIP(E.icv.alloc(vb));
+  PDEC_HIP(hipMemcpyAsync(E.icv.p, src, vb, hipMemcpyHostToDevice, E.stream));
+  const FluidDev<T> d = fluid_dev<T>(E);
+  const int gt = (E.n + E.TLn - 1) / E.TLn;
+  ProfScope ps(&E, "fluid_ic");
+  hipLaunchKernelGGL(fluid_ic_kernel<T>, dim3((E.n * E.n + 255) / 256, c.B), dim3(256), (size_t)nv * 4 * sizeof(T), E.stream,
+                     E.n, nv, (T)c.Lx, (T)c.Lx, E.icv.as<T>(), E.yreal.as<T>());
+  hipLaunchKernelGGL((fluid_fft_fast_kernel<T, -1, true>), dim3(gt, c.B), dim3(FL_NTH), E.lds_n, E.stream, d, E.yreal.p,
+                     E.tmpc.as<Z>());
+  hipLaunchKernelGGL((fluid_fft_slow_kernel<T, -1, false>), dim3(gt, c.B), dim3(FL_NTH), E.lds_n, E.stream, d,
+                     E.tmpc.as<Z>(), y_out, (T)1);
+  PDEC_HIP(hipGetLastError());
+  PDEC_HIP(hipStreamSynchronize(E.stream));      // the host array (and vt) may be reused / freed once this returns
   return PDEC_OK;
 }
 
@@ -1555,22 +1679,6 @@ extern "C" int pdec_fluid_ic(pdec_handle h, const double* vortices, int nv, void
   Env* E0 = lookup_as<Env>(h, Kind::Env);
   if (!E0 || E0->cfg.pde_kind != PDEC_PDE_FLUID_RK4) { set_error("pdec_fluid_ic: not a fluid env handle"); return PDEC_E_HANDLE; }
   PDEC_REQUIRE(vortices && y_out && nv >= 1 && nv <= 1024, "pdec_fluid_ic: bad arguments (1 <= nv <= 1024)");
-  typedef C2<double> Z;
   FluidEnv& E = static_cast<FluidEnv&>(*E0);
-  const pdec_env_cfg& c = E.cfg;
-  const size_t vb = (size_t)c.B * nv * 4 * sizeof(double);
-  if (E.icv.bytes < vb) PDEC_HIP(E.icv.alloc(vb));
-  PDEC_HIP(hipMemcpyAsync(E.icv.p, vortices, vb, hipMemcpyHostToDevice, E.stream));
-  const FluidDev<double> d = fluid_dev(E);
-  const int gt = (E.n + E.TLn - 1) / E.TLn;
-  ProfScope ps(&E, "fluid_ic");
-  hipLaunchKernelGGL(fluid_ic_kernel<double>, dim3((E.n * E.n + 255) / 256, c.B), dim3(256), (size_t)nv * 4 * sizeof(double), E.stream,
-                     E.n, nv, c.Lx, c.Lx, E.icv.as<double>(), E.yreal.as<double>());
-  hipLaunchKernelGGL((fluid_fft_fast_kernel<double, -1, true>), dim3(gt, c.B), dim3(FL_NTH), E.lds_n, E.stream, d, E.yreal.p,
-                     E.tmpc.as<Z>());
-  hipLaunchKernelGGL((fluid_fft_slow_kernel<double, -1, false>), dim3(gt, c.B), dim3(FL_NTH), E.lds_n, E.stream, d,
-                     E.tmpc.as<Z>(), y_out, 1.0);
-  PDEC_HIP(hipGetLastError());
-  PDEC_HIP(hipStreamSynchronize(E.stream));      // the host array may be reused by the caller
-  return PDEC_OK;
+  return E.cfg.dtype == PDEC_F32 ? fluid_ic_t<float>(E, vortices, nv, y_out) : fluid_ic_t<double>(E, vortices, nv, y_out);
 }

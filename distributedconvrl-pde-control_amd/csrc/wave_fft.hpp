@@ -1,15 +1,17 @@
-// wave_fft.hpp -- register-resident FFT of one line per WAVE (fp64): N = 64 * E * Q points, element n = lane + 64 j
+// wave_fft.hpp -- register-resident FFT of one line per WAVE (fp64 or fp32): N = 64 * E * Q points, element n = lane + 64 j
 // (or per half wave: N = 32 * 2 * Q, see LB below)
 // in register slot j = e + E * qd (e < E: the "exchange digit", 4 or 2; qd < Q: 1, 2 or 3).
 //
 // Decimation in frequency: radix-Q over qd (in-lane), then Q independent FFTs of size 64 E: radix-E over e, and for
 // every 2-bit (E = 4) or 1-bit (E = 2) digit of the lane id: exchange that lane digit with the register digit e
-// (v_permlane32/16_swap for lane bits 5, 4; one v_cndmask_b32_dpp per moved 32-bit word for bits 3..0) and run the
+// (v_permlane32/16_swap for lane bits 5, 4; one v_cndmask_b32_dpp per moved 32-bit word for bits 3..0 -- 4 words per complex
+// double, 2 per complex float) and run the
 // next in-lane radix-E butterfly.  No LDS, no barriers.  The forward transform leaves mode
 //     k = qd + Q * (perm(lane) + 64 e),  perm = (l>>4) + 4((l>>2)&3) + 16(l&3)  (E = 4)   or   bitrev6(l)  (E = 2)
 // in slot (qd, e); the inverse (decimation in time) consumes that order and returns natural order, so a
 // forward -> pointwise -> inverse chain never reorders data.  Same scheme as FftWave256 in env.hip, generalised
-// to the 2-D fluid's line lengths (768 / 512 / 384 / 256 / 128) and to fp64.
+// to the 2-D fluid's line lengths (768 / 512 / 384 / 256 / 128) and to fp64.  WaveFft<T, ...> is the transform of C2<T>;
+// WaveFftD<...> = WaveFft<double, ...>.
 #pragma once
 #include "fft_lds.hpp"
 
@@ -36,8 +38,24 @@ namespace pdec {
         : "vcc");                                                                                          \
     Q0 = n0_; Q1 = n1_; Q2 = n2_; Q3 = n3_;                                                                \
   }
+// the same on two (P, Q) register pairs (a complex float)
+#define PDEC_WXSTEP2(CA, CB, MASK, P0, Q0, P1, Q1)                                                          \
+  {                                                                                                        \
+    unsigned n0_, n1_;                                                                                     \
+    asm("s_nop 1\n\t"                                                                                      \
+        "s_mov_b64 vcc, %6\n\t"                                                                           \
+        "v_cndmask_b32_dpp %4, %0, %1, vcc " CA " row_mask:0xf bank_mask:0xf\n\t"                           \
+        "v_cndmask_b32_dpp %5, %2, %3, vcc " CA " row_mask:0xf bank_mask:0xf\n\t"                           \
+        "s_mov_b64 vcc, %7\n\t"                                                                           \
+        "v_cndmask_b32_dpp %0, %1, %0, vcc " CB " row_mask:0xf bank_mask:0xf\n\t"                           \
+        "v_cndmask_b32_dpp %2, %3, %2, vcc " CB " row_mask:0xf bank_mask:0xf"                                \
+        : "+v"(P0), "+v"(Q0), "+v"(P1), "+v"(Q1), "=&v"(n0_), "=&v"(n1_)                                   \
+        : "s"(MASK), "s"(~(MASK))                                                                          \
+        : "vcc");                                                                                          \
+    Q0 = n0_; Q1 = n1_;                                                                                    \
+  }
 
-// exchange the register bit (P vs Q) with lane bit BIT for the four 32-bit words of a complex double pair
+// exchange the register bit (P vs Q) with lane bit BIT for the four 32-bit words of a complex double
 template <int BIT>
 __device__ __forceinline__ void wx_bit(unsigned (&p)[4], unsigned (&q)[4]) {
   if (BIT == 5) {
@@ -58,14 +76,33 @@ __device__ __forceinline__ void wx_bit(unsigned (&p)[4], unsigned (&q)[4]) {
     PDEC_WXSTEP("quad_perm:[1,0,3,2]", "quad_perm:[1,0,3,2]", 0xAAAAAAAAAAAAAAAAull, p[0], q[0], p[1], q[1], p[2], q[2], p[3], q[3])
   }
 }
+// ... for the two 32-bit words of a complex float
 template <int BIT>
-__device__ __forceinline__ void wx_pair(C2<double>& a, C2<double>& b) {
-  unsigned p[4], q[4];
-  __builtin_memcpy(p, &a, 16);
-  __builtin_memcpy(q, &b, 16);
+__device__ __forceinline__ void wx_bit(unsigned (&p)[2], unsigned (&q)[2]) {
+  if (BIT == 5) {
+    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3" : "+v"(p[0]), "+v"(p[1]), "+v"(q[0]), "+v"(q[1]));
+  } else if (BIT == 4) {
+    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3" : "+v"(p[0]), "+v"(p[1]), "+v"(q[0]), "+v"(q[1]));
+  } else if (BIT == 3) {
+    PDEC_WXSTEP2("row_ror:8", "row_ror:8", 0xFF00FF00FF00FF00ull, p[0], q[0], p[1], q[1])
+  } else if (BIT == 2) {
+    PDEC_WXSTEP2("row_ror:12", "row_ror:4", 0xF0F0F0F0F0F0F0F0ull, p[0], q[0], p[1], q[1])
+  } else if (BIT == 1) {
+    PDEC_WXSTEP2("quad_perm:[2,3,0,1]", "quad_perm:[2,3,0,1]", 0xCCCCCCCCCCCCCCCCull, p[0], q[0], p[1], q[1])
+  } else {
+    PDEC_WXSTEP2("quad_perm:[1,0,3,2]", "quad_perm:[1,0,3,2]", 0xAAAAAAAAAAAAAAAAull, p[0], q[0], p[1], q[1])
+  }
+}
+// the word count follows the element type: 4 for C2<double>, 2 for C2<float>
+template <int BIT, class T>
+__device__ __forceinline__ void wx_pair(C2<T>& a, C2<T>& b) {
+  constexpr int NW = (int)(sizeof(C2<T>) / 4);
+  unsigned p[NW], q[NW];
+  __builtin_memcpy(p, &a, sizeof(C2<T>));
+  __builtin_memcpy(q, &b, sizeof(C2<T>));
   wx_bit<BIT>(p, q);
-  __builtin_memcpy(&a, p, 16);
-  __builtin_memcpy(&b, q, 16);
+  __builtin_memcpy(&a, p, sizeof(C2<T>));
+  __builtin_memcpy(&b, q, sizeof(C2<T>));
 }
 
 // LB = 6: one line per wave (64 lanes).  LB = 5 (E = 2 only): one line per HALF wave -- N = 32 * 2 * Q, e.g. 192 for the
@@ -73,25 +110,25 @@ __device__ __forceinline__ void wx_pair(C2<double>& a, C2<double>& b) {
 // then only use lane bits 4..0, none of which crosses the halves.
 // WQ_MEM: the radix-Q stage twiddles are read from a [(Q - 1) E][LANES] table (LDS) at use instead of held in (Q - 1) E
 // complex registers -- 32 VGPRs at E = 4, Q = 3 -- for callers at the register limit (fluid_k2p_kernel).
-template <int E, int Q, int LB = 6, bool WQ_MEM = false>
-struct WaveFftD {
+template <class T, int E, int Q, int LB = 6, bool WQ_MEM = false>
+struct WaveFft {
   static_assert(LB == 6 || (LB == 5 && E == 2), "half-wave lines need the 1-bit exchange digit");
   static constexpr int LANES = 1 << LB, LPW = 64 / LANES;   // lanes per line, lines per wave
   static constexpr int R = E * Q, N = LANES * R, M = LANES * E;
   static constexpr int NST = E == 4 ? LB / 2 : LB;    // lane-digit stages
-  C2<double> wq[(Q > 1 && !WQ_MEM) ? (Q - 1) * E : 1];   // radix-Q stage twiddles  tw_N[kq (lane + 64 e)]
-  const C2<double>* wq_tab = nullptr;                  // WQ_MEM: the same numbers, element (i, lane) at i * LANES + lane
-  __device__ __forceinline__ C2<double> wqv(int i) const {
+  C2<T> wq[(Q > 1 && !WQ_MEM) ? (Q - 1) * E : 1];   // radix-Q stage twiddles  tw_N[kq (lane + 64 e)]
+  const C2<T>* wq_tab = nullptr;                  // WQ_MEM: the same numbers, element (i, lane) at i * LANES + lane
+  __device__ __forceinline__ C2<T> wqv(int i) const {
     if constexpr (WQ_MEM) return wq_tab[i * LANES + lane];
     else return wq[i];
   }
-  C2<double> we[E - 1];                               // register-digit stage     tw_M[k lane]
-  C2<double> wl[NST > 1 ? (NST - 1) * (E - 1) : 1];   // lane-digit stages (the last one has none)
+  C2<T> we[E - 1];                               // register-digit stage     tw_M[k lane]
+  C2<T> wl[NST > 1 ? (NST - 1) * (E - 1) : 1];   // lane-digit stages (the last one has none)
   int lane;
 
   // tw: exp(-2 pi i m / N), m < N (global or LDS)
   // tab (WQ_MEM only): the table's storage; fill: this wave writes it (the caller synchronises before the first transform)
-  __device__ __forceinline__ void init(const C2<double>* tw, int lane_, C2<double>* tab = nullptr, bool fill = false) {
+  __device__ __forceinline__ void init(const C2<T>* tw, int lane_, C2<T>* tab = nullptr, bool fill = false) {
     lane = lane_ & (LANES - 1);      // position inside the line
     if constexpr (WQ_MEM) {
       wq_tab = tab;
@@ -139,14 +176,14 @@ struct WaveFftD {
     return qd + Q * (perm + LANES * e);
   }
   template <int SGN>
-  static __device__ __forceinline__ C2<double> tmul(C2<double> a, C2<double> w) {
+  static __device__ __forceinline__ C2<T> tmul(C2<T> a, C2<T> w) {
     if (SGN > 0) w.y = -w.y;
     return cmul(a, w);
   }
   template <int SGN>
-  static __device__ __forceinline__ void dftE(C2<double>* a) { dft_small<E, SGN, double>(a); }
+  static __device__ __forceinline__ void dftE(C2<T>* a) { dft_small<E, SGN, T>(a); }
   template <int ST>
-  __device__ __forceinline__ void exchange(C2<double>* b) {    // b[0..E): lane digit ST <-> register digit e
+  __device__ __forceinline__ void exchange(C2<T>* b) {    // b[0..E): lane digit ST <-> register digit e
     if constexpr (E == 4) {
       constexpr int HI = 5 - 2 * ST, LO = 4 - 2 * ST;
       wx_pair<HI>(b[0], b[2]);
@@ -158,7 +195,7 @@ struct WaveFftD {
     }
   }
   template <int ST, int SGN>
-  __device__ __forceinline__ void stage_fwd(C2<double>* b) {
+  __device__ __forceinline__ void stage_fwd(C2<T>* b) {
     exchange<ST>(b);
     dftE<SGN>(b);
     if (ST < NST - 1) {
@@ -167,7 +204,7 @@ struct WaveFftD {
     }
   }
   template <int ST, int SGN>
-  __device__ __forceinline__ void stage_inv(C2<double>* b) {
+  __device__ __forceinline__ void stage_inv(C2<T>* b) {
     if (ST < NST - 1) {
 #pragma unroll
       for (int k = 1; k < E; ++k) b[k] = tmul<SGN>(b[k], wl[ST * (E - 1) + k - 1]);
@@ -176,14 +213,14 @@ struct WaveFftD {
     exchange<ST>(b);
   }
   // natural order in -> digit-reversed out (unnormalised forward transform, e^{-2 pi i nk/N})
-  __device__ __forceinline__ void forward(C2<double> (&a)[R]) {
+  __device__ __forceinline__ void forward(C2<T> (&a)[R]) {
     if constexpr (Q > 1) {
 #pragma unroll
       for (int e = 0; e < E; ++e) {
-        C2<double> t[Q];
+        C2<T> t[Q];
 #pragma unroll
         for (int qd = 0; qd < Q; ++qd) t[qd] = a[qd * E + e];
-        dft_small<Q, -1, double>(t);
+        dft_small<Q, -1, T>(t);
 #pragma unroll
         for (int qd = 1; qd < Q; ++qd) t[qd] = cmul(t[qd], wqv((qd - 1) * E + e));
 #pragma unroll
@@ -192,7 +229,7 @@ struct WaveFftD {
     }
 #pragma unroll
     for (int qd = 0; qd < Q; ++qd) {
-      C2<double>* b = &a[qd * E];
+      C2<T>* b = &a[qd * E];
       dftE<-1>(b);
 #pragma unroll
       for (int k = 1; k < E; ++k) b[k] = cmul(b[k], we[k - 1]);
@@ -204,10 +241,10 @@ struct WaveFftD {
     }
   }
   // digit-reversed in -> natural order out (unnormalised inverse transform, e^{+2 pi i nk/N})
-  __device__ __forceinline__ void inverse(C2<double> (&a)[R]) {
+  __device__ __forceinline__ void inverse(C2<T> (&a)[R]) {
 #pragma unroll
     for (int qd = 0; qd < Q; ++qd) {
-      C2<double>* b = &a[qd * E];
+      C2<T>* b = &a[qd * E];
       if constexpr (NST > 5) stage_inv<5, +1>(b);
       if constexpr (NST > 3) { stage_inv<4, +1>(b); stage_inv<3, +1>(b); }
       stage_inv<2, +1>(b);
@@ -220,17 +257,19 @@ struct WaveFftD {
     if constexpr (Q > 1) {
 #pragma unroll
       for (int e = 0; e < E; ++e) {
-        C2<double> t[Q];
+        C2<T> t[Q];
 #pragma unroll
         for (int qd = 0; qd < Q; ++qd) t[qd] = a[qd * E + e];
 #pragma unroll
         for (int qd = 1; qd < Q; ++qd) t[qd] = tmul<+1>(t[qd], wqv((qd - 1) * E + e));
-        dft_small<Q, +1, double>(t);
+        dft_small<Q, +1, T>(t);
 #pragma unroll
         for (int qd = 0; qd < Q; ++qd) a[qd * E + e] = t[qd];
       }
     }
   }
 };
+template <int E, int Q, int LB = 6, bool WQ_MEM = false>
+using WaveFftD = WaveFft<double, E, Q, LB, WQ_MEM>;
 
 }  // namespace pdec

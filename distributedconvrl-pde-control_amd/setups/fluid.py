@@ -197,9 +197,13 @@ class FluidSetup:
     def error_detection(self, y):
         """scripts/Fluid/setup/FluidSetup.jl:263-273, handed to PDEhook (FluidSetup.jl:373-377; src/PDEhook.jl:78-82): an episode
         that ended early counts as errored when neighbouring cells of real(ifft(y)) differ by more than 10 along either axis.
-        `y`: the spectral field of the env, [ny, nx] or a batch [B, ny, nx] (device tensor or array); batched: any trajectory."""
+        `y`: the spectral field of the env, [ny, nx] or a batch [B, ny, nx] (device tensor or array); batched: any trajectory.
+        A real `y` whose last axis has length 2 is the environment's own layout (env.y: [.., nx, ny] x (re, im), fp64 or fp32);
+        the test is symmetric in the two axes, so the transposed memory image gives the same answer."""
         import torch
         yt = torch.as_tensor(y)
+        if not yt.is_complex() and yt.dim() >= 3 and yt.shape[-1] == 2:
+            yt = torch.view_as_complex(yt.contiguous())
         w = torch.fft.ifft2(yt, dim=(-2, -1)).real
         y_x = (torch.roll(w, 1, dims=-2) - w).abs()
         y_y = (torch.roll(w, 1, dims=-1) - w).abs()

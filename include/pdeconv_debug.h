@@ -14,6 +14,9 @@ extern "C" {
  * lines of `len` complex doubles (device), natural order in and out, unnormalised forward (sgn < 0) / inverse
  * (sgn > 0) with FFTW's conventions (src/fluid_rk4.jl uses FFTW's fft / ifft).  len in {128,256,384,512,768}. */
 int pdec_debug_wave_fft(const void* in_dev, void* out_dev, int len, int nlines, int sgn);
+/* The same for `len` complex floats (the transform of the fp32 fluid environment); twiddles computed in fp64 and rounded
+ * once.  len in {64,128,192,256,384,512,768}. */
+int pdec_debug_wave_fft_f32(const void* in_dev, void* out_dev, int len, int nlines, int sgn);
 
 /* Measurement aid of bench.py (no reference counterpart): arm = 1 makes the NEXT fused critic pass launched on `critic`
  * (the behaviour critic of a 3-layer pair, src/PDEagent.jl:385-400) record s_memtime / s_memrealtime stamps at its phase

@@ -163,6 +163,13 @@ function fluid_do_step(h::UInt64, y::Matrix{ComplexF64}, p::Matrix{ComplexF64})
                 h, y, p, ynew, C_NULL))
     ynew
 end
+# ... of an fp32 environment (cfg.dtype = F32): ComplexF32[ny, nx]
+function fluid_do_step(h::UInt64, y::Matrix{ComplexF32}, p::Matrix{ComplexF32})
+    ynew = similar(y)
+    check(ccall((:pdec_pde_step_host, LIB), Cint, (UInt64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}),
+                h, y, p, ynew, C_NULL))
+    ynew
+end
 # generate_random_init() (FluidSetup.jl:386-394 -> ic(3)/ic(4), src/fluid_rk4.jl:72-120): the random draws stay in
 # Julia, the 9-image Taylor-vortex sums and the fft2 run on the GPU.  vort: 4 x nv (x0, y0, a0, U_max), y0_dev: device
 fluid_ic!(h::UInt64, vort::Matrix{Float64}, y0_dev::Ptr{Cvoid}) =

@@ -23,7 +23,9 @@ def main():
     ap.add_argument("--cases", default="128:16,256:16,512:16", help="nx:B list")
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--substeps", type=int, default=0, help="override K (0 = floor(16 nx dt) as in FluidSetup.jl:47)")
+    ap.add_argument("--dtype", choices=("f64", "f32"), default="f64", help="environment dtype (complex128 / complex64 spectra)")
     args = ap.parse_args()
+    dt_t = {"f64": torch.float64, "f32": torch.float32}[args.dtype]
     pkg = importlib.import_module("distributedconvrl-pde-control_amd")
     L = pkg._lib
     for case in args.cases.split(","):
@@ -33,9 +35,9 @@ def main():
         rng = np.random.default_rng(0)
         y0 = np.stack([setup.ic(3, rng)] * 1)
         y0 = np.repeat(y0, B, axis=0)
-        env = pkg.PDEenv(setup, B=B, dtype=torch.float64, y0=y0)
+        env = pkg.PDEenv(setup, B=B, dtype=dt_t, y0=y0)
         lib = env.lib
-        act = torch.zeros(env._ashape, dtype=torch.float64, device="cuda:0")
+        act = torch.zeros(env._ashape, dtype=dt_t, device="cuda:0")
         env(act)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -55,8 +57,8 @@ def main():
             kern[lab] = ms.value
         L.check(lib.pdec_prof_enable(env.handle, 0))
         p = 3 * n // 2
-        z16 = 16
-        # compulsory HBM bytes per trajectory and launch (complex fp64 = 16 B): K1 reads w (+ mirrored line) and writes
+        z16 = 2 * torch.empty((), dtype=dt_t).element_size()        # bytes of a complex element: 16 (fp64) / 8 (fp32)
+        # compulsory HBM bytes per trajectory and launch (z16 per complex element): K1 reads w (+ mirrored line) and writes
         # 2 (n+1) p; K2 reads that and writes n p; K3 reads n p + w + p^ (+ f, acc in RK4 stages) and writes rhs
         bytes_k = {"fluid_k1": (2 * n * n + 2 * (n + 1) * p) * z16, "fluid_k2": (2 * (n + 1) * p + n * p) * z16,
                    "fluid_k3": (n * p + 3 * n * n) * z16}
@@ -64,8 +66,9 @@ def main():
                     "frac_of_8TBs": (B * bytes_k[k] / (kern[k] * 1e-3) / 8e12) if kern[k] else None} for k in kern}
         K = setup.oversampling
         rhs_ms = sum(kern.values())
-        print(json.dumps({"metric": "env-steps/sec (2-D fluid rk4, fp64)", "value": B / dt, "unit": "env-steps/s",
-                          "ms_per_step": dt * 1e3, "config": {"workload": f"fluid nx=ny={n} ifpad=1 K={K} B={B} fp64"},
+        print(json.dumps({"metric": f"env-steps/sec (2-D fluid rk4, {args.dtype.replace('f', 'fp')})", "value": B / dt,
+                          "unit": "env-steps/s", "ms_per_step": dt * 1e3,
+                          "config": {"workload": f"fluid nx=ny={n} ifpad=1 K={K} B={B} {args.dtype.replace('f', 'fp')}"},
                           "rhs_ms": rhs_ms, "rhs_share_of_step": 4 * K * rhs_ms / (dt * 1e3),
                           "algorithmic_GB_per_env_step_reference_unfused": 141.0 * (n / 512.0) ** 2 * (K / 163.0),
                           "kernels": roof}))
