@@ -216,7 +216,7 @@ class CustomDDPGPolicy:
     def __init__(self, *, behavior_actor, behavior_critic, target_actor, target_critic, rng, gamma=0.99, rho=0.995,
                  batch_size=3, start_steps=6, start_policy=None, update_after=10, update_freq=1, update_loops=1,
                  reset_stage=POST_EPISODE_STAGE, act_limit=1.0, act_noise=1.2, memory_size=0, number_actuators=1,
-                 quirk_target_broadcast=True, quirk_frozen_targets=True, noise_seed=0, reducer=None):
+                 quirk_target_broadcast=True, quirk_frozen_targets=True, noise_seed=0, reducer=None, reward_group=None):
         self.behavior_actor, self.behavior_critic = behavior_actor, behavior_critic
         self.target_actor, self.target_critic = target_actor, target_critic
         self.rng = rng
@@ -226,6 +226,18 @@ class CustomDDPGPolicy:
         self.reset_stage, self.act_limit, self.act_noise, self.memory_size = reset_stage, act_limit, act_noise, memory_size
         self.number_actuators = number_actuators
         self.quirk = quirk_target_broadcast               # (1xBu) .+ (Bu) broadcast of r
+        # reward groups (include/pdeconv.h, pdec_ddpg_set_reward_groups): an update of Bu columns read as the mean of Bu / g
+        # reference-sized minibatch losses, each column's target broadcasting the mean reward of its own group of g.  None: the
+        # whole-batch broadcast.  The interleave L of the groups is the caller's: update(..., interleave=A) for fresh columns
+        # c = b A + a (TrainPipeline), 1 for replay-sampled minibatches.
+        if reward_group is not None:
+            if not quirk_target_broadcast:
+                raise ValueError("reward groups refine the reward broadcast: they need quirk_target_broadcast=True")
+            if int(reward_group) != reward_group or int(reward_group) < 1:
+                raise ValueError(f"reward group size must be an integer >= 1 (got {reward_group!r})")
+            reward_group = int(reward_group)
+        self.reward_group = reward_group
+        self._rg_set = None                               # (g, L) last handed to the critic
         # The reference's Polyak loop (src/PDEagent.jl:415-417) runs over zip(Flux.params([At, Ct]), Flux.params([A, C])), and
         # both are EMPTY: src/custom_nna.jl:20 defines a `functor` of its own (not Functors.functor), so Flux sees a
         # CustomNeuralNetworkApproximator inside a Vector as a leaf without parameters.  The loop body never runs and the target
@@ -251,6 +263,16 @@ class CustomDDPGPolicy:
         self._noise = None
         self._actions = None
         self._set_noise_rows(m)
+
+    def set_reward_interleave(self, interleave):
+        """hand the reward groups (g = self.reward_group, L = interleave) to the behaviour critic for the updates that follow
+        (sticky on the handle; no-op without reward groups)"""
+        if self.reward_group is None:
+            return
+        key = (self.reward_group, max(1, int(interleave)))
+        if key != self._rg_set:
+            _lib.check(self.lib.pdec_ddpg_set_reward_groups(self.behavior_critic.model.handle, *key))
+            self._rg_set = key
 
     def _set_noise_rows(self, model):
         """action memory: exploration noise on the driving rows only (src/PDEagent.jl:201: actions[1:end-memory_size, :] += ...);
@@ -318,10 +340,13 @@ class CustomDDPGPolicy:
             self._noise_off += (cols * na + 3) // 4
 
     # ---- update!(policy, batch) (src/PDEagent.jl:363-418), fused on the device
-    def update(self, batch, before_actor_half=None):
+    def update(self, batch, before_actor_half=None, interleave=1):
         """batch: dict(state [Bu,ns], action [Bu,na], reward [Bu], terminal [Bu], next_state [Bu,ns]).
         before_actor_half: optional callable run between the critic half and the actor half of the update
-        (e.g. a stream wait on the event of a concurrent acting kernel that still reads the actor)."""
+        (e.g. a stream wait on the event of a concurrent acting kernel that still reads the actor).
+        interleave: the L of the reward groups (set_reward_interleave) -- A when the batch holds B trajectories x A
+        actuators as columns b A + a, 1 for a sampled minibatch."""
+        self.set_reward_interleave(interleave)
         A, Cn, At, Ct = (self.behavior_actor.model, self.behavior_critic.model, self.target_actor.model,
                          self.target_critic.model)
         dt = Cn.dtype
@@ -346,7 +371,7 @@ class CustomDDPGPolicy:
                 A.handle, Cn.handle, At.handle, Ct.handle, _lib.ptr(s), Bu, self.rho_effective, float(oa.eta),
                 C.c_void_p(L.data_ptr())))
             return
-        self.update_critic_half(batch)
+        self.update_critic_half(batch, interleave)
         if before_actor_half is not None:
             before_actor_half()
         self.actor_grads(batch)
@@ -361,9 +386,10 @@ class CustomDDPGPolicy:
         self._batch_keepalive = arrs
         return arrs
 
-    def update_critic_half(self, batch):
+    def update_critic_half(self, batch, interleave=1):
         """critic pass + ADAM(C) + Polyak(Ct) (src/PDEagent.jl:385-400, :415-417 for the critic pair): the local fused form when
         only the policy gradient is exchanged, gradient pass -> all-reduce -> apply launch otherwise"""
+        self.set_reward_interleave(interleave)
         A, Cn, At, Ct = (self.behavior_actor.model, self.behavior_critic.model, self.target_actor.model,
                          self.target_critic.model)
         s, a, r, t, sn = self._batch_arrays(batch)
@@ -399,8 +425,11 @@ class CustomDDPGPolicy:
 
     def small_update_ok(self):
         A, Cn = self.behavior_actor.model, self.behavior_critic.model
+        # reward groups that split the minibatch have no small kernel: the batched update serves them (pdec_ddpg_update_small)
+        split = self.reward_group is not None and 2 <= self.reward_group < self.batch_size
         return (self.use_small_update and (self.reducer is None or not self.reducer.active) and self.batch_size <= 16
-                and A.dtype == torch.float32 and Cn.dtype == torch.float32 and len(A.acts) <= 4 and len(Cn.acts) <= 4)
+                and not split and A.dtype == torch.float32 and Cn.dtype == torch.float32 and len(A.acts) <= 4
+                and len(Cn.acts) <= 4)
 
     def update_small(self, tr, slots):
         """update_loops x update!(policy, batch) (src/PDEagent.jl:357-418) in one launch, sampling straight from the
@@ -408,6 +437,7 @@ class CustomDDPGPolicy:
         A, Cn, At, Ct = (self.behavior_actor.model, self.behavior_critic.model, self.target_actor.model,
                          self.target_critic.model)
         d = torch.as_tensor(np.ascontiguousarray(slots, dtype=np.int32), device=self.device)
+        self.set_reward_interleave(1)
         oc, oa = self.behavior_critic.optimizer, self.behavior_actor.optimizer
         L = self._losses
         _lib.check(self.lib.pdec_ddpg_update_small(
@@ -422,6 +452,7 @@ class CustomDDPGPolicy:
         A, Cn, At, Ct = (self.behavior_actor.model, self.behavior_critic.model, self.target_actor.model,
                          self.target_critic.model)
         oc, oa = self.behavior_critic.optimizer, self.behavior_actor.optimizer
+        self.set_reward_interleave(1)
         _lib.check(self.lib.pdec_ddpg_update_small_rng(
             A.handle, Cn.handle, At.handle, Ct.handle, _lib.ptr(tr.state), _lib.ptr(tr.action), _lib.ptr(tr.reward),
             _lib.ptr(tr.terminal), int(self.update_loops), int(self.batch_size), self._sample_seed, self._sample_off,
@@ -523,14 +554,19 @@ def resolve_target_networks(setup, requested=None, stacklevel=2):
 
 
 def create_agent(*, setup, B=1, rng=None, dtype=torch.float32, device="cuda:0", start_policy=None, mono=None,
-                 max_update_cols=None, reducer=None, stream=None, **overrides):
+                 max_update_cols=None, reducer=None, stream=None, target_broadcast_group=None, **overrides):
     """src/PDEagent.jl:58-119 with the setup's agent constants (KSSetup.jl:38-77).
 
     Target networks: `quirk_frozen_targets` defaults PER SETUP to the regime under which this path reproduces the reference's
     saved runs of that experiment family (`setup.reproduces_reference_with`: "frozen" for KSSetup -- the reference as its
     committed source runs --, "moving" for the Keller-Segel and fluid setups, whose artifacts a later session of the authors
     wrote; HISTORY.md 5.1).  Passing the other value explicitly is honoured and raises a TargetNetworkWarning that names the
-    measured consequence."""
+    measured consequence.
+
+    target_broadcast_group: None (default) -- the reward broadcast over the whole update batch, as the reference writes it;
+    an integer g or "setup" (g = setup.batch_size, the reference's minibatch) -- every column's target broadcasts the mean
+    reward of its own group of g columns (CustomDDPGPolicy.reward_group, include/pdeconv.h pdec_ddpg_set_reward_groups).
+    Needs quirk_target_broadcast=True."""
     rng = rng or np.random.default_rng(0)
     frozen = resolve_target_networks(setup, overrides.get("quirk_frozen_targets"), stacklevel=3)
     g = lambda k: overrides.get(k, getattr(setup, k))
@@ -538,6 +574,9 @@ def create_agent(*, setup, B=1, rng=None, dtype=torch.float32, device="cuda:0", 
     mono = setup.mono if mono is None else mono
     na = setup.action_shape[0]
     batch_size = g("batch_size")
+    group = batch_size if target_broadcast_group == "setup" else target_broadcast_group
+    if isinstance(group, str):
+        raise ValueError(f"target_broadcast_group: None, an integer or \"setup\" (got {target_broadcast_group!r})")
     max_cols = max(B * cols_per_env, batch_size, max_update_cols or 0)
     mk = lambda actor, lr: create_NNA(na=na, ns=ns, is_actor=actor, init_rng=rng,
                                       nna_scale=g("nna_scale") if actor else g("nna_scale_critic"),
@@ -559,7 +598,7 @@ def create_agent(*, setup, B=1, rng=None, dtype=torch.float32, device="cuda:0", 
         number_actuators=cols_per_env, reducer=reducer,
         quirk_target_broadcast=overrides.get("quirk_target_broadcast", True),
         quirk_frozen_targets=bool(frozen),
-        noise_seed=overrides.get("noise_seed", 0))
+        noise_seed=overrides.get("noise_seed", 0), reward_group=group)
     trajectory = CircularArraySARTTrajectory(g("trajectory_length") * B, ns, na, stride, torch.device(device))
     trajectory.bind(behavior_critic.model)         # stage kernels on the networks' stream (row F1)
     return Agent(policy, trajectory)

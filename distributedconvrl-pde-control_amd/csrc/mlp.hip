@@ -276,11 +276,11 @@ __global__ void ddpg_stats_kernel(const T* __restrict__ q, const T* __restrict__
 template <class T>
 __global__ void ddpg_critic_dq_kernel(const T* __restrict__ q, const T* __restrict__ qt, const T* __restrict__ r,
                                       const T* __restrict__ t, int n, T gamma, int quirk, const T* __restrict__ stats,
-                                      T* __restrict__ dq, T* __restrict__ loss_out) {
+                                      T* __restrict__ dq, T* __restrict__ loss_out, const T* __restrict__ loss_add) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i == 0 && loss_out) {
-    // quirk: mean_ij (r_j + c_i)^2 = mean(c^2) + 2 mean(c) mean(r) + mean(r^2)
-    *loss_out = quirk ? stats[1] + (T)2 * stats[0] * stats[2] + stats[3] : stats[5];
+    // quirk: mean_ij (r_j + c_i)^2 = mean(c^2) + 2 mean(c) mean(r) + mean(r^2); loss_add: reward groups (reward_group_route)
+    *loss_out = quirk ? stats[1] + (T)2 * stats[0] * stats[2] + stats[3] : stats[5] + (loss_add ? *loss_add : (T)0);
   }
   if (i >= n) return;
   const T c = gamma * ((T)1 - t[i]) * qt[i] - q[i];
@@ -746,9 +746,99 @@ int pdec_randn(pdec_handle any_handle, void* dst, size_t n, int dtype, uint64_t 
 }  // extern "C"
 
 // ------------------------------------------------------------------ DDPG
+// Reward groups (pdec_ddpg_set_reward_groups): column c belongs to group (c / (g L)) L + c % L, whose members are the
+// columns base + k L, k = 0 .. g-1, base = (c / (g L)) g L + c % L.  rg[c] = (sum over k in that order) / g -- every
+// column of a group sums the same values in the same order, so all of them hold the same mean -- and
+// corr = mean_c (r_c - rg[c])^2 (= mean(r^2) - mean(rg^2)): the per-block partials (fixed tree, double) are added in block
+// order by the block that finishes last, which resets the counter for the next launch (graph replays included).
+#define RG_THREADS 256
+template <class T>
+__global__ __launch_bounds__(RG_THREADS) void reward_group_mean_kernel(const T* __restrict__ r, int n, int g, int L,
+                                                                        T* __restrict__ rg, double* __restrict__ part,
+                                                                        unsigned* __restrict__ counter) {
+  __shared__ double red[RG_THREADS];
+  __shared__ bool last;
+  const int tid = threadIdx.x, c = blockIdx.x * RG_THREADS + tid;
+  double e = 0.0;
+  if (c < n) {
+    const int gl = g * L, base = (c / gl) * gl + c % L;
+    T sum = r[base];
+    for (int k = 1; k < g; ++k) sum += r[base + k * L];
+    const T m = sum / (T)g;
+    rg[c] = m;
+    const T d = r[c] - m;
+    e = (double)d * (double)d;
+  }
+  red[tid] = e;
+  __syncthreads();
+  for (int s = RG_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    part[blockIdx.x] = red[0];
+    __threadfence();
+    last = atomicAdd(counter, 1u) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  __threadfence();
+  double a = 0.0;
+  for (int b = tid; b < (int)gridDim.x; b += RG_THREADS) a += __hip_atomic_load(part + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  red[tid] = a;
+  __syncthreads();
+  for (int s = RG_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    rg[n] = (T)(red[0] / n);
+    *counter = 0u;
+  }
+}
+
+int pdec::reward_group_route(Mlp* C, const void* r, int Bu, int quirk, CriticRoute* out) {
+  *out = CriticRoute{r, quirk, nullptr};
+  const int g = C->rg_g, L = C->rg_L;
+  if (!quirk || g == 0) return PDEC_OK;
+  if (g == 1) {                                   // groups of one column: the diagonal TD target
+    out->quirk = 0;
+    return PDEC_OK;
+  }
+  if ((int64_t)g * L >= Bu) return PDEC_OK;        // one group spans the batch: the whole-batch broadcast
+  PDEC_REQUIRE(Bu % (g * L) == 0,
+               "reward groups: the batch of %d columns is not a whole number of g x L = %d x %d column blocks", Bu, g, L);
+  const size_t ts = dtype_size(C->dtype);
+  const int nblk = cdiv(Bu, RG_THREADS);
+  if (C->rg_vals.bytes < (size_t)(Bu + 1) * ts) PDEC_HIP(C->rg_vals.alloc((size_t)(Bu + 1) * ts));
+  const size_t work = (size_t)nblk * 8 + 8;
+  if (C->rg_work.bytes < work) {
+    PDEC_HIP(C->rg_work.alloc(work));
+    PDEC_HIP(hipMemset(C->rg_work.p, 0, work));   // the last-block counter starts (and every launch leaves it) at zero
+    PDEC_HIP(hipDeviceSynchronize());
+  }
+  double* part = C->rg_work.as<double>();
+  unsigned* counter = (unsigned*)(C->rg_work.as<char>() + C->rg_work.bytes - 8);
+  {
+    ProfScope ps(C, "ddpg_reward_groups");
+    if (C->dtype == PDEC_F64)
+      hipLaunchKernelGGL((reward_group_mean_kernel<double>), dim3(nblk), dim3(RG_THREADS), 0, C->stream, (const double*)r, Bu, g,
+                         L, C->rg_vals.as<double>(), part, counter);
+    else
+      hipLaunchKernelGGL((reward_group_mean_kernel<float>), dim3(nblk), dim3(RG_THREADS), 0, C->stream, (const float*)r, Bu, g, L,
+                         C->rg_vals.as<float>(), part, counter);
+    PDEC_HIP(hipGetLastError());
+  }
+  out->r = C->rg_vals.p;
+  out->quirk = 0;
+  out->loss_add = C->rg_vals.as<char>() + (size_t)Bu * ts;
+  return PDEC_OK;
+}
+
 template <class T>
 static int critic_grads_t(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const void* a, const void* r, const void* t,
-                          const void* snext, int Bu, double gamma, int quirk, double grad_scale, void* loss_dev) {
+                          const void* snext, int Bu, double gamma, int quirk, double grad_scale, void* loss_dev,
+                          const void* loss_add) {
   const int ns = At->dims[0], na = At->dims[At->L];
   PDEC_REQUIRE(C->dims[0] == ns + na && Ct->dims[0] == ns + na && C->dims[C->L] == 1 && Ct->dims[Ct->L] == 1,
                "ddpg: critic must map ns+na -> 1");
@@ -776,7 +866,7 @@ static int critic_grads_t(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const
       hipLaunchKernelGGL((ddpg_diag_loss_kernel<T>), dim3(1), dim3(256), 0, C->stream, q, qt, (const T*)r, (const T*)t, Bu, gm, stats);
     // dq goes straight into dz of the identity output layer (feature-major [1][Bu])
     hipLaunchKernelGGL((ddpg_critic_dq_kernel<T>), dim3(cdiv(Bu, 256)), dim3(256), 0, C->stream, q, qt, (const T*)r, (const T*)t, Bu,
-                       gm, quirk, stats, C->dy_buf<T>(Bu), (T*)loss_dev);
+                       gm, quirk, stats, C->dy_buf<T>(Bu), (T*)loss_dev, (const T*)loss_add);
     PDEC_HIP(hipGetLastError());
   }
   return C->backward<T>(C->dy_buf<T>(Bu), 1, Bu, true, false, grad_scale);
@@ -807,6 +897,28 @@ static int actor_grads_t(Mlp* A, Mlp* C, const void* s, int Bu, double grad_scal
   return A->backward<T>(dA, 1, Bu, true, false, grad_scale);
 }
 
+// the critic pass on arguments reward_group_route has already settled (loss_add: its loss correction, or null)
+static int critic_grads_routed(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const void* a, const void* r, const void* t,
+                               const void* snext, int Bu, double gamma, int quirk, double grad_scale, void* critic_loss_dev,
+                               const void* loss_add) {
+  int rc;
+  if (fused_supported(A, C) && A->stream == C->stream && At->stream == C->stream && Ct->stream == C->stream)
+    rc = fused_critic_grads(A, C, At, Ct, s, a, r, t, snext, Bu, (double)(float)gamma, quirk, grad_scale, critic_loss_dev, nullptr,
+                            loss_add);
+  else if (fused2_supported(A, C) && A->stream == C->stream && At->stream == C->stream && Ct->stream == C->stream)
+    rc = fused2_critic_grads(A, C, At, Ct, s, a, r, t, snext, Bu, (double)(float)gamma, quirk, grad_scale, critic_loss_dev, nullptr,
+                             loss_add);
+  else
+    rc = C->dtype == PDEC_F64
+             ? critic_grads_t<double>(A, C, At, Ct, s, a, r, t, snext, Bu, gamma, quirk, grad_scale, critic_loss_dev, loss_add)
+             : critic_grads_t<float>(A, C, At, Ct, s, a, r, t, snext, Bu, gamma, quirk, grad_scale, critic_loss_dev, loss_add);
+  if (rc == PDEC_OK && C->reduce_event) {     // see pdec_ddpg_actor_grads
+    PDEC_HIP(hipEventRecord(C->reduce_event, C->stream));
+    C->reduce_event = nullptr;
+  }
+  return rc;
+}
+
 extern "C" {
 
 int pdec_ddpg_critic_grads(pdec_handle hA, pdec_handle hC, pdec_handle hAt, pdec_handle hCt, const void* s,
@@ -819,20 +931,18 @@ int pdec_ddpg_critic_grads(pdec_handle hA, pdec_handle hC, pdec_handle hAt, pdec
   PDEC_REQUIRE(s && a && r && t && snext && Bu >= 1, "pdec_ddpg_critic_grads: null/empty batch");
   PDEC_REQUIRE(A->dtype == C->dtype && At->dtype == C->dtype && Ct->dtype == C->dtype, "ddpg: dtype mismatch");
   PDEC_REQUIRE(At->dims == A->dims && Ct->dims == C->dims, "ddpg: target networks must have the behaviour networks' shapes");
-  int rc;
-  if (fused_supported(A, C) && A->stream == C->stream && At->stream == C->stream && Ct->stream == C->stream)
-    rc = fused_critic_grads(A, C, At, Ct, s, a, r, t, snext, Bu, (double)(float)gamma, quirk, grad_scale, critic_loss_dev, nullptr);
-  else if (fused2_supported(A, C) && A->stream == C->stream && At->stream == C->stream && Ct->stream == C->stream)
-    rc = fused2_critic_grads(A, C, At, Ct, s, a, r, t, snext, Bu, (double)(float)gamma, quirk, grad_scale, critic_loss_dev, nullptr);
-  else
-    rc = C->dtype == PDEC_F64
-             ? critic_grads_t<double>(A, C, At, Ct, s, a, r, t, snext, Bu, gamma, quirk, grad_scale, critic_loss_dev)
-             : critic_grads_t<float>(A, C, At, Ct, s, a, r, t, snext, Bu, gamma, quirk, grad_scale, critic_loss_dev);
-  if (rc == PDEC_OK && C->reduce_event) {     // see pdec_ddpg_actor_grads
-    PDEC_HIP(hipEventRecord(C->reduce_event, C->stream));
-    C->reduce_event = nullptr;
-  }
-  return rc;
+  CriticRoute rt;
+  int rc = reward_group_route(C, r, Bu, quirk, &rt);
+  if (rc) return rc;
+  return critic_grads_routed(A, C, At, Ct, s, a, rt.r, t, snext, Bu, gamma, rt.quirk, grad_scale, critic_loss_dev, rt.loss_add);
+}
+
+int pdec_ddpg_set_reward_groups(pdec_handle critic, int g, int L) {
+  GET_MLP(C, critic);
+  PDEC_REQUIRE(g >= 0 && L >= 1, "pdec_ddpg_set_reward_groups: needs g >= 0 (0: off) and L >= 1 (got g = %d, L = %d)", g, L);
+  C->rg_g = g;
+  C->rg_L = g ? L : 1;
+  return PDEC_OK;
 }
 
 int pdec_ddpg_actor_grads(pdec_handle hA, pdec_handle hC, const void* s, int Bu, double grad_scale, void* actor_loss_dev) {
@@ -924,11 +1034,19 @@ static int ddpg_update_phases(int phase, pdec_handle hA, pdec_handle hC, pdec_ha
   char* l1 = l0 ? l0 + ts : nullptr;
   const bool one_stream = A->stream == C->stream && At->stream == C->stream && Ct->stream == C->stream;
   int rc;
+  const void* loss_add = nullptr;
+  if (phase & 1) {          // reward groups: routed once here (the generic branch below hands the routed arguments on unchanged)
+    CriticRoute rt;
+    if ((rc = reward_group_route(C, r, Bu, quirk, &rt))) return rc;
+    r = rt.r;
+    quirk = rt.quirk;
+    loss_add = rt.loss_add;
+  }
   if (fused_supported(A, C) && one_stream) {
     // 4 launches: critic pass, reduce+ADAM(C)+Polyak(Ct), actor pass (updated critic), reduce+ADAM(A)+Polyak(At)
     const AdamPolyak apc{eta_critic, 0.9, 0.999, 1e-8, rho}, apa{eta_actor, 0.9, 0.999, 1e-8, rho};
     if ((phase & 1) &&
-        (rc = fused_critic_grads(A, C, At, Ct, s, a, r, t, snext, Bu, (double)(float)gamma, quirk, 1.0, l0, &apc)))
+        (rc = fused_critic_grads(A, C, At, Ct, s, a, r, t, snext, Bu, (double)(float)gamma, quirk, 1.0, l0, &apc, loss_add)))
       return rc;
     if (phase & 2) return fused_actor_grads(A, C, At, s, Bu, 1.0, l1, &apa);
     return PDEC_OK;
@@ -936,13 +1054,13 @@ static int ddpg_update_phases(int phase, pdec_handle hA, pdec_handle hC, pdec_ha
   if (fused2_supported(A, C) && one_stream && Bu >= 64) {      // 2-layer nets, large batches: same 4 launches
     const AdamPolyak apc{eta_critic, 0.9, 0.999, 1e-8, rho}, apa{eta_actor, 0.9, 0.999, 1e-8, rho};
     if ((phase & 1) &&
-        (rc = fused2_critic_grads(A, C, At, Ct, s, a, r, t, snext, Bu, (double)(float)gamma, quirk, 1.0, l0, &apc)))
+        (rc = fused2_critic_grads(A, C, At, Ct, s, a, r, t, snext, Bu, (double)(float)gamma, quirk, 1.0, l0, &apc, loss_add)))
       return rc;
     if (phase & 2) return fused2_actor_grads(A, C, At, s, Bu, 1.0, l1, &apa);
     return PDEC_OK;
   }
   if (phase & 1) {
-    if ((rc = pdec_ddpg_critic_grads(hA, hC, hAt, hCt, s, a, r, t, snext, Bu, gamma, quirk, 1.0, l0))) return rc;
+    if ((rc = critic_grads_routed(A, C, At, Ct, s, a, r, t, snext, Bu, gamma, quirk, 1.0, l0, loss_add))) return rc;
     if ((rc = pdec_adam_step(hC, eta_critic, 0.9, 0.999, 1e-8))) return rc;         // :400
     if ((rc = pdec_polyak(hCt, hC, rho))) return rc;                                // :415-417 (critic pair)
   }

@@ -24,6 +24,9 @@ struct Mlp : Object {
   const float* rpart_ext = nullptr;  // per-workgroup reward sums of the producer (pdec_ddpg_set_reward_partials), consumed likewise
   int rpart_n = 0;
   const void* rbar_ext = nullptr;    // batch-mean reward reduced elsewhere (pdec_ddpg_set_reward_mean), consumed by the next critic pass
+  int rg_g = 0, rg_L = 1;            // reward groups of the broadcast target (pdec_ddpg_set_reward_groups; g = 0: off), sticky
+  DevBuf rg_vals;                    // per-column group-mean reward [cols] + loss correction [1] (dtype of the net)
+  DevBuf rg_work;                    // per-block partials of the correction (double) + the last-block counter (zero between launches)
   DevBuf noise_ctr;                  // uint64 [2]: double-buffered exploration-noise counter of pdec_policy_act_rng_dev
   int nc_sel = 0;
   int noise_rows = -1;   // pdec_mlp_set_noise_rows: exploration noise on the first rows of the output only (-1: all)
@@ -82,6 +85,18 @@ __device__ __forceinline__ void bp_advance(const BpArgs& a, double b1, double b2
   a.next[1] = p1;
 }
 
+// Reward groups (pdec_ddpg_set_reward_groups).  For a broadcast-target critic pass (quirk = 1) of Bu columns that the groups
+// split (2 <= g, g L < Bu) this enqueues on C's stream the per-column group means rg and the loss correction
+// mean_c (r_c - rg_c)^2, and returns the arguments of the pass that gives the grouped gradient: the diagonal target
+// (quirk 0) on rg, the correction added to the loss.  g = 1 -> the diagonal pass on r; off, or g L >= Bu -> the arguments
+// unchanged (whole-batch broadcast).  Refuses Bu % (g L) != 0.  Idempotent: a second call on its own output changes nothing.
+struct CriticRoute {
+  const void* r;
+  int quirk;
+  const void* loss_add;    // device scalar of the net's dtype added to the critic loss, or null
+};
+int reward_group_route(Mlp* C, const void* r, int Bu, int quirk, CriticRoute* out);
+
 // mlp_mfma.hip: fused fp32 MFMA DDPG passes (3-layer actor/critic pairs)
 struct AdamPolyak {
   double eta, b1, b2, eps, rho;
@@ -92,7 +107,7 @@ bool fused_net_supported(const Mlp* M);
 // the padded weight images (single-GPU path: no all-reduce between gradient and update)
 int fused_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const void* a, const void* r, const void* t,
                        const void* sn, int Bu, double gamma, int quirk, double grad_scale, void* loss_dev,
-                       const AdamPolyak* apply);
+                       const AdamPolyak* apply, const void* loss_add = nullptr);
 int fused_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
                       const AdamPolyak* apply);
 int fused_adam_polyak(Mlp* M, Mlp* Mt, const AdamPolyak& ap);
@@ -113,7 +128,7 @@ int fused2_policy_act(Mlp* A, const void* state, int cols, double act_noise, dou
 int fused2_adam_polyak(Mlp* M, Mlp* Mt, const AdamPolyak& ap);
 int fused2_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const void* a, const void* r, const void* t,
                         const void* sn, int Bu, double gamma, int quirk, double grad_scale, void* loss_dev,
-                        const AdamPolyak* apply);
+                        const AdamPolyak* apply, const void* loss_add = nullptr);
 int fused2_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
                        const AdamPolyak* apply);
 

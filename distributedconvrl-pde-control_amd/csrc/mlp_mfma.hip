@@ -655,6 +655,7 @@ struct FinishArgs {
   float scale;
   int mode, Bu, quirk;         // loss finalisation (mode 0 critic, 1 actor)
   float* loss_out;
+  const float* loss_add;       // != null: device scalar added to the critic loss (reward groups, reward_group_route)
   int apply;                   // != 0: ADAM step on p, Polyak into pt, refresh the padded images
   float *p, *m, *v, *pt, *fw, *fwt;
   float* fwp;                  // published copy of the updated image (double-buffered: a concurrent acting kernel
@@ -789,7 +790,7 @@ __global__ __launch_bounds__(1024) void fused_finish_ref_kernel(FinishArgs g_in)
       const double inv = 1.0 / g.Bu;
       if (g.mode == 0)   // critic: quirk -> mean(c^2) + 2 mean(c) mean(r) + mean(r^2); else mean((r+c)^2)
         *g.loss_out = (float)(g.quirk ? red[1][0] * inv + 2.0 * (red[0][0] * inv) * (red[2][0] * inv) + red[3][0] * inv
-                                      : red[4][0] * inv);
+                                      : red[4][0] * inv + (g.loss_add ? (double)*g.loss_add : 0.0));
       else               // actor: -mean(q)
         *g.loss_out = (float)(-red[0][0] * inv);
     }
@@ -893,7 +894,7 @@ __global__ __launch_bounds__(FIN_THREADS) void fused_finish_kernel(FinishArgs g_
       const double inv = 1.0 / g.Bu;
       if (g.mode == 0)   // critic: quirk -> mean(c^2) + 2 mean(c) mean(r) + mean(r^2); else mean((r+c)^2)
         *g.loss_out = (float)(g.quirk ? red[1][0] * inv + 2.0 * (red[0][0] * inv) * (red[2][0] * inv) + red[3][0] * inv
-                                      : red[4][0] * inv);
+                                      : red[4][0] * inv + (g.loss_add ? (double)*g.loss_add : 0.0));
       else               // actor: -mean(q)
         *g.loss_out = (float)(-red[0][0] * inv);
     }
@@ -1134,11 +1135,12 @@ static int ensure_slab(Mlp* M, size_t floats) {
 // Slab reduction (nslab > 0) and/or the parameter update (apply): ADAM on M with M->adam_* hyper-parameters,
 // Polyak into Mt, refresh of both padded images.  One launch.
 static int launch_finish(Mlp* M, Mlp* Mt, const float* slabs, int nslab, int MT, double grad_scale, int mode,
-                         int Bu, int quirk, void* loss_dev, const AdamPolyak* ap) {
+                         int Bu, int quirk, void* loss_dev, const AdamPolyak* ap, const void* loss_add = nullptr) {
   FinishArgs g{};
   g.slabs = slabs; g.nslab = nslab; g.K0 = M->dims[0]; g.H = M->dims[1]; g.MT = MT;
   g.grads = M->grads.as<float>(); g.scale = (float)grad_scale; g.mode = mode; g.Bu = Bu; g.quirk = quirk;
   g.loss_out = (float*)loss_dev;
+  g.loss_add = (const float*)loss_add;
   g.apply = ap != nullptr;
   g.prio = env_prio("PDEC_PRIO_MFMA", 2);
   if (ap) {
@@ -1235,7 +1237,7 @@ int fused_adam_polyak(Mlp* M, Mlp* Mt, const AdamPolyak& ap) {
 
 int fused_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const void* a, const void* r, const void* t,
                        const void* sn, int Bu, double gamma, int quirk, double grad_scale, void* loss_dev,
-                       const AdamPolyak* apply) {
+                       const AdamPolyak* apply, const void* loss_add) {
   int rc;
   if ((rc = ensure_prepped(C)) || (rc = ensure_prepped(At)) || (rc = ensure_prepped(Ct))) return rc;
   const int mt = mt_of(C->dims[1]), mta = mt_of(A->dims[1]);
@@ -1263,7 +1265,8 @@ int fused_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const vo
   else if (mt == 2 && mta == 2) rc = launch_critic<2, 2>(C, g, grid);
   else rc = launch_critic<2, 1>(C, g, grid);
   if (rc) return rc;
-  return launch_finish(C, apply ? Ct : nullptr, C->fslab.as<float>(), grid, mt, grad_scale, 0, Bu, quirk, loss_dev, apply);
+  return launch_finish(C, apply ? Ct : nullptr, C->fslab.as<float>(), grid, mt, grad_scale, 0, Bu, quirk, loss_dev, apply,
+                       loss_add);
 }
 
 int fused_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,

@@ -573,6 +573,7 @@ struct Finish2Args {
   float scale;
   int mode, Bu, quirk;
   float* loss_out;
+  const float* loss_add;      // != null: device scalar added to the critic loss (reward groups, reward_group_route)
   int apply;
   float *p, *m, *v, *pt;
   double eta, b1, b2, eps, omb1p, omb2p;   // omb*p = 1 - beta^t: filled in by the kernels from `bp` (device resident)
@@ -664,7 +665,7 @@ __global__ __launch_bounds__(1024) void finish2_kernel(Finish2Args g_in) {
       const double inv = 1.0 / g.Bu;
       if (g.mode == 0)
         *g.loss_out = (float)(g.quirk ? red[1][0] * inv + 2.0 * (red[0][0] * inv) * (red[2][0] * inv) + red[3][0] * inv
-                                      : red[4][0] * inv);
+                                      : red[4][0] * inv + (g.loss_add ? (double)*g.loss_add : 0.0));
       else
         *g.loss_out = (float)(-red[0][0] * inv);
     }
@@ -824,11 +825,12 @@ static int dispatch2(Mlp* M, const Fused2Args& g, int grid, bool actor_pass, int
 }
 
 static int launch_finish2(Mlp* M, Mlp* Mt, int nslab, int MT, int nR, double grad_scale, int mode, int Bu, int quirk,
-                          void* loss_dev, const AdamPolyak* ap) {
+                          void* loss_dev, const AdamPolyak* ap, const void* loss_add = nullptr) {
   Finish2Args g{};
   g.slabs = M->fslab.as<float>(); g.nslab = nslab; g.K0 = M->dims[0]; g.H = M->dims[1]; g.MT = MT; g.nR = nR;
   g.grads = M->grads.as<float>(); g.scale = (float)grad_scale; g.mode = mode; g.Bu = Bu; g.quirk = quirk;
   g.loss_out = (float*)loss_dev;
+  g.loss_add = (const float*)loss_add;
   g.apply = ap != nullptr;
   if (ap) {
     int rcb = bp_begin(M, ap->b1, ap->b2, &g.bp);
@@ -918,7 +920,7 @@ int launch_rmean(Mlp* C, const float* r, int n, float** out) {
 
 int fused2_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const void* a, const void* r, const void* t,
                         const void* sn, int Bu, double gamma, int quirk, double grad_scale, void* loss_dev,
-                        const AdamPolyak* apply) {
+                        const AdamPolyak* apply, const void* loss_add) {
   const int mt = mt2_of(C->dims[1]), mta = mt2_of(A->dims[1]), nR = nr_of(C->dims[0]);
   int tpw = 8;
   const int grid = grid2_of(Bu, &tpw);
@@ -940,7 +942,7 @@ int fused2_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const v
   C->rbar_ext = nullptr;
   int rc = dispatch2(C, g, grid, false, mt, mta);
   if (rc) return rc;
-  return launch_finish2(C, apply ? Ct : nullptr, grid, mt, nR, grad_scale, 0, Bu, quirk, loss_dev, apply);
+  return launch_finish2(C, apply ? Ct : nullptr, grid, mt, nR, grad_scale, 0, Bu, quirk, loss_dev, apply, loss_add);
 }
 
 int fused2_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,

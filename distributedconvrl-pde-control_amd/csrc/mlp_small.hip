@@ -1189,6 +1189,7 @@ enum SmallKernelId {
   SK_S2_10_9_4,
   SK_S2_13_12_4,
   SK_S2_16_15_4,
+  SK_BATCHED,         // no kernel (not in the name table): reward groups that split the minibatch, served by the batched update
 };
 static const char* const small_kernel_names[] = {
     "ddpg_small_kernel",
@@ -1214,9 +1215,17 @@ struct SmallPlan {
 };
 
 // the kernel a call launches, its block and its dynamic LDS -- or the error the call raises.  Reads the env switches
-// PDEC_SMALL_GENERIC / PDEC_SMALL_OWN / PDEC_SMALL_SPLIT per call (the identity tests switch them).
-static int small_plan(const Mlp* A, const Mlp* C, int loops, int Bu, float rho, bool sampling, SmallPlan* pl) {
+// PDEC_SMALL_GENERIC / PDEC_SMALL_OWN / PDEC_SMALL_SPLIT per call (the identity tests switch them).  A broadcast target
+// (quirk) whose reward groups (pdec_ddpg_set_reward_groups) split the minibatch -- 2 <= g, g L < Bu -- has no small kernel:
+// SK_BATCHED, which the call refuses (the caller updates through pdec_ddpg_update_async); g = 1 is the diagonal target and
+// g L >= Bu the whole-minibatch broadcast, both served by the small kernels as they are.
+static int small_plan(const Mlp* A, const Mlp* C, int loops, int Bu, float rho, bool sampling, int quirk, SmallPlan* pl) {
   PDEC_REQUIRE(loops >= 1 && Bu >= 1 && Bu <= 16, "pdec_ddpg_update_small: needs 1 <= Bu <= 16 (got %d)", Bu);
+  if (quirk && C->rg_g >= 2 && (int64_t)C->rg_g * C->rg_L < Bu) {
+    *pl = SmallPlan{};
+    pl->id = SK_BATCHED;
+    return PDEC_OK;
+  }
   PDEC_REQUIRE(A->L <= SM_MAXL && C->L <= SM_MAXL, "small update: at most %d layers", SM_MAXL);
   const int ns = A->dims[0];
   int maxw = 1;
@@ -1317,7 +1326,11 @@ static int ddpg_update_small_impl(pdec_handle hA, pdec_handle hC, pdec_handle hA
   PDEC_REQUIRE(state_trace && action_trace && reward_trace && terminal_trace && (smp || (idx_s && idx_rt && idx_sn)),
                "pdec_ddpg_update_small: null argument");
   SmallPlan pl{};
-  if ((rc = small_plan(A, C, loops, Bu, (float)rho, smp != nullptr, &pl))) return rc;
+  if ((rc = small_plan(A, C, loops, Bu, (float)rho, smp != nullptr, quirk, &pl))) return rc;
+  PDEC_REQUIRE(pl.id != SK_BATCHED,
+               "pdec_ddpg_update_small: reward groups g = %d, L = %d split the minibatch of %d; update through pdec_ddpg_update_async",
+               C->rg_g, C->rg_L, Bu);
+  if (quirk && C->rg_g == 1) quirk = 0;            // groups of one column: the diagonal target
   const int ns = A->dims[0], na = A->dims[A->L];
   SmallArgs g{};
   if ((rc = fill_net(g.A, A, At)) || (rc = fill_net(g.C, C, Ct))) return rc;
@@ -1386,8 +1399,9 @@ extern "C" int pdec_debug_small_update_kernel(pdec_handle hA, pdec_handle hC, pd
   PDEC_REQUIRE(name && name_len > 0 && lds_bytes, "pdec_debug_small_update_kernel: null argument");
   if ((rc = small_nets(hA, hC, hAt, hCt, &A, &C, &At, &Ct))) return rc;
   SmallPlan pl{};
-  if ((rc = small_plan(A, C, loops, Bu, (float)rho, sampling != 0, &pl))) return rc;
-  if (pl.id == SK_GENERIC) snprintf(name, name_len, "ddpg_small_kernel/lds_params=%d", pl.lds_params);
+  if ((rc = small_plan(A, C, loops, Bu, (float)rho, sampling != 0, 1, &pl))) return rc;   // as a broadcast-target call would
+  if (pl.id == SK_BATCHED) snprintf(name, name_len, "generic_path/reward_groups");
+  else if (pl.id == SK_GENERIC) snprintf(name, name_len, "ddpg_small_kernel/lds_params=%d", pl.lds_params);
   else snprintf(name, name_len, "%s", small_kernel_names[pl.id]);
   *lds_bytes = (int64_t)pl.lds;
   return PDEC_OK;

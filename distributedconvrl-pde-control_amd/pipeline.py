@@ -137,7 +137,11 @@ class TrainPipeline:
             self.state0 = empty(env._sshape, **kw)
         # the reference's reward broadcast (quirk) needs the batch-mean reward: reduced on the env stream
         # right behind the env step instead of by every workgroup of the critic pass
-        self.pre_rbar = bool(self.policy.quirk) and dt == torch.float32 and not self.use_replay
+        # (not with reward groups: the critic call reduces the group means itself, CustomDDPGPolicy.reward_group)
+        self.pre_rbar = (bool(self.policy.quirk) and dt == torch.float32 and not self.use_replay
+                         and self.policy.reward_group is None)
+        # interleave of the reward groups: the fresh batch holds column b A + a, the replay's minibatch is drawn at random
+        self.reward_interleave = 1 if self.use_replay else A
         # ... and for the fused KS step + 3-layer fused critic without any extra launch: the env step leaves one reward sum
         # per workgroup, the critic pass adds them
         self.rpart, self.n_rpart = None, 0
@@ -405,9 +409,9 @@ class TrainPipeline:
                 if self.ar_off_chain:
                     self._update_ar_off_chain(k, batch, between_halves, use_stop)
                 elif kick or (self.act_in_place and not self.serial):
-                    pol.update(batch, before_actor_half=between_halves)
+                    pol.update(batch, before_actor_half=between_halves, interleave=self.reward_interleave)
                 else:
-                    pol.update(batch)
+                    pol.update(batch, interleave=self.reward_interleave)
             if self.ar_off_chain and batch is not None:
                 pass                                    # (the completion event was recorded on the side stream)
             elif use_stop:
@@ -425,7 +429,7 @@ class TrainPipeline:
         next acting kernel (env stream) and the next actor pass (update stream) wait for."""
         pol, lib, L = self.policy, self.lib, _lib
         A, At = pol.behavior_actor.model, pol.target_actor.model
-        pol.update_critic_half(batch)
+        pol.update_critic_half(batch, self.reward_interleave)
         between_halves()
         red_on_launch = use_stop and lib.pdec_mlp_set_reduce_event(A.handle, self.ev_red.h) == 0
         pol.actor_grads(batch)                                      # (records a reduce event its launches did not carry)
@@ -560,7 +564,7 @@ class TrainPipeline:
         pol = self.policy
         return (float(pol.act_noise), float(pol.act_limit), float(pol.behavior_actor.optimizer.eta),
                 float(pol.behavior_critic.optimizer.eta), float(pol.y), float(pol.rho_effective), int(bool(pol.quirk)),
-                bool(self.kick_env_after_critic), int(self.noise_seed))
+                pol.reward_group, bool(self.kick_env_after_critic), int(self.noise_seed))
 
     def _check_key(self):
         """a noise / learning-rate schedule (or load_agent restoring act_noise) changed a frozen scalar: drop the recorded

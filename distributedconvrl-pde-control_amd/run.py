@@ -224,6 +224,7 @@ def _fast_issue(lib, pol, tr, env, agent, logs, T, cols, A, sync, seq):
     f0, f1 = sync.data_ptr(), sync.data_ptr() + 8
     noise, limit = float(pol.act_noise), float(pol.act_limit)
     loops, Bu = int(pol.update_loops), int(pol.batch_size)
+    pol.set_reward_interleave(1)          # the raw small-update calls below sample their minibatches from the replay
     gamma, rho, quirk = float(pol.y), pol.rho_effective, int(pol.quirk)
     eta_a, eta_c = float(pol.behavior_actor.optimizer.eta), float(pol.behavior_critic.optimizer.eta)
     pL = pol._losses.data_ptr()

@@ -400,6 +400,23 @@ int pdec_env_set_part_streams(pdec_handle env, void* const* hip_streams, int n);
 int pdec_ddpg_set_reward_partials(pdec_handle critic, const void* partial_sums, int n);
 int pdec_ddpg_set_reward_mean(pdec_handle critic, const void* mean_dev);
 
+/* Reward groups: the reference's broadcast target (quirk = 1) read at batch scale.  The reference updates on minibatches of
+ * g = batch_size transitions (KSSetup.jl:66: 3); an update of Bu columns is taken as the mean of Bu / g such minibatch losses.
+ * Column c belongs to group (c / (g L)) L + c % L -- with interleave L = A (columns c = b A + a of B trajectories of A
+ * actuators) group members are actuator a of g consecutive trajectories, with L = 1 g consecutive columns.  With r_bar(c)
+ * the mean reward of c's group (summed in member order, the same in every group) and d_c = gamma (1 - t_c) q'_c - q_c:
+ *   dL/dq_c = -(2 / Bu) (r_bar(c) + d_c),   loss = mean(d^2) + 2 mean_c(d_c r_bar(c)) + mean(r^2),
+ * the mean over groups of the reference's per-group loss mean_ij (r_j + d_i)^2.  Bu % (g L) == 0 is required
+ * (PDEC_E_INVALID otherwise).  g = 1 is the diagonal target (quirk = 0) and g L >= Bu the whole-batch broadcast: both run
+ * the existing passes unchanged.  Otherwise one extra launch ahead of the critic pass, on the critic's stream, writes the
+ * per-column group means and the loss term mean_c (r_c - r_bar(c))^2, and the pass runs as the diagonal target on those
+ * means; the whole-batch hand-overs (pdec_ddpg_set_reward_mean / _partials) are not read.  Sticky on the critic handle,
+ * g = 0 switches it off; it applies to pdec_ddpg_critic_grads, pdec_ddpg_update(_async), the critic half and the split
+ * multi-rank sequence, with fp32 and fp64 critics.  pdec_ddpg_update_small(_rng) serve g = 1 and g L >= Bu and refuse the
+ * rest.  Groups that never span ranks (B_local % g == 0 with L = A) make N ranks compute one rank's gradient on the
+ * concatenated batch. */
+int pdec_ddpg_set_reward_groups(pdec_handle critic, int g, int L);
+
 /* the same with pde_sample (src/PDEagent.jl:317-321) INSIDE the kernel: draw k = loop * Bu + column is word k % 4 of the
  * Philox block (seed; counter offset + k / 4), ind = (word * (n_valid - stride)) >> 32, logical index
  * max(0, n_rt - capacity) + ind, slots (lg mod (capacity + stride), lg mod capacity, (lg + stride) mod (capacity + stride)).

@@ -40,7 +40,9 @@ int pdec_debug_spin_us(void* hip_stream, double us);
  * (sampling != 0) would launch for these four networks, `loops`, `Bu` and `rho`, with the env switches as they are now --
  * launches nothing.  Writes the instantiation's name (e.g. "ddpg_small2f_kernel<2,1,3,1,3>", "ddpg_small_kernel/lds_params=0")
  * to name[name_len] and the dynamic LDS bytes of the launch, slot table included, to *lds_bytes; or returns the error the call
- * would return. */
+ * would return.  Reported for a broadcast-target call (quirk = 1): "generic_path/reward_groups" (0 bytes) when the critic's
+ * reward groups split the minibatch (pdec_ddpg_set_reward_groups, 2 <= g, g L < Bu) -- the call refuses that case and the
+ * batched update (pdec_ddpg_update_async) serves it. */
 int pdec_debug_small_update_kernel(pdec_handle actor, pdec_handle critic, pdec_handle target_actor, pdec_handle target_critic,
                                    int loops, int Bu, double rho, int sampling, char* name, int name_len, int64_t* lds_bytes);
 

@@ -193,14 +193,23 @@ mutable struct HipMLP
     acts::Vector{Int32}
 end
 nparams(m::HipMLP) = sum(m.dims[i] * m.dims[i + 1] + m.dims[i + 1] for i in 1:length(m.acts))
-function HipMLP(chain::Flux.Chain; max_cols = 1)        # upload an existing Flux Chain(Dense...)
+# reward_group (critic only): the update's reward broadcast per group of that many columns instead of over the whole batch
+# (pdec_ddpg_set_reward_groups in include/pdeconv.h; 0 = whole batch, the reference as written); reward_interleave: the
+# groups' column stride L (1 for sampled minibatches)
+function HipMLP(chain::Flux.Chain; max_cols = 1, reward_group = 0, reward_interleave = 1)   # upload an existing Flux Chain(Dense...)
     dims = Int32[size(chain[1].weight, 2); [size(l.weight, 1) for l in chain]...]
     acts = Int32[l.σ === relu ? 1 : l.σ === tanh ? 2 : 0 for l in chain]
     flat = reduce(vcat, [vcat(vec(l.weight), l.bias) for l in chain])      # Flux.params order, W column-major
     h = Ref{UInt64}(0)
     check(ccall((:pdec_mlp_create, LIB), Cint, (Ref{UInt64}, Cint, Cint, Ptr{Int32}, Ptr{Int32}, Ptr{Cvoid}, Cint),
                 h, F32, length(acts), dims, acts, Float32.(flat), max_cols))
-    HipMLP(h[], dims, acts)
+    m = HipMLP(h[], dims, acts)
+    reward_group > 0 && set_reward_groups!(m, reward_group, reward_interleave)
+    m
+end
+# sticky on the critic: every later update through it broadcasts each column's group-mean reward (g = 0: off)
+function set_reward_groups!(critic::HipMLP, g::Integer, interleave::Integer = 1)
+    check(ccall((:pdec_ddpg_set_reward_groups, LIB), Cint, (UInt64, Cint, Cint), critic.h, g, interleave))
 end
 function unflatten(m::HipMLP, flat::Vector{Float32})
     out, o = Any[], 0
