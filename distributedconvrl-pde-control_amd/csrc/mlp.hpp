@@ -111,6 +111,8 @@ int fused_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const vo
 int fused_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
                       const AdamPolyak* apply);
 int fused_adam_polyak(Mlp* M, Mlp* Mt, const AdamPolyak& ap);
+// flat parameters of the published image the next acting kernel reads (fw_pub[pub]), enqueued on `stream`
+int fused_unpack_published(Mlp* A, float* flat_out, hipStream_t stream);
 // ctr_cur != null: the noise offset is *ctr_cur (+ offset) and one thread writes *ctr_next = that + ctr_inc
 int fused_policy_act(Mlp* A, const void* state, int cols, double act_noise, double act_limit, int learning,
                      uint64_t seed, uint64_t offset, void* actions_out, const uint64_t* ctr_cur = nullptr,

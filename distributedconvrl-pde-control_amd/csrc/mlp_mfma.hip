@@ -78,6 +78,23 @@ __global__ void prep_fused_kernel(const float* __restrict__ p, float* __restrict
   out[i] = v;
 }
 
+// the inverse of prep_fused_kernel: flat parameters [W1, b1, W2, b2, W3, b3] out of a padded image (W2 from its row-major
+// block); the episode ledger's snapshot of the image an acting kernel read (pdec_ledger_snapshot)
+__global__ void unpack_fused_kernel(const float* __restrict__ img, float* __restrict__ p, FNet f) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int K0 = f.K0, H = f.H;
+  const int pb1 = H * K0, pW2 = pb1 + H, pb2 = pW2 + H * H, pW3 = pb2 + H, pb3 = pW3 + H;
+  if (i > pb3) return;
+  float v;
+  if (i < pb1) v = img[f.oW1 + (i / K0) * LDW1 + i % K0];
+  else if (i < pW2) v = img[f.ob1 + (i - pb1)];
+  else if (i < pb2) v = img[f.oW2 + ((i - pW2) / H) * f.LDW + (i - pW2) % H];
+  else if (i < pW3) v = img[f.ob2 + (i - pb2)];
+  else if (i < pb3) v = img[f.ow3 + (i - pW3)];
+  else v = img[f.ob3];
+  p[i] = v;
+}
+
 // ------------------------------------------------------------------ device building blocks
 // LDS image of the "small" part of a net: W1 [HP][LDW1], b1 [HP], b2 [HP], w3 [HP], b3 [4]
 struct SmallLds {
@@ -1192,6 +1209,18 @@ static int launch_finish(Mlp* M, Mlp* Mt, const float* slabs, int nslab, int MT,
     bp_done(M);
     flip(M->pub);
   }
+  return PDEC_OK;
+}
+
+int fused_unpack_published(Mlp* A, float* flat_out, hipStream_t stream) {
+  PDEC_REQUIRE(fused_net_supported(A), "fused_unpack_published: not a fused 3-layer network");
+  int rc = ensure_prepped(A);
+  if (rc) return rc;
+  FNet f = make_fnet_layout(A->dims[0], A->dims[1]);
+  PDEC_REQUIRE(A->nparams == f.H * f.K0 + f.H + f.H * f.H + f.H + f.H + 1, "fused_unpack_published: parameter count");
+  hipLaunchKernelGGL(unpack_fused_kernel, dim3((A->nparams + 255) / 256), dim3(256), 0, stream, A->fw_pub[A->pub].as<float>(),
+                     flat_out, f);
+  PDEC_HIP(hipGetLastError());
   return PDEC_OK;
 }
 

@@ -181,6 +181,61 @@ __global__ void random_init_kernel(T* __restrict__ y, int N, int nsp, int nsin, 
   }
 }
 
+// The 2-D Keller-Segel setup (setups/keller_segel2d.py generate_random_init: KellerSegelSetup.jl:373-384 with the sine sums
+// taken along x and along y): per species s the coefficients a[s][0 .. nsx + nsy) of the same Philox convention (nc = 2 (nsx +
+// nsy) uniforms, normalised over all nc),
+//   y0[s](x_i, y_j) = 1 + sum_{k=1..nsx} a[s][k-1] sin(k x_i / fx) + sum_{k=1..nsy} a[s][nsx+k-1] sin(k y_j / fy),
+// x_i = i dx (i = 1..nx), y_j = j dx, fx = 2 pi Lx / 22, fy = 2 pi (ny dx) / 22.  One workgroup per trajectory: the two
+// profiles of both species go to LDS ([2][nx] | [2][ny], dynamic), then the [ny][nx][2] field is written.
+template <class T>
+__global__ void random_init_2d_kernel(T* __restrict__ y, int nx, int ny, int nsx, int nsy, double dx, double fx, double fy,
+                                      uint64_t seed, uint64_t offset) {
+  __shared__ double a[RI_MAXC];
+  extern __shared__ double prof[];     // px [2][nx], py [2][ny]
+  const int b = blockIdx.x, tid = threadIdx.x, per = nsx + nsy, nc = 2 * per, nblk = (nc + 3) / 4;
+  if (tid == 0) {
+    double nrm = 0;
+    for (int blk = 0; blk < nblk; ++blk) {
+      const uint64_t ctr = offset + (uint64_t)b * nblk + blk;
+      uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
+      philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+      for (int i = 0; i < 4 && 4 * blk + i < nc; ++i) {
+        const double v = 2.0 * (((double)c[i] + 0.5) * (1.0 / 4294967296.0)) - 1.0;
+        a[4 * blk + i] = v;
+        nrm += v * v;
+      }
+    }
+    nrm = sqrt(nrm);
+    for (int i = 0; i < nc; ++i) a[i] /= nrm;
+  }
+  __syncthreads();
+  double* px = prof;
+  double* py = prof + 2 * nx;
+  for (int t = tid; t < 2 * nx; t += blockDim.x) {
+    const int sp = t / nx, i = t - sp * nx;
+    const double x = (i + 1) * dx;
+    double v = 0;
+    for (int k = 1; k <= nsx; ++k) v += a[sp * per + k - 1] * sin(k * x / fx);
+    px[t] = v;
+  }
+  for (int t = tid; t < 2 * ny; t += blockDim.x) {
+    const int sp = t / ny, j = t - sp * ny;
+    const double yy = (j + 1) * dx;
+    double v = 0;
+    for (int k = 1; k <= nsy; ++k) v += a[sp * per + nsx + k - 1] * sin(k * yy / fy);
+    py[t] = v;
+  }
+  __syncthreads();
+  const size_t plane = (size_t)nx * ny;
+  T* yb = y + (size_t)b * plane * 2;
+  for (size_t t = tid; t < plane * 2; t += blockDim.x) {
+    const int sp = (int)(t & 1);
+    const size_t cell = t >> 1;
+    const int j = (int)(cell / nx), i = (int)(cell - (size_t)j * nx);
+    yb[t] = (T)((1.0 + px[sp * nx + i]) + py[sp * ny + j]);
+  }
+}
+
 // device-scope events: created without the system-scope fence of a default HIP event (hipEventDisableSystemFence),
 // so a record / wait pair between two streams of the SAME device does not flush and invalidate the caches towards the
 // host -- the cross-stream hand-offs of the control step sit on its critical path
@@ -398,8 +453,26 @@ int pdec_env_random_init(pdec_handle henv, uint64_t seed, uint64_t offset, void*
     nsp = 1; nsin = 8; fdiv = two_pi; base = 0.0; l2 = 30.0;                                  // KSSetup.jl:288-298
   } else if (c.pde_kind == PDEC_PDE_KSEG_RK4) {
     nsp = 2; nsin = (int)ceil(c.Lx / 3.0); fdiv = two_pi * (c.Lx / 22.0); base = 1.0; l2 = 0.0;   // KellerSegelSetup.jl:373-384
+  } else if (c.pde_kind == PDEC_PDE_KSEG2D_RK4) {
+    const int nx = c.N, ny = c.Ny;
+    const double dx = c.Lx / nx, Ly = ny * dx;
+    const int nsx = (int)ceil(c.Lx / 3.0), nsy = (int)ceil(Ly / 3.0);
+    PDEC_REQUIRE(2 * (nsx + nsy) <= RI_MAXC, "pdec_env_random_init: %d sine coefficients exceed the kernel's table",
+                 2 * (nsx + nsy));
+    const size_t lds = (size_t)2 * (nx + ny) * sizeof(double);
+    PDEC_REQUIRE(nx >= 1 && ny >= 1 && lds <= 60 * 1024, "pdec_env_random_init: %d x %d grid too large for the profiles", nx, ny);
+    const double fx = two_pi * (c.Lx / 22.0), fy = two_pi * (Ly / 22.0);
+    ProfScope ps(E, "env_random_init");
+    if (c.dtype == PDEC_F64)
+      hipLaunchKernelGGL((random_init_2d_kernel<double>), dim3(c.B), dim3(256), lds, E->stream, (double*)y0_out, nx, ny, nsx, nsy,
+                         dx, fx, fy, seed, offset);
+    else
+      hipLaunchKernelGGL((random_init_2d_kernel<float>), dim3(c.B), dim3(256), lds, E->stream, (float*)y0_out, nx, ny, nsx, nsy,
+                         dx, fx, fy, seed, offset);
+    PDEC_HIP(hipGetLastError());
+    return PDEC_OK;
   } else {
-    set_error("pdec_env_random_init: 1-D setups only (the fluid initialiser is pdec_fluid_ic)");
+    set_error("pdec_env_random_init: KS, Keller-Segel and 2-D Keller-Segel only (the fluid initialiser is pdec_fluid_ic)");
     return PDEC_E_INVALID;
   }
   PDEC_REQUIRE(nsp * nsin <= RI_MAXC, "pdec_env_random_init: %d sine coefficients exceed the kernel's table", nsp * nsin);

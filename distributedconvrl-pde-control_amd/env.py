@@ -277,14 +277,21 @@ class PDEenv:
         return out
 
     def random_init(self, seed, offset, out=None):
-        """generate_random_init() of the 1-D setups on the device (pdec_env_random_init; scripts/KS/setup/KSSetup.jl:288-298,
-        scripts/Keller-Segel/setup/KellerSegelSetup.jl:373-384): fills `out` (default: a new tensor shaped like env.y) from
-        the Philox stream (seed, offset) and returns the number of counters consumed"""
+        """generate_random_init() of the KS, Keller-Segel and 2-D Keller-Segel setups on the device (pdec_env_random_init;
+        scripts/KS/setup/KSSetup.jl:288-298, scripts/Keller-Segel/setup/KellerSegelSetup.jl:373-384, and its 2-D form in
+        setups/keller_segel2d.py): fills `out` (default: a new tensor shaped like env.y) from the Philox stream
+        (seed, offset) and returns the number of counters consumed"""
         out = torch.empty_like(self.y) if out is None else out
         _lib.check(self.lib.pdec_env_random_init(self._h, int(seed), int(offset), _lib.ptr(out)))
         self._last_random_init = out
-        nc = 8 if self.setup.y_shape == (self.setup.nx,) else 2 * int(np.ceil(self.setup.Lx / 3))
-        return self.B * ((nc + 3) // 4)
+        return self.B * ((self.random_init_coefficients() + 3) // 4)
+
+    def random_init_coefficients(self):
+        """sine coefficients per trajectory of random_init (each takes one uniform of the Philox stream)"""
+        st = self.setup
+        if getattr(st, "is_kseg2d", False):
+            return 2 * (int(np.ceil(st.Lx / 3)) + int(np.ceil(st.ny * st.dx / 3)))
+        return 8 if st.y_shape == (st.nx,) else 2 * int(np.ceil(st.Lx / 3))
 
     # ---- reset!(env), src/PDEenv.jl:183-193
     def reset(self):

@@ -30,7 +30,14 @@ captured ONCE into HIP graphs (pdec_capture_begin / _end) and replayed with one 
 calls per step.  Inside a chunk the cross-stream events above become graph edges; a chunk forks the update branch off
 the env stream at its first step and joins it at its last.  The first and the last step of an episode
 (initial-condition pointers, time-out terminal flags; te / dt + 1 = 51 steps in scripts/KS/KS22) are issued eagerly.  Eager and replayed runs enqueue the same kernels with the same arguments and are
-bit-identical (tests/test_gpu_agent.py)."""
+bit-identical (tests/test_gpu_agent.py).
+
+Episode bookkeeping (opt-in; PDEhook's, src/PDEhook.jl:42-97): `log_episodes` keeps an episode ledger on the device -- one
+small launch behind every env step adds the step's per-trajectory mean reward to an fp64 running return (a library call like
+the others, so recorded steps and graphs carry it), and the episode's last step, which is eager, snapshots the parameters
+its acting kernel read, writes the episode's row and makes the hook's best-episode decision without a read-back.
+`random_init` draws a new initial field for every episode at its (eager) first step, on the env stream, before the acting
+kernel reads it."""
 import ctypes as C
 import os
 
@@ -75,10 +82,25 @@ class _TorchEvent:
         stream.wait_event(self.ev)
 
 
+class _Ledger:
+    """the episode ledger of a pipeline (pdec_ledger_create), released with it"""
+
+    def __init__(self, lib, env_handle, actor_handle, capacity):
+        self.lib, self.h = lib, _lib.Handle()
+        _lib.check(lib.pdec_ledger_create(C.byref(self.h), env_handle, actor_handle, int(capacity)))
+
+    def __del__(self):
+        try:
+            self.lib.pdec_destroy(self.h)
+        except Exception:
+            pass
+
+
 class TrainPipeline:
     def __init__(self, env, agent, lag=2, episode_steps=51, stream_env=None, stream_upd=None, use_graphs=True,
                  chunks=(24, 6, 1), use_replay=False, noise_seed=1234, kick_env_after_critic=None, stream_ar=None,
-                 ar_off_chain=None):
+                 ar_off_chain=None, log_episodes=0, min_best_episode=0, random_init=False, init_seed=0, init_rng=None,
+                 init_rank=(0, 1)):
         """env: PDEenv on `stream_env`; agent: create_agent(..., stream=stream_upd).  lag: the update of step k trains on
         the transition of step k - lag (>= 1).  episode_steps: lock-stepped episodes of that many control steps (0: one
         endless episode): the last transition is terminal (done = time >= te, src/PDEenv.jl:227) and the next step starts
@@ -87,7 +109,17 @@ class TrainPipeline:
         (:317-340) instead of the B * A fresh ones (eager only).  stream_ar: a third stream for the gradient all-reduce + the
         actor's ADAM launch of a data-parallel run (module docstring); ar_off_chain: None = whenever that order is legal
         (split update, policy-gradient-only exchange, frozen targets, stream_ar given), False = keep the collective on the update
-        stream, True = insist (raises when illegal)."""
+        stream, True = insist (raises when illegal).
+
+        log_episodes = N > 0: the episode ledger (module docstring) keeps the last N episodes' per-trajectory returns and
+        blow-up bits (episode_returns(), rewards) and the best actor (best_actor(), bestreward, bestepisode: an episode whose
+        1-based number is >= min_best_episode and whose batch-mean return is >= every earlier such one, PDEhook.jl:65-76; a
+        NaN mean is never chosen and does not block later episodes).  Needs episode_steps > 0.  With an active reducer the
+        returns are this rank's trajectories and the best actor is not tracked.  An episode cut by reset_from() is not logged.
+        random_init: every episode starts from a new field -- KS / Keller-Segel / 2-D Keller-Segel: env.random_init(init_seed,
+        off), episode e of rank r of W (init_rank = (r, W)) drawing from off = (e W + r) * n with n = B ceil(nc / 4) the
+        counters of one call, so W ranks of B trajectories draw together what one rank of W B draws ((0, 1): PDEhook's
+        advance); the fluid: setup.random_init_device(env, init_rng).  A field given to reset_from() is used as it is."""
         self.env, self.agent, self.policy = env, agent, agent.policy
         self.lib = env.lib
         self.LAG = max(1, int(lag))
@@ -219,7 +251,56 @@ class TrainPipeline:
         self._recapture = False
         self._captured = False
         self.n_graph_launches = self.n_eager_steps = 0
+        self._setup_episodes(log_episodes, min_best_episode, random_init, init_seed, init_rng, init_rank)
         self.reset_from(env.y0)
+        self._keep_y0 = False
+
+    def _setup_episodes(self, log_episodes, min_best_episode, random_init, init_seed, init_rng, init_rank):
+        env = self.env
+        self.log_episodes, self.min_best_episode = int(log_episodes), int(min_best_episode)
+        self.ledger, self.track_best, self.n_episodes = None, False, 0
+        if self.log_episodes < 0:
+            raise _lib.PdecError(f"TrainPipeline(log_episodes={log_episodes}): a capacity >= 0")
+        if self.log_episodes > 0:
+            if self.E <= 0:
+                raise _lib.PdecError("TrainPipeline(log_episodes=...) needs episodes: episode_steps > 0")
+            if self.multi_rank and self.min_best_episode != 0:
+                raise _lib.PdecError("TrainPipeline: best-actor tracking (min_best_episode) is not available with an active "
+                                     "reducer: each rank would choose on its own trajectories")
+            self.track_best = not self.multi_rank
+            self.ledger = _Ledger(self.lib, env.handle, self.actor.handle if self.track_best else 0, self.log_episodes)
+        self.random_init = bool(random_init)
+        self.init_seed = int(init_seed)
+        self.init_rng = init_rng if init_rng is not None else np.random.default_rng(0)
+        r, W = (int(v) for v in init_rank)
+        if not 0 <= r < W:
+            raise _lib.PdecError(f"TrainPipeline(init_rank={tuple(init_rank)}): rank r of W needs 0 <= r < W")
+        self.init_rank = (r, W)
+        self.init_offsets = []        # Philox offset of every initial field drawn (KS / Keller-Segel)
+        self._init_ep = 0
+        if self.random_init:
+            if env.is_fluid:
+                if not hasattr(env.setup, "random_init_device"):
+                    raise _lib.PdecError("TrainPipeline(random_init=True): the setup has no random_init_device")
+            elif not getattr(env.setup, "device_random_init", True):
+                raise _lib.PdecError("TrainPipeline(random_init=True): the setup has no device initialiser")
+            if env.y0.data_ptr() == env.y.data_ptr():
+                env.y0 = env.y0.clone()
+
+    def _draw_init(self):
+        """a new initial field into env.y0 and its features into state0, on the env stream (the first step of an episode)"""
+        env = self.env
+        with torch.cuda.stream(self.s_env):
+            if env.is_fluid:
+                env.y0.copy_(env.setup.random_init_device(env, self.init_rng))
+            else:
+                r, W = self.init_rank
+                n = env.B * ((env.random_init_coefficients() + 3) // 4)
+                off = (self._init_ep * W + r) * n
+                env.random_init(self.init_seed, off, out=env.y0)
+                self.init_offsets.append(off)
+            _lib.check(self.lib.pdec_featurize(env.handle, _lib.ptr(env.y0), None, _lib.ptr(self.state0)))
+        self._init_ep += 1
 
     def set_ar_order(self, off_chain):
         """switch between the two places of the gradient all-reduce (module docstring) in a running pipeline: drains the
@@ -240,6 +321,9 @@ class TrainPipeline:
     def reset_from(self, y0):
         """(re)start: the next step is the first of an episode from initial condition y0 ([B, ...] device tensor)"""
         env = self.env
+        self._keep_y0 = True          # (random_init: this episode starts from y0, the next ones draw again)
+        if self.ledger is not None and self.tick > self.ep_start:
+            _lib.check(self.lib.pdec_ledger_discard(self.ledger.h))      # the cut episode is not logged
         with torch.cuda.stream(self.s_env):
             if y0.data_ptr() != env.y0.data_ptr():
                 env.y0.copy_(y0)
@@ -304,6 +388,9 @@ class TrainPipeline:
                 self.ev_upd[(k - 1) % 2].wait(self.s_env)      # ADAM(actor)_{k-1} ran on the side stream
             with torch.cuda.stream(self.s_env):
                 if first:                                  # reset!(env): this step starts from the initial condition
+                    if self.random_init and not self._keep_y0:
+                        self._draw_init()
+                    self._keep_y0 = False
                     y_in.copy_(env.y0)
                     s_in.copy_(self.state0)
                     act_prev = self.azero
@@ -312,6 +399,9 @@ class TrainPipeline:
                 L.check(lib.pdec_policy_act_rng_dev(self.actor.handle, L.ptr(s_in), self.cols, float(pol.act_noise),
                                                     float(pol.act_limit), 1, self.noise_seed, L.ptr(act)))
                 L.check(lib.pdec_set_stream(self.actor.handle, self._sp_upd))
+                if last and self.track_best:
+                    # what this acting kernel read, before the actor half that waits for ev_act may rewrite it
+                    L.check(lib.pdec_ledger_snapshot(self.ledger.h))
                 if not self.serial and self.LAG >= 2:
                     self.ev_act[k % 2].record(self.s_env)
             if self.drain_between:
@@ -332,8 +422,14 @@ class TrainPipeline:
                     L.check(lib.pdec_env_set_reward_partials_out(env.handle, L.ptr(self.rpart[k % 3]), None))
                 L.check(lib.pdec_env_step(env.handle, L.ptr(y_in), L.ptr(act), L.ptr(act_prev), L.ptr(s_in), L.ptr(y_out),
                                           L.ptr(self.pbuf), L.ptr(s_out), L.ptr(rew), L.ptr(flags)))
+                if self.ledger is not None:
+                    L.check(lib.pdec_ledger_step(self.ledger.h, L.ptr(rew), L.ptr(flags)))
                 if last:
                     term.fill_(1.0)                    # time-out: done = time >= te -> terminal transition
+                    if self.ledger is not None:
+                        L.check(lib.pdec_ledger_close(self.ledger.h, self.n_episodes, self.min_best_episode,
+                                                      int(self.track_best)))
+                        self.n_episodes += 1
                 if self.pre_rbar and self.rpart is None:
                     L.check(lib.pdec_reward_mean(env.handle, L.ptr(rew), self.cols, L.ptr(self.rbar[k % 3])))
                 if self.use_replay:
@@ -650,6 +746,63 @@ class TrainPipeline:
 
     def step(self):
         self.run(1)
+
+    # ------------------------------------------------------------------ episode ledger (host accessors: synchronise)
+    def _need_ledger(self, best=False):
+        if self.ledger is None:
+            raise _lib.PdecError("TrainPipeline: the episode ledger is off (log_episodes=0)")
+        if best and not self.track_best:
+            raise _lib.PdecError("TrainPipeline: the best actor is not tracked with an active reducer")
+
+    def episode_returns(self):
+        """(returns [n, B] float64, blew_up [n, B] bool, dropped): the last n = min(episodes, log_episodes) logged
+        episodes, oldest first, and how many earlier ones the ring has overwritten"""
+        self._need_ledger()
+        N, B = self.log_episodes, self.env.B
+        ret, blew = np.empty((N, B)), np.empty((N, B), dtype=np.int32)
+        _lib.check(self.lib.pdec_ledger_read(self.ledger.h, _lib.ptr(ret), _lib.ptr(blew), None))
+        n = min(self.n_episodes, N)
+        rows = [e % N for e in range(self.n_episodes - n, self.n_episodes)]
+        return ret[rows], blew[rows] != 0, self.n_episodes - n
+
+    @property
+    def rewards(self):
+        """batch-mean return of each logged episode (PDEhook.rewards), the last min(episodes, log_episodes)"""
+        self._need_ledger()
+        N = self.log_episodes
+        means = np.empty(N)
+        _lib.check(self.lib.pdec_ledger_read(self.ledger.h, None, None, _lib.ptr(means)))
+        n = min(self.n_episodes, N)
+        return [float(means[e % N]) for e in range(self.n_episodes - n, self.n_episodes)]
+
+    def _best(self):
+        self._need_ledger(best=True)
+        v, e = C.c_double(), C.c_int64()
+        _lib.check(self.lib.pdec_ledger_best(self.ledger.h, C.byref(v), C.byref(e)))
+        return v.value, e.value
+
+    @property
+    def bestreward(self):
+        """PDEhook.bestreward: -1e6 until an episode has been chosen"""
+        return self._best()[0]
+
+    @property
+    def bestepisode(self):
+        """PDEhook.bestepisode: 1-based number of the best episode (0: none yet)"""
+        return self._best()[1]
+
+    def best_actor(self):
+        """the actor of the best episode as it acted in that episode's last step: a CustomNeuralNetworkApproximator
+        shaped like the behaviour actor (PDEhook.bestNNA)"""
+        from .nna import CustomNeuralNetworkApproximator, HipMLP
+        if self.bestepisode == 0:
+            raise _lib.PdecError("TrainPipeline.best_actor: no episode has been chosen yet")
+        A = self.policy.behavior_actor
+        m = A.model
+        out = HipMLP(m.dims, m.acts, None, m.dtype, m.device, m.max_cols, m.stream)
+        _lib.check(self.lib.pdec_ledger_best_params(self.ledger.h, out.handle))
+        import copy
+        return CustomNeuralNetworkApproximator(out, copy.copy(A.optimizer))
 
     def sync(self):
         self.s_env.synchronize()

@@ -474,10 +474,38 @@ int pdec_set_episode_halt(pdec_handle any_handle, int32_t* flag);
 int pdec_env_autoreset(pdec_handle env, const int32_t* done, void* y, const void* y0, void* state, const void* state0,
                        void* action, const void* action0, void* reward);
 /* generate_random_init() of the 1-D setups (scripts/KS/setup/KSSetup.jl:288-298,
- * scripts/Keller-Segel/setup/KellerSegelSetup.jl:373-384) on the device, one workgroup per trajectory: y0_out [B][...] in
- * the environment's layout and dtype; uniforms from the Philox stream (seed, offset) (Julia's global RNG cannot be
- * reproduced, only the distribution; oracle/rng.py restates this stream).  Consumes B * ceil(n_coefficients / 4) counters. */
+ * scripts/Keller-Segel/setup/KellerSegelSetup.jl:373-384) and of the 2-D Keller-Segel setup (the same sine sums along x and
+ * along y, both species: n_coefficients = 2 (ceil(Lx / 3) + ceil(Ly / 3)), memory [ny][nx][2]) on the device, one workgroup
+ * per trajectory: y0_out [B][...] in the environment's layout and dtype; uniforms from the Philox stream (seed, offset)
+ * (Julia's global RNG cannot be reproduced, only the distribution; oracle/rng.py restates this stream).  Consumes
+ * B * ceil(n_coefficients / 4) counters. */
 int pdec_env_random_init(pdec_handle env, uint64_t seed, uint64_t offset, void* y0_out);
+
+/* ---------------------------------------------------------------- episode ledger (PDEhook's bookkeeping, src/PDEhook.jl:51-97) */
+/* The episode returns, blow-up bits and best actor of a batched training run, kept on the device: no launch argument depends
+ * on anything but the caller's ring buffers, so pdec_ledger_step can be part of a recorded step or a captured graph.  All
+ * launches go to the environment's stream.  `actor` (0: none) is the behaviour actor whose parameters the best-episode
+ * snapshot keeps; `capacity` rows of logged episodes are kept (row = episode mod capacity). */
+int pdec_ledger_create(pdec_handle* ledger, pdec_handle env, pdec_handle actor, int capacity);
+/* behind the env step: ret_b += (sum_a (double) reward[b][a]) / R (sum in a order), blew_b |= flags[b] != 0.  reward [B][R] in
+ * the environment's dtype, flags [B] (the env step's outputs) */
+int pdec_ledger_step(pdec_handle ledger, const void* reward, const int32_t* flags);
+/* behind the acting kernel of an episode's last step, before anything may rewrite what it read: copies the parameters that
+ * kernel read (the published image of a fused 3-layer actor, unpacked; the flat parameters otherwise) to the staging buffer */
+int pdec_ledger_snapshot(pdec_handle ledger);
+/* at the episode's last step (0-based `episode`): row episode mod capacity <- returns [B] (fp64), blow-up bits [B] and the
+ * batch mean (sum_b ret_b) / B in b order.  track_best: an episode with episode + 1 >= min_best_episode whose mean is >= every
+ * earlier such mean becomes the best (its snapshot is kept); a NaN mean is never chosen and does not take part in later
+ * comparisons.  The running sums restart from 0.  Nothing is read back. */
+int pdec_ledger_close(pdec_handle ledger, int64_t episode, int64_t min_best_episode, int track_best);
+/* the running sums restart from 0 without a row (an episode cut short) */
+int pdec_ledger_discard(pdec_handle ledger);
+/* host accessors (synchronise the environment's stream): all rows [capacity][B] / [capacity] (any pointer may be NULL), the
+ * best value (-1e6 before any choice) and 1-based episode number (0: none), the best parameters into an MLP of the actor's
+ * layer sizes (PDEC_E_INVALID otherwise; converted when its dtype differs) */
+int pdec_ledger_read(pdec_handle ledger, double* returns, int32_t* blew_up, double* means);
+int pdec_ledger_best(pdec_handle ledger, double* value, int64_t* episode);
+int pdec_ledger_best_params(pdec_handle ledger, pdec_handle mlp);
 
 /* ---------------------------------------------------------------- HIP graphs -- */
 /* Record everything enqueued on the stream of `origin` (pdec_set_stream; not the null stream) -- library calls, and any
