@@ -100,6 +100,15 @@ SIGNATURES = {
     "pdec_set_episode_halt": [Handle, _vp],
     "pdec_env_autoreset": [Handle] + [_vp] * 8,
     "pdec_env_random_init": [Handle, _u64, _u64, _vp],
+    "pdec_env_random_init_members": [Handle, _vp, _vp, _vp],
+    "pdec_env_set_member_layout": [Handle, C.c_int],
+    "pdec_population_create": [C.POINTER(Handle), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _i, _d, _d, _i,
+                               _d, _d, _i64, _i64, _i64, _vp],
+    "pdec_population_glue": [Handle, _i, _vp, _vp, _vp, _vp],
+    "pdec_population_update": [Handle],
+    "pdec_population_bp_sel": [Handle, _vp, _i],
+    "pdec_population_set_actor_copies": [Handle, _vp, _vp],
+    "pdec_population_copy_actors": [Handle, _vp],
     "pdec_ledger_create": [C.POINTER(Handle), Handle, Handle, _i], "pdec_ledger_step": [Handle, _vp, _vp],
     "pdec_ledger_snapshot": [Handle], "pdec_ledger_close": [Handle, _i64, _i64, _i], "pdec_ledger_discard": [Handle],
     "pdec_ledger_read": [Handle, _vp, _vp, _vp], "pdec_ledger_best": [Handle, _pd, C.POINTER(_i64)],

@@ -505,13 +505,22 @@ class Agent:
             else:
                 tr.push_rt(r, env.done.to(torch.float32).repeat_interleave(cols_per_env))
         elif stage == POST_EPISODE_STAGE:     # :215-224, :291-314
-            if stage == p.reset_stage:
-                p.update_step = 0
-            s = env.state.reshape(-1, env.state.shape[-1])
-            tr.push_sa(s, None)
+            self.end_episode(env.state.reshape(-1, env.state.shape[-1]))
         elif stage == POST_EXPERIMENT_STAGE:
             if stage == p.reset_stage:
                 p.update_step = 0
+
+    def end_episode(self, state, pushed=False):
+        """POST_EPISODE (src/PDEagent.jl:215-224, :291-314): the policy's reset stage, then the push of the final state
+        `state` [cols, ns] with the zero action -- enqueued here, or (pushed=True) already enqueued by the caller (a Population
+        pushes every member's in one launch), whose rows are then only counted"""
+        p, tr = self.policy, self.trajectory
+        if POST_EPISODE_STAGE == p.reset_stage:
+            p.update_step = 0
+        if pushed:
+            tr.n_sa += state.shape[0]
+        else:
+            tr.push_sa(state, None)
 
     def _maybe_update(self):
         p, tr = self.policy, self.trajectory

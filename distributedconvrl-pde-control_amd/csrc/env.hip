@@ -871,8 +871,9 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
   T* part = dots + 2 * e.S;               // [8][2][S]
   T* red = part + 16 * e.S;               // [16]
 
-  const int b0 = 2 * blockIdx.x, b1 = b0 + 1;
-  const bool has1 = b1 < e.B;
+  // member layout (pdec_env_set_member_layout): trajectory blockIdx.x alone, exactly the arithmetic of the B = 1 launch
+  const int b0 = e.member ? (int)blockIdx.x : 2 * (int)blockIdx.x, b1 = b0 + 1;
+  const bool has1 = !e.member && b1 < e.B;
   const size_t o0 = (size_t)b0 * N, o1 = (size_t)b1 * N;
 
   if (FUSED) {
@@ -2059,6 +2060,7 @@ static EnvDev<T> make_dev(const Env& E) {
   e.c1 = E.c1.as<T>(); e.c2 = E.c2.as<T>(); e.c3 = E.c3.as<T>(); e.c4 = E.c4.as<T>(); e.g = E.g.as<T>();
   e.dhat = E.dhat.as<C2<T>>(); e.tw = E.tw.as<C2<T>>();
   e.fft = E.fft;
+  e.member = E.member ? 1 : 0;
   return e;
 }
 
@@ -2089,7 +2091,7 @@ static int launch_step(Env& E, bool fused, int mode, const void* y_in, const voi
   const LaunchSync sync = E.sync;
   E.sync = LaunchSync{};
   if (sync.wait || sync.done) {        // served by the SYNC instantiations below, refused everywhere else
-    const bool ok = c.pde_kind == PDEC_PDE_KS_CNAB2 && fused && c.B <= 2 && sizeof(T) == 8 && (E.r4_log == 7 || E.r4_log == 8 || E.r4_log == 9) &&
+    const bool ok = c.pde_kind == PDEC_PDE_KS_CNAB2 && fused && c.B <= 2 && !E.member && sizeof(T) == 8 && (E.r4_log == 7 || E.r4_log == 8 || E.r4_log == 9) &&
                     !(E.prof && E.prof_reps > 1);
     PDEC_REQUIRE(ok, "pdec_env_step: a launch sync is set (pdec_set_launch_sync) and this step is not the fused single-workgroup fp64 "
                      "KS step of 192 / 240 / 600 cells");
@@ -2110,7 +2112,7 @@ static int launch_step(Env& E, bool fused, int mode, const void* y_in, const voi
     }
   }
   if (c.pde_kind == PDEC_PDE_KS_CNAB2) {
-    dim3 grid((c.B + 1) / 2), block(E.nthreads);
+    dim3 grid(E.member ? c.B : (c.B + 1) / 2), block(E.nthreads);
     // replay is safe when the step does not run in place (y_out != y_in)
     // the training pipeline's form of the step, profiled in the pipeline (one launch per event pair): timed by the
     // dispatch's own timestamps (PDEC_TIMED_LAUNCH) so that the measurement puts no packets around the kernel
@@ -2523,10 +2525,25 @@ int pdec_env_set_simd_sharing(pdec_handle h, int on, int* effective) {
   return PDEC_OK;
 }
 
+// Population (population.py): every trajectory of the batch is an independent member; the KS step runs one trajectory per
+// workgroup instead of two per complex FFT, so each member's result is bit for bit its B = 1 step and a blown-up member's
+// NaNs stay in its own workgroup.  The other 1-D kinds already run one trajectory per workgroup.
+int pdec_env_set_member_layout(pdec_handle h, int on) {
+  Env* E = lookup_as<Env>(h, Kind::Env);
+  if (!E) { set_error("pdec_env_set_member_layout: bad handle"); return PDEC_E_HANDLE; }
+  const int k = E->cfg.pde_kind;
+  PDEC_REQUIRE(!on || k == PDEC_PDE_KS_CNAB2 || k == PDEC_PDE_KSEG_RK4,
+               "pdec_env_set_member_layout: the 1-D KS and Keller-Segel environments only (pde kind %d)", k);
+  PDEC_REQUIRE(!on || !E->rsum_out, "pdec_env_set_member_layout: per-pair reward partials are set (pdec_env_set_reward_partials_out)");
+  E->member = on != 0;
+  return PDEC_OK;
+}
+
 int pdec_env_set_reward_partials_out(pdec_handle h, void* partial_sums, int* n_partials) {
   Env* E = lookup_as<Env>(h, Kind::Env);
   if (!E) { set_error("pdec_env_set_reward_partials_out: bad handle"); return PDEC_E_HANDLE; }
   const bool ks = E->cfg.pde_kind == PDEC_PDE_KS_CNAB2, ksfd = E->cfg.pde_kind == PDEC_PDE_KS_RK4_FD;
+  PDEC_REQUIRE(!E->member || partial_sums == nullptr, "pdec_env_set_reward_partials_out: the member layout is set");
   PDEC_REQUIRE(((ks || ksfd) && E->cfg.memory_size == 0) || partial_sums == nullptr,
                "pdec_env_set_reward_partials_out: provided by the fused KS steps only (use pdec_reward_mean elsewhere)");
   E->rsum_out = (float*)partial_sums;

@@ -30,6 +30,7 @@ struct EnvDev {
   const C2<T>* tw;       // exp(-2 pi i k/N)
   FftPlan fft;
   LaunchSync sync;       // pdec_set_launch_sync (SYNC instantiations of the fused KS step only)
+  int member = 0;        // pdec_env_set_member_layout: the KS step integrates ONE trajectory per workgroup (b0 = blockIdx.x)
 };
 
 struct Env : Object {
@@ -42,6 +43,7 @@ struct Env : Object {
   void* term_out = nullptr;
   float* rsum_out = nullptr;
   bool share_simd = false;   // pdec_env_set_simd_sharing: launch the 64-VGPR form of the fused KS step
+  bool member = false;       // pdec_env_set_member_layout: one KS trajectory per workgroup, the B = 1 launch's arithmetic
   FftPlan fft;
   int nthreads = 64;
   int r4_log = 0;        // 4 / 5: N = 256 / 1024 use the register-resident radix-4 FFT engine

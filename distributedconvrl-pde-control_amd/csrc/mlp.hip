@@ -1194,11 +1194,46 @@ struct StepGlueArgs {
   long long cap_sa, start_sa, n_sa;
   int* halt;
   LaunchSync sync;             // pdec_set_launch_sync on the actor's handle: wait before the first read, signal behind the last store
+  // population (pdec_population_glue): != null -> workgroup m serves member m, with its pointers from pm[m], its counters from
+  // rows[m] and its slices of r / done / state / out (r_bytes, s_bytes, o_bytes apart); phase 0: a control step, 1: the
+  // time-out push of the last step, 2: the POST_EPISODE push of the final state (active members, halt ignored)
+  const PopMember* pm;
+  long long* rows;
+  int phase;
+  long long d_noise, start_steps;
+  size_t r_bytes, s_bytes, o_bytes;
 };
 template <class T, class TP>
-__global__ __launch_bounds__(256) void step_glue_kernel(StepGlueArgs g) {
+__global__ __launch_bounds__(256) void step_glue_kernel(StepGlueArgs g_in) {
   extern __shared__ __align__(16) unsigned char small_act_smem[];
   const int tid = threadIdx.x;
+  StepGlueArgs g = g_in;
+  long long* mrow = nullptr;
+  bool macting = false;
+  if (g.pm) {                         // population member blockIdx.x: the solo call's arguments from its table entries
+    const int mb = blockIdx.x;
+    const PopMember& pm = g.pm[mb];
+    mrow = g.rows + (size_t)mb * POP_ROW;
+    g.tr = pm.tr; g.tt = pm.tt; g.ts = pm.ts; g.ta = pm.ta;
+    g.act.p = pm.actor_p; g.act.seed = pm.noise_seed; g.act.offset = (uint64_t)mrow[POP_NOISE];
+    g.act.act_noise = __longlong_as_double(mrow[POP_NOISE_AMP]); g.act.lim = __longlong_as_double(mrow[POP_LIMIT]);
+    g.start_rt = mrow[POP_NRT] % g.cap_rt;
+    g.start_sa = mrow[POP_NSA] % g.cap_sa;
+    if (g.r) g.r = static_cast<const char*>(g.r) + mb * g.r_bytes;
+    if (g.done) g.done += mb;
+    if (g.state) g.state = static_cast<const char*>(g.state) + mb * g.s_bytes;
+    if (g.out) g.out = static_cast<char*>(g.out) + mb * g.o_bytes;
+    if (g.phase == 0) {               // acting = update_step > start_steps, with this step's update_step (run.py)
+      macting = mrow[POP_USTEP] + 1 > g.start_steps;
+      g.act_mode = macting ? 1 : 2;
+    }
+    if (g.phase == 2) {
+      g.halt = nullptr;
+      if (!mrow[POP_ACTIVE]) g.n_sa = 0;
+    } else {
+      g.halt = reinterpret_cast<int*>(mrow + POP_HALT);
+    }
+  }
   launch_sync_wait(g.sync);           // (the env step that wrote reward / done / state, on another stream)
   const bool was = g.halt && *g.halt;
   const bool ended = was || (g.halt && g.n_rt && g.done && g.done[0] != 0);
@@ -1231,6 +1266,16 @@ __global__ __launch_bounds__(256) void step_glue_kernel(StepGlueArgs g) {
         const long long j = i - na_, row = j / g.na, c = j - row * g.na;
         g.ta[((g.start_sa + row) % g.cap_sa) * g.na + c] = acts ? (float)acts[j] : 0.f;
       }
+    }
+  }
+  // the member's counters move as run.py settles the solo run's: the push of the step that ends the episode counts, the rest of
+  // that step does not; nothing moves once the halt flag is up (every thread read the row before the barrier above)
+  if (mrow && tid == 0 && g.phase != 2 && !was) {
+    if (g.n_rt) mrow[POP_NRT] += g.n_rt;
+    if (g.phase == 0 && !ended) {
+      mrow[POP_USTEP] += 1;
+      mrow[POP_NSA] += g.n_sa;
+      if (macting) mrow[POP_NOISE] += g.d_noise;
     }
   }
   launch_sync_done(g.sync);
@@ -1388,6 +1433,180 @@ int pdec_step_glue(pdec_handle actor, pdec_handle trajectory_handle, int dtype, 
   else if (dtype == PDEC_F64) hipExtLaunchKernelGGL((step_glue_kernel<double, double>), dim3(1), dim3(256), lds, M->stream, nullptr, ev, 0, g);
   else hipExtLaunchKernelGGL((step_glue_kernel<float, float>), dim3(1), dim3(256), lds, M->stream, nullptr, ev, 0, g);
   PDEC_HIP(hipGetLastError());
+  return PDEC_OK;
+}
+
+// ---- populations (include/pdeconv.h, population.py)
+int pdec_population_create(pdec_handle* out, int M, const pdec_handle* actors, const pdec_handle* critics,
+                           const pdec_handle* target_actors, const pdec_handle* target_critics, void* const* traces,
+                           const uint64_t* seeds, void* const* losses, int env_dtype, int cols, int64_t capacity, int stride,
+                           int loops, int Bu, double gamma, double rho, int quirk, double eta_actor, double eta_critic,
+                           int64_t update_after_rows, int64_t update_freq, int64_t start_steps, int64_t* rows) {
+  PDEC_REQUIRE(out && M >= 1 && actors && critics && target_actors && target_critics && traces && seeds && losses && rows,
+               "pdec_population_create: null argument");
+  PDEC_REQUIRE(env_dtype == PDEC_F32 || env_dtype == PDEC_F64, "pdec_population_create: bad dtype %d", env_dtype);
+  PDEC_REQUIRE(cols >= 1 && capacity >= 1 && stride >= 1 && loops >= 1 && Bu >= 1 && update_freq >= 1 && update_after_rows >= stride,
+               "pdec_population_create: bad argument (cols %d, capacity %lld, stride %d, update_after rows %lld)", cols,
+               (long long)capacity, stride, (long long)update_after_rows);
+  auto P = std::make_unique<Population>();
+  P->M = M; P->cols = cols; P->dtype = env_dtype; P->rows = (long long*)rows;
+  P->cap = capacity; P->cap1 = capacity + stride; P->stride = stride; P->after = update_after_rows; P->freq = update_freq;
+  P->start_steps = start_steps; P->loops = loops; P->Bu = Bu; P->quirk = quirk;
+  P->gamma = gamma; P->rho = rho; P->eta_a = eta_actor; P->eta_c = eta_critic;
+  std::vector<PopMember> tab(M);
+  for (int m = 0; m < M; ++m) {
+    Mlp* A = lookup_as<Mlp>(actors[m], Kind::Mlp);
+    Mlp* C = lookup_as<Mlp>(critics[m], Kind::Mlp);
+    Mlp* At = lookup_as<Mlp>(target_actors[m], Kind::Mlp);
+    Mlp* Ct = lookup_as<Mlp>(target_critics[m], Kind::Mlp);
+    if (!A || !C || !At || !Ct) { set_error("pdec_population_create: bad network handle of member %d", m); return PDEC_E_HANDLE; }
+    PDEC_REQUIRE(A->dtype == PDEC_F32 && C->dtype == PDEC_F32 && At->dtype == PDEC_F32 && Ct->dtype == PDEC_F32,
+                 "pdec_population_create: member %d: fp32 networks only", m);
+    PDEC_REQUIRE(A->stream == C->stream && At->stream == C->stream && Ct->stream == C->stream,
+                 "pdec_population_create: member %d: its four networks must share one stream", m);
+    if (m > 0) {
+      Mlp* A0 = P->A[0];
+      Mlp* C0 = P->C[0];
+      PDEC_REQUIRE(A->dims == A0->dims && A->acts == A0->acts && C->dims == C0->dims && C->acts == C0->acts &&
+                   At->dims == A0->dims && Ct->dims == C0->dims,
+                   "pdec_population_create: member %d: network shapes differ from member 0's", m);
+      PDEC_REQUIRE(A->stream == A0->stream, "pdec_population_create: member %d: update stream differs from member 0's", m);
+      PDEC_REQUIRE(A->noise_rows == A0->noise_rows, "pdec_population_create: member %d: noise rows differ", m);
+    }
+    PDEC_REQUIRE(!A->halt && !C->halt, "pdec_population_create: member %d: an episode halt flag is attached", m);
+    BpArgs bp{};
+    int rc;
+    if ((rc = bp_begin(A, 0.9, 0.999, &bp)) || (rc = bp_begin(C, 0.9, 0.999, &bp))) return rc;   // (uploads the powers once)
+    PopMember& e = tab[m];
+    e.actor_p = A->params.p;
+    e.ts = (float*)traces[4 * m]; e.ta = (float*)traces[4 * m + 1]; e.tr = (float*)traces[4 * m + 2]; e.tt = (float*)traces[4 * m + 3];
+    PDEC_REQUIRE(e.ts && e.ta && e.tr && e.tt && losses[m], "pdec_population_create: member %d: null trace or loss slot", m);
+    e.noise_seed = seeds[2 * m]; e.sample_seed = seeds[2 * m + 1];
+    e.Ap = A->params.as<float>(); e.Ag = A->grads.as<float>(); e.Am = A->m.as<float>(); e.Av = A->v.as<float>(); e.Apt = At->params.as<float>();
+    e.Cp = C->params.as<float>(); e.Cg = C->grads.as<float>(); e.Cm = C->m.as<float>(); e.Cv = C->v.as<float>(); e.Cpt = Ct->params.as<float>();
+    e.bpA = A->bpd.as<double>(); e.bpC = C->bpd.as<double>();
+    e.losses = (float*)losses[m];
+    P->A.push_back(A); P->C.push_back(C); P->At.push_back(At); P->Ct.push_back(Ct);
+  }
+  Mlp* A0 = P->A[0];
+  PDEC_REQUIRE(step_glue_served(A0, A0, env_dtype, 1, cols, cols),
+               "pdec_population_create: the single-launch glue does not serve these networks at %d columns of dtype %d", cols, env_dtype);
+  PDEC_HIP(P->tab.alloc(sizeof(PopMember) * M));
+  PDEC_HIP(hipMemcpy(P->tab.p, tab.data(), sizeof(PopMember) * M, hipMemcpyHostToDevice));
+  P->stream = A0->stream;
+  *out = register_object(std::move(P));
+  return PDEC_OK;
+}
+
+int pdec_population_glue(pdec_handle pop, int phase, const void* reward, const int32_t* done_flags, const void* state,
+                         void* actions_out) {
+  Population* P = lookup_as<Population>(pop, Kind::Population);
+  if (!P) { set_error("pdec_population_glue: bad handle"); return PDEC_E_HANDLE; }
+  PDEC_REQUIRE(phase >= 0 && phase <= 2, "pdec_population_glue: bad phase %d", phase);
+  PDEC_REQUIRE(phase == 2 || !reward == !done_flags, "pdec_population_glue: reward and done flags go together");
+  PDEC_REQUIRE(phase != 1 || reward, "pdec_population_glue: the time-out push needs the rewards");
+  PDEC_REQUIRE(phase == 1 || state, "pdec_population_glue: null state");
+  PDEC_REQUIRE(phase != 0 || actions_out, "pdec_population_glue: null actions");
+  Mlp* M = P->A[0];
+  const int cols = P->cols, ns = M->dims[0], na = M->dims[M->L];
+  const size_t ts = dtype_size(P->dtype);
+  StepGlueArgs g{};
+  g.r = phase == 2 ? nullptr : reward; g.done = phase == 2 ? nullptr : done_flags;
+  g.cols_per_traj = cols; g.force = phase == 1; g.cap_rt = P->cap; g.n_rt = g.r ? cols : 0;
+  g.act_mode = 0; g.state = phase == 1 ? nullptr : state; g.out = phase == 0 ? actions_out : nullptr;
+  g.ns = ns; g.na = na; g.cap_sa = P->cap1; g.n_sa = phase == 1 ? 0 : cols;
+  g.pm = P->tab.as<PopMember>(); g.rows = P->rows; g.phase = phase;
+  g.d_noise = ((long long)cols * na + 3) / 4; g.start_steps = P->start_steps;
+  g.r_bytes = (size_t)cols * ts; g.s_bytes = (size_t)cols * ns * ts; g.o_bytes = (size_t)cols * na * ts;
+  SmallActArgs& a = g.act;
+  a.L = M->L; a.cols = cols; a.learning = 1;
+  a.maxw = 1;
+  for (int l = 0; l <= M->L; ++l) { a.dims[l] = M->dims[l]; a.maxw = std::max(a.maxw, M->dims[l]); }
+  for (int l = 0; l < M->L; ++l) { a.acts[l] = M->acts[l]; a.woff[l] = (int)M->w_off[l]; a.boff[l] = (int)M->b_off[l]; }
+  a.nrows = M->noise_rows < 0 ? M->dims[M->L] : M->noise_rows;
+  const size_t lds = phase == 0 ? (size_t)2 * a.maxw * cols * ts : 16;
+  ProfScope ps(P, "population_glue");
+  if (P->dtype == PDEC_F64) hipLaunchKernelGGL((step_glue_kernel<double, float>), dim3(P->M), dim3(256), lds, P->stream, g);
+  else hipLaunchKernelGGL((step_glue_kernel<float, float>), dim3(P->M), dim3(256), lds, P->stream, g);
+  PDEC_HIP(hipGetLastError());
+  return PDEC_OK;
+}
+
+// the members' beta-power slots: get = write each member's (actor, critic) bp_sel into rows_host[m][POP_BPA / POP_BPC];
+// set = adopt them from there (and mark the networks' derived images stale after the updates of an episode)
+int pdec_population_bp_sel(pdec_handle pop, int64_t* rows_host, int set) {
+  Population* P = lookup_as<Population>(pop, Kind::Population);
+  if (!P) { set_error("pdec_population_bp_sel: bad handle"); return PDEC_E_HANDLE; }
+  PDEC_REQUIRE(rows_host, "pdec_population_bp_sel: null");
+  for (int m = 0; m < P->M; ++m) {
+    int64_t* r = rows_host + (size_t)m * POP_ROW;
+    if (set) {
+      PDEC_REQUIRE((r[POP_BPA] == 0 || r[POP_BPA] == 1) && (r[POP_BPC] == 0 || r[POP_BPC] == 1), "pdec_population_bp_sel: bad slot");
+      P->A[m]->bp_sel = (int)r[POP_BPA]; P->C[m]->bp_sel = (int)r[POP_BPC];
+      P->A[m]->fw_dirty = P->C[m]->fw_dirty = P->At[m]->fw_dirty = P->Ct[m]->fw_dirty = true;
+    } else {
+      r[POP_BPA] = P->A[m]->bp_sel; r[POP_BPC] = P->C[m]->bp_sel;
+    }
+  }
+  return PDEC_OK;
+}
+
+}  // extern "C"
+
+// the hooks' actor snapshots at the end of an episode (PDEhook POST_EPISODE: bestNNA on a new best, currentNNA every episode)
+// for all members in one launch: member m (blockIdx.y) copies its behaviour actor's parameters to snap[2m] when bit 0 of
+// which[m] is set and to snap[2m + 1] when bit 1 is -- the bytes pdec_mlp_copy moves between two fp32 networks
+__global__ __launch_bounds__(256) void pop_copy_actors_kernel(const PopMember* __restrict__ pm, float* const* __restrict__ snap,
+                                                              const int32_t* __restrict__ which, int n) {
+  const int m = blockIdx.y, w = which[m];
+  float* d0 = (w & 1) ? snap[2 * m] : nullptr;
+  float* d1 = (w & 2) ? snap[2 * m + 1] : nullptr;
+  if (!d0 && !d1) return;
+  const float* src = static_cast<const float*>(pm[m].actor_p);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const float v = src[i];
+    if (d0) d0[i] = v;
+    if (d1) d1[i] = v;
+  }
+}
+
+extern "C" {
+
+int pdec_population_set_actor_copies(pdec_handle pop, const pdec_handle* best, const pdec_handle* current) {
+  Population* P = lookup_as<Population>(pop, Kind::Population);
+  if (!P) { set_error("pdec_population_set_actor_copies: bad handle"); return PDEC_E_HANDLE; }
+  PDEC_REQUIRE(best && current, "pdec_population_set_actor_copies: null");
+  std::vector<float*> tab(2 * (size_t)P->M, nullptr);
+  std::vector<Mlp*> nets;
+  for (int m = 0; m < P->M; ++m) {
+    const pdec_handle h2[2] = {best[m], current[m]};
+    for (int k = 0; k < 2; ++k) {
+      if (!h2[k]) continue;
+      Mlp* D = lookup_as<Mlp>(h2[k], Kind::Mlp);
+      if (!D) { set_error("pdec_population_set_actor_copies: bad network handle of member %d", m); return PDEC_E_HANDLE; }
+      PDEC_REQUIRE(D->dims == P->A[m]->dims && D->dtype == PDEC_F32 && D->stream == P->stream,
+                   "pdec_population_set_actor_copies: member %d: a snapshot must be an fp32 network of the actor's shape on its stream", m);
+      tab[2 * m + k] = D->params.as<float>();
+      nets.push_back(D);
+    }
+  }
+  if (!P->snap.p) PDEC_HIP(P->snap.alloc(sizeof(float*) * 2 * P->M));
+  PDEC_HIP(hipStreamSynchronize(P->stream));       // (an earlier copy launch may still read the table)
+  PDEC_HIP(hipMemcpy(P->snap.p, tab.data(), sizeof(float*) * 2 * P->M, hipMemcpyHostToDevice));
+  P->snap_nets = nets;
+  return PDEC_OK;
+}
+
+int pdec_population_copy_actors(pdec_handle pop, const int32_t* which) {
+  Population* P = lookup_as<Population>(pop, Kind::Population);
+  if (!P) { set_error("pdec_population_copy_actors: bad handle"); return PDEC_E_HANDLE; }
+  PDEC_REQUIRE(which && P->snap.p, "pdec_population_copy_actors: null flags or no snapshot table (pdec_population_set_actor_copies)");
+  const int n = P->A[0]->nparams;
+  const dim3 grid((unsigned)std::min(cdiv(n, 256), 16), (unsigned)P->M);
+  ProfScope ps(P, "population_copy_actors");
+  hipLaunchKernelGGL(pop_copy_actors_kernel, grid, dim3(256), 0, P->stream, P->tab.as<PopMember>(), P->snap.as<float*>(), which, n);
+  PDEC_HIP(hipGetLastError());
+  for (Mlp* D : P->snap_nets) D->fw_dirty = true;
   return PDEC_OK;
 }
 

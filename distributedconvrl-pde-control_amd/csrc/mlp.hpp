@@ -57,6 +57,32 @@ struct Mlp : Object {
   T* dy_buf(int) { return dy.as<T>(); }
 };
 
+// ---- populations (pdec_population_create, population.py): M independent single-trajectory learners whose per-step launches
+// are ONE launch of M workgroups each.  Workgroup m reads member m's pointers from a device table (PopMember) and its counters
+// from row m of a device int64 table that the host writes once per episode and reads back once per episode.
+#define POP_ROW 16
+enum PopSlot {
+  POP_USTEP = 0,    // policy.update_step
+  POP_NSA,          // trajectory.n_sa
+  POP_NRT,          // trajectory.n_rt
+  POP_NOISE,        // policy._noise_off (Philox counters of the exploration noise)
+  POP_SAMPLE,       // policy._sample_off (Philox counters of the minibatch draws)
+  POP_HALT,         // the member's episode halt flag (low 32 bits; pdec_set_episode_halt's protocol)
+  POP_ACTIVE,       // 1: the member runs this episode (0: its stop condition has fired)
+  POP_BPA,          // slot of the actor's / critic's double-buffered ADAM beta powers (Mlp::bp_sel)
+  POP_BPC,
+  POP_NOISE_AMP,    // act_noise, act_limit (bit patterns of doubles)
+  POP_LIMIT,
+};
+struct PopMember {
+  const void* actor_p;                          // behaviour actor parameters (acting)
+  float *ts, *ta, *tr, *tt;                     // replay traces: state, action, reward, terminal
+  uint64_t noise_seed, sample_seed;
+  float *Ap, *Ag, *Am, *Av, *Apt, *Cp, *Cg, *Cm, *Cv, *Cpt;   // the small update's learner state
+  double *bpA, *bpC;                            // [2][2] beta powers
+  float* losses;                                // [2]
+};
+
 // Philox4x32-10 counter-based generator (the exploration noise that replaces randn(rng), src/PDEagent.jl:201)
 __device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t k1) {
   for (int r = 0; r < 10; ++r) {
@@ -133,5 +159,18 @@ int fused2_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const v
                         const AdamPolyak* apply, const void* loss_add = nullptr);
 int fused2_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
                        const AdamPolyak* apply);
+
+struct Population : Object {
+  int M = 0, cols = 0, dtype = PDEC_F64;
+  std::vector<Mlp*> A, C, At, Ct;
+  DevBuf tab;                        // PopMember [M]
+  DevBuf snap;                       // float* [M][2]: the hooks' best / current actor parameters (pdec_population_set_actor_copies)
+  std::vector<Mlp*> snap_nets;       // (their objects: a copy makes their derived images stale)
+  long long* rows = nullptr;         // [M][POP_ROW] (the caller's device buffer)
+  long long cap = 0, cap1 = 0, after = 0, freq = 1, start_steps = 0;
+  int stride = 0, loops = 1, Bu = 1, quirk = 0;
+  double gamma = 0.99, rho = 1.0, eta_a = 0, eta_c = 0;
+  Population() : Object(Kind::Population) {}
+};
 
 }  // namespace pdec

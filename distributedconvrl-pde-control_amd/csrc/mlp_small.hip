@@ -45,7 +45,41 @@ struct SmallArgs {
   uint32_t smp_hi;
   int64_t smp_base;
   int smp_cap, smp_cap1, smp_stride;
+  // population (pdec_population_update): != null -> workgroup m updates member m (sm_member_begin)
+  const PopMember* pm;
+  long long* rows;
+  long long m_after, m_freq, m_dsample;
 };
+
+// population member blockIdx.x: Agent._maybe_update's trigger (agent.py) from the member's counters -- false: the member does not
+// update at this step and the whole workgroup returns --, else its pointers, sampling bounds and beta-power slots into g as
+// ddpg_update_small_impl sets them for its solo call; the row moves on as the host's counters do behind that call
+__device__ __forceinline__ bool sm_member_begin(SmallArgs& g) {
+  const int mb = blockIdx.x;
+  long long* row = g.rows + (size_t)mb * POP_ROW;
+  const long long n_rt = row[POP_NRT], ustep = row[POP_USTEP], soff = row[POP_SAMPLE];
+  const int sa = (int)row[POP_BPA], sc = (int)row[POP_BPC];
+  const long long nv = n_rt < (long long)g.smp_cap ? n_rt : (long long)g.smp_cap;      // length(trajectory)
+  if (row[POP_HALT] || !(nv > g.m_after) || ustep % g.m_freq != 0) return false;
+  const PopMember& pm = g.pm[mb];
+  g.A.p = pm.Ap; g.A.g = pm.Ag; g.A.m = pm.Am; g.A.v = pm.Av; g.A.pt = pm.Apt;
+  g.C.p = pm.Cp; g.C.g = pm.Cg; g.C.m = pm.Cm; g.C.v = pm.Cv; g.C.pt = pm.Cpt;
+  g.state = pm.ts; g.action = pm.ta; g.reward = pm.tr; g.terminal = pm.tt;
+  g.bpA.cur = pm.bpA + 2 * sa; g.bpA.next = pm.bpA + 2 * (sa ^ 1);
+  g.bpC.cur = pm.bpC + 2 * sc; g.bpC.next = pm.bpC + 2 * (sc ^ 1);
+  g.losses = pm.losses;
+  g.halt = nullptr;
+  g.smp_seed = pm.sample_seed; g.smp_offset = (uint64_t)soff;
+  g.smp_hi = (uint32_t)(nv - g.smp_stride);
+  g.smp_base = n_rt > (long long)g.smp_cap ? n_rt - g.smp_cap : 0;
+  __syncthreads();                    // every thread has read the row
+  if (threadIdx.x == 0) {
+    row[POP_SAMPLE] = soff + g.m_dsample;
+    row[POP_BPA] = sa ^ 1;
+    row[POP_BPC] = sc ^ 1;
+  }
+  return true;
+}
 
 // draw the [loops][Bu] slot tables into LDS (see SmallArgs); every thread then reads them after a barrier
 __device__ __forceinline__ void sm_draw_slots(const SmallArgs& g, int* tab, int tid, int nt) {
@@ -168,6 +202,7 @@ __device__ void sm_polyak(const SmallNet& n, float rho, float omr, int tid) {
 
 __global__ __launch_bounds__(SM_THREADS) void ddpg_small_kernel(SmallArgs g_in) {
   SmallArgs g = g_in;
+  if (g.pm && !sm_member_begin(g)) return;
   extern __shared__ __align__(16) float sm[];
   const int tid = threadIdx.x, Bu = g.Bu, ns = g.ns, na = g.na, K0 = ns + na;
   const int W = g.maxw * Bu;             // floats per activation buffer
@@ -412,7 +447,9 @@ __device__ __forceinline__ void s2_adam(float& p, float& m, float& v, float& pt,
 // wave waited.  Gradients reach their owners and the new weights (and targets) their units through LDS, inside the wave (LDS
 // operations of one wave execute in order: no barrier).  Same arithmetic per parameter.  Needs nA <= 64, (ns + 2) nA <= 64 OS.
 template <int KC, int KA, int BUT, bool EXACT, int OS = 0>
-__global__ __launch_bounds__(512) void ddpg_small2_kernel(Small2Args a_in) {
+__global__ __launch_bounds__(512) void ddpg_small2_kernel(Small2Args a_m) {
+  Small2Args a_in = a_m;
+  if (a_in.g.pm && !sm_member_begin(a_in.g)) return;
   const SmallArgs& g = a_in.g;
   extern __shared__ __align__(16) float sm[];
   const int tid = threadIdx.x, nt = blockDim.x, nw = nt >> 6;
@@ -746,7 +783,9 @@ __global__ __launch_bounds__(512) void ddpg_small2_kernel(Small2Args a_in) {
 // NWC: the number of critic waves, a compile-time constant (3 for the KS nets' 140 critic units): the row loop of the actor wave
 // unrolls and its 18 wave sums interleave
 template <int KC, int KA, int BUT, bool EXACT, int NWC>
-__global__ __launch_bounds__(512) void ddpg_small2f_kernel(Small2Args a_in) {
+__global__ __launch_bounds__(512) void ddpg_small2f_kernel(Small2Args a_m) {
+  Small2Args a_in = a_m;
+  if (a_in.g.pm && !sm_member_begin(a_in.g)) return;
   const SmallArgs& g = a_in.g;
   extern __shared__ __align__(16) float sm[];
   const int tid = threadIdx.x, nt = blockDim.x, nwc = NWC, wv = tid >> 6, lane = tid & 63;
@@ -1389,6 +1428,64 @@ static int ddpg_update_small_impl(pdec_handle hA, pdec_handle hC, pdec_handle hA
   bp_done(A);
   bp_done(C);
   A->fw_dirty = C->fw_dirty = At->fw_dirty = Ct->fw_dirty = true;
+  return PDEC_OK;
+}
+
+// one launch of M workgroups: member m's small update with device-side sampling where its own trigger fires (sm_member_begin)
+extern "C" int pdec_population_update(pdec_handle pop) {
+  Population* P = lookup_as<Population>(pop, Kind::Population);
+  if (!P) { set_error("pdec_population_update: bad handle"); return PDEC_E_HANDLE; }
+  Mlp *A = P->A[0], *C = P->C[0], *At = P->At[0], *Ct = P->Ct[0];
+  SmallPlan pl{};
+  int rc;
+  if ((rc = small_plan(A, C, P->loops, P->Bu, (float)P->rho, true, P->quirk, &pl))) return rc;
+  PDEC_REQUIRE(pl.id != SK_BATCHED, "pdec_population_update: reward groups that split the minibatch are not served");
+  int quirk = P->quirk;
+  if (quirk && C->rg_g == 1) quirk = 0;
+  SmallArgs g{};
+  if ((rc = fill_net(g.A, A, At)) || (rc = fill_net(g.C, C, Ct))) return rc;
+  g.maxw = pl.maxw;
+  g.lds_params = pl.lds_params;
+  g.loops = P->loops; g.Bu = P->Bu; g.ns = A->dims[0]; g.na = A->dims[A->L]; g.quirk = quirk;
+  g.gamma = (float)P->gamma; g.rho = (float)P->rho;
+  g.eta_a = P->eta_a; g.eta_c = P->eta_c; g.b1 = 0.9; g.b2 = 0.999; g.eps = 1e-8;
+  g.smp_on = 1;
+  g.smp_cap = (int)P->cap; g.smp_cap1 = (int)P->cap1; g.smp_stride = P->stride;
+  g.smp_lds = pl.smp_lds;
+  g.pm = P->tab.as<PopMember>(); g.rows = P->rows;
+  g.m_after = P->after; g.m_freq = P->freq; g.m_dsample = ((long long)P->loops * P->Bu + 3) / 4;
+  static size_t attr[sizeof(small_kernel_names) / sizeof(small_kernel_names[0])] = {};
+  const dim3 grid(P->M);
+  ProfScope ps(P, "population_update");
+  if (pl.id == SK_GENERIC) {
+    if ((rc = small_lds_attr(ddpg_small_kernel, 160 * 1024, &attr[SK_GENERIC]))) return rc;
+    hipLaunchKernelGGL(ddpg_small_kernel, grid, dim3(SM_THREADS), pl.lds, P->stream, g);
+  } else {
+    Small2Args a2{};
+    a2.g = g;
+    a2.g.lds_params = 0;
+    a2.nC = C->dims[1]; a2.nA = A->dims[1];
+#define S2_LAUNCH(ID, ...)                                                                                             \
+  case ID:                                                                                                             \
+    if ((rc = small_lds_attr(__VA_ARGS__, pl.lds, &attr[ID]))) return rc;                                              \
+    hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(pl.threads), pl.lds, P->stream, a2);                                  \
+    break;
+    switch (pl.id) {
+      S2_LAUNCH(SK_S2F_2_1_3, ddpg_small2f_kernel<2, 1, 3, true, 3>)
+      S2_LAUNCH(SK_S2_2_1_3, ddpg_small2_kernel<2, 1, 3, true>)
+      S2_LAUNCH(SK_S2_13_12_3_OS5, ddpg_small2_kernel<13, 12, 3, true, 5>)
+      S2_LAUNCH(SK_S2_10_9_3_OS4, ddpg_small2_kernel<10, 9, 3, true, 4>)
+      S2_LAUNCH(SK_S2_13_12_3, ddpg_small2_kernel<13, 12, 3, true>)
+      S2_LAUNCH(SK_S2_10_9_3, ddpg_small2_kernel<10, 9, 3, true>)
+      S2_LAUNCH(SK_S2_4_3_4, ddpg_small2_kernel<4, 3, S2_BU, false>)
+      S2_LAUNCH(SK_S2_10_9_4, ddpg_small2_kernel<10, 9, S2_BU, false>)
+      S2_LAUNCH(SK_S2_13_12_4, ddpg_small2_kernel<13, 12, S2_BU, false>)
+      S2_LAUNCH(SK_S2_16_15_4, ddpg_small2_kernel<16, 15, S2_BU, false>)
+      default: set_error("pdec_population_update: no kernel for plan %d", (int)pl.id); return PDEC_E_INVALID;
+    }
+#undef S2_LAUNCH
+  }
+  PDEC_HIP(hipGetLastError());
   return PDEC_OK;
 }
 

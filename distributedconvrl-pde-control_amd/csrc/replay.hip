@@ -134,14 +134,18 @@ __global__ void autoreset_kernel(ResetArgs g) {
 #define RI_MAXC 64
 template <class T>
 __global__ void random_init_kernel(T* __restrict__ y, int N, int nsp, int nsin, double dx, double fdiv, double base, double l2_target,
-                                   uint64_t seed, uint64_t offset) {
+                                   uint64_t seed, uint64_t offset, const uint64_t* __restrict__ mseed = nullptr,
+                                   const uint64_t* __restrict__ moff = nullptr) {
   __shared__ double a[RI_MAXC];
   __shared__ double red[256];
   const int b = blockIdx.x, tid = threadIdx.x, nc = nsp * nsin, nblk = (nc + 3) / 4;
+  // per-member streams (pdec_env_random_init_members): trajectory b draws what a B = 1 call with (mseed[b], moff[b]) draws
+  const uint64_t cb = mseed ? 0 : (uint64_t)b;
+  if (mseed) { seed = mseed[b]; offset = moff[b]; }
   if (tid == 0) {
     double nrm = 0;
     for (int blk = 0; blk < nblk; ++blk) {
-      const uint64_t ctr = offset + (uint64_t)b * nblk + blk;
+      const uint64_t ctr = offset + cb * nblk + blk;
       uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
       philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
       for (int i = 0; i < 4 && 4 * blk + i < nc; ++i) {
@@ -437,6 +441,37 @@ int pdec_env_autoreset(pdec_handle henv, const int32_t* done, void* y, const voi
   g.reward = reward; g.reward_len = c.mono ? 1 : c.A;
   ProfScope ps(E, "env_autoreset");
   hipLaunchKernelGGL(autoreset_kernel, dim3(c.B), dim3(256), 0, E->stream, g);
+  PDEC_HIP(hipGetLastError());
+  return PDEC_OK;
+}
+
+// one launch for the members of a population: trajectory b from the Philox stream (seeds[b], offsets[b]) exactly as a B = 1
+// pdec_env_random_init(seeds[b], offsets[b]) draws it (device arrays of B entries; the 1-D KS and Keller-Segel setups)
+int pdec_env_random_init_members(pdec_handle henv, const uint64_t* seeds, const uint64_t* offsets, void* y0_out) {
+  Env* E = lookup_as<Env>(henv, Kind::Env);
+  if (!E) { set_error("pdec_env_random_init_members: bad handle"); return PDEC_E_HANDLE; }
+  PDEC_REQUIRE(y0_out && seeds && offsets, "pdec_env_random_init_members: null");
+  const pdec_env_cfg& c = E->cfg;
+  int nsp, nsin;
+  double fdiv, base, l2;
+  const double two_pi = 6.283185307179586;
+  if (c.pde_kind == PDEC_PDE_KS_CNAB2 || c.pde_kind == PDEC_PDE_KS_RK4_FD) {
+    nsp = 1; nsin = 8; fdiv = two_pi; base = 0.0; l2 = 30.0;
+  } else if (c.pde_kind == PDEC_PDE_KSEG_RK4) {
+    nsp = 2; nsin = (int)ceil(c.Lx / 3.0); fdiv = two_pi * (c.Lx / 22.0); base = 1.0; l2 = 0.0;
+  } else {
+    set_error("pdec_env_random_init_members: the 1-D KS and Keller-Segel setups only");
+    return PDEC_E_INVALID;
+  }
+  PDEC_REQUIRE(nsp * nsin <= RI_MAXC, "pdec_env_random_init_members: %d sine coefficients exceed the kernel's table", nsp * nsin);
+  const double dx = c.Lx / c.N;
+  ProfScope ps(E, "env_random_init");
+  if (c.dtype == PDEC_F64)
+    hipLaunchKernelGGL((random_init_kernel<double>), dim3(c.B), dim3(256), 0, E->stream, (double*)y0_out, c.N, nsp, nsin, dx, fdiv,
+                       base, l2, (uint64_t)0, (uint64_t)0, seeds, offsets);
+  else
+    hipLaunchKernelGGL((random_init_kernel<float>), dim3(c.B), dim3(256), 0, E->stream, (float*)y0_out, c.N, nsp, nsin, dx, fdiv,
+                       base, l2, (uint64_t)0, (uint64_t)0, seeds, offsets);
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
 }

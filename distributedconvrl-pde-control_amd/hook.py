@@ -58,6 +58,29 @@ class PDEhook:
                                        reward=r.cpu().numpy().astype(np.float64)))
         self._rows_dev = []
 
+    def end_episode(self, env):
+        """the host bookkeeping of POST_EPISODE (src/PDEhook.jl:65-97).  Returns True when the episode is a new best: the
+        caller then copies the actor into bestNNA, and with collect_NNA every episode's into currentNNA (this hook's own
+        POST_EPISODE through pdec_mlp_copy; a Population for all its members in one launch)"""
+        self._flush(env)
+        new_best = False
+        if env.time >= env.te and self.ep >= self.min_best_episode:
+            self.rewards_compare.append(self.reward)
+            if self.collect_NNA and self.reward >= max(self.rewards_compare):
+                new_best = True
+                self.bestreward, self.bestepisode = self.reward, self.ep
+                if self.collect_bestDF:
+                    self.bestDF = list(self.currentDF)
+        if env.time < env.te and self.error_detection(env.y):
+            self.errored_episodes.append(self.ep)
+        if self.collect_history:
+            self.history.append(self.currentDF)
+        self.currentDF = []
+        self.ep += 1
+        self.rewards.append(self.reward)
+        self.reward = 0.0
+        return new_best
+
     def __call__(self, stage, agent, env):
         # the hook's device ops (clones, accumulators, re-initialisation) are ordered with the env's kernels
         from .env import _on_stream
@@ -103,22 +126,8 @@ class PDEhook:
                     self._rows_dev.append((env.steps, env.action[b].clone(), env.p[b].clone(), env.y[b].clone(),
                                            env.reward[b].clone()))
         elif stage == POST_EPISODE_STAGE:                       # :65-97
-            self._flush(env)
-            if env.time >= env.te and self.ep >= self.min_best_episode:
-                self.rewards_compare.append(self.reward)
-                if self.collect_NNA and self.reward >= max(self.rewards_compare):
-                    self.bestNNA.copyto(agent.policy.behavior_actor)
-                    self.bestreward, self.bestepisode = self.reward, self.ep
-                    if self.collect_bestDF:
-                        self.bestDF = list(self.currentDF)
-            if env.time < env.te and self.error_detection(env.y):
-                self.errored_episodes.append(self.ep)
-            if self.collect_history:
-                self.history.append(self.currentDF)
-            self.currentDF = []
-            self.ep += 1
-            self.rewards.append(self.reward)
-            self.reward = 0.0
+            if self.end_episode(env):
+                self.bestNNA.copyto(agent.policy.behavior_actor)
             if self.collect_NNA:
                 self.currentNNA.copyto(agent.policy.behavior_actor)
         elif stage == POST_EXPERIMENT_STAGE:                    # :99-103

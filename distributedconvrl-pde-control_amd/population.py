@@ -1,0 +1,310 @@
+"""Populations: M independently seeded reference-shaped learners trained side by side on one GPU.
+
+Every member is an ordinary `Agent` (create_agent(setup=..., B=1, stream=s_upd)) with its own `PDEhook`; `Population.run`
+leaves each of them bit for bit where `run(agent_m, PDEenv(setup, B=1, ...), stops[m], hook_m)` leaves it.  The control steps
+of an episode are issued as in run._run_device_episodes, but each of the three per-step launches -- the glue (POST_ACT push,
+acting, PRE_ACT push), the small update, the env step -- is ONE launch of M workgroups: workgroup m reads member m's pointers
+from a device table and its counters (ring positions, Philox offsets, update_step, halt flag) from row m of a device int64
+table (include/pdeconv.h, pdec_population_create).  The host writes that table once per episode, reads it back once, and
+settles each member's host state exactly as the solo loop does at its number of executed steps."""
+import ctypes as C
+import time
+
+import numpy as np
+import torch
+
+from . import _lib
+from .agent import Agent, PRE_EXPERIMENT_STAGE, PRE_EPISODE_STAGE, POST_EXPERIMENT_STAGE
+from .env import PDEenv, _on_stream
+from .hook import PDEhook
+from .run import (StopAfterEpisode, StopAfterEpisodeWithMinSteps, _EpisodeLogs, _add_episode_reward, _episode_steps,
+                  _episode_time, _stop_fired)
+
+ROW = 16
+USTEP, NSA, NRT, NOISE, SAMPLE, HALT, ACTIVE, BPA, BPC, NOISE_AMP, LIMIT = range(11)
+
+
+class _MemberEnv:
+    """what a member's hook sees of the population's environment at the end of its episode of n steps"""
+
+    def __init__(self, env, m, n):
+        self.setup, self.te, self.dt, self.is_fluid = env.setup, env.te, env.dt, env.is_fluid
+        self.stream, self.B = env.stream, 1
+        self.y = env.y[m:m + 1]
+        self.time = _episode_time(env.dt, n)
+
+
+def _refuse(msg):
+    raise _lib.PdecError("Population: " + msg)
+
+
+class Population:
+    def __init__(self, setup, agents, hooks, stream_env, dtype=torch.float64, device="cuda:0"):
+        from .run import device_episodes_ok
+        M = len(agents)
+        if M < 1 or len(hooks) != M:
+            _refuse("needs one hook per agent and at least one member")
+        name = type(setup).__name__
+        if getattr(setup, "is_fluid", False) or getattr(setup, "is_kseg2d", False):
+            _refuse(f"{name} is not served (its batched step, part streams and initialisers need their own check); "
+                    "KSSetup and KellerSegelSetup are")
+        if dtype != torch.float64:
+            _refuse("fp64 environments only (the shape of every reference-shaped run)")
+        if getattr(setup, "memory_size", 0):
+            _refuse("memory_size > 0 is not on the device-episode path")
+        if stream_env is None:
+            _refuse("needs an explicit environment stream (make_streams)")
+        self.setup, self.agents, self.hooks, self.M = setup, list(agents), list(hooks), M
+        probe = PDEenv(setup, B=1, dtype=dtype, device=device, stream=stream_env, autoreset=False)
+        a0 = agents[0]
+        for m, (ag, hk) in enumerate(zip(agents, hooks)):
+            if not isinstance(ag, Agent) or type(hk) is not PDEhook:
+                _refuse(f"member {m}: an Agent with a PDEhook is needed")
+            pol = ag.policy
+            if getattr(pol, "mono", None) or getattr(pol, "reward_group", None) is not None:
+                _refuse(f"member {m}: the global/mono agent and reward groups are not served")
+            if pol.reducer is not None:
+                _refuse(f"member {m}: a reducer is not on the device-episode path")
+            if pol.memory_size:
+                _refuse(f"member {m}: memory_size > 0 is not on the device-episode path")
+            if pol.sampling != "device":
+                _refuse(f"member {m}: host sampling is not on the device-episode path")
+            if hk.log_trajectory != 0:
+                _refuse(f"member {m}: log_trajectory != 0 is not on the device-episode path")
+            if not device_episodes_ok(ag, probe, StopAfterEpisode(1), hk):
+                _refuse(f"member {m}: a solo run would not take the device-episode path (run.device_episodes_ok: "
+                        "start policy, sampling, small update, streams)")
+            for k in ("update_after", "update_freq", "update_loops", "batch_size", "start_steps", "y", "quirk",
+                      "quirk_frozen_targets", "act_limit", "p"):
+                if getattr(pol, k) != getattr(a0.policy, k):
+                    _refuse(f"member {m}: hyper-parameter {k} differs from member 0's")
+            for attr in ("behavior_actor", "behavior_critic"):
+                if getattr(pol, attr).optimizer.eta != getattr(a0.policy, attr).optimizer.eta:
+                    _refuse(f"member {m}: {attr} learning rate differs from member 0's")
+                if getattr(pol, attr).model.dims != getattr(a0.policy, attr).model.dims:
+                    _refuse(f"member {m}: network shapes differ from member 0's")
+            if type(pol.start_policy) is not type(a0.policy.start_policy):
+                _refuse(f"member {m}: start policy differs from member 0's")
+            tr = ag.trajectory
+            if tr.capacity != a0.trajectory.capacity or tr.stride != a0.trajectory.stride:
+                _refuse(f"member {m}: replay capacity differs from member 0's")
+            if tr.stream.cuda_stream != a0.trajectory.stream.cuda_stream:
+                _refuse(f"member {m}: update stream differs from member 0's")
+        probe.close()
+        self.stream_env, self.stream_upd = stream_env, a0.trajectory.stream
+        if self.stream_env.cuda_stream == self.stream_upd.cuda_stream:
+            _refuse("the environment and the networks need two different streams")
+        self.env = PDEenv(setup, B=M, dtype=dtype, device=device, stream=stream_env, autoreset=False)
+        self.lib = lib = self.env.lib
+        _lib.check(lib.pdec_env_set_member_layout(self.env.handle, 1))
+        ns, A = setup.state_shape
+        self.cols = A
+        pol0, tr0 = a0.policy, a0.trajectory
+        with _on_stream(self.stream_upd):
+            self.rows = torch.zeros((M, ROW), dtype=torch.int64, device=self.env.device)
+        H = (_lib.Handle * M)
+        hs = [H(*[int(getattr(getattr(ag.policy, k).model.handle, "value", getattr(ag.policy, k).model.handle)) for ag in agents])
+              for k in ("behavior_actor", "behavior_critic", "target_actor", "target_critic")]
+        traces = (C.c_void_p * (4 * M))(*[t.data_ptr() for ag in agents for t in (ag.trajectory.state, ag.trajectory.action,
+                                                                                    ag.trajectory.reward, ag.trajectory.terminal)])
+        seeds = (C.c_uint64 * (2 * M))(*[s for ag in agents for s in (ag.policy._noise_seed, ag.policy._sample_seed)])
+        losses = (C.c_void_p * M)(*[ag.policy._losses.data_ptr() for ag in agents])
+        self._h = _lib.Handle()
+        _lib.check(lib.pdec_population_create(
+            C.byref(self._h), M, hs[0], hs[1], hs[2], hs[3], traces, seeds, losses, _lib.dtype_code(dtype), A, tr0.capacity,
+            tr0.stride, int(pol0.update_loops), int(pol0.batch_size), float(pol0.y), pol0.rho_effective, int(pol0.quirk),
+            float(pol0.behavior_actor.optimizer.eta), float(pol0.behavior_critic.optimizer.eta), int(pol0.update_after * tr0.stride),
+            int(pol0.update_freq), int(pol0.start_steps), _lib.ptr(self.rows)))
+        for ag in agents:
+            ag.policy.set_reward_interleave(1)
+        with _on_stream(self.stream_upd):
+            self._which = torch.zeros(M, dtype=torch.int32, device=self.env.device)
+        self.episode_steps = []       # per episode: the control steps each member executed (0: idle)
+        # host seconds per phase, summed over episodes: issue = initialisers + every enqueue up to the read-back,
+        # readback = waiting for the device, settle = the members' host bookkeeping and the boundary launches
+        self.timing = dict(episodes=0, issue_s=0.0, readback_s=0.0, settle_s=0.0)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.pdec_destroy(self._h)
+            self._h = _lib.Handle()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- the episode loop
+    def run(self, stops):
+        if len(stops) != self.M or any(type(s) not in (StopAfterEpisode, StopAfterEpisodeWithMinSteps) for s in stops):
+            _refuse("one StopAfterEpisode / StopAfterEpisodeWithMinSteps per member")
+        env, M = self.env, self.M
+        s_env, s_upd = self.stream_env, self.stream_upd
+        for ag, hk in zip(self.agents, self.hooks):
+            hk(PRE_EXPERIMENT_STAGE, ag, env)
+            ag(PRE_EXPERIMENT_STAGE, env)
+        # the hooks' best / current actors (made at PRE_EXPERIMENT): the targets of the one copy launch per episode
+
+        def handle(nna):
+            return int(getattr(nna.model.handle, "value", nna.model.handle))
+        best = (_lib.Handle * M)(*[handle(hk.bestNNA) if hk.collect_NNA else 0 for hk in self.hooks])
+        cur = (_lib.Handle * M)(*[handle(hk.currentNNA) if hk.collect_NNA else 0 for hk in self.hooks])
+        _lib.check(self.lib.pdec_population_set_actor_copies(self._h, best, cur))
+        active = np.ones(M, dtype=bool)
+
+        def join():
+            s_upd.wait_stream(s_env)
+            s_env.wait_stream(s_upd)
+
+        while active.any():
+            join()
+            self._episode(active, stops)
+        join()
+        for ag, hk in zip(self.agents, self.hooks):
+            hk(POST_EXPERIMENT_STAGE, ag, env)
+        return self.hooks
+
+    def _pre_episode(self, active):
+        """env.reset(), agent PRE_EPISODE (the dummy pop), hook PRE_EPISODE (random inits: one launch for all members); the
+        rows of idle members are restored afterwards"""
+        env, M, lib = self.env, self.M, self.lib
+        idle = np.flatnonzero(~active)
+        with _on_stream(self.stream_env):
+            keep_y, keep_s = (env.y[idle].clone(), env.state[idle].clone()) if idle.size else (None, None)
+        env.reset()
+        for m in np.flatnonzero(active):
+            self.agents[m](PRE_EPISODE_STAGE, env)          # host counters only (pop_sa)
+        rnd = [m for m in np.flatnonzero(active) if self.hooks[m].use_random_init]
+        with _on_stream(self.stream_env):
+            if rnd:
+                nblk = (env.random_init_coefficients() + 3) // 4
+                seeds = torch.tensor([self.hooks[m].init_seed if m in rnd else 0 for m in range(M)], dtype=torch.int64)
+                offs = torch.tensor([self.hooks[m]._init_off if m in rnd else 0 for m in range(M)], dtype=torch.int64)
+                so = torch.stack([seeds, offs]).to(env.device, non_blocking=False)
+                drawn = torch.empty_like(env.y)
+                _lib.check(lib.pdec_env_random_init_members(env.handle, _lib.ptr(so[0]), _lib.ptr(so[1]), _lib.ptr(drawn)))
+                for m in rnd:
+                    self.hooks[m]._init_off += nblk
+                mask = torch.zeros(M, dtype=torch.bool)
+                mask[rnd] = True
+                mask = mask.to(env.device)
+                y0 = torch.where(mask.view((M,) + (1,) * (env.y.dim() - 1)), drawn, env.y0)
+                env.y0 = y0
+                env.y.copy_(y0)
+                # the re-initialised members' states only: the others keep their reset state, as their solo hooks leave it
+                st = env.featurize(env.y, env.state if env.setup.temporal_steps > 1 else None)
+                env.state.copy_(torch.where(mask.view((M,) + (1,) * (env.state.dim() - 1)), st, env.state))
+                env._state0.copy_(env.state)
+            if idle.size:
+                ii = torch.as_tensor(idle, device=env.device)
+                env.y.index_copy_(0, ii, keep_y)
+                env.state.index_copy_(0, ii, keep_s)
+
+    def _episode(self, active, stops):
+        env, M, lib, cols = self.env, self.M, self.lib, self.cols
+        s_env, s_upd = self.stream_env, self.stream_upd
+        P = _lib.ptr
+        t0 = time.perf_counter()
+        self._pre_episode(active)
+        T = _episode_steps(env)
+        logs = getattr(self, "_logs", None)
+        if logs is None or logs.T != T:
+            with _on_stream(s_env):
+                logs = self._logs = _EpisodeLogs(env, T)
+                self._flags = torch.zeros((T, M), dtype=torch.int32, device=env.device)     # per step: the members' done flags
+        flags = self._flags
+        # ---- the counter table of this episode (one upload)
+        rows = np.zeros((M, ROW), dtype=np.int64)
+        for m, ag in enumerate(self.agents):
+            pol, tr = ag.policy, ag.trajectory
+            rows[m, [USTEP, NSA, NRT, NOISE, SAMPLE]] = (pol.update_step, tr.n_sa, tr.n_rt, pol._noise_off, pol._sample_off)
+            rows[m, HALT], rows[m, ACTIVE] = (0, 1) if active[m] else (1, 0)
+            rows[m, NOISE_AMP:LIMIT + 1] = np.array([float(pol.act_noise), float(pol.act_limit)], dtype=np.float64).view(np.int64)
+        _lib.check(lib.pdec_population_bp_sel(self._h, rows.ctypes.data_as(C.c_void_p), 0))
+        start = rows.copy()
+        with _on_stream(s_env):
+            logs.y[0].copy_(env.y)
+            logs.state[0].copy_(env.state)
+            flags.zero_()
+        with _on_stream(s_upd):
+            self.rows.copy_(torch.from_numpy(rows))
+        from .pipeline import _Event
+        ev_act, ev_env = _Event(lib), _Event(lib)
+        s_upd.wait_stream(s_env)
+        s_env.wait_stream(s_upd)
+        # (per step: the member-indexed glue and update on the networks' stream, the member-layout env step on the env's)
+        for t in range(T):
+            _lib.check(lib.pdec_population_glue(self._h, 0, P(logs.reward[t - 1]) if t else None, P(flags[t - 1]) if t else None,
+                                                P(logs.state[t]), P(logs.action[t + 1])))
+            ev_act.record(s_upd)
+            ev_act.wait(s_env)
+            _lib.check(lib.pdec_population_update(self._h))
+            _lib.check(lib.pdec_env_step(env.handle, P(logs.y[t]), P(logs.action[t + 1]), P(logs.action[t]), P(logs.state[t]),
+                                         P(logs.y[t + 1]), P(logs.p[t]), P(logs.state[t + 1]), P(logs.reward[t]), P(flags[t])))
+            ev_env.record(s_env)
+            ev_env.wait(s_upd)
+        _lib.check(lib.pdec_population_glue(self._h, 1, P(logs.reward[T - 1]), P(flags[T - 1]), None, None))   # the time-out push
+        with _on_stream(s_upd):
+            # the per-step episode reward of PDEhook (mean over the actuators), member-major rows as a B = 1 run reduces them
+            means = logs.reward.transpose(0, 1).contiguous().reshape(M * T, -1).mean(dim=1)
+            pack = torch.cat([self.rows.view(-1).view(torch.uint8), flags.view(-1).view(torch.uint8), means.view(-1).view(torch.uint8)])
+            t1 = time.perf_counter()
+            host = pack.cpu().numpy()                                          # the one read-back (bytes)
+        t2 = time.perf_counter()
+        nr, nf = M * ROW * 8, T * M * 4
+        rows_out = host[:nr].copy().view(np.int64).reshape(M, ROW)
+        fl = host[nr:nr + nf].copy().view(np.int32).reshape(T, M)
+        mean_h = host[nr + nf:].copy().view(np.float64).reshape(M, T)
+        # ---- settle every member at its number of executed steps
+        n_of = np.zeros(M, dtype=np.int64)
+        for m in range(M):
+            if not active[m]:
+                continue
+            bad = np.flatnonzero(fl[:, m])
+            n_of[m] = int(bad[0]) + 1 if bad.size and bad[0] < T - 1 else T
+        self.episode_steps.append(n_of.copy())
+        _lib.check(lib.pdec_population_bp_sel(self._h, rows_out.ctypes.data_as(C.c_void_p), 1))
+        with _on_stream(s_env):
+            ii = torch.as_tensor(n_of, device=env.device)
+            ar = torch.arange(M, device=env.device)
+            env.y = logs.y[ii, ar].contiguous()
+            env.state = logs.state[ii, ar].contiguous()
+            # POST_EPISODE push of the final states with the zero action (active members; one launch)
+        s_upd.wait_stream(s_env)
+        _lib.check(lib.pdec_population_glue(self._h, 2, None, None, P(env.state), None))
+        want_rows = any(self.hooks[m].collect_bestDF for m in np.flatnonzero(active))
+        if want_rows:
+            with _on_stream(s_env):
+                la, lp, ly, lr = (x.cpu() for x in (logs.action, logs.p, logs.y, logs.reward))
+        np_dt = np.float64
+        which = np.zeros(M, dtype=np.int32)
+        for m in np.flatnonzero(active):
+            ag, hk, n = self.agents[m], self.hooks[m], int(n_of[m])
+            pol, tr = ag.policy, ag.trajectory
+            r = rows_out[m]
+            pol.update_step, tr.n_sa, tr.n_rt, pol._noise_off, pol._sample_off = (int(r[USTEP]), int(r[NSA]), int(r[NRT]),
+                                                                                   int(r[NOISE]), int(r[SAMPLE]))
+            if pol.update_step != start[m, USTEP] + n or tr.n_sa != start[m, NSA] + n * cols:
+                raise RuntimeError(f"Population: member {m}'s device counters disagree with its {n} executed steps")
+            _add_episode_reward(hk, mean_h[m, :n], np_dt)
+            if hk.collect_bestDF:
+                hk._rows_bulk = (list(range(1, n + 1)), la[1:n + 1, m], lp[:n, m], ly[1:n + 1, m], lr[:n, m])
+            fired = _stop_fired(stops[m], ag, n)
+            ag.end_episode(env.state[m], pushed=True)          # POST_EPISODE: its push went out above, one launch for all
+            with _on_stream(s_env):
+                new_best = hk.end_episode(_MemberEnv(env, m, n))
+            which[m] = (1 if new_best else 0) | (2 if hk.collect_NNA else 0)
+            if fired:
+                active[m] = False
+        if which.any():                                        # the hooks' best / current actor copies: one launch
+            with _on_stream(s_upd):
+                self._which.copy_(torch.from_numpy(which))
+            _lib.check(lib.pdec_population_copy_actors(self._h, P(self._which)))
+        s_env.wait_stream(s_upd)
+        t3 = time.perf_counter()
+        tm = self.timing
+        tm["episodes"] += 1
+        tm["issue_s"] += t1 - t0
+        tm["readback_s"] += t2 - t1
+        tm["settle_s"] += t3 - t2

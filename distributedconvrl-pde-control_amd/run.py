@@ -157,6 +157,42 @@ def _episode_steps(env):
             return n
 
 
+class _Ended:
+    """what the stop condition sees of the environment at a step of an episode issued in one go"""
+
+    def __init__(self, ended):
+        self.ended = ended
+
+    def is_terminated(self):
+        return self.ended
+
+
+def _episode_time(dt, n):
+    """env.time after n control steps, with the floating-point sum the step loop makes"""
+    t = 0.0
+    for _ in range(n):
+        t += dt
+    return t
+
+
+def _add_episode_reward(hook, means, np_dt):
+    """PDEhook's POST_ACT reward bookkeeping of an episode's n steps (src/PDEhook.jl:51-63) in the order the step loop adds:
+    means = the n per-step means over the actuators (host array)"""
+    m = means.astype(np_dt)
+    acc = m[0]
+    for v in m[1:]:
+        acc = np_dt(acc + v)
+    hook.reward += float(acc)
+
+
+def _stop_fired(stop_condition, agent, n):
+    """the stop condition called once per executed step of an episode, as the stage loop calls it; True when it fired"""
+    fired = False
+    for i in range(n):
+        fired = stop_condition(agent, _Ended(i == n - 1)) or fired
+    return fired
+
+
 def _launch_sync_ok(env):
     """the fused fp64 KS step of one trajectory with 192 / 240 / 600 cells: the launch that honours pdec_set_launch_sync"""
     import torch
@@ -319,13 +355,6 @@ def _run_device_episodes(agent, env, stop_condition, hook, s_env, s_upd):
             s_upd.wait_stream(s_env)
             s_env.wait_stream(s_upd)
 
-    class _Ended:                      # what the stop condition sees of the environment at a step
-        def __init__(self, ended):
-            self.ended = ended
-
-        def is_terminated(self):
-            return self.ended
-
     def episode():
         """enqueue the T control steps, read back once, settle the host state; returns True when the stop condition fired"""
         with _on_stream(s_env):
@@ -410,22 +439,13 @@ def _run_device_episodes(agent, env, stop_condition, hook, s_env, s_upd):
         env._adopted.update((env.action.data_ptr(), env._action_prev.data_ptr()))          # views of the log: never written by the env
         env.p, env.reward, env._done_flags = logs.p[n - 1], logs.reward[n - 1], logs.done[n - 1:n]
         env.steps = n
-        env.time = 0.0
-        for _ in range(n):
-            env.time += env.dt
+        env.time = _episode_time(env.dt, n)
         env._done_stale = True
         # ---- the hook's POST_ACT bookkeeping of the n steps (src/PDEhook.jl:51-63)
-        m = means[:n].cpu().numpy().astype(np_dt)
-        acc = m[0]
-        for v in m[1:]:
-            acc = np_dt(acc + v)
-        hook.reward += float(acc)
+        _add_episode_reward(hook, means[:n].cpu().numpy(), np_dt)
         if hook.collect_bestDF:
             hook._rows_bulk = (list(range(1, n + 1)), logs.action[1:n + 1, 0], logs.p[:n, 0], logs.y[1:n + 1, 0], logs.reward[:n, 0])
-        fired = False
-        for i in range(n):
-            fired = stop_condition(agent, _Ended(i == n - 1)) or fired
-        return fired
+        return _stop_fired(stop_condition, agent, n)
 
     hook(PRE_EXPERIMENT_STAGE, agent, env)
     agent(PRE_EXPERIMENT_STAGE, env)

@@ -480,6 +480,44 @@ int pdec_env_autoreset(pdec_handle env, const int32_t* done, void* y, const void
  * (Julia's global RNG cannot be reproduced, only the distribution; oracle/rng.py restates this stream).  Consumes
  * B * ceil(n_coefficients / 4) counters. */
 int pdec_env_random_init(pdec_handle env, uint64_t seed, uint64_t offset, void* y0_out);
+/* the same for the members of a population (the 1-D KS and Keller-Segel setups): trajectory b drawn from the stream
+ * (seeds[b], offsets[b]) exactly as a B = 1 pdec_env_random_init(seeds[b], offsets[b]) draws it; seeds / offsets are DEVICE
+ * arrays of B entries.  One launch. */
+int pdec_env_random_init_members(pdec_handle env, const uint64_t* seeds, const uint64_t* offsets, void* y0_out);
+/* Populations (population.py): every trajectory of the batch is an independent member.  on = 1: the KS step integrates one
+ * trajectory per workgroup instead of two per complex FFT, so trajectory b's outputs are bit for bit those of a B = 1 step
+ * on its inputs, whatever the other trajectories hold (the 1-D Keller-Segel step already runs one per workgroup). */
+int pdec_env_set_member_layout(pdec_handle env, int on);
+
+/* ---------------------------------------------------------------- populations of single-trajectory learners
+ * M independent reference-shaped DDPG learners (B = 1, small-batch update with device-side sampling, glue launch) whose
+ * per-step launches are ONE launch of M workgroups each.  Member m: its four networks (fp32, one stream shared by all
+ * members), traces[4m .. 4m+3] = its replay's state / action / reward / terminal traces (capacity + stride rows for s / a,
+ * capacity for r / t), seeds[2m], seeds[2m+1] = its noise / sample seeds, losses[m] = its fp32 loss pair.  rows = a DEVICE
+ * int64 [M][16] table of per-member counters in the order update_step, n_sa, n_rt, noise offset, sample offset, halt flag,
+ * active, actor / critic beta-power slot, act_noise, act_limit (the last two as bit patterns of doubles); the caller writes
+ * it before an episode, the launches below advance it as the solo run's host counters advance, and the caller reads it back
+ * after the episode.  The members' slices of the per-step buffers lie cols * width * dtype-size bytes apart. */
+int pdec_population_create(pdec_handle* out, int M, const pdec_handle* actors, const pdec_handle* critics,
+                           const pdec_handle* target_actors, const pdec_handle* target_critics, void* const* traces,
+                           const uint64_t* seeds, void* const* losses, int env_dtype, int cols, int64_t capacity, int stride,
+                           int loops, int Bu, double gamma, double rho, int quirk, double eta_actor, double eta_critic,
+                           int64_t update_after_rows, int64_t update_freq, int64_t start_steps, int64_t* rows);
+/* phase 0: pdec_step_glue of one control step for every member (reward / done_flags of the previous step or both NULL,
+ * state [M][cols][ns], actions_out [M][cols][na]); phase 1: the time-out push of the last step's rewards; phase 2: the
+ * POST_EPISODE push of the final state with a zero action for the active members.  One launch of M workgroups. */
+int pdec_population_glue(pdec_handle pop, int phase, const void* reward, const int32_t* done_flags, const void* state,
+                         void* actions_out);
+/* pdec_ddpg_update_small_rng for every member whose own trigger fires (min(n_rt, capacity) > update_after_rows,
+ * update_step % update_freq == 0, not halted); one launch of M workgroups */
+int pdec_population_update(pdec_handle pop);
+/* set = 0: write each member's beta-power slots into rows_host[m][7], [m][8]; set = 1: adopt them from there */
+int pdec_population_bp_sel(pdec_handle pop, int64_t* rows_host, int set);
+/* the members' hooks' actor snapshots (best[m], current[m]: fp32 networks of the actor's shape on the networks' stream, 0 =
+ * none); pdec_population_copy_actors then copies member m's behaviour actor parameters into best[m] where bit 0 of which[m]
+ * is set and into current[m] where bit 1 is (which: DEVICE int32 [M]), for all members in one launch */
+int pdec_population_set_actor_copies(pdec_handle pop, const pdec_handle* best, const pdec_handle* current);
+int pdec_population_copy_actors(pdec_handle pop, const int32_t* which);
 
 /* ---------------------------------------------------------------- episode ledger (PDEhook's bookkeeping, src/PDEhook.jl:51-97) */
 /* The episode returns, blow-up bits and best actor of a batched training run, kept on the device: no launch argument depends
