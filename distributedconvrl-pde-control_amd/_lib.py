@@ -134,6 +134,7 @@ DEBUG_SIGNATURES = {
     "pdec_debug_kseg2d_probe": [Handle, _i, _i, _i, _pd],
     "pdec_debug_spin_us": [_vp, _d],
     "pdec_debug_small_update_kernel": [Handle, Handle, Handle, Handle, _i, _i, _d, _i, C.c_char_p, _i, C.POINTER(_i64)],
+    "pdec_debug_batched_update_route": [Handle, Handle, Handle, Handle, _i, _i, C.c_char_p, _i, C.POINTER(_i64)],
 }
 _RESTYPES = {"pdec_last_error": C.c_char_p}
 

@@ -897,15 +897,28 @@ static int actor_grads_t(Mlp* A, Mlp* C, const void* s, int Bu, double grad_scal
   return A->backward<T>(dA, 1, Bu, true, false, grad_scale);
 }
 
+// Which family serves the pass of a pair: the 3-layer fused kernels (mlp_mfma.hip), the 2-layer ones (mlp_mfma2.hip) or the
+// generic fp32 / fp64 launch sequence.  one_stream: the networks the pass touches all run on the critic's stream.
+enum PassRoute { ROUTE_GENERIC = 0, ROUTE_FUSED3 = 1, ROUTE_FUSED2 = 2 };
+static PassRoute pass_route(const Mlp* A, const Mlp* C, bool one_stream) {
+  if (one_stream && fused_supported(A, C)) return ROUTE_FUSED3;
+  if (one_stream && fused2_supported(A, C)) return ROUTE_FUSED2;
+  return ROUTE_GENERIC;
+}
+// pdec_ddpg_update_async applies ADAM + Polyak inside the finish launch of a fused pass (4 launches); the 2-layer family only
+// from 64 columns on -- below, the passes are the same kernels and ADAM / Polyak are launches of their own
+static bool update_applies_in_finish(PassRoute rt, int Bu) { return rt == ROUTE_FUSED3 || (rt == ROUTE_FUSED2 && Bu >= 64); }
+
 // the critic pass on arguments reward_group_route has already settled (loss_add: its loss correction, or null)
 static int critic_grads_routed(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const void* a, const void* r, const void* t,
                                const void* snext, int Bu, double gamma, int quirk, double grad_scale, void* critic_loss_dev,
                                const void* loss_add) {
   int rc;
-  if (fused_supported(A, C) && A->stream == C->stream && At->stream == C->stream && Ct->stream == C->stream)
+  const PassRoute route = pass_route(A, C, A->stream == C->stream && At->stream == C->stream && Ct->stream == C->stream);
+  if (route == ROUTE_FUSED3)
     rc = fused_critic_grads(A, C, At, Ct, s, a, r, t, snext, Bu, (double)(float)gamma, quirk, grad_scale, critic_loss_dev, nullptr,
                             loss_add);
-  else if (fused2_supported(A, C) && A->stream == C->stream && At->stream == C->stream && Ct->stream == C->stream)
+  else if (route == ROUTE_FUSED2)
     rc = fused2_critic_grads(A, C, At, Ct, s, a, r, t, snext, Bu, (double)(float)gamma, quirk, grad_scale, critic_loss_dev, nullptr,
                              loss_add);
   else
@@ -951,8 +964,9 @@ int pdec_ddpg_actor_grads(pdec_handle hA, pdec_handle hC, const void* s, int Bu,
   PDEC_REQUIRE(s && Bu >= 1, "pdec_ddpg_actor_grads: null/empty batch");
   PDEC_REQUIRE(A->dtype == C->dtype, "ddpg: dtype mismatch");
   int rc;
-  if (fused_supported(A, C) && A->stream == C->stream) rc = fused_actor_grads(A, C, nullptr, s, Bu, grad_scale, actor_loss_dev, nullptr);
-  else if (fused2_supported(A, C) && A->stream == C->stream) rc = fused2_actor_grads(A, C, nullptr, s, Bu, grad_scale, actor_loss_dev, nullptr);
+  const PassRoute route = pass_route(A, C, A->stream == C->stream);
+  if (route == ROUTE_FUSED3) rc = fused_actor_grads(A, C, nullptr, s, Bu, grad_scale, actor_loss_dev, nullptr);
+  else if (route == ROUTE_FUSED2) rc = fused2_actor_grads(A, C, nullptr, s, Bu, grad_scale, actor_loss_dev, nullptr);
   else rc = C->dtype == PDEC_F64 ? actor_grads_t<double>(A, C, s, Bu, grad_scale, actor_loss_dev)
                                  : actor_grads_t<float>(A, C, s, Bu, grad_scale, actor_loss_dev);
   // a reduce event (pdec_mlp_set_reduce_event) that the path taken did not put on its reduction launch: recorded behind it
@@ -1042,7 +1056,8 @@ static int ddpg_update_phases(int phase, pdec_handle hA, pdec_handle hC, pdec_ha
     quirk = rt.quirk;
     loss_add = rt.loss_add;
   }
-  if (fused_supported(A, C) && one_stream) {
+  const PassRoute route = pass_route(A, C, one_stream);
+  if (route == ROUTE_FUSED3 && update_applies_in_finish(route, Bu)) {
     // 4 launches: critic pass, reduce+ADAM(C)+Polyak(Ct), actor pass (updated critic), reduce+ADAM(A)+Polyak(At)
     const AdamPolyak apc{eta_critic, 0.9, 0.999, 1e-8, rho}, apa{eta_actor, 0.9, 0.999, 1e-8, rho};
     if ((phase & 1) &&
@@ -1051,7 +1066,7 @@ static int ddpg_update_phases(int phase, pdec_handle hA, pdec_handle hC, pdec_ha
     if (phase & 2) return fused_actor_grads(A, C, At, s, Bu, 1.0, l1, &apa);
     return PDEC_OK;
   }
-  if (fused2_supported(A, C) && one_stream && Bu >= 64) {      // 2-layer nets, large batches: same 4 launches
+  if (route == ROUTE_FUSED2 && update_applies_in_finish(route, Bu)) {      // 2-layer nets, large batches: same 4 launches
     const AdamPolyak apc{eta_critic, 0.9, 0.999, 1e-8, rho}, apa{eta_actor, 0.9, 0.999, 1e-8, rho};
     if ((phase & 1) &&
         (rc = fused2_critic_grads(A, C, At, Ct, s, a, r, t, snext, Bu, (double)(float)gamma, quirk, 1.0, l0, &apc, loss_add)))
@@ -1059,16 +1074,18 @@ static int ddpg_update_phases(int phase, pdec_handle hA, pdec_handle hC, pdec_ha
     if (phase & 2) return fused2_actor_grads(A, C, At, s, Bu, 1.0, l1, &apa);
     return PDEC_OK;
   }
+  // ADAM + Polyak through pdec_adam_polyak_step, the entry the data-parallel split sequence calls behind its all-reduce: a
+  // network that entry updates with the fused families' fp32 apply kernel (any fp32 2-layer net, a 3-layer net with an image)
+  // is updated by the same kernel here, so one GPU and several leave the same bits on every shape (the generic pdec_adam_step
+  // rounds once from double: a last-bit difference from the second step on)
   if (phase & 1) {
     if ((rc = critic_grads_routed(A, C, At, Ct, s, a, r, t, snext, Bu, gamma, quirk, 1.0, l0, loss_add))) return rc;
-    if ((rc = pdec_adam_step(hC, eta_critic, 0.9, 0.999, 1e-8))) return rc;         // :400
-    if ((rc = pdec_polyak(hCt, hC, rho))) return rc;                                // :415-417 (critic pair)
+    if ((rc = pdec_adam_polyak_step(hC, hCt, eta_critic, 0.9, 0.999, 1e-8, rho))) return rc;      // :400, :415-417 (critic pair)
   }
   if (phase & 2) {
     if ((rc = pdec_ddpg_actor_grads(hA, hC, s, Bu, 1.0, l1))) return rc;
     if (A->stream != C->stream) PDEC_HIP(hipStreamSynchronize(C->stream));
-    if ((rc = pdec_adam_step(hA, eta_actor, 0.9, 0.999, 1e-8))) return rc;          // :412
-    if ((rc = pdec_polyak(hAt, hA, rho))) return rc;                                // :415-417 (actor pair)
+    if ((rc = pdec_adam_polyak_step(hA, hAt, eta_actor, 0.9, 0.999, 1e-8, rho))) return rc;       // :412, :415-417 (actor pair)
   }
   return PDEC_OK;
 }
@@ -1315,16 +1332,29 @@ static int small_act(Mlp* M, int dtype, const void* state, int cols, double act_
   return PDEC_OK;
 }
 
+// a 3-layer fp32 actor whose published image the fused acting kernel reads
+static bool fused_act_ok(const Mlp* M) { return fused_net_supported(M) && M->dims[M->L] == 1 && M->dims[1] <= 31; }
+
+// what serves pdec_policy_act_rng for `cols` states
+enum ActRoute { ACT_GENERIC = 0, ACT_FUSED3 = 1, ACT_FUSED2 = 2, ACT_SMALL = 3 };
+static ActRoute act_route(const Mlp* M, int cols) {
+  if (fused_act_ok(M)) return ACT_FUSED3;
+  if (fused2_act_supported(M, cols)) return ACT_FUSED2;
+  if (small_act_ok(M, M->dtype, cols)) return ACT_SMALL;
+  return ACT_GENERIC;
+}
+
 extern "C" {
 
 static int policy_act_rng_impl(pdec_handle actor, Mlp* M, const void* state, int cols, double act_noise, double act_limit,
                                int learning, uint64_t seed, uint64_t offset, void* actions_out, const uint64_t* ctr_cur,
                                uint64_t* ctr_next, uint64_t ctr_inc) {
-  if (fused_net_supported(M) && M->dims[M->L] == 1 && M->dims[1] <= 31)
+  const ActRoute route = act_route(M, cols);
+  if (route == ACT_FUSED3)
     return fused_policy_act(M, state, cols, act_noise, act_limit, learning, seed, offset, actions_out, ctr_cur, ctr_next, ctr_inc);
-  if (fused2_act_supported(M, cols))
+  if (route == ACT_FUSED2)
     return fused2_policy_act(M, state, cols, act_noise, act_limit, learning, seed, offset, actions_out, ctr_cur, ctr_next, ctr_inc);
-  if (small_act_ok(M, M->dtype, cols))
+  if (route == ACT_SMALL)
     return small_act(M, M->dtype, state, cols, act_noise, act_limit, learning, seed, offset, actions_out, ctr_cur, ctr_next, ctr_inc);
   void* noise = nullptr;
   const size_t n = (size_t)cols * M->dims[M->L];
@@ -1352,6 +1382,45 @@ int pdec_policy_act_rng(pdec_handle actor, const void* state, int cols, double a
 // agent(env) for an environment that computes in `state_dtype` with an actor of another parameter type (the reference: fp64
 // fields, Float32 networks) WITHOUT a promoted copy of the actor: *served = 1 and the action is enqueued when the single-launch
 // form covers the case, *served = 0 (nothing enqueued) otherwise -- the caller then acts through a promoted clone.
+int pdec_debug_batched_update_route(pdec_handle hA, pdec_handle hC, pdec_handle hAt, pdec_handle hCt, int Bu, int which, char* name,
+                                    int name_len, int64_t* lds_bytes) {
+  PDEC_REQUIRE(name && name_len > 0 && lds_bytes, "pdec_debug_batched_update_route: null argument");
+  PDEC_REQUIRE(which >= 0 && which <= 4 && Bu >= 1, "pdec_debug_batched_update_route: which = %d, Bu = %d", which, Bu);
+  GET_MLP(A, hA);
+  *lds_bytes = 0;
+  if (which == 4) {                    // pdec_policy_act_rng on Bu states
+    const ActRoute ar = act_route(A, Bu);
+    if (ar == ACT_FUSED3) return fused_act_describe(A, name, name_len, lds_bytes);
+    if (ar == ACT_FUSED2) return fused2_act_describe(A, name, name_len, lds_bytes);
+    snprintf(name, name_len, "%s", ar == ACT_SMALL ? "small_act_kernel" : "generic");
+    return PDEC_OK;
+  }
+  GET_MLP(C, hC);
+  const bool actor_pass = which == 1 || which == 3, all_four = !(which == 1);
+  PDEC_REQUIRE(A->dtype == C->dtype, "ddpg: dtype mismatch");
+  bool one_stream = A->stream == C->stream;
+  if (all_four) {
+    GET_MLP(At, hAt);
+    GET_MLP(Ct, hCt);
+    PDEC_REQUIRE(At->dtype == C->dtype && Ct->dtype == C->dtype, "ddpg: dtype mismatch");
+    PDEC_REQUIRE(At->dims == A->dims && Ct->dims == C->dims, "ddpg: target networks must have the behaviour networks' shapes");
+    one_stream = one_stream && At->stream == C->stream && Ct->stream == C->stream;
+  }
+  // inside the update's generic branch the actor pass is pdec_ddpg_actor_grads, which looks at A and C only
+  const PassRoute full = pass_route(A, C, one_stream);
+  const PassRoute rt = (which == 3 && !update_applies_in_finish(full, Bu)) ? pass_route(A, C, A->stream == C->stream) : full;
+  int rc = PDEC_OK;
+  if (rt == ROUTE_FUSED3) rc = fused_describe(A, C, actor_pass, name, name_len, lds_bytes);
+  else if (rt == ROUTE_FUSED2) rc = fused2_describe(A, C, actor_pass, name, name_len, lds_bytes);
+  else snprintf(name, name_len, "generic");
+  if (rc) return rc;
+  if (which >= 2 && rt != ROUTE_GENERIC && !update_applies_in_finish(full, Bu)) {
+    const size_t n = strlen(name);
+    snprintf(name + n, (size_t)name_len > n ? name_len - n : 0, "/adam_apart");
+  }
+  return PDEC_OK;
+}
+
 int pdec_policy_act_rng_as(pdec_handle actor, int state_dtype, const void* state, int cols, double act_noise, double act_limit,
                            int learning, uint64_t seed, uint64_t offset, void* actions_out, int* served) {
   GET_MLP(M, actor);
@@ -1647,7 +1716,7 @@ int pdec_mlp_set_noise_rows(pdec_handle actor, int rows) {
 int pdec_mlp_acts_on_published_copy(pdec_handle actor, int* yes) {
   GET_MLP(M, actor);
   PDEC_REQUIRE(yes, "pdec_mlp_acts_on_published_copy: null");
-  *yes = (fused_net_supported(M) && M->dims[M->L] == 1 && M->dims[1] <= 31) ? 1 : 0;
+  *yes = fused_act_ok(M) ? 1 : 0;
   return PDEC_OK;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -123,6 +124,11 @@ struct CriticRoute {
 };
 int reward_group_route(Mlp* C, const void* r, int Bu, int quirk, CriticRoute* out);
 
+// a padded tile count as a type: the dispatch of the fused passes hands the instantiation it picked to a generic lambda, so the
+// launch and the report of pdec_debug_batched_update_route go through one chain of comparisons
+template <int N>
+using tile_c = std::integral_constant<int, N>;
+
 // mlp_mfma.hip: fused fp32 MFMA DDPG passes (3-layer actor/critic pairs)
 struct AdamPolyak {
   double eta, b1, b2, eps, rho;
@@ -144,6 +150,10 @@ int fused_policy_act(Mlp* A, const void* state, int cols, double act_noise, doub
                      uint64_t seed, uint64_t offset, void* actions_out, const uint64_t* ctr_cur = nullptr,
                      uint64_t* ctr_next = nullptr, uint64_t ctr_inc = 0);
 
+// kernel name and dynamic LDS bytes of the pass / acting launch the functions above would make (nothing is launched)
+int fused_describe(const Mlp* A, const Mlp* C, bool actor_pass, char* name, int name_len, int64_t* lds);
+int fused_act_describe(const Mlp* A, char* name, int name_len, int64_t* lds);
+
 // mlp_mfma2.hip: the same passes for the reference-shaped 2-layer nets [ns, h, 1] / [ns+1, H, 1] (flat parameters, no image)
 // mean of r[0..n) in a fixed order, one block; *out = device scalar owned by C (mlp_mfma2.hip)
 int launch_rmean(Mlp* C, const float* r, int n, float** out);
@@ -159,6 +169,9 @@ int fused2_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const v
                         const AdamPolyak* apply, const void* loss_add = nullptr);
 int fused2_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
                        const AdamPolyak* apply);
+
+int fused2_describe(const Mlp* A, const Mlp* C, bool actor_pass, char* name, int name_len, int64_t* lds);
+int fused2_act_describe(const Mlp* A, char* name, int name_len, int64_t* lds);
 
 struct Population : Object {
   int M = 0, cols = 0, dtype = PDEC_F64;

@@ -978,6 +978,30 @@ __global__ __launch_bounds__(ACT_THREADS) void policy_act_fused_kernel(FNet f, c
 // ------------------------------------------------------------------ host side
 static int mt_of(int H) { return (H + 1 + 15) / 16; }
 
+// The instantiations of the two passes, X(critic tiles MT, actor tiles MTA): the ONE list behind the predicate
+// (fused_supported), the launches and the report of pdec_debug_batched_update_route
+#define FUSED3_TILES(X) X(9, 2) X(9, 1) X(2, 2) X(2, 1)
+// the acting kernel's, X(actor tiles MTA)
+#define FUSED3_ACT_TILES(X) X(2) X(1)
+
+// f(tile_c<MT>, tile_c<MTA>) of the pair's instantiation; PDEC_E_INVALID for a pair the list does not have
+template <class F>
+static int visit_tiles(int mt, int mta, F&& f) {
+#define X(MT_, MTA_) if (mt == MT_ && mta == MTA_) return f(tile_c<MT_>{}, tile_c<MTA_>{});
+  FUSED3_TILES(X)
+#undef X
+  set_error("fused 3-layer pass: no instantiation for %d critic / %d actor tiles", mt, mta);
+  return PDEC_E_INVALID;
+}
+template <class F>
+static int visit_act_tiles(int mta, F&& f) {
+#define X(MTA_) if (mta == MTA_) return f(tile_c<MTA_>{});
+  FUSED3_ACT_TILES(X)
+#undef X
+  set_error("fused act: no instantiation for %d actor tiles", mta);
+  return PDEC_E_INVALID;
+}
+
 static bool fused_disabled() {
   static int v = -1;
   if (v < 0) {
@@ -1006,7 +1030,11 @@ bool fused_supported(const Mlp* A, const Mlp* C) {
   if (A->acts[0] != PDEC_ACT_RELU || A->acts[1] != PDEC_ACT_RELU || A->acts[2] != PDEC_ACT_TANH) return false;
   if (C->acts[0] != PDEC_ACT_RELU || C->acts[1] != PDEC_ACT_RELU || C->acts[2] != PDEC_ACT_IDENTITY) return false;
   const int mt = mt_of(C->dims[1]), mta = mt_of(A->dims[1]);
-  return (mt == 9 || mt == 2) && (mta == 2 || mta == 1);
+  bool ok = false;
+#define X(MT_, MTA_) ok = ok || (mt == MT_ && mta == MTA_);
+  FUSED3_TILES(X)
+#undef X
+  return ok;
 }
 
 static int ensure_prepped(Mlp* M) {
@@ -1224,6 +1252,16 @@ int fused_unpack_published(Mlp* A, float* flat_out, hipStream_t stream) {
   return PDEC_OK;
 }
 
+// tiles and dynamic LDS bytes of the acting kernel of a fused 3-layer actor, or the refusal
+static int fused_act_plan(const Mlp* A, int* mta, size_t* lds) {
+  *mta = mt_of(A->dims[1]);
+  const int HPa = 16 * *mta;
+  *lds = ((size_t)small_floats(HPa) + (size_t)big_floats(HPa)) * 4;
+  PDEC_REQUIRE(A->acts[2] == PDEC_ACT_TANH || A->acts[2] == PDEC_ACT_IDENTITY, "fused act: unsupported output activation");
+  PDEC_REQUIRE(*mta <= 2 && *lds <= 64 * 1024, "fused act: hidden width %d too large", A->dims[1]);
+  return PDEC_OK;
+}
+
 int fused_policy_act(Mlp* A, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
                      uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc) {
   int rc = ensure_prepped(A);
@@ -1234,27 +1272,35 @@ int fused_policy_act(Mlp* A, const void* state, int cols, double act_noise, doub
   // rewritten two updates later; callers that overlap acting and updating on different streams must order update
   // t+1 behind the acting kernel of step t-1 (bench.py waits on that event at the start of each update).
   f.w = A->fw_pub[A->pub].as<float>();
-  const int mta = mt_of(A->dims[1]);
-  const int HPa = 16 * mta;
-  const size_t lds = ((size_t)small_floats(HPa) + (size_t)big_floats(HPa)) * 4;
+  int mta = 0;
+  size_t lds = 0;
+  if ((rc = fused_act_plan(A, &mta, &lds))) return rc;
   const int tanh_out = A->acts[2] == PDEC_ACT_TANH;
-  PDEC_REQUIRE(A->acts[2] == PDEC_ACT_TANH || A->acts[2] == PDEC_ACT_IDENTITY, "fused act: unsupported output activation");
-  PDEC_REQUIRE(mta <= 2 && lds <= 64 * 1024, "fused act: hidden width %d too large", A->dims[1]);
   const int prio = env_prio("PDEC_PRIO_ACT", 3);
   const dim3 grid((cols + 63) / 64), block(ACT_THREADS);
+  rc = visit_act_tiles(mta, [&](auto MTA) {
+    auto kern = policy_act_fused_kernel<decltype(MTA)::value>;
 #define ACT_ARGS f, (const float*)state, cols, A->dims[0], (float)act_noise, (float)act_limit, learning, tanh_out, seed, offset, \
                  (float*)actions_out, ctr_cur, ctr_next, ctr_inc, prio
-  if (A->prof) {
-    if (mta == 1) PDEC_TIMED_LAUNCH(A, "policy_act_fused", policy_act_fused_kernel<1>, grid, block, lds, ACT_ARGS);
-    else PDEC_TIMED_LAUNCH(A, "policy_act_fused", policy_act_fused_kernel<2>, grid, block, lds, ACT_ARGS);
-  } else if (mta == 1) {
-    hipLaunchKernelGGL(policy_act_fused_kernel<1>, grid, block, lds, A->stream, ACT_ARGS);
-  } else {
-    hipLaunchKernelGGL(policy_act_fused_kernel<2>, grid, block, lds, A->stream, ACT_ARGS);
-  }
+    if (A->prof) PDEC_TIMED_LAUNCH(A, "policy_act_fused", kern, grid, block, lds, ACT_ARGS);
+    else hipLaunchKernelGGL(kern, grid, block, lds, A->stream, ACT_ARGS);
 #undef ACT_ARGS
+    return (int)PDEC_OK;
+  });
+  if (rc) return rc;
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
+}
+
+int fused_act_describe(const Mlp* A, char* name, int name_len, int64_t* lds_out) {
+  int mta = 0;
+  size_t lds = 0;
+  if (int rc = fused_act_plan(A, &mta, &lds)) return rc;
+  return visit_act_tiles(mta, [&](auto MTA) {
+    snprintf(name, name_len, "policy_act_fused_kernel<%d>", decltype(MTA)::value);
+    *lds_out = (int64_t)lds;
+    return (int)PDEC_OK;
+  });
 }
 
 // ADAM(M) + Polyak(Mt <- M) + image refresh from the gradient buffer (after an external all-reduce)
@@ -1289,13 +1335,24 @@ int fused_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const vo
   }
   C->rbar_ext = nullptr;
   C->rpart_ext = nullptr;
-  if (mt == 9 && mta == 2) rc = launch_critic<9, 2>(C, g, grid);
-  else if (mt == 9 && mta == 1) rc = launch_critic<9, 1>(C, g, grid);
-  else if (mt == 2 && mta == 2) rc = launch_critic<2, 2>(C, g, grid);
-  else rc = launch_critic<2, 1>(C, g, grid);
+  rc = visit_tiles(mt, mta, [&](auto MT, auto MTA) {
+    return launch_critic<decltype(MT)::value, decltype(MTA)::value>(C, g, grid);
+  });
   if (rc) return rc;
   return launch_finish(C, apply ? Ct : nullptr, C->fslab.as<float>(), grid, mt, grad_scale, 0, Bu, quirk, loss_dev, apply,
                        loss_add);
+}
+
+// what fused_critic_grads / fused_actor_grads would launch for this pair (pdec_debug_batched_update_route): through the same
+// visitor and the same lds_bytes<> as launch_critic / launch_actor
+int fused_describe(const Mlp* A, const Mlp* C, bool actor_pass, char* name, int name_len, int64_t* lds) {
+  if (int rc = split_refused()) return rc;
+  return visit_tiles(mt_of(C->dims[1]), mt_of(A->dims[1]), [&](auto MT, auto MTA) {
+    constexpr int mt_ = decltype(MT)::value, mta_ = decltype(MTA)::value;
+    snprintf(name, name_len, "%s<%d,%d>", actor_pass ? "ddpg_actor_fused_kernel" : "ddpg_critic_fused_kernel", mt_, mta_);
+    *lds = (int64_t)lds_bytes<mt_, mta_>(actor_pass);
+    return (int)PDEC_OK;
+  });
 }
 
 int fused_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
@@ -1312,10 +1369,9 @@ int fused_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double gra
   g.prio = env_prio("PDEC_PRIO_MFMA", 2);
   // the actor pass is launched on the critic's stream object for profiling labels but must follow
   // ADAM(C); both handles share one stream in every caller (checked by the dispatcher)
-  if (mt == 9 && mta == 2) rc = launch_actor<9, 2>(C, g, grid);
-  else if (mt == 9 && mta == 1) rc = launch_actor<9, 1>(C, g, grid);
-  else if (mt == 2 && mta == 2) rc = launch_actor<2, 2>(C, g, grid);
-  else rc = launch_actor<2, 1>(C, g, grid);
+  rc = visit_tiles(mt, mta, [&](auto MT, auto MTA) {
+    return launch_actor<decltype(MT)::value, decltype(MTA)::value>(C, g, grid);
+  });
   if (rc) return rc;
   (void)C;
   return launch_finish(A, apply ? At : nullptr, A->fslab.as<float>(), grid, mta, grad_scale, 1, Bu, 0, loss_dev, apply);

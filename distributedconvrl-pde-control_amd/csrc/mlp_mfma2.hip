@@ -20,7 +20,7 @@
 
 namespace pdec {
 
-#define K2MAX 6            // k-blocks of 8: ns + 1 <= 48
+#define K2MAX 6            // k-blocks of 8: the critic's ns + 1 inputs and the ones row of its staging image fit, ns + 2 <= 48
 
 struct Net2 {              // flat parameters [W1 [H][K0] row-major, b1 [H], W2 [1][H], b2 [1]]
   const float* p;
@@ -734,6 +734,46 @@ __global__ __launch_bounds__(256) void policy_act2_kernel(Net2 n, const float* _
 // ------------------------------------------------------------------ host side
 static int mt2_of(int H) { return (H + 1 + 15) / 16; }
 
+// The instantiations of the two passes, X(critic tiles MT, actor tiles MTA) x Y(k-blocks KB): the ONE list behind the
+// predicate (fused2_supported), the launches and the report of pdec_debug_batched_update_route.  The number of 8-row k-blocks
+// is a compile-time constant (a smaller net runs the next larger variant on zero-padded rows: FUSED2_KBS ascends), so the
+// MFMA chains carry no control flow.  The acting kernel: X(actor tiles MTA) x Y(k-blocks KB).
+#define FUSED2_TILES(X) X(22, 2) X(22, 1) X(9, 2) X(9, 1)
+#define FUSED2_ACT_TILES(X) X(2) X(1)
+#define FUSED2_KBS(Y) Y(2) Y(5) Y(6)
+static_assert(K2MAX == 6, "FUSED2_KBS ends at K2MAX");
+
+// f(tile_c<KB>) of the first variant with kb <= KB k-blocks
+template <class F>
+static int visit2_kb(int kb, F&& f) {
+#define Y(KB_) if (kb <= KB_) return f(tile_c<KB_>{});
+  FUSED2_KBS(Y)
+#undef Y
+  set_error("fused 2-layer pass: no instantiation for %d k-blocks", kb);
+  return PDEC_E_INVALID;
+}
+// f(tile_c<MT>, tile_c<MTA>, tile_c<KB>) of the pair's instantiation
+template <class F>
+static int visit2(int kb, int mt, int mta, F&& f) {
+  return visit2_kb(kb, [&](auto KB) {
+#define X(MT_, MTA_) if (mt == MT_ && mta == MTA_) return f(tile_c<MT_>{}, tile_c<MTA_>{}, KB);
+    FUSED2_TILES(X)
+#undef X
+    set_error("fused 2-layer pass: no instantiation for %d critic / %d actor tiles", mt, mta);
+    return (int)PDEC_E_INVALID;
+  });
+}
+template <class F>
+static int visit2_act(int kb, int mta, F&& f) {
+  return visit2_kb(kb, [&](auto KB) {
+#define X(MTA_) if (mta == MTA_) return f(tile_c<MTA_>{}, KB);
+    FUSED2_ACT_TILES(X)
+#undef X
+    set_error("fused 2-layer act: no instantiation for %d actor tiles", mta);
+    return (int)PDEC_E_INVALID;
+  });
+}
+
 static bool fused2_disabled() {
   static int v = -1;
   if (v < 0) {
@@ -751,7 +791,11 @@ bool fused2_supported(const Mlp* A, const Mlp* C) {
   if (A->acts[0] != PDEC_ACT_RELU || A->acts[1] != PDEC_ACT_TANH) return false;
   if (C->acts[0] != PDEC_ACT_RELU || C->acts[1] != PDEC_ACT_IDENTITY) return false;
   const int mt = mt2_of(C->dims[1]), mta = mt2_of(A->dims[1]);
-  return (mt == 22 || mt == 9) && (mta == 2 || mta == 1);
+  bool ok = false;
+#define X(MT_, MTA_) ok = ok || (mt == MT_ && mta == MTA_);
+  FUSED2_TILES(X)
+#undef X
+  return ok;
 }
 
 // Workgroups of a pass and wave tiles (16 columns) per workgroup.  Up to one 128-column chunk per CU: one chunk each.  Beyond
@@ -790,9 +834,16 @@ static size_t lds2_bytes(const Fused2Args& g, bool actor_pass) {
 }
 
 template <int MT, int MTA, int KB>
+static int lds2_checked(const Fused2Args& g, bool actor_pass, size_t* lds) {
+  *lds = lds2_bytes<MT, MTA, KB>(g, actor_pass);
+  PDEC_REQUIRE(*lds <= 160 * 1024, "fused 2-layer pass needs %zu B of LDS", *lds);
+  return PDEC_OK;
+}
+
+template <int MT, int MTA, int KB>
 static int launch2(Mlp* M, const Fused2Args& g, int grid, bool actor_pass) {
-  const size_t lds = lds2_bytes<MT, MTA, KB>(g, actor_pass);
-  PDEC_REQUIRE(lds <= 160 * 1024, "fused 2-layer pass needs %zu B of LDS", lds);
+  size_t lds = 0;
+  if (int rc = lds2_checked<MT, MTA, KB>(g, actor_pass, &lds)) return rc;
   const void* kern = actor_pass ? reinterpret_cast<const void*>(ddpg2_actor_kernel<MT, MTA, KB>)
                                 : reinterpret_cast<const void*>(ddpg2_critic_kernel<MT, MTA, KB>);
   static size_t attr_lds[2] = {0, 0};          // per template instantiation and pass
@@ -809,19 +860,17 @@ static int launch2(Mlp* M, const Fused2Args& g, int grid, bool actor_pass) {
   return PDEC_OK;
 }
 
-template <int KB>
-static int dispatch2k(Mlp* M, const Fused2Args& g, int grid, bool actor_pass, int mt, int mta) {
-  if (mt == 22 && mta == 2) return launch2<22, 2, KB>(M, g, grid, actor_pass);
-  if (mt == 22 && mta == 1) return launch2<22, 1, KB>(M, g, grid, actor_pass);
-  if (mt == 9 && mta == 2) return launch2<9, 2, KB>(M, g, grid, actor_pass);
-  return launch2<9, 1, KB>(M, g, grid, actor_pass);
+// the instantiation of a pass on these arguments: the CRITIC's k-blocks decide KB in both passes (its input is the actor's rows
+// and the action row) -- the launch (dispatch2) and the report (fused2_describe) both come through here
+template <class F>
+static int visit2_pass(const Fused2Args& g, int mt, int mta, F&& f) {
+  return visit2(g.C.kb, mt, mta, f);
 }
-// the number of 8-row k-blocks is a compile-time constant (2, 5 or 6: a smaller net runs the next larger variant
-// on zero-padded rows), so the MFMA chains carry no control flow
+
 static int dispatch2(Mlp* M, const Fused2Args& g, int grid, bool actor_pass, int mt, int mta) {
-  if (g.C.kb <= 2) return dispatch2k<2>(M, g, grid, actor_pass, mt, mta);
-  if (g.C.kb <= 5) return dispatch2k<5>(M, g, grid, actor_pass, mt, mta);
-  return dispatch2k<6>(M, g, grid, actor_pass, mt, mta);
+  return visit2_pass(g, mt, mta, [&](auto MT, auto MTA, auto KB) {
+    return launch2<decltype(MT)::value, decltype(MTA)::value, decltype(KB)::value>(M, g, grid, actor_pass);
+  });
 }
 
 static int launch_finish2(Mlp* M, Mlp* Mt, int nslab, int MT, int nR, double grad_scale, int mode, int Bu, int quirk,
@@ -864,22 +913,34 @@ bool fused2_act_supported(const Mlp* A, int cols) {
   return A->dims[0] <= 8 * K2MAX && mt2_of(A->dims[1]) <= 2;
 }
 
+template <int MTA, int KB>
+static size_t act2_lds() { return (size_t)lds2_floats(16 * MTA, 8 * KB + 4) * 4; }
+
 int fused2_policy_act(Mlp* A, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
                       uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc) {
   const Net2 n = net2_of(A);
   const int mta = mt2_of(A->dims[1]), tanh_out = A->acts[1] == PDEC_ACT_TANH;
   const dim3 grid((cols + 63) / 64), block(256);
   ProfScope ps(A, "policy_act_fused");
-#define ACT2(MTA, KB)                                                                                                       \
-  hipLaunchKernelGGL((policy_act2_kernel<MTA, KB>), grid, block, (size_t)lds2_floats(16 * MTA, 8 * KB + 4) * 4, A->stream, n, \
-                     (const float*)state, cols, (float)act_noise, (float)act_limit, learning, tanh_out, seed, offset,       \
-                     (float*)actions_out, ctr_cur, ctr_next, ctr_inc)
-  if (n.kb <= 2) { if (mta == 1) ACT2(1, 2); else ACT2(2, 2); }
-  else if (n.kb <= 5) { if (mta == 1) ACT2(1, 5); else ACT2(2, 5); }
-  else { if (mta == 1) ACT2(1, 6); else ACT2(2, 6); }
-#undef ACT2
+  int rc = visit2_act(n.kb, mta, [&](auto MTA, auto KB) {
+    constexpr int mta_ = decltype(MTA)::value, kb_ = decltype(KB)::value;
+    const size_t lds = act2_lds<mta_, kb_>();
+    hipLaunchKernelGGL((policy_act2_kernel<mta_, kb_>), grid, block, lds, A->stream, n, (const float*)state, cols, (float)act_noise,
+                       (float)act_limit, learning, tanh_out, seed, offset, (float*)actions_out, ctr_cur, ctr_next, ctr_inc);
+    return (int)PDEC_OK;
+  });
+  if (rc) return rc;
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
+}
+
+int fused2_act_describe(const Mlp* A, char* name, int name_len, int64_t* lds) {
+  return visit2_act(net2_of(A).kb, mt2_of(A->dims[1]), [&](auto MTA, auto KB) {
+    constexpr int mta_ = decltype(MTA)::value, kb_ = decltype(KB)::value;
+    snprintf(name, name_len, "policy_act2_kernel<%d,%d>", mta_, kb_);
+    *lds = (int64_t)act2_lds<mta_, kb_>();
+    return (int)PDEC_OK;
+  });
 }
 
 bool fused2_net_supported(const Mlp* M) { return !fused2_disabled() && M->dtype == PDEC_F32 && M->L == 2; }
@@ -959,6 +1020,21 @@ int fused2_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double gr
   int rc = dispatch2(C, g, grid, true, mt, mta);       // on the critic's stream object (shared stream, checked by the caller)
   if (rc) return rc;
   return launch_finish2(A, apply ? At : nullptr, grid, mta, nRa, grad_scale, 1, Bu, 0, loss_dev, apply);
+}
+
+// what fused2_critic_grads / fused2_actor_grads would launch for this pair (pdec_debug_batched_update_route): the networks go
+// into the arguments as they do there, then the same visitor and the same LDS check as launch2
+int fused2_describe(const Mlp* A, const Mlp* C, bool actor_pass, char* name, int name_len, int64_t* lds) {
+  Fused2Args g{};
+  g.C = net2_of(C); g.A = net2_of(A);
+  return visit2_pass(g, mt2_of(C->dims[1]), mt2_of(A->dims[1]), [&](auto MT, auto MTA, auto KB) {
+    constexpr int mt_ = decltype(MT)::value, mta_ = decltype(MTA)::value, kb_ = decltype(KB)::value;
+    size_t b = 0;
+    if (int rc = lds2_checked<mt_, mta_, kb_>(g, actor_pass, &b)) return rc;
+    snprintf(name, name_len, "%s<%d,%d,%d>", actor_pass ? "ddpg2_actor_kernel" : "ddpg2_critic_kernel", mt_, mta_, kb_);
+    *lds = (int64_t)b;
+    return (int)PDEC_OK;
+  });
 }
 
 }  // namespace pdec

@@ -46,6 +46,19 @@ int pdec_debug_spin_us(void* hip_stream, double us);
 int pdec_debug_small_update_kernel(pdec_handle actor, pdec_handle critic, pdec_handle target_actor, pdec_handle target_critic,
                                    int loops, int Bu, double rho, int sampling, char* name, int name_len, int64_t* lds_bytes);
 
+/* Unit-test entry (no reference counterpart): what the batched DDPG update would launch for these four networks on Bu columns, with
+ * the env switches and the networks' streams as they are now -- launches nothing.  which = 0: the critic pass of pdec_ddpg_critic_grads,
+ * 1: the actor pass of pdec_ddpg_actor_grads (looks at actor and critic only), 2 / 3: the critic / actor pass of
+ * pdec_ddpg_update_async, 4: the acting kernel of pdec_policy_act_rng on Bu states (looks at the actor only).  Writes the
+ * instantiation's name -- "ddpg_critic_fused_kernel<9,2>", "ddpg2_actor_kernel<22,2,6>", "policy_act_fused_kernel<1>",
+ * "policy_act2_kernel<1,5>", "small_act_kernel", or "generic" for the generic launch sequence -- to name[name_len] and the
+ * dynamic LDS bytes of that launch (0 for the last two) to *lds_bytes; or returns the error the call would return.  For which = 2 / 3
+ * the name carries the suffix "/adam_apart" where the update runs a fused pass but ADAM and Polyak as launches of their own
+ * (2-layer pairs below 64 columns).  Computed by the host code that dispatches (csrc/mlp.hip pass_route / act_route, the
+ * visitors of csrc/mlp_mfma.hip and csrc/mlp_mfma2.hip). */
+int pdec_debug_batched_update_route(pdec_handle actor, pdec_handle critic, pdec_handle target_actor, pdec_handle target_critic,
+                                    int Bu, int which, char* name, int name_len, int64_t* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif
