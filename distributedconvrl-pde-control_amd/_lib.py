@@ -86,6 +86,7 @@ SIGNATURES = {
     "pdec_ddpg_update_actor_async": [Handle] * 4 + [_vp, _i, _d, _d, _vp],
     "pdec_policy_act": [Handle, _vp, _vp, _i, _d, _d, _vp],
     "pdec_rollout": [Handle, Handle, _i, _vp, _vp, _vp, _d, _d, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pdec_rollout_members": [Handle, _vp, _i, _i, _i, _vp, _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i)],
     "pdec_randn": [Handle, _vp, _sz, _i, _u64, _u64],
     "pdec_policy_act_rng_dev": [Handle, _vp, _i, _d, _d, _i, _u64, _vp],
     "pdec_mlp_acts_on_published_copy": [Handle, C.POINTER(_i)],

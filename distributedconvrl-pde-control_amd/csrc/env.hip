@@ -1108,6 +1108,13 @@ struct RollActor {
   int L, nparams, rows;    // rows = widest layer: the height of an activation plane
   int dims[4], acts[3];
 };
+// member form (pdec_rollout_members): the batch is M blocks of K trajectories, block m driven by the actor whose flat
+// parameters params[m] points to; all M actors have the shape of the RollActor argument.  Greedy (no exploration noise).
+struct RollMembers {
+  const void* const* params;   // device table [M]
+  int K;                       // trajectories per member
+  int f32;                     // the parameters are Float32 whatever the environment's dtype (promoted while the image is filled)
+};
 template <class T>
 struct RollArgs {
   int steps, learning;
@@ -1140,15 +1147,16 @@ __host__ __device__ inline int ro_image_elems(const int* dims, int L) {
   for (int l = 0; l < L; ++l) n += (dims[l] + 1) * RO_W;
   return n;
 }
-template <class T>
-__device__ __forceinline__ void ro_load_image(const RollActor& A, T* wl, int tid, int nt) {
-  const T* src = static_cast<const T*>(A.params);
+// S: the type of the flat parameters; S = float into T = double promotes exactly (what pdec_mlp_copy's cast would store)
+template <class T, class S = T>
+__device__ __forceinline__ void ro_load_image(const RollActor& A, const void* params, T* wl, int tid, int nt) {
+  const S* src = static_cast<const S*>(params);
   int so = 0, dof = 0;
   for (int l = 0; l < A.L; ++l) {
     const int din = A.dims[l], dout = A.dims[l + 1];
     for (int i = tid; i < (din + 1) * RO_W; i += nt) {
       const int r = i / RO_W, o = i - r * RO_W;                    // r < din: weight row, r == din: bias
-      wl[dof + i] = o < dout ? (r < din ? src[so + o * din + r] : src[so + din * dout + o]) : (T)0;
+      wl[dof + i] = o < dout ? (T)(r < din ? src[so + o * din + r] : src[so + din * dout + o]) : (T)0;
     }
     so += din * dout + dout;
     dof += (din + 1) * RO_W;
@@ -1220,8 +1228,11 @@ __device__ __forceinline__ typename RoPair<T>::type ro_actor_pair(const RollActo
   return pin[0];
 }
 
-template <class T, class ENG>
-__global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, RollActor actor, RollArgs<T> g) {
+// MEM: the member form -- workgroup w serves pair w % ceil(K/2) of member w / ceil(K/2), i.e. the trajectories
+// m K + 2 pair (+ 1 while 2 pair + 1 < K): the pairing a solo launch on B = K trajectories makes, so both trajectories of a
+// complex FFT (and of a thread's column pair) belong to ONE member and a member's arithmetic is that of its solo rollout.
+template <class T, class ENG, bool MEM>
+__global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, RollActor actor, RollArgs<T> g, RollMembers pm) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int N = e.N, tid = threadIdx.x, nt = blockDim.x, A = e.A, ns = e.ns;
   set_wave_prio(e.prio);
@@ -1240,12 +1251,22 @@ __global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, 
   using T2 = typename RoPair<T>::type;
   T2* hb = reinterpret_cast<T2*>(wl + ((ro_image_elems(actor.dims, actor.L) + 3) & ~3));   // [2][rows][nt] column pairs
 
-  const int b0 = 2 * blockIdx.x, b1 = b0 + 1;
-  const bool has1 = b1 < e.B;
+  int bfirst = 2 * blockIdx.x;
+  bool pair_full = bfirst + 1 < e.B;
+  const void* params = actor.params;      // (the argument itself stays untouched: a modified copy would live in scratch)
+  if constexpr (MEM) {
+    const int hp = (pm.K + 1) / 2, m = blockIdx.x / hp, pr = blockIdx.x - m * hp;
+    bfirst = m * pm.K + 2 * pr;
+    pair_full = 2 * pr + 1 < pm.K;
+    params = pm.params[m];
+  }
+  const int b0 = bfirst, b1 = b0 + 1;
+  const bool has1 = pair_full;
   const size_t o0 = (size_t)b0 * N, o1 = (size_t)b1 * N;
   const size_t cols = (size_t)e.B * A;
 
-  ro_load_image<T>(actor, wl, tid, nt);
+  if (MEM && pm.f32 && sizeof(T) != sizeof(float)) ro_load_image<T, float>(actor, params, wl, tid, nt);
+  else ro_load_image<T>(actor, params, wl, tid, nt);
   for (int i = tid; i < A * ns; i += nt) {
     stl[i] = g.state[(size_t)b0 * A * ns + i];
     stl[A * ns + i] = has1 ? g.state[(size_t)b1 * A * ns + i] : (T)0;
@@ -1287,7 +1308,7 @@ __global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, 
         for (int s = 0; s < 2; ++s) {
           const int idx = idx0 + s, r = idx / A, a = idx - r * A;
           T o = s == 0 ? o2.x : o2.y;
-          if (g.learning && (r == 0 || has1)) {
+          if (!MEM && g.learning && (r == 0 || has1)) {
             const uint64_t c = (uint64_t)(r == 0 ? b0 : b1) * A + a;          // global column = element of the noise stream
             if ((c >> 2) != cprev) {
               const uint64_t ctr = g.offset + (uint64_t)t * ((cols + 3) / 4) + (c >> 2);
@@ -1580,8 +1601,11 @@ __global__ void kseg_env_step_kernel(EnvDev<T> e, const T* __restrict__ y_in, co
 // in LDS, the actor (<= 3 Dense layers of <= RO_W units, 12 -> 20 -> 20 -> 1 in the shipped script) is evaluated in the kernel,
 // one thread per (actuator, unit), and the exploration noise is the same Philox stream element for element (column c = b A + a
 // of step t) as the acting kernel's, so the launch tracks the step-by-step loop to the actor's summation order.
-template <class T>
-__global__ void kseg_rollout_kernel(EnvDev<T> e, RollActor actor, RollArgs<T> g) {
+// MEM: the member form -- trajectory b (one workgroup) takes the actor of member b / K from the table.  NT: the largest
+// workgroup the instantiation is launched with (1024: any; the member form has a 256-thread instantiation, whose register
+// budget holds the fp64 loop without spills).
+template <class T, bool MEM, int NT>
+__global__ void __launch_bounds__(NT) kseg_rollout_kernel(EnvDev<T> e, RollActor actor, RollArgs<T> g, RollMembers pm) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int N = e.N, tid = threadIdx.x, nt = blockDim.x, b = blockIdx.x, A = e.A, ns = e.ns;
   T* su = reinterpret_cast<T*>(smem_raw);  // [N+2]
@@ -1602,7 +1626,10 @@ __global__ void kseg_rollout_kernel(EnvDev<T> e, RollActor actor, RollArgs<T> g)
   const bool live = n < N;
   const size_t yo = (size_t)b * 2 * N, cols = (size_t)e.B * A;
 
-  ro_load_image<T>(actor, wl, tid, nt);
+  const void* params = actor.params;
+  if constexpr (MEM) params = pm.params[b / pm.K];
+  if (MEM && pm.f32 && sizeof(T) != sizeof(float)) ro_load_image<T, float>(actor, params, wl, tid, nt);
+  else ro_load_image<T>(actor, params, wl, tid, nt);
   for (int i = tid; i < A * ns; i += nt) stl[i] = g.state[(size_t)b * A * ns + i];
   for (int a = tid; a < A; a += nt) {
     act[a] = g.action[(size_t)b * A + a];
@@ -1635,7 +1662,7 @@ __global__ void kseg_rollout_kernel(EnvDev<T> e, RollActor actor, RollArgs<T> g)
       }
       for (int a = tid; a < A; a += nt) {
         T o = in[a * RO_W];
-        if (g.learning) {
+        if (!MEM && g.learning) {
           const uint64_t c = (uint64_t)b * A + a;                          // global column = element of the noise stream
           const uint64_t ctr = g.offset + (uint64_t)t * ((cols + 3) / 4) + (c >> 2);
           uint32_t ph[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
@@ -2200,19 +2227,22 @@ static size_t ks_rollout_lds(const Env& E, const Mlp& A) {
   const size_t ts = dtype_size(c.dtype);
   return E.lds_bytes + ((size_t)2 * c.A * env_ns(c) + 4 * (size_t)c.A + ((ro_image_elems(A.dims.data(), A.L) + 3) & ~3) + (size_t)4 * *std::max_element(A.dims.begin(), A.dims.begin() + A.L + 1) * E.nthreads) * ts + 16;
 }
-bool ks_rollout_supported(const Env& E, const Mlp& A) {
+// (everything but the parameters' dtype: the member form reads Float32 parameters into an fp64 image)
+static bool ks_rollout_shape_ok(const Env& E, const Mlp& A) {
   const pdec_env_cfg& c = E.cfg;
   const char* off = getenv("PDEC_ROLLOUT_PERSISTENT");
   if (off && off[0] == '0') return false;
   if (c.pde_kind != PDEC_PDE_KS_CNAB2 || c.mono || c.temporal_steps != 1 || c.check_max_value == 2) return false;
-  if ((E.nthreads & 1) || A.L < 1 || A.L > 3 || A.dims[A.L] != 1 || A.dtype != c.dtype || A.dims[0] != env_ns(c)) return false;
+  if ((E.nthreads & 1) || A.L < 1 || A.L > 3 || A.dims[A.L] != 1 || A.dims[0] != env_ns(c)) return false;
   for (int l = 0; l <= A.L; ++l)
     if (A.dims[l] > RO_W) return false;
   return ks_rollout_lds(E, A) <= 64 * 1024;
 }
+bool ks_rollout_supported(const Env& E, const Mlp& A) { return A.dtype == E.cfg.dtype && ks_rollout_shape_ok(E, A); }
 
+// pm = null: the solo form.  Member form: A is member 0's actor (the shape all members share), the grid M ceil(K / 2)
 template <class T>
-static int ks_rollout_launch(Env& E, const Mlp& A, const RollArgs<T>& g) {
+static int ks_rollout_launch(Env& E, const Mlp& A, const RollArgs<T>& g, const RollMembers* pm = nullptr) {
   EnvDev<T> e = make_dev<T>(E);
   const pdec_env_cfg& c = E.cfg;
   RollActor ra{};
@@ -2220,9 +2250,13 @@ static int ks_rollout_launch(Env& E, const Mlp& A, const RollArgs<T>& g) {
   for (int l = 0; l <= A.L; ++l) { ra.dims[l] = A.dims[l]; ra.rows = std::max(ra.rows, A.dims[l]); }
   for (int l = 0; l < A.L; ++l) ra.acts[l] = A.acts[l];
   const size_t lds = ks_rollout_lds(E, A);
-  dim3 grid((c.B + 1) / 2), block(E.nthreads);
-  ProfScope ps(&E, "ks_rollout");
-#define KS_ROLL(ENG) hipLaunchKernelGGL((ks_rollout_kernel<T, ENG>), grid, block, lds, E.stream, e, ra, g)
+  dim3 grid(pm ? (c.B / pm->K) * ((pm->K + 1) / 2) : (c.B + 1) / 2), block(E.nthreads);
+  ProfScope ps(&E, pm ? "ks_rollout_members" : "ks_rollout");
+#define KS_ROLL(ENG)                                                                                                        \
+  do {                                                                                                                      \
+    if (pm) hipLaunchKernelGGL((ks_rollout_kernel<T, ENG, true>), grid, block, lds, E.stream, e, ra, g, *pm);               \
+    else hipLaunchKernelGGL((ks_rollout_kernel<T, ENG, false>), grid, block, lds, E.stream, e, ra, g, RollMembers{});       \
+  } while (0)
   if (E.r4_log == 1) KS_ROLL(FftWave256<T>);
   else if (E.r4_log == 4) KS_ROLL(FftR4<T COMMA 4>);
   else if (E.r4_log == 5) KS_ROLL(FftR4<T COMMA 5>);
@@ -2255,25 +2289,32 @@ static size_t kseg_rollout_lds(const Env& E, const Mlp& A) {
   const pdec_env_cfg& c = E.cfg;
   return E.lds_bytes + ((size_t)2 * c.A * env_ns(c) + 2 * (size_t)c.A + ((ro_image_elems(A.dims.data(), A.L) + 3) & ~3) + (size_t)2 * c.A * RO_W) * dtype_size(c.dtype) + 16;
 }
-bool kseg_rollout_supported(const Env& E, const Mlp& A) {
+static bool kseg_rollout_shape_ok(const Env& E, const Mlp& A) {
   const pdec_env_cfg& c = E.cfg;
   const char* off = getenv("PDEC_ROLLOUT_PERSISTENT");
   if (off && off[0] == '0') return false;
   if (c.pde_kind != PDEC_PDE_KSEG_RK4 || c.mono || c.check_max_value == 2) return false;
-  if (A.L < 1 || A.L > 3 || A.dims[A.L] != 1 || A.dtype != c.dtype || A.dims[0] != env_ns(c)) return false;
+  if (A.L < 1 || A.L > 3 || A.dims[A.L] != 1 || A.dims[0] != env_ns(c)) return false;
   for (int l = 0; l <= A.L; ++l)
     if (A.dims[l] > RO_W) return false;
   return kseg_rollout_lds(E, A) <= 64 * 1024;
 }
+bool kseg_rollout_supported(const Env& E, const Mlp& A) { return A.dtype == E.cfg.dtype && kseg_rollout_shape_ok(E, A); }
 template <class T>
-static int kseg_rollout_launch(Env& E, const Mlp& A, const RollArgs<T>& g) {
+static int kseg_rollout_launch(Env& E, const Mlp& A, const RollArgs<T>& g, const RollMembers* pm = nullptr) {
   EnvDev<T> e = make_dev<T>(E);
   RollActor ra{};
   ra.params = A.params.p; ra.L = A.L; ra.nparams = A.nparams;
   for (int l = 0; l <= A.L; ++l) { ra.dims[l] = A.dims[l]; ra.rows = std::max(ra.rows, A.dims[l]); }
   for (int l = 0; l < A.L; ++l) ra.acts[l] = A.acts[l];
-  ProfScope ps(&E, "kseg_rollout");
-  hipLaunchKernelGGL((kseg_rollout_kernel<T>), dim3(E.cfg.B), dim3(E.nthreads), kseg_rollout_lds(E, A), E.stream, e, ra, g);
+  ProfScope ps(&E, pm ? "kseg_rollout_members" : "kseg_rollout");
+  const size_t lds = kseg_rollout_lds(E, A);
+  if (pm && E.nthreads <= 256)
+    hipLaunchKernelGGL((kseg_rollout_kernel<T, true, 256>), dim3(E.cfg.B), dim3(E.nthreads), lds, E.stream, e, ra, g, *pm);
+  else if (pm)
+    hipLaunchKernelGGL((kseg_rollout_kernel<T, true, 1024>), dim3(E.cfg.B), dim3(E.nthreads), lds, E.stream, e, ra, g, *pm);
+  else
+    hipLaunchKernelGGL((kseg_rollout_kernel<T, false, 1024>), dim3(E.cfg.B), dim3(E.nthreads), lds, E.stream, e, ra, g, RollMembers{});
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
 }
@@ -2289,6 +2330,44 @@ int kseg_rollout_persistent(Env& E, const Mlp& A, int T, void* y, void* state, v
   RollArgs<float> g{T, learning, (float)act_noise, (float)act_limit, seed, offset, (float*)y, (float*)state, (float*)action,
                     (float*)reward_sum, (float*)log_y, (float*)log_p, (float*)log_action, (float*)log_reward, done_any, done_step};
   return kseg_rollout_launch<float>(E, A, g);
+}
+
+// The member form of both launches (pdec_rollout_members): M actors of one shape, K trajectories each, greedy.  The actors'
+// parameters may be Float32 under an fp64 environment (the reference's shape) or of the environment's dtype.  *served = 0 and
+// nothing enqueued where the solo form would not serve an actor of this shape either.
+bool rollout_members_supported(const Env& E, const std::vector<const Mlp*>& actors) {
+  const Mlp& A = *actors[0];
+  if (A.dtype != PDEC_F32 && A.dtype != E.cfg.dtype) return false;
+  return ks_rollout_shape_ok(E, A) || kseg_rollout_shape_ok(E, A);
+}
+int rollout_members_persistent(Env& E, const std::vector<const Mlp*>& actors, int K, int T, void* y, void* state, void* action,
+                               double act_limit, void* reward_sum, void* log_y, void* log_p, void* log_action, void* log_reward,
+                               int32_t* done_any, int32_t* done_step) {
+  const int M = (int)actors.size();
+  const Mlp& A = *actors[0];
+  if (!rollout_members_supported(E, actors)) { set_error("rollout_members_persistent: configuration not covered"); return PDEC_E_INVALID; }
+  PDEC_REQUIRE(K >= 1 && (long long)M * K == E.cfg.B, "rollout_members_persistent: %d members x %d trajectories are not the environment's B = %d",
+               M, K, E.cfg.B);
+  // the pointer table: uploaded on the environment's stream from host memory this object owns.  It is rewritten only when
+  // the members change, and then behind everything the stream still has to do (an earlier upload may not have read it yet)
+  std::vector<const void*> tab(M);
+  for (int m = 0; m < M; ++m) tab[m] = actors[m]->params.p;
+  if (tab != E.roll_tab_host || !E.roll_tab.p) {
+    PDEC_HIP(hipStreamSynchronize(E.stream));
+    E.roll_tab_host = tab;
+    if (E.roll_tab.bytes < sizeof(void*) * M) PDEC_HIP(E.roll_tab.alloc(sizeof(void*) * M));
+    PDEC_HIP(hipMemcpyAsync(E.roll_tab.p, E.roll_tab_host.data(), sizeof(void*) * M, hipMemcpyHostToDevice, E.stream));
+  }
+  const RollMembers pm{E.roll_tab.as<const void*>(), K, A.dtype == PDEC_F32 ? 1 : 0};
+  const bool ks = E.cfg.pde_kind == PDEC_PDE_KS_CNAB2;
+  if (E.cfg.dtype == PDEC_F64) {
+    RollArgs<double> g{T, 0, 0.0, act_limit, 0, 0, (double*)y, (double*)state, (double*)action, (double*)reward_sum,
+                       (double*)log_y, (double*)log_p, (double*)log_action, (double*)log_reward, done_any, done_step};
+    return ks ? ks_rollout_launch<double>(E, A, g, &pm) : kseg_rollout_launch<double>(E, A, g, &pm);
+  }
+  RollArgs<float> g{T, 0, 0.f, (float)act_limit, 0, 0, (float*)y, (float*)state, (float*)action, (float*)reward_sum,
+                    (float*)log_y, (float*)log_p, (float*)log_action, (float*)log_reward, done_any, done_step};
+  return ks ? ks_rollout_launch<float>(E, A, g, &pm) : kseg_rollout_launch<float>(E, A, g, &pm);
 }
 
 template <class T>

@@ -39,6 +39,8 @@ struct Env : Object {
   int Wd = 0, Cnt = 0;
   DevBuf stage;  // staging for the _host wrappers
   DevBuf roll;   // ping-pong buffers of pdec_rollout
+  DevBuf roll_tab;                          // pdec_rollout_members: the members' parameter pointers on the device ...
+  std::vector<const void*> roll_tab_host;   // ... and the host image they were uploaded from (lives as long as the object)
   DevBuf mem_scratch;   // forcing field + flags of the composed env step (cfg.memory_size > 0)
   void* term_out = nullptr;
   float* rsum_out = nullptr;
@@ -66,6 +68,11 @@ int kseg_rollout_persistent(Env& E, const Mlp& A, int T, void* y, void* state, v
 int ks_rollout_persistent(Env& E, const Mlp& A, int T, void* y, void* state, void* action, double act_noise, double act_limit,
                           int learning, uint64_t seed, uint64_t offset, void* reward_sum, void* log_y, void* log_p,
                           void* log_action, void* log_reward, int32_t* done_any, int32_t* done_step);
+// the member form of the two launches above (pdec_rollout_members): actors[m] drives trajectories m K .. m K + K - 1
+bool rollout_members_supported(const Env& E, const std::vector<const Mlp*>& actors);
+int rollout_members_persistent(Env& E, const std::vector<const Mlp*>& actors, int K, int T, void* y, void* state, void* action,
+                               double act_limit, void* reward_sum, void* log_y, void* log_p, void* log_action, void* log_reward,
+                               int32_t* done_any, int32_t* done_step);
 
 // fluid.hip: 2-D pseudo-spectral vorticity environment (src/fluid_rk4.jl + scripts/Fluid/setup/FluidSetup.jl)
 struct FluidEnv;

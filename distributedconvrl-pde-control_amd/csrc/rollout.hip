@@ -101,3 +101,34 @@ extern "C" int pdec_rollout(pdec_handle henv, pdec_handle hactor, int T, void* y
   }
   return PDEC_OK;
 }
+
+// M actors, each driving its own block of per_member trajectories of one environment, in ONE persistent launch
+// (population.py: evaluate_actors).  Greedy only: the Philox numbering of the solo launches is by global column, so a member's
+// noise stream is not defined here.
+extern "C" int pdec_rollout_members(pdec_handle henv, const pdec_handle* actors, int M, int per_member, int T, void* y, void* state,
+                                    void* action, double act_limit, int learning, void* reward_sum, void* log_y, void* log_p,
+                                    void* log_action, void* log_reward, int32_t* done_any, int32_t* done_step, int* served) {
+  Env* E = lookup_as<Env>(henv, Kind::Env);
+  if (!E) { set_error("pdec_rollout_members: bad handle"); return PDEC_E_HANDLE; }
+  PDEC_REQUIRE(served, "pdec_rollout_members: served is null");
+  *served = 0;
+  PDEC_REQUIRE(actors && M >= 1 && per_member >= 1 && T >= 1 && y && state && action, "pdec_rollout_members: null/empty argument");
+  PDEC_REQUIRE(learning == 0, "pdec_rollout_members: learning = 1 is not served (greedy evaluation only: the exploration noise is "
+                              "numbered by global column, not per member)");
+  const pdec_env_cfg& c = E->cfg;
+  PDEC_REQUIRE((long long)M * per_member == c.B, "pdec_rollout_members: %d members x %d trajectories are not the environment's B = %d",
+               M, per_member, c.B);
+  std::vector<const Mlp*> nets(M);
+  for (int m = 0; m < M; ++m) {
+    nets[m] = lookup_as<Mlp>(actors[m], Kind::Mlp);
+    if (!nets[m]) { set_error("pdec_rollout_members: bad actor handle (member %d)", m); return PDEC_E_HANDLE; }
+  }
+  for (int m = 1; m < M; ++m)
+    if (nets[m]->dims != nets[0]->dims || nets[m]->acts != nets[0]->acts || nets[m]->dtype != nets[0]->dtype)
+      return PDEC_OK;      // differing shapes: not served (the caller refuses or loops over solo rollouts)
+  if (!rollout_members_supported(*E, nets)) return PDEC_OK;
+  int rc = rollout_members_persistent(*E, nets, per_member, T, y, state, action, act_limit, reward_sum, log_y, log_p, log_action,
+                                      log_reward, done_any, done_step);
+  if (rc == PDEC_OK) *served = 1;
+  return rc;
+}

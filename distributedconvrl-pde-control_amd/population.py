@@ -38,6 +38,137 @@ def _refuse(msg):
     raise _lib.PdecError("Population: " + msg)
 
 
+# ---- evaluation: every member's actor scored on the SAME held-out initial fields, in one launch where the library serves it
+
+def member_workgroups(M, K):
+    """The workgroups of the KS member rollout (csrc/env.hip: ks_rollout_kernel, member form) for M members of K trajectories:
+    a list of (member, pair, b0, has1).  Workgroup w serves member w // ceil(K / 2), pair w % ceil(K / 2): the trajectories
+    b0 = member * K + 2 * pair and, where has1, b0 + 1 -- the pairing of a solo launch on K trajectories, so the two
+    trajectories that share a complex FFT always belong to one member."""
+    hp = (K + 1) // 2
+    out = []
+    for w in range(M * hp):
+        m, pair = divmod(w, hp)
+        out.append((m, pair, m * K + 2 * pair, 2 * pair + 1 < K))
+    return out
+
+
+def score_members(episode_reward, done_step):
+    """score [M] and order of a population from episode_reward [M, K] and done_step [M, K] (host arrays): a member's score is
+    the mean of its K episode rewards, NaN when any of its trajectories blew up (done_step >= 0) or is not finite; order =
+    member indices best first, NaN scores last, ties by index."""
+    er = np.asarray(episode_reward, dtype=np.float64)
+    ds = np.asarray(done_step)
+    bad = (ds >= 0).any(axis=1) | ~np.isfinite(er).all(axis=1)
+    score = np.where(bad, np.nan, np.where(bad[:, None], 0.0, er).mean(axis=1))
+    order = sorted(range(er.shape[0]), key=lambda m: (bool(np.isnan(score[m])), -score[m] if not np.isnan(score[m]) else 0.0, m))
+    return score, order
+
+
+def _model(actor):
+    return getattr(actor, "model", actor)
+
+
+def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, dtype=torch.float64, stream=None, act_limit=1.0,
+                    log=False, device="cuda:0"):
+    """One greedy evaluation episode of each of M actors (HipMLPs or approximators of ONE shape) from the same K initial fields:
+    `y0` [K, ...] in the environment's memory layout, or -- None -- n_inits fields drawn once with env.random_init from the
+    Philox stream (init_seed, 0).  `steps` defaults to one episode (te / dt + 1, as testrun).  The environment of
+    B = M * K trajectories is this call's own (member m: trajectories m K .. m K + K - 1) on `stream`, which waits for every
+    actor's stream.  Where the library serves it (pdec_rollout_members: KS and 1-D Keller-Segel, per-actuator actors of <= 3
+    layers no wider than 32) all M episodes are ONE launch, Float32 actors read as they are; otherwise M env.rollout calls on one
+    B = K environment with actor clones as testrun makes them -- the same numbers, member by member.
+    Returns episode_reward [M, K] (mean over actuators of the summed reward, PDEhook's figure), reward_sum [M, K, A],
+    done_step [M, K] (device tensors), score [M] (numpy; NaN: a trajectory blew up or is not finite), order (best first, NaN
+    last, ties by index), one_launch, workgroups (of the one launch; None otherwise) and with log=True the rows y, p, action,
+    reward [T, M, K, ...]."""
+    models = [_model(a) for a in actors]
+    M = len(models)
+    if M < 1:
+        raise _lib.PdecError("evaluate_actors: needs at least one actor")
+    for m, md in enumerate(models):
+        if list(md.dims) != list(models[0].dims) or list(md.acts) != list(models[0].acts):
+            raise _lib.PdecError(f"evaluate_actors: member {m}'s actor shape {list(md.dims)} / activations differ from member 0's "
+                                 f"{list(models[0].dims)}: all members must have the same shape")
+    dev = torch.device(device)
+    small = None                # the B = K environment: draws the shared fields, and serves the member-by-member form
+    T = int(round((setup.te - setup.t0) / setup.dt)) + 1 if steps is None else int(steps)
+    with _on_stream(stream):    # (the environments' own tensors are made on their stream as well)
+        if y0 is None:
+            small = PDEenv(setup, B=int(n_inits), dtype=dtype, device=device, stream=stream, autoreset=False)
+            y0 = torch.empty_like(small.y)
+            small.random_init(int(init_seed), 0, out=y0)
+        y0 = (y0 if isinstance(y0, torch.Tensor) else torch.as_tensor(np.array(y0, copy=True))).to(device=dev, dtype=dtype).contiguous()
+        K = int(y0.shape[0])
+        # the 2-D environments and the global agent have no persistent rollout at all: no B = M K environment is built to hear it
+        env = None
+        if not (getattr(setup, "is_fluid", False) or getattr(setup, "is_kseg2d", False) or getattr(setup, "mono", False)):
+            env = PDEenv(setup, B=M * K, dtype=dtype, device=device, y0=y0.repeat((M,) + (1,) * (y0.dim() - 1)), stream=stream,
+                         autoreset=False)
+    B = M * K
+    s_env = stream if stream is not None else torch.cuda.current_stream(dev)
+    others = {}
+    for md in models:
+        s = getattr(md, "stream", None)
+        if s is not None and s.cuda_stream != s_env.cuda_stream:
+            others[s.cuda_stream] = s
+    for s in others.values():
+        s_env.wait_stream(s)
+    kw = dict(dtype=dtype, device=dev)
+    served = C.c_int(0)
+    if env is not None:
+        with _on_stream(stream):
+            out = dict(reward_sum=torch.zeros((B, setup.reward_len), **kw), done_step=torch.zeros(B, dtype=torch.int32, device=dev))
+            done_any = torch.zeros(B, dtype=torch.int32, device=dev)
+            if log:
+                out.update(y=torch.empty((T,) + env._yshape, **kw), p=torch.empty((T,) + env._pshape, **kw),
+                           action=torch.empty((T,) + env._ashape, **kw), reward=torch.empty((T, B, setup.reward_len), **kw))
+        handles = (_lib.Handle * M)(*[int(getattr(md.handle, "value", md.handle)) for md in models])
+        P = _lib.ptr
+        try:
+            _lib.check(env.lib.pdec_rollout_members(
+                env.handle, handles, M, K, T, P(env.y), P(env.state), P(env.action), float(act_limit), 0, P(out["reward_sum"]),
+                P(out.get("y")), P(out.get("p")), P(out.get("action")), P(out.get("reward")), P(done_any), P(out["done_step"]),
+                C.byref(served)))
+        finally:
+            for s in others.values():       # whatever next writes the actors' parameters waits for the launch that reads them
+                s.wait_stream(s_env)
+    one = bool(served.value)
+    if not one:
+        if env is not None:
+            env.close()
+        if small is None:
+            with _on_stream(stream):
+                small = PDEenv(setup, B=K, dtype=dtype, device=device, y0=y0, stream=stream, autoreset=False)
+        else:
+            small.set_y0(y0)
+        cols = K * setup.state_shape[1]
+        parts = []
+        for md in models:
+            actor = md if (md.dtype == small.dtype and md.max_cols >= cols) else md.clone(dtype=small.dtype, max_cols=cols)
+            small.reset()
+            parts.append(small.rollout(actor, T, act_limit=act_limit, learning=False, log=log))
+        with _on_stream(stream):
+            out = {k: torch.cat([p_[k] for p_ in parts], dim=0 if k in ("reward_sum", "done_step") else 1)
+                   for k in (("reward_sum", "done_step") + (("y", "p", "action", "reward") if log else ()))}
+    with _on_stream(stream):
+        res = dict(reward_sum=out["reward_sum"].view(M, K, -1), done_step=out["done_step"].view(M, K))
+        res["episode_reward"] = res["reward_sum"].mean(dim=2)
+        for k in ("y", "p", "action", "reward"):
+            if k in out:
+                res[k] = out[k].view((T, M, K) + tuple(out[k].shape[2:]))
+        host = (res["episode_reward"].double().cpu().numpy(), res["done_step"].cpu().numpy())     # (waits for the stream)
+    res["score"], res["order"] = score_members(*host)
+    res["one_launch"] = one
+    is_ks = not (getattr(setup, "is_fluid", False) or getattr(setup, "is_kseg2d", False)) and tuple(setup.y_shape) == (setup.nx,)
+    res["workgroups"] = (len(member_workgroups(M, K)) if is_ks else B) if one else None
+    if one:
+        env.close()
+    if small is not None:
+        small.close()
+    return res
+
+
 class Population:
     def __init__(self, setup, agents, hooks, stream_env, dtype=torch.float64, device="cuda:0"):
         from .run import device_episodes_ok
@@ -134,6 +265,26 @@ class Population:
             self.close()
         except Exception:
             pass
+
+    # ---- selection
+    def evaluate(self, which="current", **kw):
+        """evaluate_actors on the members' behaviour actors ("current") or on their hooks' best actors ("best"): every member
+        scored on the same held-out initial fields.  The evaluation has its own environment; the population's environment,
+        counter table, Philox offsets and replay traces are not touched, so training that goes on afterwards is bit for bit what
+        it would have been without the call."""
+        if which == "current":
+            actors = [ag.policy.behavior_actor for ag in self.agents]
+        elif which == "best":
+            for m, hk in enumerate(self.hooks):
+                if not hk.collect_NNA or hk.bestNNA is None:
+                    _refuse(f'evaluate(which="best"): member {m}\'s hook keeps no best actor (collect_NNA, and at least one run)')
+            actors = [hk.bestNNA for hk in self.hooks]
+        else:
+            _refuse(f'evaluate: which must be "current" or "best", not {which!r}')
+        kw.setdefault("stream", self.stream_env)
+        kw.setdefault("dtype", self.env.dtype)
+        kw.setdefault("device", self.env.device)
+        return evaluate_actors(self.setup, actors, **kw)
 
     # ---- the episode loop
     def run(self, stops):

@@ -274,6 +274,22 @@ int pdec_rollout(pdec_handle env, pdec_handle actor, int T, void* y, void* state
                  double act_noise, double act_limit, int learning, uint64_t seed, uint64_t offset,
                  void* reward_sum, void* log_y, void* log_p, void* log_action, void* log_reward,
                  int32_t* done_any, int32_t* done_step);
+/* The same for M actors at once (population.py: evaluate_actors): the environment's batch is B = M * per_member trajectories,
+ * trajectory b is driven by actors[b / per_member], and the whole call is ONE persistent launch in which every workgroup takes
+ * its actor from a device table.  Array shapes and the in / out contract are pdec_rollout's.  Greedy only: learning must be 0
+ * (the exploration noise of pdec_rollout is numbered by global column, not per member; learning = 1 is an error).  Unlike
+ * pdec_rollout the actors may live on another stream -- the caller orders the streams -- and in another dtype: Float32
+ * parameters under an fp64 environment (the reference's shape) are promoted while a workgroup fills its LDS image, which is
+ * exactly the image a promoted copy of the actor (pdec_mlp_copy into an fp64 network) would load.  KS: a workgroup's two
+ * trajectories belong to one member (workgroup w: member w / ceil(per_member / 2), trajectories 2 (w % ceil(per_member / 2))
+ * and the next of that member, if it has one) -- the pairing of a solo launch on per_member trajectories, so every member's
+ * results are bit for bit those of pdec_rollout on its block alone.
+ * *served = 0 and nothing is enqueued when the environment / actor shape is not one the persistent launches of pdec_rollout
+ * cover, when the actors differ in shape or dtype, when their parameters are neither Float32 nor of the environment's dtype,
+ * or with PDEC_ROLLOUT_PERSISTENT=0: the caller then loops over pdec_rollout. */
+int pdec_rollout_members(pdec_handle env, const pdec_handle* actors, int M, int per_member, int T, void* y, void* state,
+                         void* action, double act_limit, int learning, void* reward_sum, void* log_y, void* log_p,
+                         void* log_action, void* log_reward, int32_t* done_any, int32_t* done_step, int* served);
 
 /* policy act: actions[cols][na] = clamp(actor(state) + noise*act_noise, +-act_limit)
  * (src/PDEagent.jl:183-207).  noise [cols][na] device standard normals or NULL (-> no noise,

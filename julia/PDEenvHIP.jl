@@ -138,6 +138,20 @@ function rollout!(h::UInt64, actor, T::Integer, y::Ptr{Cvoid}, state::Ptr{Cvoid}
                 h, actor.h, T, y, state, action, act_noise, act_limit, learning ? 1 : 0, seed, offset, reward_sum,
                 C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL))
 end
+# the same for M actors at once (selection after population training): y, state, action hold B = M * per_member trajectories,
+# trajectory b is driven by actors[b / per_member] (Float32 or environment-dtype parameters, any stream: order them before
+# the call), greedy, ONE launch.  Returns false when the library does not serve the configuration in one launch (nothing was
+# enqueued: call rollout! per actor instead).
+function rollout_members!(h::UInt64, actors::Vector{UInt64}, per_member::Integer, T::Integer, y::Ptr{Cvoid}, state::Ptr{Cvoid},
+                          action::Ptr{Cvoid}; act_limit = 1.0, reward_sum = C_NULL, done_step = C_NULL)
+    served = Ref{Cint}(0)
+    check(ccall((:pdec_rollout_members, LIB), Cint,
+                (UInt64, Ptr{UInt64}, Cint, Cint, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint, Ptr{Cvoid}, Ptr{Cvoid},
+                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ref{Cint}),
+                h, actors, length(actors), per_member, T, y, state, action, act_limit, 0, reward_sum, C_NULL, C_NULL, C_NULL,
+                C_NULL, C_NULL, done_step, served))
+    served[] != 0
+end
 
 # for callers that run the fused KS step beside the update passes on a second stream: its 64-VGPR form (see pdeconv.h)
 function set_simd_sharing(h::UInt64, on::Bool)
