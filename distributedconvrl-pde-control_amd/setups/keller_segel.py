@@ -9,6 +9,11 @@ def prepare_rectangles(nx, positions, half_window_size=2):
     """KellerSegelSetup.jl:112-126"""
     out = np.zeros((len(positions), nx))
     for i, position in enumerate(positions):
+        # the reference's p[position-hw : position+hw] .= 1 (:120) throws a BoundsError for a box that leaves the grid; a
+        # negative Python slice would silently give an empty or truncated box instead
+        if position - half_window_size < 1 or position + half_window_size > nx:
+            raise _lib.PdecError(f"KellerSegelSetup: sensor position {int(position)} puts its {2 * half_window_size + 1}-cell box "
+                                 f"outside the grid 1..{nx} (positions {half_window_size + 1}..{nx - half_window_size} fit)")
         out[i, position - half_window_size - 1: position + half_window_size] = 1.0
     return out
 

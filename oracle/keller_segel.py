@@ -34,6 +34,8 @@ def prepare_rectangles(cfg, half_window_size=2):
     """KellerSegelSetup.jl:112-126: box of ones on cells position-hw .. position+hw (1-based)."""
     out = []
     for position in cfg.sensor_positions:
+        if position - half_window_size < 1 or position + half_window_size > cfg.nx:   # Julia: BoundsError at :120
+            raise IndexError(f"sensor position {int(position)}: its box leaves the grid 1..{cfg.nx}")
         p = np.zeros(cfg.nx)
         p[position - half_window_size - 1: position + half_window_size] = 1.0   # :120
         out.append(p)

@@ -165,16 +165,18 @@ def test_host_pointer_wrapper(pkg):
     assert np.abs(out - g["y"][4]).max() <= 1e-12 and done[0] == 0
 
 
-@pytest.mark.parametrize("nx", [240, 256])
+@pytest.mark.parametrize("nx", [240, 256, 64, 100, 1024])
 @pytest.mark.parametrize("integ", ["rk4_fd", "midpoint_fd"])
 @pytest.mark.parametrize("prec,tol", [("f64", 1e-11), ("f32", 2e-4)])
 def test_rk4_fd_variant_matches_its_oracle(pkg, prec, tol, integ, nx, monkeypatch):
     """north-star variant: RK4 + periodic 5-point FD (stencils of KSSetup.jl:55-59); rhs, do_step and the fused
     (env)(action) against oracle/ks.py rhs_fd / do_step_rk4_fd (relative to max|value|).  nx = 256: the fused step runs in
     its one-wave-per-trajectory form (four cells per lane, neighbours by lane exchange, csrc/env.hip: ksfd_wave_step_kernel);
-    it must also agree with the general one-cell-per-thread form (PDEC_KSFD_LDS=1) to round-off."""
+    it must also agree with the general one-cell-per-thread form (PDEC_KSFD_LDS=1) to round-off.  nx = 64 / 100 / 1024: the
+    work-group sizes of ksfd_env_step_kernel (nt = ceil(N / 64) 64) without a dead lane, with 28 and with all 16 waves, at the
+    cell size of the 240-cell row (Lx = nx 200 / 240), where the explicit step is stable."""
     from oracle import ks
-    Lx, K, dtc = 200.0, 30, 0.1
+    Lx, K, dtc = (200.0 if nx in (240, 256) else nx * 200.0 / 240), 30, 0.1
     pos = np.arange(1, nx + 1, 3)
     setup = pkg.KSSetup(nx, Lx, pos, integrator=integ, mu=0.02, dt=dtc, oversampling=K, window_size=3)
     step = ks.do_step_rk4_fd if integ == "rk4_fd" else ks.do_step_midpoint_fd     # midpoint: src/PDEenv.jl:208-214

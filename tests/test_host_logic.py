@@ -344,6 +344,24 @@ def test_optional_featurize_branches_are_refused_or_restated(pkg):
     assert np.array_equal(f1[3:], f0[:3]) and np.allclose(f1[:3], 2 * f0[:3])
 
 
+def test_keller_segel_sensor_box_off_the_grid_is_refused(pkg):
+    """KellerSegelSetup.jl:120 indexes p[position-2 : position+2]: Julia throws a BoundsError for a sensor closer than 3 cells to
+    an edge; a negative Python slice would give an empty (position 2: [-1:4]) or truncated box without a word.  The setup
+    refuses the position by name, the oracle raises as the reference does, and the edge positions 3 and nx - 2 still build."""
+    from oracle import keller_segel as kg
+    for nx, bad in ((100, 2), (100, 99), (100, 0), (64, 63), (8, 7)):
+        pos = [3, bad, nx - 2]
+        with pytest.raises(pkg.PdecError, match=rf"sensor position {bad} "):
+            pkg.KellerSegelSetup(nx=nx, Lx=nx / 10, sensor_positions=pos, actuators_to_sensors=[1, 2, 3])
+        with pytest.raises(IndexError, match=rf"position {bad}:"):
+            kg.KSegConfig(nx=nx, Lx=nx / 10, sensor_positions=pos, actuators_to_sensors=[1, 2, 3])
+    for nx in (8, 65, 100):
+        s = pkg.KellerSegelSetup(nx=nx, Lx=nx / 10, sensor_positions=[3, nx - 2], actuators_to_sensors=[1, 2], window_size=1)
+        c = kg.KSegConfig(nx=nx, Lx=nx / 10, sensor_positions=[3, nx - 2], actuators_to_sensors=[1, 2], window_size=1)
+        assert np.array_equal(s.gaussians, c.gaussians) and s.gaussians.sum(axis=1).tolist() == [5.0, 5.0]
+        assert s.gaussians[0, :5].all() and s.gaussians[1, -5:].all()
+
+
 def test_graph_capture_phase_reachability(pkg):
     """which (chunk, ring phase) pairs the graph capture can ever meet -- host logic of
     pipeline.TrainPipeline._reachable, no GPU: E = 26 / 27 / 30 with chunk 24 miss phases, E = 51 (the bench) meets all"""
