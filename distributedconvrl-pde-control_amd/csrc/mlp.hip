@@ -1298,29 +1298,42 @@ __global__ __launch_bounds__(256) void step_glue_kernel(StepGlueArgs g_in) {
   launch_sync_done(g.sync);
 }
 
+static int mlp_maxw(const Mlp* M) {
+  int maxw = 1;
+  for (int l = 0; l <= M->L; ++l) maxw = std::max(maxw, M->dims[l]);
+  return maxw;
+}
+// dynamic LDS of the acting body: two activation buffers [widest layer][cols] of the state's type
+static size_t small_act_lds(const Mlp* M, int dtype, int cols) { return (size_t)2 * mlp_maxw(M) * cols * dtype_size(dtype); }
+
 // does the single-launch form serve this actor at `cols` columns of type `dtype`?  (the fused MFMA acting kernels keep fp32
 // actors at fp32 states; PDEC_SMALL_ACT=0: the generic launch sequence, for A/B tests)
 static bool small_act_ok(const Mlp* M, int dtype, int cols) {
   static const bool off = [] { const char* e = getenv("PDEC_SMALL_ACT"); return e && e[0] == '0'; }();
   if (off || M->L > SMALL_ACT_MAXL || cols < 1) return false;
   if (!(M->dtype == dtype || (M->dtype == PDEC_F32 && dtype == PDEC_F64))) return false;
-  int maxw = 1;
-  for (int l = 0; l <= M->L; ++l) maxw = std::max(maxw, M->dims[l]);
-  return (size_t)2 * maxw * cols * dtype_size(dtype) <= 48 * 1024;
+  return small_act_lds(M, dtype, cols) <= 48 * 1024;
+}
+
+// the fields of SmallActArgs that depend on the network
+static SmallActArgs small_act_args(const Mlp* M, int cols) {
+  SmallActArgs g{};
+  g.L = M->L; g.cols = cols;
+  g.maxw = mlp_maxw(M);
+  for (int l = 0; l <= M->L; ++l) g.dims[l] = M->dims[l];
+  for (int l = 0; l < M->L; ++l) { g.acts[l] = M->acts[l]; g.woff[l] = (int)M->w_off[l]; g.boff[l] = (int)M->b_off[l]; }
+  g.nrows = M->noise_rows < 0 ? M->dims[M->L] : M->noise_rows;
+  return g;
 }
 
 static int small_act(Mlp* M, int dtype, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
                      uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc) {
-  SmallActArgs g{};
-  g.L = M->L; g.cols = cols; g.learning = learning;
-  g.maxw = 1;
-  for (int l = 0; l <= M->L; ++l) { g.dims[l] = M->dims[l]; g.maxw = std::max(g.maxw, M->dims[l]); }
-  for (int l = 0; l < M->L; ++l) { g.acts[l] = M->acts[l]; g.woff[l] = (int)M->w_off[l]; g.boff[l] = (int)M->b_off[l]; }
-  g.nrows = M->noise_rows < 0 ? M->dims[M->L] : M->noise_rows;
+  SmallActArgs g = small_act_args(M, cols);
+  g.learning = learning;
   g.p = M->params.p;
   g.act_noise = act_noise; g.lim = act_limit; g.seed = seed; g.offset = offset;
   g.ctr_cur = ctr_cur; g.ctr_next = ctr_next; g.ctr_inc = ctr_inc;
-  const size_t lds = (size_t)2 * g.maxw * cols * dtype_size(dtype);
+  const size_t lds = small_act_lds(M, dtype, cols);
   ProfScope ps(M, "small_act");
   if (dtype == PDEC_F64 && M->dtype == PDEC_F32)
     hipLaunchKernelGGL((small_act_kernel<double, float>), dim3(1), dim3(256), lds, M->stream, g, (const double*)state, (double*)actions_out);
@@ -1330,6 +1343,14 @@ static int small_act(Mlp* M, int dtype, const void* state, int cols, double act_
     hipLaunchKernelGGL((small_act_kernel<float, float>), dim3(1), dim3(256), lds, M->stream, g, (const float*)state, (float*)actions_out);
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
+}
+
+// launch(step_glue_kernel<T, TP>) of the (state dtype, parameter dtype) pair; the caller brings its own launch call
+template <class F>
+static void step_glue_dispatch(int state_dtype, int param_dtype, F&& launch) {
+  if (state_dtype == PDEC_F64 && param_dtype == PDEC_F32) launch(step_glue_kernel<double, float>);
+  else if (state_dtype == PDEC_F64) launch(step_glue_kernel<double, double>);
+  else launch(step_glue_kernel<float, float>);
 }
 
 // a 3-layer fp32 actor whose published image the fused acting kernel reads
@@ -1481,15 +1502,11 @@ int pdec_step_glue(pdec_handle actor, pdec_handle trajectory_handle, int dtype, 
   g.halt = o->halt;
   g.sync = M->sync;
   M->sync = LaunchSync{};
-  SmallActArgs& a = g.act;
-  a.L = M->L; a.cols = cols; a.learning = 1;
-  a.maxw = 1;
-  for (int l = 0; l <= M->L; ++l) { a.dims[l] = M->dims[l]; a.maxw = std::max(a.maxw, M->dims[l]); }
-  for (int l = 0; l < M->L; ++l) { a.acts[l] = M->acts[l]; a.woff[l] = (int)M->w_off[l]; a.boff[l] = (int)M->b_off[l]; }
-  a.nrows = M->noise_rows < 0 ? M->dims[M->L] : M->noise_rows;
-  a.p = M->params.p;
-  a.act_noise = act_noise; a.lim = act_limit; a.seed = seed; a.offset = offset;
-  const size_t lds = act_mode == 1 ? (size_t)2 * a.maxw * cols * dtype_size(dtype) : 16;
+  g.act = small_act_args(M, cols);
+  g.act.learning = 1;
+  g.act.p = M->params.p;
+  g.act.act_noise = act_noise; g.act.lim = act_limit; g.act.seed = seed; g.act.offset = offset;
+  const size_t lds = act_mode == 1 ? small_act_lds(M, dtype, cols) : 16;
   hipEvent_t ev = nullptr;
   if (done_event) {
     ev = pdec::event_native(done_event);
@@ -1498,9 +1515,7 @@ int pdec_step_glue(pdec_handle actor, pdec_handle trajectory_handle, int dtype, 
   *served = 1;
   ProfScope ps(M, "step_glue");
   // (done_event rides on the launch as the completion event of its dispatch packet, like pdec_mlp_set_stop_event's)
-  if (dtype == PDEC_F64 && M->dtype == PDEC_F32) hipExtLaunchKernelGGL((step_glue_kernel<double, float>), dim3(1), dim3(256), lds, M->stream, nullptr, ev, 0, g);
-  else if (dtype == PDEC_F64) hipExtLaunchKernelGGL((step_glue_kernel<double, double>), dim3(1), dim3(256), lds, M->stream, nullptr, ev, 0, g);
-  else hipExtLaunchKernelGGL((step_glue_kernel<float, float>), dim3(1), dim3(256), lds, M->stream, nullptr, ev, 0, g);
+  step_glue_dispatch(dtype, M->dtype, [&](auto kern) { hipExtLaunchKernelGGL(kern, dim3(1), dim3(256), lds, M->stream, nullptr, ev, 0, g); });
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
 }
@@ -1569,8 +1584,7 @@ int pdec_population_create(pdec_handle* out, int M, const pdec_handle* actors, c
 
 int pdec_population_glue(pdec_handle pop, int phase, const void* reward, const int32_t* done_flags, const void* state,
                          void* actions_out) {
-  Population* P = lookup_as<Population>(pop, Kind::Population);
-  if (!P) { set_error("pdec_population_glue: bad handle"); return PDEC_E_HANDLE; }
+  GET_POP(P, pop);
   PDEC_REQUIRE(phase >= 0 && phase <= 2, "pdec_population_glue: bad phase %d", phase);
   PDEC_REQUIRE(phase == 2 || !reward == !done_flags, "pdec_population_glue: reward and done flags go together");
   PDEC_REQUIRE(phase != 1 || reward, "pdec_population_glue: the time-out push needs the rewards");
@@ -1587,16 +1601,11 @@ int pdec_population_glue(pdec_handle pop, int phase, const void* reward, const i
   g.pm = P->tab.as<PopMember>(); g.rows = P->rows; g.phase = phase;
   g.d_noise = ((long long)cols * na + 3) / 4; g.start_steps = P->start_steps;
   g.r_bytes = (size_t)cols * ts; g.s_bytes = (size_t)cols * ns * ts; g.o_bytes = (size_t)cols * na * ts;
-  SmallActArgs& a = g.act;
-  a.L = M->L; a.cols = cols; a.learning = 1;
-  a.maxw = 1;
-  for (int l = 0; l <= M->L; ++l) { a.dims[l] = M->dims[l]; a.maxw = std::max(a.maxw, M->dims[l]); }
-  for (int l = 0; l < M->L; ++l) { a.acts[l] = M->acts[l]; a.woff[l] = (int)M->w_off[l]; a.boff[l] = (int)M->b_off[l]; }
-  a.nrows = M->noise_rows < 0 ? M->dims[M->L] : M->noise_rows;
-  const size_t lds = phase == 0 ? (size_t)2 * a.maxw * cols * ts : 16;
+  g.act = small_act_args(M, cols);
+  g.act.learning = 1;
+  const size_t lds = phase == 0 ? small_act_lds(M, P->dtype, cols) : 16;
   ProfScope ps(P, "population_glue");
-  if (P->dtype == PDEC_F64) hipLaunchKernelGGL((step_glue_kernel<double, float>), dim3(P->M), dim3(256), lds, P->stream, g);
-  else hipLaunchKernelGGL((step_glue_kernel<float, float>), dim3(P->M), dim3(256), lds, P->stream, g);
+  step_glue_dispatch(P->dtype, M->dtype, [&](auto kern) { hipLaunchKernelGGL(kern, dim3(P->M), dim3(256), lds, P->stream, g); });
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
 }
@@ -1604,8 +1613,7 @@ int pdec_population_glue(pdec_handle pop, int phase, const void* reward, const i
 // the members' beta-power slots: get = write each member's (actor, critic) bp_sel into rows_host[m][POP_BPA / POP_BPC];
 // set = adopt them from there (and mark the networks' derived images stale after the updates of an episode)
 int pdec_population_bp_sel(pdec_handle pop, int64_t* rows_host, int set) {
-  Population* P = lookup_as<Population>(pop, Kind::Population);
-  if (!P) { set_error("pdec_population_bp_sel: bad handle"); return PDEC_E_HANDLE; }
+  GET_POP(P, pop);
   PDEC_REQUIRE(rows_host, "pdec_population_bp_sel: null");
   for (int m = 0; m < P->M; ++m) {
     int64_t* r = rows_host + (size_t)m * POP_ROW;
@@ -1642,8 +1650,7 @@ __global__ __launch_bounds__(256) void pop_copy_actors_kernel(const PopMember* _
 extern "C" {
 
 int pdec_population_set_actor_copies(pdec_handle pop, const pdec_handle* best, const pdec_handle* current) {
-  Population* P = lookup_as<Population>(pop, Kind::Population);
-  if (!P) { set_error("pdec_population_set_actor_copies: bad handle"); return PDEC_E_HANDLE; }
+  GET_POP(P, pop);
   PDEC_REQUIRE(best && current, "pdec_population_set_actor_copies: null");
   std::vector<float*> tab(2 * (size_t)P->M, nullptr);
   std::vector<Mlp*> nets;
@@ -1667,8 +1674,7 @@ int pdec_population_set_actor_copies(pdec_handle pop, const pdec_handle* best, c
 }
 
 int pdec_population_copy_actors(pdec_handle pop, const int32_t* which) {
-  Population* P = lookup_as<Population>(pop, Kind::Population);
-  if (!P) { set_error("pdec_population_copy_actors: bad handle"); return PDEC_E_HANDLE; }
+  GET_POP(P, pop);
   PDEC_REQUIRE(which && P->snap.p, "pdec_population_copy_actors: null flags or no snapshot table (pdec_population_set_actor_copies)");
   const int n = P->A[0]->nparams;
   const dim3 grid((unsigned)std::min(cdiv(n, 256), 16), (unsigned)P->M);

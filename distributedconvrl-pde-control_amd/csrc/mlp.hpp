@@ -187,3 +187,12 @@ struct Population : Object {
 };
 
 }  // namespace pdec
+
+// the population behind handle h at an entry point (the GET_MLP of populations; here because mlp.hip and mlp_small.hip
+// both have population entry points)
+#define GET_POP(P, h)                                                           \
+  pdec::Population* P = pdec::lookup_as<pdec::Population>(h, pdec::Kind::Population); \
+  if (!P) {                                                                     \
+    pdec::set_error("%s: bad handle", __func__);                                \
+    return PDEC_E_HANDLE;                                                       \
+  }

@@ -1214,34 +1214,34 @@ struct SmallSampling {     // != null: draw the slots in the kernel (pdec_ddpg_u
   int stride;
 };
 
-// Every kernel instantiation pdec_ddpg_update_small(_rng) can launch.  small_plan() picks one; the launch site and
-// pdec_debug_small_update_kernel both go through it, so the query reports exactly what a call would launch.
+// Every register-kernel instantiation pdec_ddpg_update_small(_rng) and pdec_population_update can launch, X(id, reported name,
+// kernel): the ONE list behind SmallKernelId, the names pdec_debug_small_update_kernel reports and the launch switch
+// (small_launch).  small_plan() picks one; the launch sites and the query both go through it, so the query reports exactly
+// what a call would launch.
+#define SMALL2_KERNELS(X)                                                                       \
+  X(S2F_2_1_3, "ddpg_small2f_kernel<2,1,3,1,3>", ddpg_small2f_kernel<2, 1, 3, true, 3>)         \
+  X(S2_2_1_3, "ddpg_small2_kernel<2,1,3,1>", ddpg_small2_kernel<2, 1, 3, true>)                 \
+  X(S2_13_12_3_OS5, "ddpg_small2_kernel<13,12,3,1,5>", ddpg_small2_kernel<13, 12, 3, true, 5>)  \
+  X(S2_10_9_3_OS4, "ddpg_small2_kernel<10,9,3,1,4>", ddpg_small2_kernel<10, 9, 3, true, 4>)     \
+  X(S2_13_12_3, "ddpg_small2_kernel<13,12,3,1>", ddpg_small2_kernel<13, 12, 3, true>)           \
+  X(S2_10_9_3, "ddpg_small2_kernel<10,9,3,1>", ddpg_small2_kernel<10, 9, 3, true>)              \
+  X(S2_4_3_4, "ddpg_small2_kernel<4,3,4,0>", ddpg_small2_kernel<4, 3, S2_BU, false>)            \
+  X(S2_10_9_4, "ddpg_small2_kernel<10,9,4,0>", ddpg_small2_kernel<10, 9, S2_BU, false>)         \
+  X(S2_13_12_4, "ddpg_small2_kernel<13,12,4,0>", ddpg_small2_kernel<13, 12, S2_BU, false>)      \
+  X(S2_16_15_4, "ddpg_small2_kernel<16,15,4,0>", ddpg_small2_kernel<16, 15, S2_BU, false>)
+static_assert(S2_BU == 4, "the reported names of the bounded instantiations spell S2_BU out");
 enum SmallKernelId {
-  SK_GENERIC,
-  SK_S2F_2_1_3,       // ddpg_small2f_kernel<2, 1, 3, true, 3>
-  SK_S2_2_1_3,        // ddpg_small2_kernel<2, 1, 3, true>
-  SK_S2_13_12_3_OS5,  // ddpg_small2_kernel<13, 12, 3, true, 5>
-  SK_S2_10_9_3_OS4,   // ddpg_small2_kernel<10, 9, 3, true, 4>
-  SK_S2_13_12_3,      // ddpg_small2_kernel<13, 12, 3, true>
-  SK_S2_10_9_3,       // ddpg_small2_kernel<10, 9, 3, true>
-  SK_S2_4_3_4,        // ddpg_small2_kernel<4, 3, S2_BU, false>
-  SK_S2_10_9_4,
-  SK_S2_13_12_4,
-  SK_S2_16_15_4,
+  SK_GENERIC,         // ddpg_small_kernel
+#define X(ID, NAME, ...) SK_##ID,
+  SMALL2_KERNELS(X)
+#undef X
   SK_BATCHED,         // no kernel (not in the name table): reward groups that split the minibatch, served by the batched update
 };
 static const char* const small_kernel_names[] = {
     "ddpg_small_kernel",
-    "ddpg_small2f_kernel<2,1,3,1,3>",
-    "ddpg_small2_kernel<2,1,3,1>",
-    "ddpg_small2_kernel<13,12,3,1,5>",
-    "ddpg_small2_kernel<10,9,3,1,4>",
-    "ddpg_small2_kernel<13,12,3,1>",
-    "ddpg_small2_kernel<10,9,3,1>",
-    "ddpg_small2_kernel<4,3,4,0>",
-    "ddpg_small2_kernel<10,9,4,0>",
-    "ddpg_small2_kernel<13,12,4,0>",
-    "ddpg_small2_kernel<16,15,4,0>",
+#define X(ID, NAME, ...) NAME,
+    SMALL2_KERNELS(X)
+#undef X
 };
 
 struct SmallPlan {
@@ -1344,14 +1344,46 @@ static int small_nets(pdec_handle hA, pdec_handle hC, pdec_handle hAt, pdec_hand
   return PDEC_OK;
 }
 
-// once per instantiation: allow the dynamic LDS of the launch (the register kernels ask for up to 160 KB)
-template <class K>
-static int small_lds_attr(K kern, size_t lds, size_t* done) {
-  if (*done < lds) {
-    PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    *done = lds;
-  }
+// the fields of SmallArgs that a solo call and a population launch share; the caller adds its traces and slots, sampling
+// bounds, beta-power slots and halt flag -- or the member table
+static int small_args(SmallArgs& g, const SmallPlan& pl, Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, int loops, int Bu, double gamma,
+                      double rho, int quirk, double eta_actor, double eta_critic) {
+  int rc;
+  if ((rc = fill_net(g.A, A, At)) || (rc = fill_net(g.C, C, Ct))) return rc;
+  g.maxw = pl.maxw;
+  g.lds_params = pl.lds_params;
+  g.loops = loops; g.Bu = Bu; g.ns = A->dims[0]; g.na = A->dims[A->L];
+  g.quirk = quirk && C->rg_g == 1 ? 0 : quirk;     // groups of one column: the diagonal target
+  g.gamma = (float)gamma; g.rho = (float)rho;      // Float32 in the reference (y = 0.99f0, p = 0.995f0)
+  g.eta_a = eta_actor; g.eta_c = eta_critic; g.b1 = 0.9; g.b2 = 0.999; g.eps = 1e-8;
+  g.smp_lds = pl.smp_lds;
   return PDEC_OK;
+}
+
+// the plan's kernel on `grid` workgroups; allows the launch's dynamic LDS once per kernel (the register kernels ask for up to
+// 160 KB)
+static int small_launch(const SmallPlan& pl, dim3 grid, hipStream_t stream, const SmallArgs& g, int nA, int nC) {
+  static size_t attr[SK_BATCHED] = {};
+  auto go = [&](auto kern, int threads, size_t lds_attr, const auto& args) -> int {
+    if (attr[pl.id] < lds_attr) {
+      PDEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_attr));
+      attr[pl.id] = lds_attr;
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(threads), pl.lds, stream, args);
+    PDEC_HIP(hipGetLastError());
+    return PDEC_OK;
+  };
+  if (pl.id == SK_GENERIC) return go(ddpg_small_kernel, SM_THREADS, 160 * 1024, g);
+  Small2Args a2{};
+  a2.g = g;
+  a2.g.lds_params = 0;
+  a2.nC = nC; a2.nA = nA;
+  switch (pl.id) {
+#define X(ID, NAME, ...) case SK_##ID: return go(__VA_ARGS__, pl.threads, pl.lds, a2);
+    SMALL2_KERNELS(X)
+#undef X
+    default: set_error("small update: no kernel for plan %d", (int)pl.id); return PDEC_E_INVALID;
+  }
 }
 
 static int ddpg_update_small_impl(pdec_handle hA, pdec_handle hC, pdec_handle hAt, pdec_handle hCt, const void* state_trace,
@@ -1369,18 +1401,11 @@ static int ddpg_update_small_impl(pdec_handle hA, pdec_handle hC, pdec_handle hA
   PDEC_REQUIRE(pl.id != SK_BATCHED,
                "pdec_ddpg_update_small: reward groups g = %d, L = %d split the minibatch of %d; update through pdec_ddpg_update_async",
                C->rg_g, C->rg_L, Bu);
-  if (quirk && C->rg_g == 1) quirk = 0;            // groups of one column: the diagonal target
-  const int ns = A->dims[0], na = A->dims[A->L];
   SmallArgs g{};
-  if ((rc = fill_net(g.A, A, At)) || (rc = fill_net(g.C, C, Ct))) return rc;
-  g.maxw = pl.maxw;
-  g.lds_params = pl.lds_params;
+  if ((rc = small_args(g, pl, A, C, At, Ct, loops, Bu, gamma, rho, quirk, eta_actor, eta_critic))) return rc;
   g.state = (const float*)state_trace; g.action = (const float*)action_trace;
   g.reward = (const float*)reward_trace; g.terminal = (const float*)terminal_trace;
   g.i_s = idx_s; g.i_rt = idx_rt; g.i_sn = idx_sn;
-  g.loops = loops; g.Bu = Bu; g.ns = ns; g.na = na; g.quirk = quirk;
-  g.gamma = (float)gamma; g.rho = (float)rho;      // Float32 in the reference (y = 0.99f0, p = 0.995f0)
-  g.eta_a = eta_actor; g.eta_c = eta_critic; g.b1 = 0.9; g.b2 = 0.999; g.eps = 1e-8;
   if (smp) {
     const int64_t hi = smp->n_valid - smp->stride;           // inds in 1:length(t)-number_actuators (src/PDEagent.jl:318)
     PDEC_REQUIRE(hi >= 1 && hi < ((int64_t)1 << 32) && smp->capacity >= 1 && smp->stride >= 0,
@@ -1390,41 +1415,11 @@ static int ddpg_update_small_impl(pdec_handle hA, pdec_handle hC, pdec_handle hA
     g.smp_base = smp->n_rt > smp->capacity ? smp->n_rt - smp->capacity : 0;      // logical index of the oldest entry
     g.smp_cap = (int)smp->capacity; g.smp_cap1 = (int)(smp->capacity + smp->stride); g.smp_stride = smp->stride;
   }
-  g.smp_lds = pl.smp_lds;
   if ((rc = bp_begin(A, g.b1, g.b2, &g.bpA)) || (rc = bp_begin(C, g.b1, g.b2, &g.bpC))) return rc;
   g.losses = (float*)losses_dev;
   g.halt = C->halt;
-  static size_t attr[sizeof(small_kernel_names) / sizeof(small_kernel_names[0])] = {};
   ProfScope ps(C, "ddpg_small");
-  if (pl.id == SK_GENERIC) {
-    if ((rc = small_lds_attr(ddpg_small_kernel, 160 * 1024, &attr[SK_GENERIC]))) return rc;
-    hipLaunchKernelGGL(ddpg_small_kernel, dim3(1), dim3(SM_THREADS), pl.lds, C->stream, g);
-  } else {
-    Small2Args a2{};
-    a2.g = g;
-    a2.g.lds_params = 0;
-    a2.nC = C->dims[1]; a2.nA = A->dims[1];
-#define S2_LAUNCH(ID, ...)                                                                                             \
-  case ID:                                                                                                             \
-    if ((rc = small_lds_attr(__VA_ARGS__, pl.lds, &attr[ID]))) return rc;                                              \
-    hipLaunchKernelGGL((__VA_ARGS__), dim3(1), dim3(pl.threads), pl.lds, C->stream, a2);                               \
-    break;
-    switch (pl.id) {
-      S2_LAUNCH(SK_S2F_2_1_3, ddpg_small2f_kernel<2, 1, 3, true, 3>)
-      S2_LAUNCH(SK_S2_2_1_3, ddpg_small2_kernel<2, 1, 3, true>)
-      S2_LAUNCH(SK_S2_13_12_3_OS5, ddpg_small2_kernel<13, 12, 3, true, 5>)
-      S2_LAUNCH(SK_S2_10_9_3_OS4, ddpg_small2_kernel<10, 9, 3, true, 4>)
-      S2_LAUNCH(SK_S2_13_12_3, ddpg_small2_kernel<13, 12, 3, true>)
-      S2_LAUNCH(SK_S2_10_9_3, ddpg_small2_kernel<10, 9, 3, true>)
-      S2_LAUNCH(SK_S2_4_3_4, ddpg_small2_kernel<4, 3, S2_BU, false>)
-      S2_LAUNCH(SK_S2_10_9_4, ddpg_small2_kernel<10, 9, S2_BU, false>)
-      S2_LAUNCH(SK_S2_13_12_4, ddpg_small2_kernel<13, 12, S2_BU, false>)
-      S2_LAUNCH(SK_S2_16_15_4, ddpg_small2_kernel<16, 15, S2_BU, false>)
-      default: set_error("pdec_ddpg_update_small: no kernel for plan %d", (int)pl.id); return PDEC_E_INVALID;
-    }
-#undef S2_LAUNCH
-  }
-  PDEC_HIP(hipGetLastError());
+  if ((rc = small_launch(pl, dim3(1), C->stream, g, A->dims[1], C->dims[1]))) return rc;
   bp_done(A);
   bp_done(C);
   A->fw_dirty = C->fw_dirty = At->fw_dirty = Ct->fw_dirty = true;
@@ -1433,60 +1428,20 @@ static int ddpg_update_small_impl(pdec_handle hA, pdec_handle hC, pdec_handle hA
 
 // one launch of M workgroups: member m's small update with device-side sampling where its own trigger fires (sm_member_begin)
 extern "C" int pdec_population_update(pdec_handle pop) {
-  Population* P = lookup_as<Population>(pop, Kind::Population);
-  if (!P) { set_error("pdec_population_update: bad handle"); return PDEC_E_HANDLE; }
-  Mlp *A = P->A[0], *C = P->C[0], *At = P->At[0], *Ct = P->Ct[0];
+  GET_POP(P, pop);
+  Mlp *A = P->A[0], *C = P->C[0];
   SmallPlan pl{};
   int rc;
   if ((rc = small_plan(A, C, P->loops, P->Bu, (float)P->rho, true, P->quirk, &pl))) return rc;
   PDEC_REQUIRE(pl.id != SK_BATCHED, "pdec_population_update: reward groups that split the minibatch are not served");
-  int quirk = P->quirk;
-  if (quirk && C->rg_g == 1) quirk = 0;
   SmallArgs g{};
-  if ((rc = fill_net(g.A, A, At)) || (rc = fill_net(g.C, C, Ct))) return rc;
-  g.maxw = pl.maxw;
-  g.lds_params = pl.lds_params;
-  g.loops = P->loops; g.Bu = P->Bu; g.ns = A->dims[0]; g.na = A->dims[A->L]; g.quirk = quirk;
-  g.gamma = (float)P->gamma; g.rho = (float)P->rho;
-  g.eta_a = P->eta_a; g.eta_c = P->eta_c; g.b1 = 0.9; g.b2 = 0.999; g.eps = 1e-8;
+  if ((rc = small_args(g, pl, A, C, P->At[0], P->Ct[0], P->loops, P->Bu, P->gamma, P->rho, P->quirk, P->eta_a, P->eta_c))) return rc;
   g.smp_on = 1;
   g.smp_cap = (int)P->cap; g.smp_cap1 = (int)P->cap1; g.smp_stride = P->stride;
-  g.smp_lds = pl.smp_lds;
   g.pm = P->tab.as<PopMember>(); g.rows = P->rows;
   g.m_after = P->after; g.m_freq = P->freq; g.m_dsample = ((long long)P->loops * P->Bu + 3) / 4;
-  static size_t attr[sizeof(small_kernel_names) / sizeof(small_kernel_names[0])] = {};
-  const dim3 grid(P->M);
   ProfScope ps(P, "population_update");
-  if (pl.id == SK_GENERIC) {
-    if ((rc = small_lds_attr(ddpg_small_kernel, 160 * 1024, &attr[SK_GENERIC]))) return rc;
-    hipLaunchKernelGGL(ddpg_small_kernel, grid, dim3(SM_THREADS), pl.lds, P->stream, g);
-  } else {
-    Small2Args a2{};
-    a2.g = g;
-    a2.g.lds_params = 0;
-    a2.nC = C->dims[1]; a2.nA = A->dims[1];
-#define S2_LAUNCH(ID, ...)                                                                                             \
-  case ID:                                                                                                             \
-    if ((rc = small_lds_attr(__VA_ARGS__, pl.lds, &attr[ID]))) return rc;                                              \
-    hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(pl.threads), pl.lds, P->stream, a2);                                  \
-    break;
-    switch (pl.id) {
-      S2_LAUNCH(SK_S2F_2_1_3, ddpg_small2f_kernel<2, 1, 3, true, 3>)
-      S2_LAUNCH(SK_S2_2_1_3, ddpg_small2_kernel<2, 1, 3, true>)
-      S2_LAUNCH(SK_S2_13_12_3_OS5, ddpg_small2_kernel<13, 12, 3, true, 5>)
-      S2_LAUNCH(SK_S2_10_9_3_OS4, ddpg_small2_kernel<10, 9, 3, true, 4>)
-      S2_LAUNCH(SK_S2_13_12_3, ddpg_small2_kernel<13, 12, 3, true>)
-      S2_LAUNCH(SK_S2_10_9_3, ddpg_small2_kernel<10, 9, 3, true>)
-      S2_LAUNCH(SK_S2_4_3_4, ddpg_small2_kernel<4, 3, S2_BU, false>)
-      S2_LAUNCH(SK_S2_10_9_4, ddpg_small2_kernel<10, 9, S2_BU, false>)
-      S2_LAUNCH(SK_S2_13_12_4, ddpg_small2_kernel<13, 12, S2_BU, false>)
-      S2_LAUNCH(SK_S2_16_15_4, ddpg_small2_kernel<16, 15, S2_BU, false>)
-      default: set_error("pdec_population_update: no kernel for plan %d", (int)pl.id); return PDEC_E_INVALID;
-    }
-#undef S2_LAUNCH
-  }
-  PDEC_HIP(hipGetLastError());
-  return PDEC_OK;
+  return small_launch(pl, dim3(P->M), P->stream, g, A->dims[1], C->dims[1]);
 }
 
 extern "C" int pdec_debug_small_update_kernel(pdec_handle hA, pdec_handle hC, pdec_handle hAt, pdec_handle hCt, int loops, int Bu,

@@ -17,9 +17,11 @@ from . import _lib
 from .agent import Agent, PRE_EXPERIMENT_STAGE, PRE_EPISODE_STAGE, POST_EXPERIMENT_STAGE
 from .env import PDEenv, _on_stream
 from .hook import PDEhook
-from .run import (StopAfterEpisode, StopAfterEpisodeWithMinSteps, _EpisodeLogs, _add_episode_reward, _episode_steps,
-                  _episode_time, _stop_fired)
+from .pipeline import _Event
+from .run import (StopAfterEpisode, StopAfterEpisodeWithMinSteps, _EpisodeLogs, _add_episode_reward, _episode_schedule,
+                  _episode_steps, _episode_time, _executed_steps, _join, _stop_fired, device_episodes_ok)
 
+# a member's row of the device counter table: POP_ROW and enum PopSlot of csrc/mlp.hpp (tests/test_host_logic.py compares them)
 ROW = 16
 USTEP, NSA, NRT, NOISE, SAMPLE, HALT, ACTIVE, BPA, BPC, NOISE_AMP, LIMIT = range(11)
 
@@ -69,6 +71,15 @@ def _model(actor):
     return getattr(actor, "model", actor)
 
 
+def _handle_int(model):
+    return int(getattr(model.handle, "value", model.handle))
+
+
+def _has_persistent_rollout(setup):
+    """the 2-D environments and the global agent have no persistent rollout at all"""
+    return not (getattr(setup, "is_fluid", False) or getattr(setup, "is_kseg2d", False) or getattr(setup, "mono", False))
+
+
 def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, dtype=torch.float64, stream=None, act_limit=1.0,
                     log=False, device="cuda:0"):
     """One greedy evaluation episode of each of M actors (HipMLPs or approximators of ONE shape) from the same K initial fields:
@@ -100,9 +111,8 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
             small.random_init(int(init_seed), 0, out=y0)
         y0 = (y0 if isinstance(y0, torch.Tensor) else torch.as_tensor(np.array(y0, copy=True))).to(device=dev, dtype=dtype).contiguous()
         K = int(y0.shape[0])
-        # the 2-D environments and the global agent have no persistent rollout at all: no B = M K environment is built to hear it
-        env = None
-        if not (getattr(setup, "is_fluid", False) or getattr(setup, "is_kseg2d", False) or getattr(setup, "mono", False)):
+        env = None              # without a persistent rollout no B = M K environment is built to hear it
+        if _has_persistent_rollout(setup):
             env = PDEenv(setup, B=M * K, dtype=dtype, device=device, y0=y0.repeat((M,) + (1,) * (y0.dim() - 1)), stream=stream,
                          autoreset=False)
     B = M * K
@@ -123,7 +133,7 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
             if log:
                 out.update(y=torch.empty((T,) + env._yshape, **kw), p=torch.empty((T,) + env._pshape, **kw),
                            action=torch.empty((T,) + env._ashape, **kw), reward=torch.empty((T, B, setup.reward_len), **kw))
-        handles = (_lib.Handle * M)(*[int(getattr(md.handle, "value", md.handle)) for md in models])
+        handles = (_lib.Handle * M)(*[_handle_int(md) for md in models])
         P = _lib.ptr
         try:
             _lib.check(env.lib.pdec_rollout_members(
@@ -160,7 +170,7 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
         host = (res["episode_reward"].double().cpu().numpy(), res["done_step"].cpu().numpy())     # (waits for the stream)
     res["score"], res["order"] = score_members(*host)
     res["one_launch"] = one
-    is_ks = not (getattr(setup, "is_fluid", False) or getattr(setup, "is_kseg2d", False)) and tuple(setup.y_shape) == (setup.nx,)
+    is_ks = one and tuple(setup.y_shape) == (setup.nx,)      # (served: a setup with a persistent rollout, so no 2-D one)
     res["workgroups"] = (len(member_workgroups(M, K)) if is_ks else B) if one else None
     if one:
         env.close()
@@ -171,7 +181,6 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
 
 class Population:
     def __init__(self, setup, agents, hooks, stream_env, dtype=torch.float64, device="cuda:0"):
-        from .run import device_episodes_ok
         M = len(agents)
         if M < 1 or len(hooks) != M:
             _refuse("needs one hook per agent and at least one member")
@@ -234,7 +243,7 @@ class Population:
         with _on_stream(self.stream_upd):
             self.rows = torch.zeros((M, ROW), dtype=torch.int64, device=self.env.device)
         H = (_lib.Handle * M)
-        hs = [H(*[int(getattr(getattr(ag.policy, k).model.handle, "value", getattr(ag.policy, k).model.handle)) for ag in agents])
+        hs = [H(*[_handle_int(getattr(ag.policy, k).model) for ag in agents])
               for k in ("behavior_actor", "behavior_critic", "target_actor", "target_critic")]
         traces = (C.c_void_p * (4 * M))(*[t.data_ptr() for ag in agents for t in (ag.trajectory.state, ag.trajectory.action,
                                                                                     ag.trajectory.reward, ag.trajectory.terminal)])
@@ -296,22 +305,14 @@ class Population:
             hk(PRE_EXPERIMENT_STAGE, ag, env)
             ag(PRE_EXPERIMENT_STAGE, env)
         # the hooks' best / current actors (made at PRE_EXPERIMENT): the targets of the one copy launch per episode
-
-        def handle(nna):
-            return int(getattr(nna.model.handle, "value", nna.model.handle))
-        best = (_lib.Handle * M)(*[handle(hk.bestNNA) if hk.collect_NNA else 0 for hk in self.hooks])
-        cur = (_lib.Handle * M)(*[handle(hk.currentNNA) if hk.collect_NNA else 0 for hk in self.hooks])
+        best = (_lib.Handle * M)(*[_handle_int(hk.bestNNA.model) if hk.collect_NNA else 0 for hk in self.hooks])
+        cur = (_lib.Handle * M)(*[_handle_int(hk.currentNNA.model) if hk.collect_NNA else 0 for hk in self.hooks])
         _lib.check(self.lib.pdec_population_set_actor_copies(self._h, best, cur))
         active = np.ones(M, dtype=bool)
-
-        def join():
-            s_upd.wait_stream(s_env)
-            s_env.wait_stream(s_upd)
-
         while active.any():
-            join()
+            _join(s_upd, s_env)
             self._episode(active, stops)
-        join()
+        _join(s_upd, s_env)
         for ag, hk in zip(self.agents, self.hooks):
             hk(POST_EXPERIMENT_STAGE, ag, env)
         return self.hooks
@@ -380,10 +381,8 @@ class Population:
             flags.zero_()
         with _on_stream(s_upd):
             self.rows.copy_(torch.from_numpy(rows))
-        from .pipeline import _Event
         ev_act, ev_env = _Event(lib), _Event(lib)
-        s_upd.wait_stream(s_env)
-        s_env.wait_stream(s_upd)
+        _join(s_upd, s_env)
         # (per step: the member-indexed glue and update on the networks' stream, the member-layout env step on the env's)
         for t in range(T):
             _lib.check(lib.pdec_population_glue(self._h, 0, P(logs.reward[t - 1]) if t else None, P(flags[t - 1]) if t else None,
@@ -408,13 +407,11 @@ class Population:
         fl = host[nr:nr + nf].copy().view(np.int32).reshape(T, M)
         mean_h = host[nr + nf:].copy().view(np.float64).reshape(M, T)
         # ---- settle every member at its number of executed steps
-        n_of = np.zeros(M, dtype=np.int64)
-        for m in range(M):
-            if not active[m]:
-                continue
-            bad = np.flatnonzero(fl[:, m])
-            n_of[m] = int(bad[0]) + 1 if bad.size and bad[0] < T - 1 else T
+        n_of = np.array([_executed_steps(fl[:, m], T) if active[m] else 0 for m in range(M)], dtype=np.int64)
         self.episode_steps.append(n_of.copy())
+        pol0, tr0 = self.agents[0].policy, self.agents[0].trajectory
+        sched = _episode_schedule(start[:, :SAMPLE + 1], T, cols, pol0.behavior_actor.model.dims[-1], tr0.capacity, tr0.stride,
+                                  pol0.update_after, pol0.update_freq, pol0.update_loops, pol0.batch_size, pol0.start_steps)
         _lib.check(lib.pdec_population_bp_sel(self._h, rows_out.ctypes.data_as(C.c_void_p), 1))
         with _on_stream(s_env):
             ii = torch.as_tensor(n_of, device=env.device)
@@ -433,11 +430,10 @@ class Population:
         for m in np.flatnonzero(active):
             ag, hk, n = self.agents[m], self.hooks[m], int(n_of[m])
             pol, tr = ag.policy, ag.trajectory
-            r = rows_out[m]
-            pol.update_step, tr.n_sa, tr.n_rt, pol._noise_off, pol._sample_off = (int(r[USTEP]), int(r[NSA]), int(r[NRT]),
-                                                                                   int(r[NOISE]), int(r[SAMPLE]))
-            if pol.update_step != start[m, USTEP] + n or tr.n_sa != start[m, NSA] + n * cols:
+            counters = rows_out[m, :SAMPLE + 1].tolist()
+            if counters != sched.after[m, n - 1].tolist():
                 raise RuntimeError(f"Population: member {m}'s device counters disagree with its {n} executed steps")
+            pol.update_step, tr.n_sa, tr.n_rt, pol._noise_off, pol._sample_off = counters
             _add_episode_reward(hk, mean_h[m, :n], np_dt)
             if hk.collect_bestDF:
                 hk._rows_bulk = (list(range(1, n + 1)), la[1:n + 1, m], lp[:n, m], ly[1:n + 1, m], lr[:n, m])

@@ -1,8 +1,17 @@
 """The RL.jl run loop the reference relies on (`run(agent, env, stop_condition, hook)`), with
 the stage order replicated in-tree by scripts/Fluid/setup/FluidSetup.jl:436-519, and the
 reference's stop conditions (src/StopCondition.jl:6-40)."""
+import ctypes as C
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import _lib
 from .agent import (PRE_EXPERIMENT_STAGE, PRE_EPISODE_STAGE, PRE_ACT_STAGE, POST_ACT_STAGE, POST_EPISODE_STAGE,
                     POST_EXPERIMENT_STAGE)
+from .env import _on_stream
+from .pipeline import _Event
 
 
 class StopAfterEpisode:
@@ -84,49 +93,73 @@ def run(agent, env, stop_condition, hook, overlap=None, device_episodes=None):
         if two:                                # two streams without the event protocol would race: order them every stage
             return _run_two_streams_serial(agent, env, stop_condition, hook, s_env, s_upd)
         return _run_plain(agent, env, stop_condition, hook)
-    import torch
     ev_act, ev_env = torch.cuda.Event(), torch.cuda.Event()
 
     def release_env_step():                    # between the PRE_ACT push and the update (Agent.after_push)
         ev_act.record(s_upd)
         s_env.wait_event(ev_act)
 
-    def join():                                # episode boundaries: both streams see everything the other has done
-        s_upd.wait_stream(s_env)
-        s_env.wait_stream(s_upd)
+    def env_step_done():                       # POST_ACT push and the next acting kernel read what the step wrote
+        ev_env.record(s_env)
+        s_upd.wait_event(ev_env)
 
-    prev_hook, agent.after_push = getattr(agent, "after_push", None), release_env_step
+    # agent(env) and the PRE_ACT stage on s_upd: push (s, a) | release_env_step | update; env(action) on s_env, beside the update
+    return _stage_loop(agent, env, stop_condition, hook, join=lambda: _join(s_upd, s_env), after_env_step=env_step_done,
+                       after_push=release_env_step)
+
+
+def _join(s_a, s_b):
+    """both streams see everything the other has done"""
+    s_a.wait_stream(s_b)
+    s_b.wait_stream(s_a)
+
+
+def _nothing():
+    pass
+
+
+def _call(f, *a):
+    return f(*a)
+
+
+def _stage_loop(agent, env, stop_condition, hook, staged=_call, join=_nothing, after_env_step=_nothing, after_push=None):
+    """RL.jl's stage order, written once.  staged(f, *args) surrounds every stage (the plain call, or join - call - join for
+    two streams without the event protocol), join() stands at the episode boundaries of the overlapped form, after_env_step()
+    follows env(action) (the overlapped form's event pair), after_push (not None) is Agent.after_push for the loop's duration."""
+    prev_hook = getattr(agent, "after_push", None)
+    if after_push is not None:
+        agent.after_push = after_push
     try:
-        hook(PRE_EXPERIMENT_STAGE, agent, env)
-        agent(PRE_EXPERIMENT_STAGE, env)
+        staged(hook, PRE_EXPERIMENT_STAGE, agent, env)
+        staged(agent, PRE_EXPERIMENT_STAGE, env)
         is_stop = False
         while not is_stop:
             join()
-            env.reset()
+            staged(env.reset)
             join()
-            agent(PRE_EPISODE_STAGE, env)
-            hook(PRE_EPISODE_STAGE, agent, env)
+            staged(agent, PRE_EPISODE_STAGE, env)
+            staged(hook, PRE_EPISODE_STAGE, agent, env)
             join()
             while not env.is_terminated():
-                action = agent(env)            # s_upd (behind the update of the previous step; waited for the env step below)
-                agent(PRE_ACT_STAGE, env, action)      # s_upd: push (s, a) | release_env_step | update
-                hook(PRE_ACT_STAGE, agent, env)
-                env(action)                    # s_env, beside the update
-                ev_env.record(s_env)
-                s_upd.wait_event(ev_env)       # POST_ACT push and the next acting kernel read what the step wrote
-                agent(POST_ACT_STAGE, env)
-                hook(POST_ACT_STAGE, agent, env)
+                action = staged(agent, env)
+                staged(agent, PRE_ACT_STAGE, env, action)
+                staged(hook, PRE_ACT_STAGE, agent, env)
+                staged(env, action)
+                after_env_step()
+                staged(agent, POST_ACT_STAGE, env)
+                staged(hook, POST_ACT_STAGE, agent, env)
                 if stop_condition(agent, env):
                     is_stop = True
                     break
             if env.is_terminated():
                 join()
-                agent(POST_EPISODE_STAGE, env)
-                hook(POST_EPISODE_STAGE, agent, env)
+                staged(agent, POST_EPISODE_STAGE, env)
+                staged(hook, POST_EPISODE_STAGE, agent, env)
         join()
-        hook(POST_EXPERIMENT_STAGE, agent, env)
+        staged(hook, POST_EXPERIMENT_STAGE, agent, env)
     finally:
-        agent.after_push = prev_hook
+        if after_push is not None:
+            agent.after_push = prev_hook
     return hook
 
 
@@ -135,7 +168,6 @@ class _EpisodeLogs:
     so a step issued behind the end of the episode overwrites nothing that is still needed"""
 
     def __init__(self, env, T):
-        import torch
         kw = dict(dtype=env.dtype, device=env.device)
         self.T = T
         self.y = torch.zeros((T + 1,) + env._yshape, **kw)
@@ -193,9 +225,42 @@ def _stop_fired(stop_condition, agent, n):
     return fired
 
 
+def _executed_steps(flags, T):
+    """control steps of an episode of T that count, from its per-step done flags: up to and with the first flagged step (a
+    flag at the last step is the time-out)"""
+    bad = np.flatnonzero(flags)
+    return int(bad[0]) + 1 if bad.size and bad[0] < T - 1 else T
+
+
+_Schedule = namedtuple("_Schedule", "acting before fires n_valid after")
+
+
+def _episode_schedule(start, T, cols, na, capacity, stride, update_after, update_freq, update_loops, batch_size, start_steps):
+    """The per-step scalars of an episode of T control steps, the ONE host statement of the counter movements of the stage
+    loop and of the update trigger of src/PDEagent.jl:354-355.  start = (update_step, n_sa, n_rt, noise offset, sample offset)
+    at the episode's first step, or an array [..., 5] of them (a population's members).  Arrays [..., T] (counters [..., T, 5],
+    in start's order):
+      acting   the actor acts (update_step, incremented as the step begins, is beyond start_steps); else the start policy
+      before   the counters as the step begins: where its pushes and its Philox draws go
+      fires    the update runs, on n_valid = len(trajectory) entries, drawing from sample offset before[..., 4]
+      after    the counters behind the step's POST_ACT push; after[..., n - 1, :] is the state after n executed steps"""
+    start = np.asarray(start, dtype=np.int64)[..., None, :]
+    t = np.arange(T, dtype=np.int64)
+    ustep = start[..., 0] + t + 1
+    n_sa, n_rt = start[..., 1] + t * cols, start[..., 2] + t * cols
+    acting = ustep > start_steps
+    n_valid = np.minimum(n_rt, capacity)
+    fires = (n_valid > update_after * stride) & (ustep % update_freq == 0)
+    d_noise, d_sample = (cols * na + 3) // 4, (update_loops * batch_size + 3) // 4
+    noise = start[..., 3] + d_noise * np.cumsum(acting, axis=-1)
+    sample = start[..., 4] + d_sample * np.cumsum(fires, axis=-1)
+    before = np.stack([ustep - 1, n_sa, n_rt, noise - d_noise * acting, sample - d_sample * fires], axis=-1)
+    after = np.stack([ustep, n_sa + cols, n_rt + cols, noise, sample], axis=-1)
+    return _Schedule(acting, before, fires, n_valid, after)
+
+
 def _launch_sync_ok(env):
     """the fused fp64 KS step of one trajectory with 192 / 240 / 600 cells: the launch that honours pdec_set_launch_sync"""
-    import torch
     s = env.setup
     return (getattr(s, "integrator", None) == "cnab2" and getattr(s, "nx", 0) in (192, 240, 600) and env.B == 1
             and env.dtype == torch.float64 and not getattr(s, "memory_size", 0))
@@ -204,9 +269,6 @@ def _launch_sync_ok(env):
 def _step_glue(lib, pol, tr, env, logs, t, cols, A, acting, pending_rt, done_event=None):
     """[POST_ACT push of step t - 1] + agent(env) + PRE_ACT push of step t as one launch (pdec_step_glue); False = not served,
     nothing enqueued, no counter moved"""
-    import ctypes as C
-
-    from . import _lib
     if getattr(tr, "_h", None) is None or getattr(pol, "_glue_off", False):
         return False
     m = pol.behavior_actor.model
@@ -236,11 +298,8 @@ def _fast_issue(lib, pol, tr, env, agent, logs, T, cols, A, sync, seq):
     """The step loop of _run_device_episodes for the case where every hand-over is inside the kernels (glue launch served, fused
     fp64 KS step, small-batch update with device-side sampling): the SAME library calls with the SAME arguments as the general
     loop below, issued through the raw C functions from addresses computed once -- the general loop spends ~45 us of host time per
-    step (25 pointer look-ups, five wrapped calls) where the GPU needs 57.  Returns issue(marks) or None when the case is not
-    this one."""
-    import ctypes as C
-
-    from . import _lib
+    step (25 pointer look-ups, five wrapped calls) where the GPU needs 57.  Returns issue(sched), which takes every counter
+    from the episode's schedule (_episode_schedule), or None when the case is not this one."""
     if not (pol.small_update_ok() and pol.sampling == "device" and getattr(tr, "_h", None) is not None):
         return None
     raw = lib._c
@@ -248,7 +307,6 @@ def _fast_issue(lib, pol, tr, env, agent, logs, T, cols, A, sync, seq):
     check = _lib.check
     Am, Cm, Atm, Ctm = (pol.behavior_actor.model, pol.behavior_critic.model, pol.target_actor.model, pol.target_critic.model)
     hA, hC, hAt, hCt, henv, htr = Am.handle, Cm.handle, Atm.handle, Ctm.handle, env.handle, tr._h
-    na = Am.dims[-1]
     dcode = _lib.dtype_code(env.dtype)
 
     def base(tns):                 # address of slot 0 and bytes per slot of a [slots, ...] log
@@ -264,42 +322,37 @@ def _fast_issue(lib, pol, tr, env, agent, logs, T, cols, A, sync, seq):
     gamma, rho, quirk = float(pol.y), pol.rho_effective, int(pol.quirk)
     eta_a, eta_c = float(pol.behavior_actor.optimizer.eta), float(pol.behavior_critic.optimizer.eta)
     pL = pol._losses.data_ptr()
-    d_noise, d_sample = (cols * na + 3) // 4, (loops * Bu + 3) // 4
     served = C.c_int(0)
     pserved = C.byref(served)
-    after, freq, start_steps = pol.update_after * stride, pol.update_freq, pol.start_steps
 
-    def issue(marks):
-        n_sa, n_rt, ustep, noff, soff, q = tr.n_sa, tr.n_rt, pol.update_step, pol._noise_off, pol._sample_off, seq[0]
+    def issue(sched):
+        q = seq[0]
         seed_n, seed_s = pol._noise_seed, pol._sample_seed
+        acting, before, fires, n_valid = sched.acting.tolist(), sched.before.tolist(), sched.fires.tolist(), sched.n_valid.tolist()
         for t in range(T):
-            ustep += 1
             q += 1
-            acting = ustep > start_steps
-            pend = t > 0
+            _, n_sa, n_rt, noff, soff = before[t]
+            pend = t > 0                 # the POST_ACT push of step t - 1 rides on this launch: n_rt counts it already
             rc = f_sync(hA, f1 if pend else None, q - 1, f0, q)
             rc = rc or f_glue(hA, htr, dcode, (aR + (t - 1) * sR) if pend else None, (aD + (t - 1) * 4) if pend else None, A, 0,
-                              pTR, pTT, cap, n_rt % cap, cols if pend else 0, 1 if acting else 2, aS + t * sS, cols, noise, limit,
-                              seed_n, noff, aA + (t + 1) * sA, pTS, pTA, cap1, n_sa % cap1, cols, 0, pserved)
+                              pTR, pTT, cap, (n_rt - cols if pend else n_rt) % cap, cols if pend else 0, 1 if acting[t] else 2,
+                              aS + t * sS, cols, noise, limit, seed_n, noff, aA + (t + 1) * sA, pTS, pTA, cap1, n_sa % cap1, cols, 0,
+                              pserved)
             if rc or not served.value:
                 check(rc)
                 raise RuntimeError("run(device_episodes): pdec_step_glue stopped serving the loop it served at its start")
-            if pend:
-                n_rt += cols
-            n_sa += cols
-            if acting:
-                noff += d_noise
-            if min(n_rt, cap) > after and ustep % freq == 0:                   # Agent._maybe_update, src/PDEagent.jl:354-355
-                rc = f_upd(hA, hC, hAt, hCt, pTS, pTA, pTR, pTT, loops, Bu, seed_s, soff, min(n_rt, cap), n_rt, cap, stride, gamma,
+            if fires[t]:
+                rc = f_upd(hA, hC, hAt, hCt, pTS, pTA, pTR, pTT, loops, Bu, seed_s, soff, n_valid[t], n_rt, cap, stride, gamma,
                            rho, quirk, eta_a, eta_c, pL)
-                soff += d_sample
             rc = rc or f_sync(henv, f0, q, f1, q)
             rc = rc or f_env(henv, aY + t * sY, aA + (t + 1) * sA, aA + t * sA, aS + t * sS, aY + (t + 1) * sY, aP + t * sP,
                              aS + (t + 1) * sS, aR + t * sR, aD + t * 4)
             if rc:
                 check(rc)
-            marks.append((noff, soff))
-        tr.n_sa, tr.n_rt, pol.update_step, pol._noise_off, pol._sample_off, seq[0] = n_sa, n_rt, ustep, noff, soff, q
+        seq[0] = q
+        # (the last step's POST_ACT push is the caller's time-out push: n_rt stays one push behind)
+        pol.update_step, tr.n_sa, _, pol._noise_off, pol._sample_off = sched.after[-1].tolist()
+        tr.n_rt = before[-1][2]
     return issue
 
 
@@ -311,14 +364,6 @@ def _run_device_episodes(agent, env, stop_condition, hook, s_env, s_upd):
     one thing it does not know, whether a step blew the trajectory up, is the device's halt flag: the POST_ACT push of that
     step raises it and the pushes / updates of the later steps do nothing, all their other outputs go to per-step slots.  One
     read-back per episode tells how many steps counted; the host counters are set to that."""
-    import ctypes as C
-
-    import numpy as np
-    import torch
-
-    from . import _lib
-    from .env import _on_stream
-
     pol, tr, lib = agent.policy, agent.trajectory, env.lib
     pol._glue_off = False                     # ask the library once per run whether it serves the one-launch glue
     two = s_env.cuda_stream != s_upd.cuda_stream
@@ -329,7 +374,6 @@ def _run_device_episodes(agent, env, stop_condition, hook, s_env, s_upd):
     if logs is None or logs.T != T:
         with _on_stream(s_env):
             logs = env._episode_logs = _EpisodeLogs(env, T)
-    from .pipeline import _Event
     ev_act, ev_env = _Event(lib), _Event(lib)      # device-scope events: the hand-offs are on every step's chain
     P = _lib.ptr
     # device-side hand-overs (see the step loop): flags [glue, env step] and the sequence number of the step they count
@@ -352,8 +396,7 @@ def _run_device_episodes(agent, env, stop_condition, hook, s_env, s_upd):
 
     def join():
         if two:
-            s_upd.wait_stream(s_env)
-            s_env.wait_stream(s_upd)
+            _join(s_upd, s_env)
 
     def episode():
         """enqueue the T control steps, read back once, settle the host state; returns True when the stop condition fired"""
@@ -363,14 +406,14 @@ def _run_device_episodes(agent, env, stop_condition, hook, s_env, s_upd):
             logs.done.zero_()
             logs.halt.zero_()
         join()
-        start = (pol.update_step, tr.n_sa, tr.n_rt, pol._noise_off, pol._sample_off)
-        marks = []                                        # per step: (noise draws so far, sample offset so far)
+        sched = _episode_schedule((pol.update_step, tr.n_sa, tr.n_rt, pol._noise_off, pol._sample_off), T, cols,
+                                  pol.behavior_actor.model.dims[-1], tr.capacity, tr.stride, pol.update_after, pol.update_freq, pol.update_loops, pol.batch_size, pol.start_steps)
         _lib.check(lib.pdec_set_episode_halt(tr._h, P(logs.halt)))
         try:
             with _on_stream(s_upd):
                 pending_rt = False           # the POST_ACT push of step t - 1 rides on step t's glue launch
                 if fast is not None:         # the same launches with the same arguments, issued from precomputed addresses
-                    fast(marks)
+                    fast(sched)
                 for t in (range(T) if fast is None else ()):
                     pol.update_step += 1
                     a_t = logs.action[t + 1]
@@ -408,11 +451,12 @@ def _run_device_episodes(agent, env, stop_condition, hook, s_env, s_upd):
                         ev_env.record(s_env)
                         ev_env.wait(s_upd)
                     pending_rt = True
-                    marks.append((pol._noise_off, pol._sample_off))
                 if fast is not None:
                     ev_env.record(s_env)
                     ev_env.wait(s_upd)
                 tr.push_rt_flags(logs.reward[T - 1].view(-1), logs.done[T - 1:T], A, True)      # the last step's: a time-out
+                if (pol.update_step, tr.n_sa, tr.n_rt, pol._noise_off, pol._sample_off) != tuple(sched.after[-1].tolist()):
+                    raise RuntimeError("run(device_episodes): the agent's counters left the episode's schedule")
                 join()
                 # the per-step episode reward of PDEhook (src/PDEhook.jl:51-63): mean over the actuators, summed over the steps
                 means = logs.reward.reshape(T, -1).mean(dim=1)
@@ -428,12 +472,9 @@ def _run_device_episodes(agent, env, stop_condition, hook, s_env, s_upd):
             if nto.value != timeouts0[0]:
                 timeouts0[0] = nto.value
                 raise RuntimeError("run(device_episodes): a device-side hand-over between the glue launch and the env step timed out")
-        bad = np.flatnonzero(flags)
-        n = int(bad[0]) + 1 if bad.size and bad[0] < T - 1 else T
+        n = _executed_steps(flags, T)
         # ---- settle the host state at n executed steps
-        pol.update_step = start[0] + n
-        tr.n_sa, tr.n_rt = start[1] + n * cols, start[2] + n * cols
-        pol._noise_off, pol._sample_off = marks[n - 1]
+        pol.update_step, tr.n_sa, tr.n_rt, pol._noise_off, pol._sample_off = sched.after[n - 1].tolist()
         env.y, env.state, env.prev_state = logs.y[n], logs.state[n], logs.state[n - 1]
         env.action, env._action_prev = logs.action[n], logs.action[n - 1]
         env._adopted.update((env.action.data_ptr(), env._action_prev.data_ptr()))          # views of the log: never written by the env
@@ -469,63 +510,17 @@ def _run_device_episodes(agent, env, stop_condition, hook, s_env, s_upd):
 
 def _run_two_streams_serial(agent, env, stop_condition, hook, s_env, s_upd):
     """the plain stage order for an environment and an agent that live on two streams: every stage sees all the other stream did"""
-    def join():
-        s_upd.wait_stream(s_env)
-        s_env.wait_stream(s_upd)
-
     def staged(f, *a):
-        join()
+        _join(s_upd, s_env)
         out = f(*a)
-        join()
+        _join(s_upd, s_env)
         return out
 
-    staged(hook, PRE_EXPERIMENT_STAGE, agent, env)
-    staged(agent, PRE_EXPERIMENT_STAGE, env)
-    is_stop = False
-    while not is_stop:
-        staged(env.reset)
-        staged(agent, PRE_EPISODE_STAGE, env)
-        staged(hook, PRE_EPISODE_STAGE, agent, env)
-        while not env.is_terminated():
-            action = staged(agent, env)
-            staged(agent, PRE_ACT_STAGE, env, action)
-            staged(hook, PRE_ACT_STAGE, agent, env)
-            staged(env, action)
-            staged(agent, POST_ACT_STAGE, env)
-            staged(hook, POST_ACT_STAGE, agent, env)
-            if stop_condition(agent, env):
-                is_stop = True
-                break
-        if env.is_terminated():
-            staged(agent, POST_EPISODE_STAGE, env)
-            staged(hook, POST_EPISODE_STAGE, agent, env)
-    staged(hook, POST_EXPERIMENT_STAGE, agent, env)
-    return hook
+    return _stage_loop(agent, env, stop_condition, hook, staged=staged)
 
 
 def _run_plain(agent, env, stop_condition, hook):
-    hook(PRE_EXPERIMENT_STAGE, agent, env)
-    agent(PRE_EXPERIMENT_STAGE, env)
-    is_stop = False
-    while not is_stop:
-        env.reset()
-        agent(PRE_EPISODE_STAGE, env)
-        hook(PRE_EPISODE_STAGE, agent, env)
-        while not env.is_terminated():
-            action = agent(env)
-            agent(PRE_ACT_STAGE, env, action)
-            hook(PRE_ACT_STAGE, agent, env)
-            env(action)
-            agent(POST_ACT_STAGE, env)
-            hook(POST_ACT_STAGE, agent, env)
-            if stop_condition(agent, env):
-                is_stop = True
-                break
-        if env.is_terminated():
-            agent(POST_EPISODE_STAGE, env)
-            hook(POST_EPISODE_STAGE, agent, env)
-    hook(POST_EXPERIMENT_STAGE, agent, env)
-    return hook
+    return _stage_loop(agent, env, stop_condition, hook)
 
 
 def testrun(agent, env, steps=None, use_best=None, noise=False, log=True, seed=0):

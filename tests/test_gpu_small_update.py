@@ -276,9 +276,11 @@ def test_in_kernel_sampling_equals_host_slots(rig, pkg):
 def _kernel_names_of_the_dispatch():
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                             "distributedconvrl-pde-control_amd", "csrc", "mlp_small.hip")).read()
-    table = re.search(r"small_kernel_names\[\] = \{(.*?)\};", src, re.S).group(1)
-    names = re.findall(r'"([^"]+)"', table)
-    assert names[0] == "ddpg_small_kernel"
+    table = re.search(r"small_kernel_names\[\] = \{(.*?)\};", src, re.S).group(1)      # the generic kernel + the list's names
+    assert "SMALL2_KERNELS(X)" in table
+    kernels = re.search(r"#define SMALL2_KERNELS\(X\)((?:.*\\\n)*.*)", src).group(1)     # X(id, "name", kernel) ...
+    names = re.findall(r'"([^"]+)"', table) + re.findall(r'"([^"]+)"', kernels)
+    assert names[0] == "ddpg_small_kernel" and len(names) == 1 + kernels.count("X(")
     return {n for n in names[1:]} | {GEN0, GEN1}
 
 
