@@ -16,4 +16,4 @@ from .hook import PDEhook  # noqa: F401
 from .run import run, testrun, StopAfterEpisode, StopAfterEpisodeWithMinSteps  # noqa: F401
 from . import julia_compat, distributed, checkpoint  # noqa: F401
 from .pipeline import TrainPipeline  # noqa: F401
-from .population import Population, evaluate_actors  # noqa: F401
+from .population import Population, evaluate_actors, plan_exploit  # noqa: F401

@@ -110,6 +110,8 @@ SIGNATURES = {
     "pdec_population_bp_sel": [Handle, _vp, _i],
     "pdec_population_set_actor_copies": [Handle, _vp, _vp],
     "pdec_population_copy_actors": [Handle, _vp],
+    "pdec_population_set_member_hyper": [Handle, _i],
+    "pdec_population_clone": [Handle, _vp, _vp, _vp],
     "pdec_ledger_create": [C.POINTER(Handle), Handle, Handle, _i], "pdec_ledger_step": [Handle, _vp, _vp],
     "pdec_ledger_snapshot": [Handle], "pdec_ledger_close": [Handle, _i64, _i64, _i], "pdec_ledger_discard": [Handle],
     "pdec_ledger_read": [Handle, _vp, _vp, _vp], "pdec_ledger_best": [Handle, _pd, C.POINTER(_i64)],

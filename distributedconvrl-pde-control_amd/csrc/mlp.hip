@@ -1685,6 +1685,99 @@ int pdec_population_copy_actors(pdec_handle pop, const int32_t* which) {
   return PDEC_OK;
 }
 
+}  // extern "C"
+
+// n floats src -> dst by the threads of grid row blockIdx.y: 16-byte accesses where source and destination are both aligned
+// (or reach alignment after the same scalar head), single floats for heads, tails and differently aligned pairs
+__device__ __forceinline__ void clone_floats(float* __restrict__ dst, const float* __restrict__ src, long long n) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x, nt = (long long)gridDim.x * 256;
+  const uintptr_t as = reinterpret_cast<uintptr_t>(src), ad = reinterpret_cast<uintptr_t>(dst);
+  if (((as ^ ad) & 15) != 0 || (as & 3) != 0) {
+    for (long long i = t; i < n; i += nt) dst[i] = src[i];
+    return;
+  }
+  long long head = (long long)(((16 - (as & 15)) & 15) >> 2);
+  if (head > n) head = n;
+  const long long nv = (n - head) >> 2, tail = head + 4 * nv;
+  for (long long i = t; i < head; i += nt) dst[i] = src[i];
+  const float4* s4 = reinterpret_cast<const float4*>(src + head);
+  float4* d4 = reinterpret_cast<float4*>(dst + head);
+  for (long long i = t; i < nv; i += nt) d4[i] = s4[i];
+  for (long long i = tail + t; i < n; i += nt) dst[i] = src[i];
+}
+
+// pdec_population_clone: destination blockIdx.y of the table takes over its source's learner -- parameters and both ADAM moments
+// of the behaviour actor and critic, the parameters of the two target networks, the source's CURRENT beta powers into the
+// destination's CURRENT slot, the loss pair and, where asked, the filled prefix of the four replay traces (rows past it are not
+// touched).  The gradient buffers are scratch of the update -- every small-update kernel writes a gradient before it reads it,
+// and the register kernels never touch the buffers at all -- so they stay.  No member is both a source and a destination
+// (the entry point refuses it), so no workgroup reads what another writes.
+__global__ __launch_bounds__(256) void pop_clone_members_kernel(const PopMember* __restrict__ pm, const PopClone* __restrict__ tab,
+                                                                int nA, int nC, int ns, int na) {
+  const PopClone c = tab[blockIdx.y];
+  const PopMember& S = pm[c.src];
+  const PopMember& D = pm[c.dst];
+  clone_floats(D.Ap, S.Ap, nA); clone_floats(D.Am, S.Am, nA); clone_floats(D.Av, S.Av, nA); clone_floats(D.Apt, S.Apt, nA);
+  clone_floats(D.Cp, S.Cp, nC); clone_floats(D.Cm, S.Cm, nC); clone_floats(D.Cv, S.Cv, nC); clone_floats(D.Cpt, S.Cpt, nC);
+  if (blockIdx.x == 0 && threadIdx.x < 4) {
+    const int k = threadIdx.x & 1;
+    if (threadIdx.x < 2) D.bpA[2 * c.bpa_dst + k] = S.bpA[2 * c.bpa_src + k];
+    else D.bpC[2 * c.bpc_dst + k] = S.bpC[2 * c.bpc_src + k];
+  }
+  clone_floats(D.losses, S.losses, 2);
+  if (c.rows_sa) {
+    clone_floats(D.ts, S.ts, c.rows_sa * ns);
+    clone_floats(D.ta, S.ta, c.rows_sa * na);
+  }
+  if (c.rows_rt) {
+    clone_floats(D.tr, S.tr, c.rows_rt);
+    clone_floats(D.tt, S.tt, c.rows_rt);
+  }
+}
+
+extern "C" {
+
+int pdec_population_clone(pdec_handle pop, const int32_t* src, const int64_t* rows_sa, const int64_t* rows_rt) {
+  GET_POP(P, pop);
+  PDEC_REQUIRE(src && rows_sa && rows_rt, "pdec_population_clone: null");
+  const int M = P->M;
+  std::vector<char> is_src(M, 0);
+  for (int d = 0; d < M; ++d) {
+    PDEC_REQUIRE(src[d] >= 0 && src[d] < M, "pdec_population_clone: member %d: source %d is not one of the %d members", d, (int)src[d], M);
+    if (src[d] != d) is_src[src[d]] = 1;
+  }
+  std::vector<PopClone> tab;
+  long long most = std::max(P->A[0]->nparams, P->C[0]->nparams);
+  const int ns = P->A[0]->dims[0], na = P->A[0]->dims[P->A[0]->L];
+  for (int d = 0; d < M; ++d) {
+    if (src[d] == d) continue;
+    PDEC_REQUIRE(!is_src[d], "pdec_population_clone: member %d is both a source and a destination (one launch copies all pairs: "
+                 "no member may be read and written)", d);
+    PDEC_REQUIRE(rows_sa[d] >= 0 && rows_sa[d] <= P->cap1 && rows_rt[d] >= 0 && rows_rt[d] <= P->cap,
+                 "pdec_population_clone: member %d: %lld / %lld replay rows exceed the traces (%lld / %lld)", d,
+                 (long long)rows_sa[d], (long long)rows_rt[d], P->cap1, P->cap);
+    const int s = src[d];
+    PDEC_REQUIRE(P->A[s]->bp_init && P->C[s]->bp_init && P->A[d]->bp_init && P->C[d]->bp_init,
+                 "pdec_population_clone: member %d or %d: beta powers not initialised", s, d);
+    tab.push_back(PopClone{s, d, P->A[s]->bp_sel, P->C[s]->bp_sel, P->A[d]->bp_sel, P->C[d]->bp_sel, rows_sa[d], rows_rt[d]});
+    most = std::max(most, std::max((long long)rows_sa[d] * std::max(ns, na), (long long)rows_rt[d]));
+  }
+  if (tab.empty()) return PDEC_OK;
+  if (!P->clones.p) PDEC_HIP(P->clones.alloc(sizeof(PopClone) * M));
+  PDEC_HIP(hipStreamSynchronize(P->stream));       // (an earlier clone launch may still read the table)
+  PDEC_HIP(hipMemcpy(P->clones.p, tab.data(), sizeof(PopClone) * tab.size(), hipMemcpyHostToDevice));
+  // one 16-byte access per thread and trip over the longest array, at most ~2048 workgroups in all
+  const long long want = cdiv(cdiv(most, 4), 256), cap = std::max<long long>(1, 2048 / (long long)tab.size());
+  const dim3 grid((unsigned)std::max<long long>(1, std::min(want, cap)), (unsigned)tab.size());
+  ProfScope ps(P, "population_clone");
+  hipLaunchKernelGGL(pop_clone_members_kernel, grid, dim3(256), 0, P->stream, P->tab.as<PopMember>(), P->clones.as<PopClone>(),
+                     P->A[0]->nparams, P->C[0]->nparams, ns, na);
+  PDEC_HIP(hipGetLastError());
+  for (const PopClone& c : tab)
+    P->A[c.dst]->fw_dirty = P->C[c.dst]->fw_dirty = P->At[c.dst]->fw_dirty = P->Ct[c.dst]->fw_dirty = true;
+  return PDEC_OK;
+}
+
 static int ensure_noise_ctr(Mlp* M) {
   if (!M->noise_ctr.p) {
     PDEC_HIP(M->noise_ctr.alloc(2 * sizeof(uint64_t)));

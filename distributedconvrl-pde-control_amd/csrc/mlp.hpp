@@ -75,6 +75,15 @@ enum PopSlot {
   POP_NOISE_AMP,    // act_noise, act_limit (bit patterns of doubles)
   POP_LIMIT,
 };
+// a member's own hyper-parameters (bit patterns of doubles), read by the small update's prologue (sm_member_begin) when
+// pdec_population_set_member_hyper is on; with it off the launch-wide values of pdec_population_create hold and the slots are
+// not read.  Slot 15 stays free.
+enum PopHyperSlot {
+  POP_GAMMA = 11,   // policy.y
+  POP_RHO,          // policy.rho_effective
+  POP_ETA_A,        // behaviour actor's / critic's ADAM step size
+  POP_ETA_C,
+};
 struct PopMember {
   const void* actor_p;                          // behaviour actor parameters (acting)
   float *ts, *ta, *tr, *tt;                     // replay traces: state, action, reward, terminal
@@ -82,6 +91,12 @@ struct PopMember {
   float *Ap, *Ag, *Am, *Av, *Apt, *Cp, *Cg, *Cm, *Cv, *Cpt;   // the small update's learner state
   double *bpA, *bpC;                            // [2][2] beta powers
   float* losses;                                // [2]
+};
+// one destination of pdec_population_clone: member `dst` takes over member `src`'s learner; bp*: the CURRENT beta-power slots
+// (Mlp::bp_sel) of the two members' actors / critics, rows_*: the replay rows that go along (0: the destination keeps its replay)
+struct PopClone {
+  int src, dst, bpa_src, bpc_src, bpa_dst, bpc_dst;
+  long long rows_sa, rows_rt;
 };
 
 // Philox4x32-10 counter-based generator (the exploration noise that replaces randn(rng), src/PDEagent.jl:201)
@@ -177,12 +192,14 @@ struct Population : Object {
   int M = 0, cols = 0, dtype = PDEC_F64;
   std::vector<Mlp*> A, C, At, Ct;
   DevBuf tab;                        // PopMember [M]
+  DevBuf clones;                     // PopClone [M] (pdec_population_clone)
   DevBuf snap;                       // float* [M][2]: the hooks' best / current actor parameters (pdec_population_set_actor_copies)
   std::vector<Mlp*> snap_nets;       // (their objects: a copy makes their derived images stale)
   long long* rows = nullptr;         // [M][POP_ROW] (the caller's device buffer)
   long long cap = 0, cap1 = 0, after = 0, freq = 1, start_steps = 0;
   int stride = 0, loops = 1, Bu = 1, quirk = 0;
-  double gamma = 0.99, rho = 1.0, eta_a = 0, eta_c = 0;
+  double gamma = 0.99, rho = 1.0, eta_a = 0, eta_c = 0;   // member 0's at creation: they select the kernel, and hold for
+  int member_hyper = 0;                                    // every member unless member_hyper (pdec_population_set_member_hyper)
   Population() : Object(Kind::Population) {}
 };
 

@@ -49,11 +49,28 @@ struct SmallArgs {
   const PopMember* pm;
   long long* rows;
   long long m_after, m_freq, m_dsample;
+  int m_hyper;              // != 0: gamma, rho and the two ADAM step sizes are the member's own (row slots enum PopHyperSlot)
 };
+
+// a row slot that holds the bit pattern of a double, as a wave-uniform value (every lane loads the same word; the halves go
+// through the scalar registers the launch argument it replaces would sit in)
+__device__ __forceinline__ double sm_row_double(const long long* row, int slot) {
+  const long long b = row[slot];
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
 
 // population member blockIdx.x: Agent._maybe_update's trigger (agent.py) from the member's counters -- false: the member does not
 // update at this step and the whole workgroup returns --, else its pointers, sampling bounds and beta-power slots into g as
-// ddpg_update_small_impl sets them for its solo call; the row moves on as the host's counters do behind that call
+// ddpg_update_small_impl sets them for its solo call; the row moves on as the host's counters do behind that call.  With
+// m_hyper the member's own gamma, rho and step sizes replace the launch's: the doubles its solo call would pass, through the
+// conversions small_args applies to them -- every kernel below reads them from its copy of g behind this prologue (omr, frz and
+// the frozen kernel's up-front TD targets included), so the arithmetic is the solo call's.
+// HYPER = false compiles that out: the launch's values are kernel arguments the compiler re-reads where it needs them, a
+// member's own stay in registers for the whole launch, and the bounded register kernels (ddpg_small2_kernel, EXACT = false)
+// have none left -- they would spill to scratch.  small_serves_member_hyper() tells the host which kernels serve it.
+template <bool HYPER = true>
 __device__ __forceinline__ bool sm_member_begin(SmallArgs& g) {
   const int mb = blockIdx.x;
   long long* row = g.rows + (size_t)mb * POP_ROW;
@@ -72,6 +89,10 @@ __device__ __forceinline__ bool sm_member_begin(SmallArgs& g) {
   g.smp_seed = pm.sample_seed; g.smp_offset = (uint64_t)soff;
   g.smp_hi = (uint32_t)(nv - g.smp_stride);
   g.smp_base = n_rt > (long long)g.smp_cap ? n_rt - g.smp_cap : 0;
+  if (HYPER && g.m_hyper) {
+    g.gamma = (float)sm_row_double(row, POP_GAMMA); g.rho = (float)sm_row_double(row, POP_RHO);
+    g.eta_a = sm_row_double(row, POP_ETA_A); g.eta_c = sm_row_double(row, POP_ETA_C);
+  }
   __syncthreads();                    // every thread has read the row
   if (threadIdx.x == 0) {
     row[POP_SAMPLE] = soff + g.m_dsample;
@@ -449,7 +470,7 @@ __device__ __forceinline__ void s2_adam(float& p, float& m, float& v, float& pt,
 template <int KC, int KA, int BUT, bool EXACT, int OS = 0>
 __global__ __launch_bounds__(512) void ddpg_small2_kernel(Small2Args a_m) {
   Small2Args a_in = a_m;
-  if (a_in.g.pm && !sm_member_begin(a_in.g)) return;
+  if (a_in.g.pm && !sm_member_begin<EXACT>(a_in.g)) return;
   const SmallArgs& g = a_in.g;
   extern __shared__ __align__(16) float sm[];
   const int tid = threadIdx.x, nt = blockDim.x, nw = nt >> 6;
@@ -1326,6 +1347,12 @@ static int small_plan(const Mlp* A, const Mlp* C, int loops, int Bu, float rho, 
   return PDEC_OK;
 }
 
+// do the kernels of this plan read a member's own gamma, rho and step sizes (sm_member_begin<HYPER>)?  All but the bounded
+// instantiations of ddpg_small2_kernel
+static bool small_serves_member_hyper(const SmallPlan& pl) {
+  return !(pl.id == SK_S2_4_3_4 || pl.id == SK_S2_10_9_4 || pl.id == SK_S2_13_12_4 || pl.id == SK_S2_16_15_4);
+}
+
 // the shape checks of a small update on the four networks
 static int small_nets(pdec_handle hA, pdec_handle hC, pdec_handle hAt, pdec_handle hCt, Mlp** pA, Mlp** pC, Mlp** pAt, Mlp** pCt) {
   Mlp* A = lookup_as<Mlp>(hA, Kind::Mlp);
@@ -1440,8 +1467,27 @@ extern "C" int pdec_population_update(pdec_handle pop) {
   g.smp_cap = (int)P->cap; g.smp_cap1 = (int)P->cap1; g.smp_stride = P->stride;
   g.pm = P->tab.as<PopMember>(); g.rows = P->rows;
   g.m_after = P->after; g.m_freq = P->freq; g.m_dsample = ((long long)P->loops * P->Bu + 3) / 4;
+  PDEC_REQUIRE(!P->member_hyper || small_serves_member_hyper(pl),
+               "pdec_population_update: %s does not serve per-member hyper-parameters (pdec_population_set_member_hyper)",
+               small_kernel_names[pl.id]);
+  g.m_hyper = P->member_hyper;
   ProfScope ps(P, "population_update");
   return small_launch(pl, dim3(P->M), P->stream, g, A->dims[1], C->dims[1]);
+}
+
+extern "C" int pdec_population_set_member_hyper(pdec_handle pop, int on) {
+  GET_POP(P, pop);
+  if (on) {
+    SmallPlan pl{};
+    int rc;
+    if ((rc = small_plan(P->A[0], P->C[0], P->loops, P->Bu, (float)P->rho, true, P->quirk, &pl))) return rc;
+    PDEC_REQUIRE(pl.id != SK_BATCHED && small_serves_member_hyper(pl),
+                 "pdec_population_set_member_hyper: the update kernel of these networks (%s) takes one gamma, rho and pair of step "
+                 "sizes for the whole launch: members of this shape cannot differ in them",
+                 pl.id == SK_BATCHED ? "reward groups" : small_kernel_names[pl.id]);
+  }
+  P->member_hyper = on ? 1 : 0;
+  return PDEC_OK;
 }
 
 extern "C" int pdec_debug_small_update_kernel(pdec_handle hA, pdec_handle hC, pdec_handle hAt, pdec_handle hCt, int loops, int Bu,

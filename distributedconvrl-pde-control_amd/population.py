@@ -6,7 +6,13 @@ of an episode are issued as in run._run_device_episodes, but each of the three p
 acting, PRE_ACT push), the small update, the env step -- is ONE launch of M workgroups: workgroup m reads member m's pointers
 from a device table and its counters (ring positions, Philox offsets, update_step, halt flag) from row m of a device int64
 table (include/pdeconv.h, pdec_population_create).  The host writes that table once per episode, reads it back once, and
-settles each member's host state exactly as the solo loop does at its number of executed steps."""
+settles each member's host state exactly as the solo loop does at its number of executed steps.
+
+Members may differ in their hyper-parameters (gamma, Polyak rho, the two learning rates, act_noise, act_limit): the agents' own
+attributes are read into the row table of every episode, so a sweep is M agents created with different values, and a change
+between two `run` calls takes effect as it does in a solo run.  `Population.clone` copies a member's learner into others in one
+launch, and `Population.exploit` applies it to an evaluation's ranking (population-based selection: the worst members take
+over the best members' learners and go on with perturbed hyper-parameters)."""
 import ctypes as C
 import time
 
@@ -24,6 +30,10 @@ from .run import (StopAfterEpisode, StopAfterEpisodeWithMinSteps, _EpisodeLogs, 
 # a member's row of the device counter table: POP_ROW and enum PopSlot of csrc/mlp.hpp (tests/test_host_logic.py compares them)
 ROW = 16
 USTEP, NSA, NRT, NOISE, SAMPLE, HALT, ACTIVE, BPA, BPC, NOISE_AMP, LIMIT = range(11)
+# a member's own gamma, rho and ADAM step sizes (bit patterns of doubles): enum PopHyperSlot of csrc/mlp.hpp; slot 15 is free
+GAMMA, RHO, ETA_A, ETA_C = range(11, 15)
+HYPER_KEYS = ("gamma", "rho", "actor_lr", "critic_lr", "act_noise", "act_limit")
+PERTURBED = ("actor_lr", "critic_lr", "act_noise")      # what exploit's perturbation multiplies
 
 
 class _MemberEnv:
@@ -65,6 +75,37 @@ def score_members(episode_reward, done_step):
     score = np.where(bad, np.nan, np.where(bad[:, None], 0.0, er).mean(axis=1))
     order = sorted(range(er.shape[0]), key=lambda m: (bool(np.isnan(score[m])), -score[m] if not np.isnan(score[m]) else 0.0, m))
     return score, order
+
+
+# ---- selection: who takes over whom (pure host logic)
+
+def plan_exploit(score, order, frac=0.25):
+    """[(dst, src), ...] of one exploit step on M members from an evaluation's `score` [M] (NaN: not rankable) and `order` (best
+    first, NaN last, ties by index: score_members).  n = max(1, floor(frac M)), frac <= 0.5; the sources are the best n members
+    of `order` with a finite score, the destinations the worst n of `order` followed by every NaN-scored member not among them
+    (each group in `order`'s sequence); destination k takes source k mod n_sources.  Empty when no score is finite.  No member is
+    both a source and a destination."""
+    score = np.asarray(score, dtype=np.float64)
+    order = [int(m) for m in order]
+    M = len(order)
+    if not 0.0 < frac <= 0.5:
+        raise ValueError(f"plan_exploit: frac must lie in (0, 0.5] (got {frac!r})")
+    if score.shape != (M,) or sorted(order) != list(range(M)):
+        raise ValueError("plan_exploit: score [M] and order (a permutation of the M members) are needed")
+    n = max(1, int(np.floor(frac * M)))
+    sources = [m for m in order[:n] if np.isfinite(score[m])]
+    if not sources:
+        return []
+    worst = order[M - n:]
+    dests = [m for m in worst + [m for m in order[:M - n] if not np.isfinite(score[m])] if m not in sources]
+    return [(d, sources[k % len(sources)]) for k, d in enumerate(dests)]
+
+
+def perturb_factors(rng, n, lo, hi):
+    """[n, len(PERTURBED)] factors of exploit's perturbation, each `lo` or `hi` with equal probability, from ONE draw of the
+    numpy Generator `rng` (row k: destination k of the plan; columns: PERTURBED)"""
+    pick = rng.integers(0, 2, size=(int(n), len(PERTURBED)))
+    return np.where(pick == 0, float(lo), float(hi))
 
 
 def _model(actor):
@@ -214,13 +255,11 @@ class Population:
             if not device_episodes_ok(ag, probe, StopAfterEpisode(1), hk):
                 _refuse(f"member {m}: a solo run would not take the device-episode path (run.device_episodes_ok: "
                         "start policy, sampling, small update, streams)")
-            for k in ("update_after", "update_freq", "update_loops", "batch_size", "start_steps", "y", "quirk",
-                      "quirk_frozen_targets", "act_limit", "p"):
+            # (gamma, rho, the learning rates, act_noise and act_limit are each member's own: _hyper_rows)
+            for k in ("update_after", "update_freq", "update_loops", "batch_size", "start_steps", "quirk"):
                 if getattr(pol, k) != getattr(a0.policy, k):
                     _refuse(f"member {m}: hyper-parameter {k} differs from member 0's")
             for attr in ("behavior_actor", "behavior_critic"):
-                if getattr(pol, attr).optimizer.eta != getattr(a0.policy, attr).optimizer.eta:
-                    _refuse(f"member {m}: {attr} learning rate differs from member 0's")
                 if getattr(pol, attr).model.dims != getattr(a0.policy, attr).model.dims:
                     _refuse(f"member {m}: network shapes differ from member 0's")
             if type(pol.start_policy) is not type(a0.policy.start_policy):
@@ -231,6 +270,11 @@ class Population:
             if tr.stream.cuda_stream != a0.trajectory.stream.cuda_stream:
                 _refuse(f"member {m}: update stream differs from member 0's")
         probe.close()
+        # the update kernel is chosen once for the whole launch, from member 0's rho at this point (small_plan: the frozen-target
+        # kernel at rho == 1, compared as the Float32 the kernels compute with)
+        self._launch_wide = None
+        self._frozen_launch = bool(np.float32(a0.policy.rho_effective) == np.float32(1.0))
+        self._hyper_rows()
         self.stream_env, self.stream_upd = stream_env, a0.trajectory.stream
         if self.stream_env.cuda_stream == self.stream_upd.cuda_stream:
             _refuse("the environment and the networks need two different streams")
@@ -255,6 +299,10 @@ class Population:
             tr0.stride, int(pol0.update_loops), int(pol0.batch_size), float(pol0.y), pol0.rho_effective, int(pol0.quirk),
             float(pol0.behavior_actor.optimizer.eta), float(pol0.behavior_critic.optimizer.eta), int(pol0.update_after * tr0.stride),
             int(pol0.update_freq), int(pol0.start_steps), _lib.ptr(self.rows)))
+        # (refused for network shapes whose update kernel takes one set for the whole launch: members then must not differ)
+        if lib.pdec_population_set_member_hyper(self._h, 1) != 0:
+            self._launch_wide = (lib.pdec_last_error().decode(errors="replace"), self._hyper_rows()[0, :4].copy())
+            self._hyper_rows()
         for ag in agents:
             ag.policy.set_reward_interleave(1)
         with _on_stream(self.stream_upd):
@@ -275,7 +323,116 @@ class Population:
         except Exception:
             pass
 
+    # ---- per-member hyper-parameters: the agents' own attributes are the truth, read when an episode's row table is written
+    def _hyper_rows(self):
+        """[M, 6] doubles in HYPER_KEYS' order with rho = rho_effective (what the kernels receive), after the rule for rho: the
+        update kernel is one for the whole launch, so either every member's targets are frozen (rho_effective == 1) or none's are"""
+        q0 = self.agents[0].policy.quirk_frozen_targets
+        out = np.empty((self.M, len(HYPER_KEYS)), dtype=np.float64)
+        for m, ag in enumerate(self.agents):
+            pol = ag.policy
+            if pol.quirk_frozen_targets != q0:
+                _refuse(f"member {m}: quirk_frozen_targets differs from member 0's (frozen and moving target networks take "
+                        "different update kernels, and the kernel is one for the whole launch)")
+            rho = float(pol.rho_effective)
+            if bool(np.float32(rho) == np.float32(1.0)) != self._frozen_launch:
+                _refuse(f"member {m}: rho_effective = {rho:g} beside "
+                        f"{'frozen targets (rho_effective = 1)' if self._frozen_launch else 'moving targets (rho_effective < 1)'} "
+                        "of the population: rho may differ between members only while every member's rho_effective is < 1 "
+                        "(rho == 1 selects the frozen-target kernel for the whole launch)")
+            out[m] = (float(pol.y), rho, float(pol.behavior_actor.optimizer.eta), float(pol.behavior_critic.optimizer.eta),
+                      float(pol.act_noise), float(pol.act_limit))
+            if self._launch_wide is not None and not np.array_equal(out[m, :4], self._launch_wide[1]):
+                _refuse(f"member {m}: gamma, rho or a learning rate differs from the population's at its creation, and "
+                        f"{self._launch_wide[0]}")
+        return out
+
+    def hyper(self):
+        """the members' hyper-parameters as a dict of numpy arrays [M]: gamma (policy.y), rho (policy.p), rho_effective (what
+        the update receives: 1 under quirk_frozen_targets), actor_lr, critic_lr, act_noise, act_limit"""
+        t = self._hyper_rows()
+        out = {k: t[:, i].copy() for i, k in enumerate(HYPER_KEYS)}
+        out["rho_effective"] = out["rho"]
+        out["rho"] = np.array([float(ag.policy.p) for ag in self.agents])
+        return out
+
+    def set_hyper(self, m, gamma=None, rho=None, actor_lr=None, critic_lr=None, act_noise=None, act_limit=None):
+        """write member m's agent attributes (None: keep); legal between `run` calls, in force from the next episode on"""
+        pol = self.agents[m].policy
+        if gamma is not None:
+            pol.y = gamma
+        if rho is not None:
+            pol.p = rho
+        if actor_lr is not None:
+            pol.behavior_actor.optimizer.eta = actor_lr
+        if critic_lr is not None:
+            pol.behavior_critic.optimizer.eta = critic_lr
+        if act_noise is not None:
+            pol.act_noise = act_noise
+        if act_limit is not None:
+            pol.act_limit = act_limit
+        self._hyper_rows()              # (the rule for rho)
+
     # ---- selection
+    def clone(self, pairs, replay="copy"):
+        """pairs {dst: src}: member dst takes over member src's learner -- the four networks, the ADAM moments and beta powers,
+        the loss pair and, with replay="copy", the filled prefix of src's replay traces with its counters (replay="keep": dst
+        keeps its own replay) -- in ONE launch for all pairs (pdec_population_clone).  Exactly what load_agent(dst) of
+        save_agent(src, with_trajectory=(replay == "copy")) does to the learner; dst keeps its own update_step, noise and sample
+        seeds and offsets, host rng, hook (a log: rewards history and best actor stay dst's), environment row and
+        hyper-parameters.  Legal between `run` calls.  No member may be both a source and a destination."""
+        if replay not in ("copy", "keep"):
+            _refuse(f'clone: replay must be "copy" or "keep", not {replay!r}')
+        M = self.M
+        src = np.arange(M, dtype=np.int32)
+        rows_sa, rows_rt = np.zeros(M, dtype=np.int64), np.zeros(M, dtype=np.int64)
+        for d, s in pairs.items():
+            if not 0 <= int(d) < M:
+                _refuse(f"clone: destination {d} is not one of the {M} members")
+            src[int(d)] = int(s) if -2 ** 31 <= int(s) < 2 ** 31 else -1
+        moved = [(d, int(src[d])) for d in range(M) if src[d] != d]
+        if replay == "copy":
+            for d, s in moved:
+                if 0 <= s < M:
+                    tr = self.agents[s].trajectory
+                    rows_sa[d], rows_rt[d] = min(tr.n_sa, tr.capacity + tr.stride), min(tr.n_rt, tr.capacity)
+        s_env, s_upd = self.stream_env, self.stream_upd
+        _join(s_upd, s_env)
+        try:
+            _lib.check(self.lib.pdec_population_clone(self._h, src.ctypes.data_as(C.c_void_p), rows_sa.ctypes.data_as(C.c_void_p),
+                                                      rows_rt.ctypes.data_as(C.c_void_p)))
+        finally:
+            _join(s_upd, s_env)
+        if replay == "copy":
+            for d, s in moved:
+                td, ts = self.agents[d].trajectory, self.agents[s].trajectory
+                td.n_sa, td.n_rt = ts.n_sa, ts.n_rt
+        return moved
+
+    def exploit(self, result=None, frac=0.25, perturb=None, rng=None, replay="copy"):
+        """One step of population-based selection: plan_exploit on `result` (an evaluation's dict with score and order; None:
+        self.evaluate()), `clone` of the plan, then every destination inherits its source's gamma, rho, learning rates,
+        act_noise and act_limit -- with perturb=(lo, hi) its actor_lr, critic_lr and act_noise each times lo or hi, drawn from the
+        numpy Generator `rng` (perturb_factors).  Returns [{dst, src, hyper}, ...] in the plan's order."""
+        if perturb is not None and rng is None:
+            _refuse("exploit: perturb=(lo, hi) needs rng (a numpy.random.Generator)")
+        if result is None:
+            result = self.evaluate()
+        plan = plan_exploit(result["score"], result["order"], frac)
+        if not plan:
+            return []
+        self.clone(dict(plan), replay=replay)
+        fac = perturb_factors(rng, len(plan), *perturb) if perturb is not None else np.ones((len(plan), len(PERTURBED)))
+        table = self.hyper()
+        applied = []
+        for k, (d, s) in enumerate(plan):
+            h = {key: float(table[key][s]) for key in HYPER_KEYS}
+            for j, key in enumerate(PERTURBED):
+                h[key] = h[key] * float(fac[k, j])
+            self.set_hyper(d, **h)
+            applied.append(dict(dst=d, src=s, hyper=h))
+        return applied
+
     def evaluate(self, which="current", **kw):
         """evaluate_actors on the members' behaviour actors ("current") or on their hooks' best actors ("best"): every member
         scored on the same held-out initial fields.  The evaluation has its own environment; the population's environment,
@@ -368,6 +525,7 @@ class Population:
         flags = self._flags
         # ---- the counter table of this episode (one upload)
         rows = np.zeros((M, ROW), dtype=np.int64)
+        rows[:, GAMMA:ETA_C + 1] = self._hyper_rows()[:, :4].copy().view(np.int64)
         for m, ag in enumerate(self.agents):
             pol, tr = ag.policy, ag.trajectory
             rows[m, [USTEP, NSA, NRT, NOISE, SAMPLE]] = (pol.update_step, tr.n_sa, tr.n_rt, pol._noise_off, pol._sample_off)

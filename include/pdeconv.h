@@ -534,6 +534,22 @@ int pdec_population_bp_sel(pdec_handle pop, int64_t* rows_host, int set);
  * is set and into current[m] where bit 1 is (which: DEVICE int32 [M]), for all members in one launch */
 int pdec_population_set_actor_copies(pdec_handle pop, const pdec_handle* best, const pdec_handle* current);
 int pdec_population_copy_actors(pdec_handle pop, const int32_t* which);
+/* Per-member hyper-parameters.  on = 1: the update launch takes member m's gamma, Polyak rho and actor / critic ADAM step
+ * sizes from rows[m][11], [12], [13], [14] (bit patterns of doubles: the values a solo pdec_ddpg_update_small_rng call of that
+ * member would be given, converted as that call converts them) instead of pdec_population_create's; the caller writes them
+ * with the rest of the row.  Off (the default) the slots are not read and the launch-wide values hold.  The kernel is
+ * selected from pdec_population_create's rho for the whole launch: either every member's rho is 1 (frozen targets) or none's
+ * is.  act_noise and act_limit (slots 9, 10) are per member either way.  Slot 15 is free.  Refused (on = 1) for networks
+ * whose update takes a bounded instantiation of the register kernel (pdec_debug_small_update_kernel reports a name that ends
+ * in ",0>"): those have no register left for a member's own values. */
+int pdec_population_set_member_hyper(pdec_handle pop, int on);
+/* Member d takes over the learner of member src[d] (src: HOST int32 [M]; src[d] == d: d stays as it is), all pairs in ONE
+ * launch on the population's stream: parameters and ADAM moments of the behaviour actor and critic, the parameters of the two
+ * target networks, the source's current beta powers (into the destination's current slot), the loss pair and the first
+ * rows_sa[d] rows of the state / action traces and rows_rt[d] rows of the reward / terminal traces (HOST int64 [M]; 0: the
+ * destination keeps its replay; rows past the prefix are not touched).  Counters, seeds and offsets are the caller's.  Refuses
+ * a source out of range and a member that is both a source and a destination. */
+int pdec_population_clone(pdec_handle pop, const int32_t* src, const int64_t* rows_sa, const int64_t* rows_rt);
 
 /* ---------------------------------------------------------------- episode ledger (PDEhook's bookkeeping, src/PDEhook.jl:51-97) */
 /* The episode returns, blow-up bits and best actor of a batched training run, kept on the device: no launch argument depends

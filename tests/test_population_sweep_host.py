@@ -1,0 +1,129 @@
+"""Host rules of population sweeps (population.py): the hyper-parameter slots of the row table against csrc/mlp.hpp, the exploit
+plan and its perturbation.  No GPU."""
+import importlib
+import os
+import re
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def pop(pkg):
+    return importlib.import_module(pkg.__name__ + ".population")
+
+
+def _enum(hpp, name):
+    body = re.sub(r"//.*", "", re.search(r"enum %s \{(.*?)\};" % name, hpp, re.S).group(1))
+    out, nxt = {}, 0
+    for item in (x.strip() for x in body.split(",")):
+        if not item:
+            continue
+        if "=" in item:
+            item, v = (x.strip() for x in item.split("="))
+            nxt = int(v)
+        out[item] = nxt
+        nxt += 1
+    return out
+
+
+def test_hyper_slots_equal_the_device_enum(pop):
+    hpp = open(os.path.join(ROOT, "distributedconvrl-pde-control_amd", "csrc", "mlp.hpp")).read()
+    slots, hyper = _enum(hpp, "PopSlot"), _enum(hpp, "PopHyperSlot")
+    assert hyper == dict(POP_GAMMA=11, POP_RHO=12, POP_ETA_A=13, POP_ETA_C=14)
+    assert [pop.GAMMA, pop.RHO, pop.ETA_A, pop.ETA_C] == [hyper[k] for k in ("POP_GAMMA", "POP_RHO", "POP_ETA_A", "POP_ETA_C")]
+    assert len(slots) == 11 and sorted(slots.values()) == list(range(11))
+    assert not set(slots.values()) & set(hyper.values())
+    assert pop.ROW == 16 == int(re.search(r"#define POP_ROW (\d+)", hpp).group(1))
+    assert max(hyper.values()) < pop.ROW - 1          # slot 15 stays free
+    # the kernels' prologue reads exactly these names
+    small = open(os.path.join(ROOT, "distributedconvrl-pde-control_amd", "csrc", "mlp_small.hip")).read()
+    for k in hyper:
+        assert re.search(r"\b%s\b" % k, small), k
+
+
+def _check_plan(plan, score, order, n):
+    srcs, dsts = {s for _, s in plan}, [d for d, _ in plan]
+    assert not srcs & set(dsts)                                   # no member is both
+    assert len(set(dsts)) == len(dsts)
+    assert all(np.isfinite(score[s]) for s in srcs)
+    assert srcs <= set(order[:n])
+    nan = {m for m in range(len(order)) if not np.isfinite(score[m])}
+    assert set(dsts) == (set(order[len(order) - n:]) | nan) - srcs
+
+
+def test_plan_m8_quarter(pop):
+    score = np.array([-5.0, -1.0, -7.0, -2.0, -3.0, -9.0, -4.0, -6.0])
+    _, order = pop.score_members(score[:, None], np.full((8, 1), -1))
+    assert order == [1, 3, 4, 6, 0, 7, 2, 5]
+    plan = pop.plan_exploit(score, order, 0.25)
+    assert plan == [(2, 1), (5, 3)]
+    _check_plan(plan, score, order, 2)
+    assert pop.plan_exploit(score, order) == plan                 # frac defaults to 0.25
+
+
+def test_plan_small_frac_gives_one_pair(pop):
+    score = np.array([3.0, 1.0, 2.0, 0.5, 4.0])
+    order = [4, 0, 2, 1, 3]
+    assert pop.plan_exploit(score, order, 0.01) == [(3, 4)]
+    assert pop.plan_exploit(score, order, 0.39) == [(3, 4)]       # floor(1.95) = 1
+    assert pop.plan_exploit(score, order, 0.4) == [(1, 4), (3, 0)]
+    with pytest.raises(ValueError):
+        pop.plan_exploit(score, order, 0.6)
+
+
+def test_plan_nan_members_all_become_destinations(pop):
+    score = np.array([np.nan, -1.0, np.nan, -2.0, -3.0, np.nan, -4.0, -0.5])
+    _, order = pop.score_members(np.where(np.isnan(score), 0.0, score)[:, None], np.where(np.isnan(score), 3, -1)[:, None])
+    assert order == [7, 1, 3, 4, 6, 0, 2, 5]
+    plan = pop.plan_exploit(score, order, 0.25)
+    # the worst two of the order (2, 5), then the NaN member not among them (0); destination k takes source k mod 2
+    assert plan == [(2, 7), (5, 1), (0, 7)]
+    _check_plan(plan, score, order, 2)
+    # a NaN among the best n is no source
+    score2 = np.array([np.nan, np.nan, np.nan, 1.0])
+    plan2 = pop.plan_exploit(score2, [3, 0, 1, 2], 0.5)
+    assert plan2 == [(1, 3), (2, 3), (0, 3)]
+    _check_plan(plan2, score2, [3, 0, 1, 2], 2)
+
+
+def test_plan_all_nan_is_empty(pop):
+    assert pop.plan_exploit(np.full(6, np.nan), list(range(6)), 0.25) == []
+    assert pop.plan_exploit(np.array([1.0]), [0], 0.5) == []      # a lone member has nobody to take over
+
+
+def test_plan_ties_are_broken_by_index(pop):
+    er = np.zeros((6, 2))
+    score, order = pop.score_members(er, np.full((6, 2), -1))
+    assert order == [0, 1, 2, 3, 4, 5]
+    plan = pop.plan_exploit(score, order, 0.34)
+    assert plan == [(4, 0), (5, 1)]
+    assert pop.plan_exploit(score, order, 0.34) == plan           # deterministic
+    _check_plan(plan, score, order, 2)
+
+
+@pytest.mark.parametrize("M", [2, 3, 4, 7, 16, 33])
+@pytest.mark.parametrize("frac", [0.05, 0.25, 0.5])
+def test_plan_never_reads_and_writes_a_member(pop, M, frac):
+    rng = np.random.default_rng(M)
+    score = rng.normal(size=M)
+    score[rng.random(M) < 0.3] = np.nan
+    order = sorted(range(M), key=lambda m: (bool(np.isnan(score[m])), -score[m] if not np.isnan(score[m]) else 0.0, m))
+    plan = pop.plan_exploit(score, order, frac)
+    n = max(1, int(np.floor(frac * M)))
+    if not np.isfinite(score[order[:n]]).any():
+        assert plan == []
+    else:
+        _check_plan(plan, score, order, n)
+
+
+def test_perturbation_is_reproducible_and_two_valued(pop):
+    lo, hi = 0.8, 1.25
+    a = pop.perturb_factors(np.random.default_rng(0), 64, lo, hi)
+    b = pop.perturb_factors(np.random.default_rng(0), 64, lo, hi)
+    c = pop.perturb_factors(np.random.default_rng(1), 64, lo, hi)
+    assert a.shape == (64, len(pop.PERTURBED)) and pop.PERTURBED == ("actor_lr", "critic_lr", "act_noise")
+    assert np.array_equal(a, b) and not np.array_equal(a, c)
+    assert set(np.unique(a).tolist()) == {lo, hi}
