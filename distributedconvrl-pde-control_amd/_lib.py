@@ -112,6 +112,8 @@ SIGNATURES = {
     "pdec_population_copy_actors": [Handle, _vp],
     "pdec_population_set_member_hyper": [Handle, _i],
     "pdec_population_clone": [Handle, _vp, _vp, _vp],
+    "pdec_population_episode_close": [Handle, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i, _i],
+    "pdec_population_copy_best_rows": [Handle, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64],
     "pdec_ledger_create": [C.POINTER(Handle), Handle, Handle, _i], "pdec_ledger_step": [Handle, _vp, _vp],
     "pdec_ledger_snapshot": [Handle], "pdec_ledger_close": [Handle, _i64, _i64, _i], "pdec_ledger_discard": [Handle],
     "pdec_ledger_read": [Handle, _vp, _vp, _vp], "pdec_ledger_best": [Handle, _pd, C.POINTER(_i64)],

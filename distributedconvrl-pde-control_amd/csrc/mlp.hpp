@@ -84,8 +84,38 @@ enum PopHyperSlot {
   POP_ETA_A,        // behaviour actor's / critic's ADAM step size
   POP_ETA_C,
 };
+// ---- a member's book (pdec_population_episode_close, csrc/pop_book.hip): what its PDEhook and its stop condition hold between
+// two episodes, so that the episode boundary needs no host.  A caller-owned device table int64 [M][POP_BOOK] beside the rows,
+// doubles as bit patterns; population.py mirrors the names (tests/test_population_blocks_host.py compares them).
+#define POP_BOOK 16
+enum PopBookSlot {
+  PBK_EP = 0,        // hook.ep: index of the episode that is running (the close increments it)
+  PBK_MIN_BEST,      // hook.min_best_episode
+  PBK_COLLECT_NNA,   // hook.collect_NNA (0 / 1)
+  PBK_CMP_HAS,       // 1: rewards_compare is not empty
+  PBK_CMP,           // Python's max(rewards_compare) (double): the first element unless a later one compared greater
+  PBK_BESTREWARD,    // hook.bestreward (double)
+  PBK_BESTEPISODE,   // hook.bestepisode
+  PBK_STOP_KIND,     // 0: StopAfterEpisode, 1: StopAfterEpisodeWithMinSteps
+  PBK_STOP_CUR,      // the stop object's cur
+  PBK_STOP_LIMIT,    // its episode / step
+  PBK_RANDOM_INIT,   // hook.use_random_init (0 / 1)
+  PBK_INIT_SEED,     // hook.init_seed
+  PBK_INIT_OFF,      // hook._init_off: Philox offset of the member's NEXT initial field
+  PBK_INIT_INC,      // ceil(coefficients / 4): what one drawn field consumes
+  PBK_FIRED,         // phase 0 -> phase 1 of one close: the stop condition fired in this episode
+  PBK_SPARE,
+};
+// the episode log of a block, int64 [E][M][POP_ELOG]: one entry per member and episode
+#define POP_ELOG 4
+enum PopElogSlot {
+  PEL_REWARD = 0,    // the episode reward (double)
+  PEL_STEPS,         // executed control steps n (0: the member was idle)
+  PEL_NEW_BEST,      // 1: the episode is the member's new best
+  PEL_RAN,           // 1: the member ran this episode
+};
 struct PopMember {
-  const void* actor_p;                          // behaviour actor parameters (acting)
+  const void* actor_p;                         // behaviour actor parameters (acting)
   float *ts, *ta, *tr, *tt;                     // replay traces: state, action, reward, terminal
   uint64_t noise_seed, sample_seed;
   float *Ap, *Ag, *Am, *Av, *Apt, *Cp, *Cg, *Cm, *Cv, *Cpt;   // the small update's learner state

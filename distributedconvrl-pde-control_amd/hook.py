@@ -25,6 +25,7 @@ class PDEhook:
         self.bestreward, self.bestepisode = -1000000.0, 0
         self.history, self.errored_episodes = [], []
         self.error_detection = error_detection or (lambda y: False)
+        self.error_detection_given = error_detection is not None     # (a Population refuses it with episodes_per_sync > 1)
         self.init_rng = init_rng or np.random.default_rng(0)
         self.log_trajectory = log_trajectory
         self.init_seed, self._init_off = int(init_seed), 0      # Philox stream of the device-side initialisers

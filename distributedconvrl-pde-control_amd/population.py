@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .agent import Agent, PRE_EXPERIMENT_STAGE, PRE_EPISODE_STAGE, POST_EXPERIMENT_STAGE
+from .agent import Agent, PRE_EXPERIMENT_STAGE, PRE_EPISODE_STAGE, POST_EPISODE_STAGE, POST_EXPERIMENT_STAGE
 from .env import PDEenv, _on_stream
 from .hook import PDEhook
 from .pipeline import _Event
@@ -32,6 +32,13 @@ ROW = 16
 USTEP, NSA, NRT, NOISE, SAMPLE, HALT, ACTIVE, BPA, BPC, NOISE_AMP, LIMIT = range(11)
 # a member's own gamma, rho and ADAM step sizes (bit patterns of doubles): enum PopHyperSlot of csrc/mlp.hpp; slot 15 is free
 GAMMA, RHO, ETA_A, ETA_C = range(11, 15)
+# a member's book -- what its hook and its stop condition hold between two episodes -- and the episode log of a block:
+# POP_BOOK / enum PopBookSlot and POP_ELOG / enum PopElogSlot of csrc/mlp.hpp (tests/test_population_blocks_host.py compares them)
+BOOK = 16
+(BK_EP, BK_MIN_BEST, BK_COLLECT_NNA, BK_CMP_HAS, BK_CMP, BK_BESTREWARD, BK_BESTEPISODE, BK_STOP_KIND, BK_STOP_CUR, BK_STOP_LIMIT,
+ BK_RANDOM_INIT, BK_INIT_SEED, BK_INIT_OFF, BK_INIT_INC, BK_FIRED, BK_SPARE) = range(BOOK)
+ELOG = 4
+EL_REWARD, EL_STEPS, EL_NEW_BEST, EL_RAN = range(ELOG)
 HYPER_KEYS = ("gamma", "rho", "actor_lr", "critic_lr", "act_noise", "act_limit")
 PERTURBED = ("actor_lr", "critic_lr", "act_noise")      # what exploit's perturbation multiplies
 
@@ -48,6 +55,37 @@ class _MemberEnv:
 
 def _refuse(msg):
     raise _lib.PdecError("Population: " + msg)
+
+
+# ---- blocks of episodes: how many a member can still need, and Python's max() as a carried state (pure host logic)
+
+def episodes_still_needed(stop, T):
+    """the least number of episodes of at most T control steps after which `stop` (a StopAfterEpisode or
+    StopAfterEpisodeWithMinSteps as run.py writes them, in its current state) can have fired; at least 1"""
+    if type(stop) is StopAfterEpisode:          # cur += 1 per episode end, fires at cur >= episode
+        return max(1, int(stop.episode) - int(stop.cur))
+    if type(stop) is StopAfterEpisodeWithMinSteps:      # cur += 1 per step, fires at an episode end that begins with cur >= step
+        need = int(stop.step) - int(stop.cur) + 1       # steps until the call that can fire, that call included
+        return max(1, -(-need // int(T)))
+    raise TypeError(f"episodes_still_needed: {type(stop).__name__}")
+
+
+def block_length(stops, active, T, E):
+    """episodes of the next block: min(E, max over the active members of episodes_still_needed), so that no episode of a block
+    is idle for every member"""
+    return min(int(E), max(episodes_still_needed(s, T) for s, a in zip(stops, active) if a))
+
+
+def python_max_state(values):
+    """(has, cmp) of Python's max(values) carried element by element: the first element unless a later one compares greater
+    (a NaN that comes first stays; a later NaN never replaces)"""
+    has, cmp = 0, 0.0
+    for v in values:
+        if not has:
+            has, cmp = 1, v
+        elif v > cmp:
+            cmp = v
+    return has, float(cmp)
 
 
 # ---- evaluation: every member's actor scored on the SAME held-out initial fields, in one launch where the library serves it
@@ -310,7 +348,8 @@ class Population:
         self.episode_steps = []       # per episode: the control steps each member executed (0: idle)
         # host seconds per phase, summed over episodes: issue = initialisers + every enqueue up to the read-back,
         # readback = waiting for the device, settle = the members' host bookkeeping and the boundary launches
-        self.timing = dict(episodes=0, issue_s=0.0, readback_s=0.0, settle_s=0.0)
+        # (blocks: read-backs; with episodes_per_sync = 1 every episode is one)
+        self.timing = dict(episodes=0, issue_s=0.0, readback_s=0.0, settle_s=0.0, blocks=0)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -453,9 +492,26 @@ class Population:
         return evaluate_actors(self.setup, actors, **kw)
 
     # ---- the episode loop
-    def run(self, stops):
+    def run(self, stops, episodes_per_sync=1):
+        """run every member until its stop condition fires.  episodes_per_sync = E > 1: blocks of up to E whole episodes are
+        enqueued per read-back -- the episode boundary (hook, stop condition, counters, next initial field) is decided on the
+        device (pdec_population_episode_close) and the members' host state is settled once per block; every member ends bit for
+        bit where E = 1 leaves it.  Refused with E > 1: collect_history (needs every episode's rows on the host) and a hook
+        that was given an error_detection callable."""
         if len(stops) != self.M or any(type(s) not in (StopAfterEpisode, StopAfterEpisodeWithMinSteps) for s in stops):
             _refuse("one StopAfterEpisode / StopAfterEpisodeWithMinSteps per member")
+        E = int(episodes_per_sync)
+        if E < 1 or E != episodes_per_sync:
+            _refuse(f"episodes_per_sync must be a whole number >= 1 (got {episodes_per_sync!r}) for members 0..{self.M - 1}")
+        if E > 1:
+            for m, (ag, hk) in enumerate(zip(self.agents, self.hooks)):
+                if hk.collect_history:
+                    _refuse(f"member {m}: collect_history needs every episode's rows on the host; run it with episodes_per_sync=1")
+                if hk.error_detection_given:
+                    _refuse(f"member {m}: a hook with an error_detection callable is settled on the host every episode; run it "
+                            "with episodes_per_sync=1")
+                if (ag.policy.reset_stage == POST_EPISODE_STAGE) != (self.agents[0].policy.reset_stage == POST_EPISODE_STAGE):
+                    _refuse(f"member {m}: reset_stage differs from member 0's (one boundary launch serves all members)")
         env, M = self.env, self.M
         s_env, s_upd = self.stream_env, self.stream_upd
         for ag, hk in zip(self.agents, self.hooks):
@@ -468,7 +524,11 @@ class Population:
         active = np.ones(M, dtype=bool)
         while active.any():
             _join(s_upd, s_env)
-            self._episode(active, stops)
+            if E == 1:
+                self._episode(active, stops)
+                self.timing["blocks"] = self.timing.get("blocks", 0) + 1
+            else:
+                self._block(active, stops, block_length(stops, active, _episode_steps(env), E))
         _join(s_upd, s_env)
         for ag, hk in zip(self.agents, self.hooks):
             hk(POST_EXPERIMENT_STAGE, ag, env)
@@ -610,6 +670,189 @@ class Population:
         t3 = time.perf_counter()
         tm = self.timing
         tm["episodes"] += 1
+        tm["issue_s"] += t1 - t0
+        tm["readback_s"] += t2 - t1
+        tm["settle_s"] += t3 - t2
+
+    # ---- blocks of episodes (run(stops, episodes_per_sync > 1)): the episode boundary on the device
+    def _open_episode(self, any_random):
+        """_pre_episode with the members masked by the device columns ACTIVE (rows) and use_random_init / init seed / init offset
+        (book) instead of host lists: env.reset(), the random fields of all members in one launch, idle members keep y and state"""
+        env, lib = self.env, self.lib
+        M = self.M
+        with _on_stream(self.stream_env):
+            act = self.rows[:, ACTIVE] != 0
+            keep_y, keep_s = env.y.clone(), env.state.clone()
+        env.reset()
+        with _on_stream(self.stream_env):
+            if any_random:
+                seeds, offs = self._book[:, BK_INIT_SEED].contiguous(), self._book[:, BK_INIT_OFF].contiguous()
+                drawn = torch.empty_like(env.y)
+                _lib.check(lib.pdec_env_random_init_members(env.handle, _lib.ptr(seeds), _lib.ptr(offs), _lib.ptr(drawn)))
+                mask = act & (self._book[:, BK_RANDOM_INIT] != 0)
+                y0 = torch.where(mask.view((M,) + (1,) * (env.y.dim() - 1)), drawn, env.y0)
+                env.y0 = y0
+                env.y.copy_(y0)
+                st = env.featurize(env.y, env.state if env.setup.temporal_steps > 1 else None)
+                env.state.copy_(torch.where(mask.view((M,) + (1,) * (env.state.dim() - 1)), st, env.state))
+                env._state0.copy_(env.state)
+            env.y.copy_(torch.where(act.view((M,) + (1,) * (env.y.dim() - 1)), env.y, keep_y))
+            env.state.copy_(torch.where(act.view((M,) + (1,) * (env.state.dim() - 1)), env.state, keep_s))
+
+    def _block(self, active, stops, L):
+        """L whole episodes enqueued, one read-back, every member settled for the block"""
+        env, M, lib, cols = self.env, self.M, self.lib, self.cols
+        s_env, s_upd = self.stream_env, self.stream_upd
+        P = _lib.ptr
+        t0 = time.perf_counter()
+        T = _episode_steps(env)
+        logs = getattr(self, "_logs", None)
+        if logs is None or logs.T != T:
+            with _on_stream(s_env):
+                logs = self._logs = _EpisodeLogs(env, T)
+                self._flags = torch.zeros((T, M), dtype=torch.int32, device=env.device)     # per step: the members' done flags
+        flags = self._flags
+        want_rows = any(self.hooks[m].collect_bestDF and self.hooks[m].collect_NNA for m in np.flatnonzero(active))
+        with _on_stream(s_upd):
+            if getattr(self, "_elog", None) is None or self._elog.shape[0] < L:
+                self._book = torch.zeros((M, BOOK), dtype=torch.int64, device=env.device)
+                self._elog = torch.zeros((L, M, ELOG), dtype=torch.int64, device=env.device)
+            if want_rows and (getattr(self, "_best_rows", None) is None or self._best_rows[0].shape[1] != T):
+                self._best_rows = tuple(torch.zeros((M, T) + tuple(x.shape[2:]), dtype=x.dtype, device=env.device)
+                                        for x in (logs.action, logs.p, logs.y, logs.reward))
+        # ---- the counter table and the book of this block (one upload); PRE_EPISODE of its first episode is the host's
+        for m in np.flatnonzero(active):
+            self.agents[m](PRE_EPISODE_STAGE, env)          # host counters only (pop_sa)
+        rows = np.zeros((M, ROW), dtype=np.int64)
+        book = np.zeros((M, BOOK), dtype=np.int64)
+        rows[:, GAMMA:ETA_C + 1] = self._hyper_rows()[:, :4].copy().view(np.int64)
+        nblk = (env.random_init_coefficients() + 3) // 4
+        as_bits = lambda v: int(np.array([v], dtype=np.float64).view(np.int64)[0])      # noqa: E731
+        for m, (ag, hk) in enumerate(zip(self.agents, self.hooks)):
+            pol, tr = ag.policy, ag.trajectory
+            rows[m, [USTEP, NSA, NRT, NOISE, SAMPLE]] = (pol.update_step, tr.n_sa, tr.n_rt, pol._noise_off, pol._sample_off)
+            rows[m, HALT], rows[m, ACTIVE] = (0, 1) if active[m] else (1, 0)
+            rows[m, NOISE_AMP:LIMIT + 1] = np.array([float(pol.act_noise), float(pol.act_limit)], dtype=np.float64).view(np.int64)
+            has, cmp = python_max_state(hk.rewards_compare)
+            st = stops[m]
+            kind, lim = (0, st.episode) if type(st) is StopAfterEpisode else (1, st.step)
+            book[m, :BK_FIRED] = (hk.ep, hk.min_best_episode, int(bool(hk.collect_NNA)), has, as_bits(cmp), as_bits(hk.bestreward),
+                                  hk.bestepisode, kind, st.cur, lim, int(bool(hk.use_random_init)), hk.init_seed, hk._init_off, nblk)
+        _lib.check(lib.pdec_population_bp_sel(self._h, rows.ctypes.data_as(C.c_void_p), 0))
+        start = rows.copy()
+        with _on_stream(s_upd):
+            self.rows.copy_(torch.from_numpy(rows))
+            self._book.copy_(torch.from_numpy(book))
+        any_random = bool(book[:, BK_RANDOM_INIT].any())
+        reset_post = int(self.agents[0].policy.reset_stage == POST_EPISODE_STAGE)
+        ysz, ssz = env.y[0].numel(), env.state[0].numel()
+        ev_act, ev_env = _Event(lib), _Event(lib)
+        for e in range(L):
+            _join(s_upd, s_env)
+            self._open_episode(any_random)
+            with _on_stream(s_env):
+                logs.y[0].copy_(env.y)
+                logs.state[0].copy_(env.state)
+                flags.zero_()
+            _join(s_upd, s_env)
+            # (per step: the member-indexed glue and update on the networks' stream, the member-layout env step on the env's)
+            for t in range(T):
+                _lib.check(lib.pdec_population_glue(self._h, 0, P(logs.reward[t - 1]) if t else None, P(flags[t - 1]) if t else None,
+                                                    P(logs.state[t]), P(logs.action[t + 1])))
+                ev_act.record(s_upd)
+                ev_act.wait(s_env)
+                _lib.check(lib.pdec_population_update(self._h))
+                _lib.check(lib.pdec_env_step(env.handle, P(logs.y[t]), P(logs.action[t + 1]), P(logs.action[t]), P(logs.state[t]),
+                                             P(logs.y[t + 1]), P(logs.p[t]), P(logs.state[t + 1]), P(logs.reward[t]), P(flags[t])))
+                ev_env.record(s_env)
+                ev_env.wait(s_upd)
+            _lib.check(lib.pdec_population_glue(self._h, 1, P(logs.reward[T - 1]), P(flags[T - 1]), None, None))   # the time-out push
+            # ---- the boundary, all on the networks' stream: close (hook, stop rule, final y / state), the POST_EPISODE push of
+            # the final states, the best episode's rows, the hooks' actor copies, then the counters of the next episode
+            with _on_stream(s_upd):
+                # the per-step episode reward of PDEhook (mean over the actuators), member-major rows as a B = 1 run reduces them
+                means = logs.reward.transpose(0, 1).contiguous().reshape(M * T, -1).mean(dim=1)
+            close = (P(self._elog[e]), P(flags), P(means), T, P(logs.y), P(logs.state), P(env.y), P(env.state), ysz, ssz,
+                     P(self._which), reset_post, int(e == L - 1))
+            _lib.check(lib.pdec_population_episode_close(self._h, 0, P(self._book), *close))
+            _lib.check(lib.pdec_population_glue(self._h, 2, None, None, P(env.state), None))
+            if want_rows:
+                la, lp, ly, lr = logs.action, logs.p, logs.y, logs.reward
+                _lib.check(lib.pdec_population_copy_best_rows(
+                    self._h, P(self._which), P(self._elog[e]), T, P(la), P(lp), P(ly), P(lr), *[P(b) for b in self._best_rows],
+                    la[0, 0].numel(), lp[0, 0].numel(), ly[0, 0].numel(), lr[0, 0].numel()))
+            _lib.check(lib.pdec_population_copy_actors(self._h, P(self._which)))
+            _lib.check(lib.pdec_population_episode_close(self._h, 1, P(self._book), *close))
+        with _on_stream(s_upd):
+            pack = torch.cat([self.rows.view(-1), self._book.view(-1), self._elog[:L].reshape(-1)])
+            t1 = time.perf_counter()
+            host = pack.cpu().numpy()                                          # the one read-back of the block
+        t2 = time.perf_counter()
+        s_env.wait_stream(s_upd)
+        rows_out = host[:M * ROW].reshape(M, ROW).copy()
+        book_out = host[M * ROW:M * (ROW + BOOK)].reshape(M, BOOK)
+        elog = host[M * (ROW + BOOK):].reshape(L, M, ELOG)
+        # ---- settle every member for the whole block: the schedule of each episode at its logged number of steps, with the
+        # boundary movements between them, must end at the device's counters
+        pol0, tr0 = self.agents[0].policy, self.agents[0].trajectory
+        was = np.flatnonzero(active)
+        ran = elog[:, :, EL_RAN] != 0
+        if not (ran[0] == active).all() or (ran[1:] & ~ran[:-1]).any():
+            raise RuntimeError("Population: the device's episode log disagrees with the members that were active")
+        cur = start[:, :SAMPLE + 1].copy()
+        for e in range(L):
+            n_of = elog[e, :, EL_STEPS].copy()
+            self.episode_steps.append(n_of)
+            idx = np.flatnonzero(ran[e])
+            sched = _episode_schedule(cur, T, cols, pol0.behavior_actor.model.dims[-1], tr0.capacity, tr0.stride, pol0.update_after,
+                                      pol0.update_freq, pol0.update_loops, pol0.batch_size, pol0.start_steps)
+            cur[idx] = sched.after[idx, n_of[idx] - 1]
+            cur[idx, NSA] += cols                               # POST_EPISODE: the final state with the zero action
+            if reset_post:
+                cur[idx, USTEP] = 0
+            if e + 1 < L:                                       # PRE_EPISODE pop of the members that go on
+                go = idx[ran[e + 1, idx] & (cur[idx, NSA] > cur[idx, NRT])]
+                cur[go, NSA] -= tr0.stride
+        for m in was:
+            if cur[m].tolist() != rows_out[m, :SAMPLE + 1].tolist():
+                raise RuntimeError(f"Population: member {m}'s device counters disagree with its executed steps of the block")
+        _lib.check(lib.pdec_population_bp_sel(self._h, rows_out.ctypes.data_as(C.c_void_p), 1))
+        rewards = elog[:, :, EL_REWARD].copy().view(np.float64)
+        changed = []
+        for m in was:
+            ag, hk, bk = self.agents[m], self.hooks[m], book_out[m]
+            pol, tr = ag.policy, ag.trajectory
+            pol.update_step, tr.n_sa, tr.n_rt, pol._noise_off, pol._sample_off = rows_out[m, :SAMPLE + 1].tolist()
+            for e in np.flatnonzero(ran[:, m]):
+                r = float(rewards[e, m])
+                if elog[e, m, EL_STEPS] == T and hk.ep >= hk.min_best_episode:
+                    hk.rewards_compare.append(r)
+                hk.rewards.append(r)
+                hk.ep += 1
+            if hk.ep != int(bk[BK_EP]):
+                raise RuntimeError(f"Population: member {m}'s device episode index disagrees with its episode log")
+            hk.bestreward = float(bk[BK_BESTREWARD:BK_BESTREWARD + 1].view(np.float64)[0])
+            hk.bestepisode = int(bk[BK_BESTEPISODE])
+            stops[m].cur = int(bk[BK_STOP_CUR])
+            hk._init_off = int(bk[BK_INIT_OFF])
+            best_e = np.flatnonzero(elog[:, m, EL_NEW_BEST])
+            if best_e.size and hk.collect_bestDF:
+                changed.append((m, int(elog[best_e[-1], m, EL_STEPS])))
+            if not rows_out[m, ACTIVE]:
+                active[m] = False
+        if changed:                                             # the best episodes' rows, through the hook's own row path
+            with _on_stream(s_upd):
+                ii = torch.as_tensor([m for m, _ in changed], device=env.device)
+                ba, bp, by, br = (b.index_select(0, ii).cpu() for b in self._best_rows)
+            for j, (m, n) in enumerate(changed):
+                hk = self.hooks[m]
+                hk._rows_bulk = (list(range(1, n + 1)), ba[j, :n], bp[j, :n], by[j, :n], br[j, :n])
+                hk._flush(env)
+                hk.bestDF, hk.currentDF = list(hk.currentDF), []
+        t3 = time.perf_counter()
+        tm = self.timing
+        tm["episodes"] += L
+        tm["blocks"] = tm.get("blocks", 0) + 1
         tm["issue_s"] += t1 - t0
         tm["readback_s"] += t2 - t1
         tm["settle_s"] += t3 - t2

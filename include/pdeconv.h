@@ -550,6 +550,35 @@ int pdec_population_set_member_hyper(pdec_handle pop, int on);
  * destination keeps its replay; rows past the prefix are not touched).  Counters, seeds and offsets are the caller's.  Refuses
  * a source out of range and a member that is both a source and a destination. */
 int pdec_population_clone(pdec_handle pop, const int32_t* src, const int64_t* rows_sa, const int64_t* rows_rt);
+/* The episode boundary of every member on the device, so that several episodes can be enqueued per read-back.  `book`: DEVICE
+ * int64 [M][16], the caller's, beside the rows -- per member (doubles as bit patterns) 0 hook.ep, 1 min_best_episode,
+ * 2 collect_NNA, 3 / 4 whether rewards_compare is non-empty and its maximum as Python's max() leaves it (the first element
+ * unless a later one compared greater: a leading NaN stays), 5 bestreward, 6 bestepisode, 7 stop kind (0 StopAfterEpisode,
+ * 1 StopAfterEpisodeWithMinSteps), 8 its cur, 9 its episode / step, 10 use_random_init, 11 init seed, 12 init offset of the
+ * next field, 13 counters one field consumes, 14 scratch (the stop fired), 15 free.
+ * phase 0 (behind pdec_population_glue phase 1; one workgroup per member): for members whose row has ACTIVE set, n = the
+ * executed steps from flags [T][M] (up to and with the first flagged step; a flag at step T - 1 is the time-out), episode
+ * reward = 0.0 + the sequential fp64 sum of means[m][0 .. n) (src/PDEhook.jl:52, :92), env_y[m] / env_state[m] = slot n of
+ * log_y / log_state ([T + 1][M][y_elems / state_elems] doubles), then src/PDEhook.jl:65-97 on the book -- eligible:
+ * n == T and ep >= min_best_episode; new best: collect_NNA and reward >= maximum, false for NaN --, which[m] = new best |
+ * collect_NNA << 1 for pdec_population_copy_actors, src/StopCondition.jl:6-40 called once per executed step with
+ * is_terminated true at the last, and elog[m] = {reward, n, new best, 1} (DEVICE int64 [M][4]).  Idle members: elog[m] = 0,
+ * which[m] = 0, nothing else.
+ * phase 1 (behind pdec_population_glue phase 2, which still reads the episode's n_sa and ACTIVE; only book, reset_post and last
+ * are read): the counters of the active members move as src/PDEagent.jl:215-224, :291-314 and :237-252 move them --
+ * n_sa += cols, update_step = 0 with reset_post, the init offset past the consumed field; where the stop fired ACTIVE = 0 and
+ * HALT = 1, else HALT = 0 and, unless `last` (the block's last episode: the host's PRE_EPISODE follows), n_sa -= stride if
+ * n_sa > n_rt. */
+int pdec_population_episode_close(pdec_handle pop, int phase, int64_t* book, int64_t* elog, const int32_t* flags,
+                                  const double* means, int T, const void* log_y, const void* log_state, void* env_y,
+                                  void* env_state, int64_t y_elems, int64_t state_elems, int32_t* which, int reset_post, int last);
+/* Where bit 0 of which[m] is set: the rows src/PDEhook.jl:54-62 logs for the n = elog[m][1] steps of this episode -- action
+ * slots 1..n, p slots 0..n-1, y slots 1..n, reward slots 0..n-1 of the episode's logs ([slots][M][elems] doubles) -- into the
+ * member's best rows best_* [M][T][elems] (src/PDEhook.jl:72-74).  One launch, grid (chunks, M). */
+int pdec_population_copy_best_rows(pdec_handle pop, const int32_t* which, const int64_t* elog, int T, const void* log_action,
+                                   const void* log_p, const void* log_y, const void* log_reward, void* best_action, void* best_p,
+                                   void* best_y, void* best_reward, int64_t action_elems, int64_t p_elems, int64_t y_elems,
+                                   int64_t reward_elems);
 
 /* ---------------------------------------------------------------- episode ledger (PDEhook's bookkeeping, src/PDEhook.jl:51-97) */
 /* The episode returns, blow-up bits and best actor of a batched training run, kept on the device: no launch argument depends
