@@ -36,8 +36,9 @@ class KellerSegelSetup:
         self.dx = self.Lx / self.nx
         self.sensor_positions = (np.arange(3, nx + 1, 5) if sensor_positions is None
                                  else np.asarray(sensor_positions, dtype=np.int64))
-        self.actuators_to_sensors = (np.arange(3, 19) if actuators_to_sensors is None
-                                     else np.asarray(actuators_to_sensors, dtype=np.int64))
+        from .ks import check_actuators_to_sensors
+        self.actuators_to_sensors = check_actuators_to_sensors(np.arange(3, 19) if actuators_to_sensors is None else actuators_to_sensors,
+                                                               len(self.sensor_positions), "KellerSegelSetup")
         self.actuator_positions = self.sensor_positions[self.actuators_to_sensors - 1]
         self.te, self.t0, self.dt = te, t0, dt
         # the reference integrates adaptively (OrdinaryDiffEq RK4(), tol 1e-8, :234-239); the

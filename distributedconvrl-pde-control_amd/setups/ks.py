@@ -40,6 +40,18 @@ def _refuse_unbuilt_branches(setup, where, memory_built=False, reward_check_with
         raise _lib.PdecError(f"temporal_steps = {setup.temporal_steps} is not supported for this setup ({where})")
 
 
+def check_actuators_to_sensors(a2s, n_sensors, who):
+    """actuators_to_sensors is 1-based (KSSetup.jl:113, KellerSegelSetup.jl:129).  An entry outside 1..S would not fail here: numpy
+    wraps index 0 - 1 to the LAST sensor on the host while the device receives -1, which featurize wraps and the reward does
+    not.  Refused by name instead."""
+    a2s = np.asarray(a2s, dtype=np.int64)
+    bad = np.flatnonzero((a2s < 1) | (a2s > n_sensors))
+    if a2s.ndim != 1 or len(a2s) == 0 or len(bad):
+        what = f"entry {int(bad[0]) + 1} is {int(a2s[bad[0]])}" if len(bad) and a2s.ndim == 1 else f"shape {a2s.shape}"
+        raise _lib.PdecError(f"{who}: actuators_to_sensors {what}; every entry is a 1-based sensor number in 1..{n_sensors}")
+    return a2s
+
+
 class KSSetup:
     # Which target-network regime reproduces the reference's saved runs of this experiment family (create_agent's default for
     # `quirk_frozen_targets`): KS22 / KS200 were produced with src/custom_nna.jl:20 as committed -- the Polyak loop of
@@ -60,11 +72,22 @@ class KSSetup:
         # "cnab2": the reference's spectral CNAB2 step (KSSetup.jl:130-160); "rk4_fd": RK4 + periodic 5-point FD variant
         self.integrator = integrator
         self.sensor_positions = np.asarray(sensor_positions, dtype=np.int64)
-        self.actuator_positions = (self.sensor_positions if actuator_positions is None
-                                   else np.asarray(actuator_positions, dtype=np.int64))
+        if actuators_to_sensors is not None:
+            actuators_to_sensors = check_actuators_to_sensors(actuators_to_sensors, len(self.sensor_positions), "KSSetup")
+        if actuator_positions is None and actuators_to_sensors is not None and not mono:
+            # KSSetup.jl:113 places actuator i at sensor actuators_to_sensors[i] (gaussians_actuators[actuators_to_sensors]),
+            # so a subset given alone names the actuators' cells; the scripts spell both lists out
+            self.actuator_positions = self.sensor_positions[actuators_to_sensors - 1]
+        else:
+            self.actuator_positions = (self.sensor_positions if actuator_positions is None
+                                       else np.asarray(actuator_positions, dtype=np.int64))
         n_act = len(self.actuator_positions)
-        self.actuators_to_sensors = (np.arange(1, n_act + 1) if actuators_to_sensors is None
-                                     else np.asarray(actuators_to_sensors, dtype=np.int64))  # 1-based
+        if actuators_to_sensors is None:
+            actuators_to_sensors = check_actuators_to_sensors(np.arange(1, n_act + 1), len(self.sensor_positions), "KSSetup")
+        self.actuators_to_sensors = actuators_to_sensors                                      # 1-based
+        if len(self.actuators_to_sensors) != n_act:
+            raise _lib.PdecError(f"KSSetup: {n_act} actuator_positions but {len(self.actuators_to_sensors)} actuators_to_sensors "
+                                 f"(one sensor number per actuator)")
         self.sigma_sensors, self.sigma_actuators, self.mu = sigma_sensors, sigma_actuators, mu
         self.te, self.t0, self.dt, self.oversampling = te, t0, dt, int(oversampling)
         self.max_value, self.check_max_value = max_value, check_max_value

@@ -20,6 +20,9 @@ class KSegConfig:
                                  else np.asarray(sensor_positions, dtype=np.int64))
         self.actuators_to_sensors = (np.arange(3, 19) if actuators_to_sensors is None
                                      else np.asarray(actuators_to_sensors, dtype=np.int64))
+        if self.actuators_to_sensors.min() < 1 or self.actuators_to_sensors.max() > len(self.sensor_positions):
+            raise IndexError(f"actuators_to_sensors {self.actuators_to_sensors.tolist()}: 1-based sensor numbers in "
+                             f"1..{len(self.sensor_positions)}")       # Julia: BoundsError at :129 (numpy would wrap 0 - 1)
         self.actuator_positions = self.sensor_positions[self.actuators_to_sensors - 1]
         self.dt, self.te, self.agent_power = dt, te, agent_power
         self.window_size, self.temporal_steps = window_size, temporal_steps

@@ -16,11 +16,19 @@ class KSConfig:
         self.nx, self.Lx = int(nx), float(Lx)
         self.dx = self.Lx / self.nx                                   # KSSetup.jl:34
         self.sensor_positions = np.asarray(sensor_positions, dtype=np.int64)      # 1-based cells
-        self.actuator_positions = (self.sensor_positions if actuator_positions is None
-                                   else np.asarray(actuator_positions, dtype=np.int64))
+        if actuator_positions is None and actuators_to_sensors is not None and not mono:
+            # KSSetup.jl:113: actuator i sits at sensor actuators_to_sensors[i]
+            self.actuator_positions = self.sensor_positions[np.asarray(actuators_to_sensors, dtype=np.int64) - 1]
+        else:
+            self.actuator_positions = (self.sensor_positions if actuator_positions is None
+                                       else np.asarray(actuator_positions, dtype=np.int64))
         n_act = len(self.actuator_positions)
         self.actuators_to_sensors = (np.arange(1, n_act + 1) if actuators_to_sensors is None
                                      else np.asarray(actuators_to_sensors, dtype=np.int64))  # 1-based
+        if len(self.actuators_to_sensors) != n_act or self.actuators_to_sensors.min() < 1 \
+                or self.actuators_to_sensors.max() > len(self.sensor_positions):
+            raise IndexError(f"actuators_to_sensors {self.actuators_to_sensors.tolist()}: one 1-based sensor number in "
+                             f"1..{len(self.sensor_positions)} per each of the {n_act} actuators")   # Julia: BoundsError
         self.sigma_sensors, self.sigma_actuators = sigma_sensors, sigma_actuators
         self.mu, self.dt, self.oversampling = mu, dt, int(oversampling)
         self.max_value, self.agent_power = max_value, agent_power

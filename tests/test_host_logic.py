@@ -362,6 +362,53 @@ def test_keller_segel_sensor_box_off_the_grid_is_refused(pkg):
         assert s.gaussians[0, :5].all() and s.gaussians[1, -5:].all()
 
 
+def test_actuators_to_sensors_outside_the_sensors_is_refused(pkg):
+    """actuators_to_sensors is 1-based.  numpy wraps index 0 - 1 to the LAST sensor on the host while the device would receive
+    -1, which featurize wraps and the reward does not; an entry above S reads past the table.  Both setups refuse the entry by
+    name, the oracle raises as Julia's BoundsError does, and the edge values 1 and S still build."""
+    from oracle import ks, keller_segel as kg
+    pos = np.arange(1, 257, 4)
+    for bad, where in (([3, 0, 5], 2), ([65, 1], 1), ([1, 2, -1], 3)):
+        with pytest.raises(pkg.PdecError, match=rf"KSSetup: actuators_to_sensors entry {where} is {bad[where - 1]}; .* 1\.\.64"):
+            pkg.KSSetup(256, 256 * 200 / 240, pos, actuators_to_sensors=bad)
+        with pytest.raises(pkg.PdecError, match=rf"KSSetup: actuators_to_sensors entry {where} is {bad[where - 1]};"):
+            pkg.KSSetup(256, 256 * 200 / 240, pos, actuator_positions=pos[:len(bad)], actuators_to_sensors=bad, mono=True)
+        with pytest.raises(IndexError):
+            ks.KSConfig(256, 256 * 200 / 240, pos, actuators_to_sensors=bad)
+    for bad, where in (([3, 0, 5], 2), ([21, 1], 1), ([1, 2, -1], 3)):
+        with pytest.raises(pkg.PdecError, match=rf"KellerSegelSetup: actuators_to_sensors entry {where} is {bad[where - 1]}; .* 1\.\.20"):
+            pkg.KellerSegelSetup(actuators_to_sensors=bad)
+        with pytest.raises(IndexError):
+            kg.KSegConfig(actuators_to_sensors=bad)
+    assert pkg.KSSetup(256, 256 * 200 / 240, pos, actuators_to_sensors=[64, 1]).n_actuators == 2
+    assert pkg.KellerSegelSetup(actuators_to_sensors=[20, 1]).n_actuators == 2
+    with pytest.raises(pkg.PdecError, match=r"entry 9 is 9; .* 1\.\.8"):      # mono, more actuators than sensors: say which sensors they read
+        pkg.KSSetup(192, 22.0, np.arange(1, 193, 24), actuator_positions=np.arange(5, 193, 11), mono=True)
+
+
+def test_actuator_subset_given_alone_places_the_actuators_on_its_sensors(pkg):
+    """KSSetup(..., actuators_to_sensors=subset) without actuator_positions built len(subset) actuator kernels and reported
+    n_actuators = len(sensor_positions); the oracle then failed with an IndexError and the device would have read past the
+    table.  The actuators of a per-actuator agent sit on their sensors (KSSetup.jl:113), so the subset alone names their cells;
+    a count that contradicts it is refused.  Setup and oracle agree."""
+    from oracle import ks
+    pos, sub = np.arange(1, 257, 4), [40, 3, 64, 17, 1]
+    s = pkg.KSSetup(256, 256 * 200 / 240, pos, actuators_to_sensors=sub, window_size=3)
+    c = ks.KSConfig(256, 256 * 200 / 240, pos, actuators_to_sensors=sub, window_size=3)
+    assert s.n_actuators == 5 and s.state_shape == (3, 5) and s.action_shape == (1, 5) and s.reward_len == 5
+    assert np.array_equal(s.actuator_positions, pos[np.array(sub) - 1]) and np.array_equal(c.actuator_positions, s.actuator_positions)
+    assert s.gaussians_actuators.shape == (5, 256) and np.array_equal(s.gaussians_actuators, c.gaussians_actuators)
+    assert s.env_cfg(1, 0).A == 5 and s.tables()[2].tolist() == [39, 2, 63, 16, 0]
+    a = np.linspace(-1, 1, 5)[None]
+    assert ks.prepare_action(c, a).shape == (256,) and ks.reward_function(c, s.y0_standard(), a, a).shape == (5,)
+    assert ks.featurize(c, s.y0_standard()).shape == (3, 5)
+    for kw in (dict(actuator_positions=pos[:4], actuators_to_sensors=sub), dict(actuators_to_sensors=sub, mono=True)):
+        with pytest.raises(pkg.PdecError, match=r"actuator_positions but 5 actuators_to_sensors"):
+            pkg.KSSetup(256, 256 * 200 / 240, pos, **kw)
+        with pytest.raises(IndexError):
+            ks.KSConfig(256, 256 * 200 / 240, pos, **kw)
+
+
 def test_graph_capture_phase_reachability(pkg):
     """which (chunk, ring phase) pairs the graph capture can ever meet -- host logic of
     pipeline.TrainPipeline._reachable, no GPU: E = 26 / 27 / 30 with chunk 24 miss phases, E = 51 (the bench) meets all"""
