@@ -87,6 +87,7 @@ SIGNATURES = {
     "pdec_policy_act": [Handle, _vp, _vp, _i, _d, _d, _vp],
     "pdec_rollout": [Handle, Handle, _i, _vp, _vp, _vp, _d, _d, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdec_rollout_members": [Handle, _vp, _i, _i, _i, _vp, _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i)],
+    "pdec_policy_act_members": [Handle, _vp, _i, _vp, _i, _d, _vp, C.POINTER(_i)],
     "pdec_randn": [Handle, _vp, _sz, _i, _u64, _u64],
     "pdec_policy_act_rng_dev": [Handle, _vp, _i, _d, _d, _i, _u64, _vp],
     "pdec_mlp_acts_on_published_copy": [Handle, C.POINTER(_i)],
@@ -140,6 +141,7 @@ DEBUG_SIGNATURES = {
     "pdec_debug_spin_us": [_vp, _d],
     "pdec_debug_small_update_kernel": [Handle, Handle, Handle, Handle, _i, _i, _d, _i, C.c_char_p, _i, C.POINTER(_i64)],
     "pdec_debug_batched_update_route": [Handle, Handle, Handle, Handle, _i, _i, C.c_char_p, _i, C.POINTER(_i64)],
+    "pdec_debug_act_members_plan": [Handle, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i64)],
 }
 _RESTYPES = {"pdec_last_error": C.c_char_p}
 

@@ -2340,6 +2340,20 @@ bool rollout_members_supported(const Env& E, const std::vector<const Mlp*>& acto
   if (A.dtype != PDEC_F32 && A.dtype != E.cfg.dtype) return false;
   return ks_rollout_shape_ok(E, A) || kseg_rollout_shape_ok(E, A);
 }
+// the members' pointer table: uploaded on the environment's stream from host memory this object owns.  It is rewritten only when
+// the members change, and then behind everything the stream still has to do (an earlier upload may not have read it yet)
+int roll_tab_upload(Env& E, const std::vector<const Mlp*>& actors) {
+  const size_t M = actors.size();
+  std::vector<const void*> tab(M);
+  for (size_t m = 0; m < M; ++m) tab[m] = actors[m]->params.p;
+  if (tab != E.roll_tab_host || !E.roll_tab.p) {
+    PDEC_HIP(hipStreamSynchronize(E.stream));
+    E.roll_tab_host = tab;
+    if (E.roll_tab.bytes < sizeof(void*) * M) PDEC_HIP(E.roll_tab.alloc(sizeof(void*) * M));
+    PDEC_HIP(hipMemcpyAsync(E.roll_tab.p, E.roll_tab_host.data(), sizeof(void*) * M, hipMemcpyHostToDevice, E.stream));
+  }
+  return PDEC_OK;
+}
 int rollout_members_persistent(Env& E, const std::vector<const Mlp*>& actors, int K, int T, void* y, void* state, void* action,
                                double act_limit, void* reward_sum, void* log_y, void* log_p, void* log_action, void* log_reward,
                                int32_t* done_any, int32_t* done_step) {
@@ -2348,16 +2362,8 @@ int rollout_members_persistent(Env& E, const std::vector<const Mlp*>& actors, in
   if (!rollout_members_supported(E, actors)) { set_error("rollout_members_persistent: configuration not covered"); return PDEC_E_INVALID; }
   PDEC_REQUIRE(K >= 1 && (long long)M * K == E.cfg.B, "rollout_members_persistent: %d members x %d trajectories are not the environment's B = %d",
                M, K, E.cfg.B);
-  // the pointer table: uploaded on the environment's stream from host memory this object owns.  It is rewritten only when
-  // the members change, and then behind everything the stream still has to do (an earlier upload may not have read it yet)
-  std::vector<const void*> tab(M);
-  for (int m = 0; m < M; ++m) tab[m] = actors[m]->params.p;
-  if (tab != E.roll_tab_host || !E.roll_tab.p) {
-    PDEC_HIP(hipStreamSynchronize(E.stream));
-    E.roll_tab_host = tab;
-    if (E.roll_tab.bytes < sizeof(void*) * M) PDEC_HIP(E.roll_tab.alloc(sizeof(void*) * M));
-    PDEC_HIP(hipMemcpyAsync(E.roll_tab.p, E.roll_tab_host.data(), sizeof(void*) * M, hipMemcpyHostToDevice, E.stream));
-  }
+  const int rct = roll_tab_upload(E, actors);
+  if (rct) return rct;
   const RollMembers pm{E.roll_tab.as<const void*>(), K, A.dtype == PDEC_F32 ? 1 : 0};
   const bool ks = E.cfg.pde_kind == PDEC_PDE_KS_CNAB2;
   if (E.cfg.dtype == PDEC_F64) {

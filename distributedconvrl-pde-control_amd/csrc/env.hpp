@@ -74,6 +74,19 @@ int rollout_members_persistent(Env& E, const std::vector<const Mlp*>& actors, in
                                double act_limit, void* reward_sum, void* log_y, void* log_p, void* log_action, void* log_reward,
                                int32_t* done_any, int32_t* done_step);
 
+// E.roll_tab = the actors' parameter pointers, on E's stream (re-uploaded only when the members change)
+int roll_tab_upload(Env& E, const std::vector<const Mlp*>& actors);
+// act_members.hip: the acting step of M actors on one state matrix [M C][ns] in ONE launch (pdec_policy_act_members): the tile
+// plan, whether the member form equals M solo pdec_policy_act_rng calls bit for bit, and the launch on E's stream
+struct ActMembersPlan {
+  int tile_cols = 0, tiles = 0;      // columns per workgroup (a multiple of 64; 0: one tile of 64 does not fit), tiles per member
+  size_t lds = 0;                    // dynamic LDS of a workgroup
+};
+ActMembersPlan act_members_plan(const Mlp& A, int state_dtype, int cols_per_member);
+bool act_members_served(int state_dtype, const std::vector<const Mlp*>& actors, int cols_per_member);
+int act_members_launch(Env& E, const std::vector<const Mlp*>& actors, const void* state, int cols_per_member, double act_limit,
+                       void* actions_out);
+
 // fluid.hip: 2-D pseudo-spectral vorticity environment (src/fluid_rk4.jl + scripts/Fluid/setup/FluidSetup.jl)
 struct FluidEnv;
 int fluid_env_step(Env& E, const void* y_in, const void* action, const void* action_prev, const void* state_prev,

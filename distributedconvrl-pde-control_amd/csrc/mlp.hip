@@ -37,18 +37,7 @@ struct GemmArgs {
   const T* aux; long sauxm, sauxn;  // EPI_MUL_DACT: activation values at (m,n)
 };
 
-template <class T>
-__device__ __forceinline__ T apply_act(T z, int act) {
-  if (act == PDEC_ACT_RELU) return z > 0 ? z : (T)0;
-  if (act == PDEC_ACT_TANH) return (T)tanh((double)z);
-  return z;
-}
-template <>
-__device__ __forceinline__ float apply_act<float>(float z, int act) {
-  if (act == PDEC_ACT_RELU) return z > 0 ? z : 0.0f;
-  if (act == PDEC_ACT_TANH) return tanhf(z);
-  return z;
-}
+// (apply_act<T>: mlp.hpp -- csrc/act_members.hip applies the same activations)
 // derivative expressed through the activation VALUE a = act(z)
 template <class T>
 __device__ __forceinline__ T dact_from_value(T a, int act) {
@@ -1116,7 +1105,7 @@ int pdec_ddpg_update_actor_async(pdec_handle hA, pdec_handle hC, pdec_handle hAt
 // the fly (exact), activations [feature][column] in LDS, per element acc = sum_k w x in ascending k from zero, then + bias and
 // the activation -- the order of gemm_kernel's epilogue --, the Philox / Box-Muller draw of randn_kernel for element
 // column * outputs + row, then v += noise * act_noise and the clamp of act_noise_clamp_kernel.
-#define SMALL_ACT_MAXL 4
+// (SMALL_ACT_MAXL: mlp.hpp)
 struct SmallActArgs {
   int L, cols, maxw, learning, nrows;
   int dims[SMALL_ACT_MAXL + 1], acts[SMALL_ACT_MAXL], woff[SMALL_ACT_MAXL], boff[SMALL_ACT_MAXL];
@@ -1298,7 +1287,7 @@ __global__ __launch_bounds__(256) void step_glue_kernel(StepGlueArgs g_in) {
   launch_sync_done(g.sync);
 }
 
-static int mlp_maxw(const Mlp* M) {
+int pdec::mlp_maxw(const Mlp* M) {
   int maxw = 1;
   for (int l = 0; l <= M->L; ++l) maxw = std::max(maxw, M->dims[l]);
   return maxw;
@@ -1312,7 +1301,7 @@ static bool small_act_ok(const Mlp* M, int dtype, int cols) {
   static const bool off = [] { const char* e = getenv("PDEC_SMALL_ACT"); return e && e[0] == '0'; }();
   if (off || M->L > SMALL_ACT_MAXL || cols < 1) return false;
   if (!(M->dtype == dtype || (M->dtype == PDEC_F32 && dtype == PDEC_F64))) return false;
-  return small_act_lds(M, dtype, cols) <= 48 * 1024;
+  return small_act_lds(M, dtype, cols) <= SMALL_ACT_LDS;
 }
 
 // the fields of SmallActArgs that depend on the network
@@ -1363,6 +1352,11 @@ static ActRoute act_route(const Mlp* M, int cols) {
   if (fused2_act_supported(M, cols)) return ACT_FUSED2;
   if (small_act_ok(M, M->dtype, cols)) return ACT_SMALL;
   return ACT_GENERIC;
+}
+
+bool pdec::act_route_is_fused(const Mlp* M, int cols) {
+  const ActRoute r = act_route(M, cols);
+  return r == ACT_FUSED3 || r == ACT_FUSED2;
 }
 
 extern "C" {

@@ -129,6 +129,28 @@ struct PopClone {
   long long rows_sa, rows_rt;
 };
 
+// the activations of a Dense layer, as every forward pass of the library applies them (gemm_kernel's epilogue, the acting kernels)
+template <class T>
+__device__ __forceinline__ T apply_act(T z, int act) {
+  if (act == PDEC_ACT_RELU) return z > 0 ? z : (T)0;
+  if (act == PDEC_ACT_TANH) return (T)tanh((double)z);
+  return z;
+}
+template <>
+__device__ __forceinline__ float apply_act<float>(float z, int act) {
+  if (act == PDEC_ACT_RELU) return z > 0 ? z : 0.0f;
+  if (act == PDEC_ACT_TANH) return tanhf(z);
+  return z;
+}
+
+// ---- acting for few columns (mlp.hip: small_act_kernel) and its member form (act_members.hip: act_members_kernel)
+#define SMALL_ACT_MAXL 4                 // layers the two kernels take
+#define SMALL_ACT_LDS (48 * 1024)        // bytes of LDS they allow themselves: two activation buffers [widest layer][columns]
+int mlp_maxw(const Mlp* M);              // the widest layer, input included
+// would pdec_policy_act_rng on `cols` states of M take a fused MFMA acting kernel (act_route: ACT_FUSED3 / ACT_FUSED2)?  Those sum
+// in another order than small_act_kernel / gemm_kernel do.
+bool act_route_is_fused(const Mlp* M, int cols);
+
 // Philox4x32-10 counter-based generator (the exploration noise that replaces randn(rng), src/PDEagent.jl:201)
 __device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t k1) {
   for (int r = 0; r < 10; ++r) {

@@ -29,30 +29,15 @@ __global__ void rollout_or_kernel(int n, const int32_t* __restrict__ d, int32_t*
 
 using namespace pdec;
 
-extern "C" int pdec_rollout(pdec_handle henv, pdec_handle hactor, int T, void* y, void* state, void* action,
-                            double act_noise, double act_limit, int learning, uint64_t seed, uint64_t offset,
-                            void* reward_sum, void* log_y, void* log_p, void* log_action, void* log_reward,
-                            int32_t* done_any, int32_t* done_step) {
-  Env* E = lookup_as<Env>(henv, Kind::Env);
-  Mlp* A = lookup_as<Mlp>(hactor, Kind::Mlp);
-  if (!E || !A) { set_error("pdec_rollout: bad handle"); return PDEC_E_HANDLE; }
-  PDEC_REQUIRE(T >= 1 && y && state && action, "pdec_rollout: null/empty argument");
+// The per-step form of a rollout, shared by pdec_rollout and the batched route of pdec_rollout_members: T times act(t, state,
+// action_out) -- the caller's acting launch(es) on the environment's stream -- then the fused environment step, the reward sum,
+// the done flags and the log rows, ping-ponging y / state / action between the caller's buffers and the environment's scratch.
+template <class Act>
+static int rollout_step_loop(pdec_handle henv, Env* E, int T, void* y, void* state, void* action, void* reward_sum, void* log_y,
+                             void* log_p, void* log_action, void* log_reward, int32_t* done_any, int32_t* done_step, Act&& act) {
   const pdec_env_cfg& c = E->cfg;
-  PDEC_REQUIRE(A->dtype == c.dtype, "pdec_rollout: the actor and the environment must share one dtype");
-  PDEC_REQUIRE(A->stream == E->stream, "pdec_rollout: the actor and the environment must share one stream");
   const size_t ts = dtype_size(c.dtype);
-  const int ns = env_ns(c), cols = c.B * (c.mono ? 1 : c.A), na = A->dims[A->L];
-  PDEC_REQUIRE(A->dims[0] == (c.mono ? c.S : ns) && cols * na == c.B * c.A * env_na(c),
-               "pdec_rollout: actor shape %d -> %d does not match the state/action matrices", A->dims[0], na);
-  if (ks_rollout_supported(*E, *A)) {
-    // KS: the whole loop in ONE persistent launch -- the trajectories stay in registers / LDS between steps and the actor is
-    // evaluated in the kernel (csrc/env.hip: ks_rollout_kernel); reward_sum accumulates, the logs are written per step
-    return ks_rollout_persistent(*E, *A, T, y, state, action, act_noise, act_limit, learning, seed, offset, reward_sum, log_y,
-                                 log_p, log_action, log_reward, done_any, done_step);
-  }
-  if (kseg_rollout_supported(*E, *A))     // 1-D Keller-Segel: likewise one launch (csrc/env.hip: kseg_rollout_kernel)
-    return kseg_rollout_persistent(*E, *A, T, y, state, action, act_noise, act_limit, learning, seed, offset, reward_sum, log_y,
-                                   log_p, log_action, log_reward, done_any, done_step);
+  const int ns = env_ns(c);
   const size_t ny = (size_t)c.B * env_y_count(c) * ts, np = (size_t)c.B * env_p_count(c) * ts, nact = (size_t)c.B * c.A * env_na(c) * ts;
   const size_t nst = (size_t)c.B * (c.mono ? c.S : (size_t)c.A * ns) * ts, nr = (size_t)c.B * (c.mono ? 1 : c.A) * ts;
   auto al = [](size_t x) { return (x + 255) / 256 * 256; };
@@ -70,8 +55,7 @@ extern "C" int pdec_rollout(pdec_handle henv, pdec_handle hactor, int T, void* y
   if (done_step) PDEC_HIP(hipMemsetAsync(done_step, 0xFF, sizeof(int32_t) * c.B, E->stream));
   int cur = 0;
   for (int t = 0; t < T; ++t) {
-    int rc = pdec_policy_act_rng(hactor, sb[cur], cols, act_noise, act_limit, learning, seed,
-                                 offset + (uint64_t)t * (((uint64_t)cols * na + 3) / 4), ab[cur ^ 1]);
+    int rc = act(t, (const void*)sb[cur], (void*)ab[cur ^ 1]);
     if (rc) return rc;
     rc = pdec_env_step(henv, yb[cur], ab[cur ^ 1], ab[cur], sb[cur], yb[cur ^ 1], pb, sb[cur ^ 1], rb, db);
     if (rc) return rc;
@@ -102,9 +86,39 @@ extern "C" int pdec_rollout(pdec_handle henv, pdec_handle hactor, int T, void* y
   return PDEC_OK;
 }
 
-// M actors, each driving its own block of per_member trajectories of one environment, in ONE persistent launch
-// (population.py: evaluate_actors).  Greedy only: the Philox numbering of the solo launches is by global column, so a member's
-// noise stream is not defined here.
+extern "C" int pdec_rollout(pdec_handle henv, pdec_handle hactor, int T, void* y, void* state, void* action,
+                            double act_noise, double act_limit, int learning, uint64_t seed, uint64_t offset,
+                            void* reward_sum, void* log_y, void* log_p, void* log_action, void* log_reward,
+                            int32_t* done_any, int32_t* done_step) {
+  Env* E = lookup_as<Env>(henv, Kind::Env);
+  Mlp* A = lookup_as<Mlp>(hactor, Kind::Mlp);
+  if (!E || !A) { set_error("pdec_rollout: bad handle"); return PDEC_E_HANDLE; }
+  PDEC_REQUIRE(T >= 1 && y && state && action, "pdec_rollout: null/empty argument");
+  const pdec_env_cfg& c = E->cfg;
+  PDEC_REQUIRE(A->dtype == c.dtype, "pdec_rollout: the actor and the environment must share one dtype");
+  PDEC_REQUIRE(A->stream == E->stream, "pdec_rollout: the actor and the environment must share one stream");
+  const int ns = env_ns(c), cols = c.B * (c.mono ? 1 : c.A), na = A->dims[A->L];
+  PDEC_REQUIRE(A->dims[0] == (c.mono ? c.S : ns) && cols * na == c.B * c.A * env_na(c),
+               "pdec_rollout: actor shape %d -> %d does not match the state/action matrices", A->dims[0], na);
+  if (ks_rollout_supported(*E, *A)) {
+    // KS: the whole loop in ONE persistent launch -- the trajectories stay in registers / LDS between steps and the actor is
+    // evaluated in the kernel (csrc/env.hip: ks_rollout_kernel); reward_sum accumulates, the logs are written per step
+    return ks_rollout_persistent(*E, *A, T, y, state, action, act_noise, act_limit, learning, seed, offset, reward_sum, log_y,
+                                 log_p, log_action, log_reward, done_any, done_step);
+  }
+  if (kseg_rollout_supported(*E, *A))     // 1-D Keller-Segel: likewise one launch (csrc/env.hip: kseg_rollout_kernel)
+    return kseg_rollout_persistent(*E, *A, T, y, state, action, act_noise, act_limit, learning, seed, offset, reward_sum, log_y,
+                                   log_p, log_action, log_reward, done_any, done_step);
+  return rollout_step_loop(henv, E, T, y, state, action, reward_sum, log_y, log_p, log_action, log_reward, done_any, done_step,
+                           [&](int t, const void* s, void* a) {
+                             return pdec_policy_act_rng(hactor, s, cols, act_noise, act_limit, learning, seed,
+                                                        offset + (uint64_t)t * (((uint64_t)cols * na + 3) / 4), a);
+                           });
+}
+
+// M actors, each driving its own block of per_member trajectories of one environment (population.py: evaluate_actors): ONE
+// persistent launch (*served = 1: KS, 1-D Keller-Segel) or one batched step loop (*served = 2: fluid, 2-D Keller-Segel).
+// Greedy only: the Philox numbering of the solo launches is by global column, so a member's noise stream is not defined here.
 extern "C" int pdec_rollout_members(pdec_handle henv, const pdec_handle* actors, int M, int per_member, int T, void* y, void* state,
                                     void* action, double act_limit, int learning, void* reward_sum, void* log_y, void* log_p,
                                     void* log_action, void* log_reward, int32_t* done_any, int32_t* done_step, int* served) {
@@ -126,9 +140,21 @@ extern "C" int pdec_rollout_members(pdec_handle henv, const pdec_handle* actors,
   for (int m = 1; m < M; ++m)
     if (nets[m]->dims != nets[0]->dims || nets[m]->acts != nets[0]->acts || nets[m]->dtype != nets[0]->dtype)
       return PDEC_OK;      // differing shapes: not served (the caller refuses or loops over solo rollouts)
-  if (!rollout_members_supported(*E, nets)) return PDEC_OK;
-  int rc = rollout_members_persistent(*E, nets, per_member, T, y, state, action, act_limit, reward_sum, log_y, log_p, log_action,
-                                      log_reward, done_any, done_step);
-  if (rc == PDEC_OK) *served = 1;
+  if (rollout_members_supported(*E, nets)) {
+    int rc = rollout_members_persistent(*E, nets, per_member, T, y, state, action, act_limit, reward_sum, log_y, log_p, log_action,
+                                        log_reward, done_any, done_step);
+    if (rc == PDEC_OK) *served = 1;
+    return rc;
+  }
+  // the 2-D environments: no persistent launch, but ONE step loop for all members -- pdec_rollout's, with the member acting
+  // kernel in the place of the solo acting call.  A trajectory's env step does not depend on B or on its place in the batch
+  // there (grids (tiles, B), per-trajectory sensing; tests/test_gpu_act_members.py), so member m's rows are its solo rollout's.
+  if (c.pde_kind != PDEC_PDE_FLUID_RK4 && c.pde_kind != PDEC_PDE_KSEG2D_RK4) return PDEC_OK;
+  if (c.mono || c.memory_size > 0 || nets[0]->dims[0] != env_ns(c) || nets[0]->dims[nets[0]->L] != env_na(c)) return PDEC_OK;
+  const int cols_per_member = per_member * c.A;
+  if (!act_members_served(c.dtype, nets, cols_per_member)) return PDEC_OK;
+  int rc = rollout_step_loop(henv, E, T, y, state, action, reward_sum, log_y, log_p, log_action, log_reward, done_any, done_step,
+                             [&](int, const void* s, void* a) { return act_members_launch(*E, nets, s, cols_per_member, act_limit, a); });
+  if (rc == PDEC_OK) *served = 2;
   return rc;
 }

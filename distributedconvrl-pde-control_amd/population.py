@@ -159,6 +159,28 @@ def _has_persistent_rollout(setup):
     return not (getattr(setup, "is_fluid", False) or getattr(setup, "is_kseg2d", False) or getattr(setup, "mono", False))
 
 
+def _has_batched_rollout(setup):
+    """the two 2-D environments with per-actuator agents: no persistent rollout, but pdec_rollout_members enqueues ONE step loop on
+    the B = M K environment for them (served = 2), the member acting kernel in the place of the acting call"""
+    return ((getattr(setup, "is_fluid", False) or getattr(setup, "is_kseg2d", False)) and not getattr(setup, "mono", False)
+            and not getattr(setup, "memory_size", 0))
+
+
+ACT_MEMBERS_LDS = 48 * 1024      # SMALL_ACT_LDS of csrc/mlp.hpp
+
+
+def act_members_tiles(C, maxw, itemsize):
+    """The tile plan of the member acting kernel (csrc/act_members.hip: act_members_plan) for C columns per member, an actor whose
+    widest layer (input included) has maxw rows and states of `itemsize` bytes: (TC, tiles per member).  A workgroup holds two
+    activation buffers [maxw][TC] in LDS; TC is the largest multiple of 64 that fits ACT_MEMBERS_LDS, capped at C rounded up to
+    64.  (0, 0): not even 64 columns fit -- the call is not served."""
+    tc = ACT_MEMBERS_LDS // (2 * int(maxw) * int(itemsize)) // 64 * 64
+    if tc < 64 or C < 1:
+        return 0, 0
+    tc = min(tc, -(-int(C) // 64) * 64)
+    return tc, -(-int(C) // tc)
+
+
 def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, dtype=torch.float64, stream=None, act_limit=1.0,
                     log=False, device="cuda:0"):
     """One greedy evaluation episode of each of M actors (HipMLPs or approximators of ONE shape) from the same K initial fields:
@@ -166,12 +188,15 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
     Philox stream (init_seed, 0).  `steps` defaults to one episode (te / dt + 1, as testrun).  The environment of
     B = M * K trajectories is this call's own (member m: trajectories m K .. m K + K - 1) on `stream`, which waits for every
     actor's stream.  Where the library serves it (pdec_rollout_members: KS and 1-D Keller-Segel, per-actuator actors of <= 3
-    layers no wider than 32) all M episodes are ONE launch, Float32 actors read as they are; otherwise M env.rollout calls on one
-    B = K environment with actor clones as testrun makes them -- the same numbers, member by member.
+    layers no wider than 32) all M episodes are ONE launch, Float32 actors read as they are.  For the fluid and the 2-D
+    Keller-Segel setups (per-actuator agents, memory_size = 0; actors pdec_policy_act_members serves) the control steps are
+    enqueued ONCE on that B = M K environment -- the member acting kernel, then the batched env step -- instead of M times at
+    B = K.  Otherwise M env.rollout calls on one B = K environment with actor clones as testrun makes them.  The same numbers,
+    member by member and bit for bit, on all three routes.
     Returns episode_reward [M, K] (mean over actuators of the summed reward, PDEhook's figure), reward_sum [M, K, A],
     done_step [M, K] (device tensors), score [M] (numpy; NaN: a trajectory blew up or is not finite), order (best first, NaN
-    last, ties by index), one_launch, workgroups (of the one launch; None otherwise) and with log=True the rows y, p, action,
-    reward [T, M, K, ...]."""
+    last, ties by index), one_launch, workgroups (of the one launch; None otherwise), batched (True: the one step loop of the
+    2-D setups; False on the other two routes) and with log=True the rows y, p, action, reward [T, M, K, ...]."""
     models = [_model(a) for a in actors]
     M = len(models)
     if M < 1:
@@ -190,8 +215,8 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
             small.random_init(int(init_seed), 0, out=y0)
         y0 = (y0 if isinstance(y0, torch.Tensor) else torch.as_tensor(np.array(y0, copy=True))).to(device=dev, dtype=dtype).contiguous()
         K = int(y0.shape[0])
-        env = None              # without a persistent rollout no B = M K environment is built to hear it
-        if _has_persistent_rollout(setup):
+        env = None              # without a persistent rollout or a batched step loop no B = M K environment is built to hear it
+        if _has_persistent_rollout(setup) or _has_batched_rollout(setup):
             env = PDEenv(setup, B=M * K, dtype=dtype, device=device, y0=y0.repeat((M,) + (1,) * (y0.dim() - 1)), stream=stream,
                          autoreset=False)
     B = M * K
@@ -222,8 +247,8 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
         finally:
             for s in others.values():       # whatever next writes the actors' parameters waits for the launch that reads them
                 s.wait_stream(s_env)
-    one = bool(served.value)
-    if not one:
+    one, batched = served.value == 1, served.value == 2
+    if not (one or batched):
         if env is not None:
             env.close()
         if small is None:
@@ -248,10 +273,10 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
                 res[k] = out[k].view((T, M, K) + tuple(out[k].shape[2:]))
         host = (res["episode_reward"].double().cpu().numpy(), res["done_step"].cpu().numpy())     # (waits for the stream)
     res["score"], res["order"] = score_members(*host)
-    res["one_launch"] = one
+    res["one_launch"], res["batched"] = one, batched
     is_ks = one and tuple(setup.y_shape) == (setup.nx,)      # (served: a setup with a persistent rollout, so no 2-D one)
     res["workgroups"] = (len(member_workgroups(M, K)) if is_ks else B) if one else None
-    if one:
+    if one or batched:
         env.close()
     if small is not None:
         small.close()

@@ -284,9 +284,16 @@ int pdec_rollout(pdec_handle env, pdec_handle actor, int T, void* y, void* state
  * trajectories belong to one member (workgroup w: member w / ceil(per_member / 2), trajectories 2 (w % ceil(per_member / 2))
  * and the next of that member, if it has one) -- the pairing of a solo launch on per_member trajectories, so every member's
  * results are bit for bit those of pdec_rollout on its block alone.
+ * Fluid and 2-D Keller-Segel (no persistent launch): *served = 2, "batched step loop" -- the T control steps of pdec_rollout's
+ * per-step form enqueued ONCE on the B = M * per_member environment, with pdec_policy_act_members on per_member * A columns per
+ * member in the place of the acting call (same pdec_env_step, reward sums, flags, log rows and copy-back).  A trajectory's
+ * step does not depend on B or on its place in the batch in those environments, so here too every member's results are bit
+ * for bit those of pdec_rollout on its block alone.  Served when pdec_policy_act_members serves the actors (see there); not
+ * with the global agent or memory_size > 0.
  * *served = 0 and nothing is enqueued when the environment / actor shape is not one the persistent launches of pdec_rollout
- * cover, when the actors differ in shape or dtype, when their parameters are neither Float32 nor of the environment's dtype,
- * or with PDEC_ROLLOUT_PERSISTENT=0: the caller then loops over pdec_rollout. */
+ * or the batched step loop cover, when the actors differ in shape or dtype, when their parameters are neither Float32 nor of
+ * the environment's dtype, or -- KS and 1-D Keller-Segel -- with PDEC_ROLLOUT_PERSISTENT=0: the caller then loops over
+ * pdec_rollout. */
 int pdec_rollout_members(pdec_handle env, const pdec_handle* actors, int M, int per_member, int T, void* y, void* state,
                          void* action, double act_limit, int learning, void* reward_sum, void* log_y, void* log_p,
                          void* log_action, void* log_reward, int32_t* done_any, int32_t* done_step, int* served);
@@ -313,6 +320,17 @@ int pdec_policy_act_rng(pdec_handle actor, const void* state, int cols, double a
  * clone of the actor in `state_dtype` (pdec_mlp_copy + pdec_policy_act_rng).  Same arithmetic, bit for bit, either way. */
 int pdec_policy_act_rng_as(pdec_handle actor, int state_dtype, const void* state, int cols, double act_noise, double act_limit,
                            int learning, uint64_t seed, uint64_t offset, void* actions_out, int* served);
+/* agent(env), greedy, of M actors of one shape on ONE state matrix in one launch (act_members_kernel): state [M * cols_per_member][ns]
+ * and actions_out [M * cols_per_member][na] of the environment's dtype, member m owns columns m * cols_per_member ... and is
+ * driven by actors[m] (Float32 parameters, promoted on the fly, or parameters of the environment's dtype; any stream -- the
+ * caller orders them).  Runs on the environment's stream; the environment owns the device table of parameter pointers.  The
+ * arithmetic is pdec_policy_act_rng's with learning = 0 on each block alone, bit for bit.  No noise path: the exploration stream
+ * is numbered by global column.  *served = 0 and nothing is enqueued when the actors' shapes, activations or dtypes differ, when
+ * the parameter dtype is neither Float32 nor the environment's, with more than 4 layers or a widest layer of which a tile of
+ * 64 columns does not fit 48 KB of LDS, or when pdec_policy_act_rng on cols_per_member states of an actor of the
+ * environment's dtype would take a fused MFMA acting kernel (fp32 environments only; those kernels sum in another order). */
+int pdec_policy_act_members(pdec_handle env, const pdec_handle* actors, int M, const void* state, int cols_per_member,
+                            double act_limit, void* actions_out, int* served);
 /* The glue between two control steps of a single-trajectory training loop in ONE launch (src/PDEagent.jl:276-289, :175-209,
  * :254-274 in the order RL.jl's run loop calls them): pdec_replay_push_rt of the step that just ran (n_rt == 0: none), then
  * agent(env) for the next step -- act_mode 1: pdec_policy_act_rng_as on `state` [cols][ns] of type `dtype` with learning = 1;

@@ -59,6 +59,13 @@ int pdec_debug_small_update_kernel(pdec_handle actor, pdec_handle critic, pdec_h
 int pdec_debug_batched_update_route(pdec_handle actor, pdec_handle critic, pdec_handle target_actor, pdec_handle target_critic,
                                     int Bu, int which, char* name, int name_len, int64_t* lds_bytes);
 
+/* Unit-test entry (no reference counterpart): the tile plan of pdec_policy_act_members for an actor of this shape under states of
+ * `state_dtype` with cols_per_member columns per member -- launches nothing.  *tile_cols = columns per workgroup (the largest
+ * multiple of 64 whose two activation buffers [widest layer][tile_cols] fit 48 KB, capped at cols_per_member rounded up to 64;
+ * 0: not even 64 fit, the call is not served), *tiles = workgroups per member, *lds_bytes = dynamic LDS of a workgroup. */
+int pdec_debug_act_members_plan(pdec_handle actor, int state_dtype, int cols_per_member, int* tile_cols, int* tiles,
+                                int64_t* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif

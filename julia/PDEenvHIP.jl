@@ -140,7 +140,8 @@ function rollout!(h::UInt64, actor, T::Integer, y::Ptr{Cvoid}, state::Ptr{Cvoid}
 end
 # the same for M actors at once (selection after population training): y, state, action hold B = M * per_member trajectories,
 # trajectory b is driven by actors[b / per_member] (Float32 or environment-dtype parameters, any stream: order them before
-# the call), greedy, ONE launch.  Returns false when the library does not serve the configuration in one launch (nothing was
+# the call), greedy: ONE persistent launch (KS, 1-D Keller-Segel; served = 1) or one batched step loop with act_members! in the
+# place of the acting call (fluid, 2-D Keller-Segel; served = 2).  Returns false when the library serves neither (nothing was
 # enqueued: call rollout! per actor instead).
 function rollout_members!(h::UInt64, actors::Vector{UInt64}, per_member::Integer, T::Integer, y::Ptr{Cvoid}, state::Ptr{Cvoid},
                           action::Ptr{Cvoid}; act_limit = 1.0, reward_sum = C_NULL, done_step = C_NULL)
@@ -150,6 +151,18 @@ function rollout_members!(h::UInt64, actors::Vector{UInt64}, per_member::Integer
                  Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ref{Cint}),
                 h, actors, length(actors), per_member, T, y, state, action, act_limit, 0, reward_sum, C_NULL, C_NULL, C_NULL,
                 C_NULL, C_NULL, done_step, served))
+    served[] != 0
+end
+
+# agent(env), greedy, of M actors on one state matrix [M * cols_per_member][ns] in ONE launch on the environment's stream: member m
+# owns columns m * cols_per_member ... of state / actions (device arrays of the environment's dtype).  Returns false when the
+# library does not serve the actors (nothing was enqueued: act per member instead).
+function act_members!(h::UInt64, actors::Vector{UInt64}, state::Ptr{Cvoid}, cols_per_member::Integer, actions::Ptr{Cvoid};
+                      act_limit = 1.0)
+    served = Ref{Cint}(0)
+    check(ccall((:pdec_policy_act_members, LIB), Cint,
+                (UInt64, Ptr{UInt64}, Cint, Ptr{Cvoid}, Cint, Cdouble, Ptr{Cvoid}, Ref{Cint}),
+                h, actors, length(actors), state, cols_per_member, act_limit, actions, served))
     served[] != 0
 end
 
