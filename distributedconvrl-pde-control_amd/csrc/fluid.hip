@@ -999,11 +999,63 @@ __global__ void fluid_ic_kernel(int n, int nv, T Lx, T Ly, const T* __restrict__
   out[(size_t)b * n * n + idx] = total;
 }
 
+// the vortex table of an fp32 environment from the caller's doubles, on the device (pdec_fluid_ic_dev)
+__global__ void fluid_round_kernel(const double* __restrict__ in, float* __restrict__ out, size_t cnt) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < cnt) out[i] = (float)in[i];
+}
+
+// error_detection (scripts/Fluid/setup/FluidSetup.jl:263-273) on w = real(ifft2(y)) [B][n][n]: the largest |w[r][i] - w[r-1][i]|
+// and |w[r][i] - w[r][i-1]|, periodic along both axes.  grid (ceil(n / FL_JUMP_ROWS), B): a workgroup walks its rows downwards,
+// a thread keeps the row above in a register (one halo row per tile) and takes its left neighbour from the lane beside it
+// (lane 0: one more load), so every row is read once, coalesced along the fast axis.  The maximum PROPAGATES NaN, as the host's
+// torch max does; wave: shuffles, workgroup: LDS; then ONE integer OR per workgroup into bits[b]: 1 = above 10, 2 = NaN.
+#define FL_JUMP_ROWS 16
+#define FL_JUMP_NTH 256
+template <class T>
+__device__ __forceinline__ T nanmax(T a, T b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
+
+template <class T>
+__global__ __launch_bounds__(FL_JUMP_NTH) void fluid_jump_kernel(int n, const T* __restrict__ w, int32_t* __restrict__ bits) {
+  __shared__ T part[FL_JUMP_NTH / 64];
+  const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.y;
+  const int r0 = blockIdx.x * FL_JUMP_ROWS, r1 = min(r0 + FL_JUMP_ROWS, n);
+  const T* wb = w + (size_t)b * n * n;
+  T m = 0;
+  for (int i0 = 0; i0 < n; i0 += FL_JUMP_NTH) {        // (uniform trip count: the shuffle below is executed by whole waves)
+    const int i = i0 + tid;
+    const bool live = i < n;
+    const int il = i == 0 ? n - 1 : i - 1;
+    T up = live ? wb[(size_t)(r0 == 0 ? n - 1 : r0 - 1) * n + i] : (T)0;
+    for (int r = r0; r < r1; ++r) {
+      const T cur = live ? wb[(size_t)r * n + i] : (T)0;
+      T left = __shfl_up(cur, 1);
+      if (live && lane == 0) left = wb[(size_t)r * n + il];
+      if (live) m = nanmax(m, nanmax(fabs(cur - up), fabs(cur - left)));
+      up = cur;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) m = nanmax(m, __shfl_xor(m, off));
+  if (lane == 0) part[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) {
+    for (int k = 1; k < FL_JUMP_NTH / 64; ++k) m = nanmax(m, part[k]);
+    const int v = m != m ? 2 : (m > (T)10 ? 1 : 0);
+    if (v) atomicOr(&bits[b], v);
+  }
+}
+
+// errored[b] = the NaN-propagating maximum is above 10: some workgroup saw a jump and none saw a NaN
+__global__ void fluid_jump_finish_kernel(int B, const int32_t* __restrict__ bits, int32_t* __restrict__ errored) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) errored[b] = bits[b] == 1 ? 1 : 0;
+}
+
 struct FluidEnv : Env {
   int n = 0, p = 0, nl = 0, TL = 0, TLn = 0, BH = 0, BW = 0, nb1 = 0;
   FftPlan plp, pln;
   DevBuf k, twp, twn, sbox, sorg, abox, aorg, a2s_d, blkptr, blkidx;
-  DevBuf W, W2, fs, acc, yreal, tmpc, dots, phat, icv;
+  DevBuf W, W2, fs, acc, yreal, tmpc, dots, phat, icv, errbits;
   size_t lds_p = 0, lds_n = 0;
   int wave_E = 0, wave_Q = 0;     // != 0: the one-line-per-wave transforms serve the padded length p
   int wave_LB = 6;                // 5: one line per HALF wave (p = 192, 64)
@@ -1577,6 +1629,10 @@ static int fluid_make(std::unique_ptr<FluidEnv>& out, const pdec_env_cfg& c, int
   PDEC_HIP(E->phat.alloc(Bz * nn * zs));
   PDEC_HIP(E->yreal.alloc(Bz * nn * ts));
   PDEC_HIP(E->dots.alloc(Bz * c.S * ts));
+  // pdec_fluid_error_detection's bits and the vortex table of ic(3) / ic(4) (50 vortices; a longer table grows it): made here, so
+  // that the device entry points only enqueue
+  PDEC_HIP(E->errbits.alloc(Bz * sizeof(int32_t)));
+  PDEC_HIP(E->icv.alloc(Bz * 50 * 4 * ts));
   if ((rc = (c.dtype == PDEC_F32 ? fluid_set_attrs<float>(*E) : fluid_set_attrs<double>(*E)))) return rc;
   out = std::move(E);
   return PDEC_OK;
@@ -1645,12 +1701,28 @@ extern "C" int pdec_debug_wave_fft_f32(const void* in_dev, void* out_dev, int le
   return debug_wave_fft<float>("pdec_debug_wave_fft_f32", in_dev, out_dev, len, nlines, sgn);
 }
 
+// the initialiser and the forward 2-D FFT on the environment's stream; vort: DEVICE [B][nv][4] in the environment's dtype
+template <class T>
+static int fluid_ic_launch(FluidEnv& E, const T* vort, int nv, void* y_out) {
+  typedef C2<T> Z;
+  const pdec_env_cfg& c = E.cfg;
+  const FluidDev<T> d = fluid_dev<T>(E);
+  const int gt = (E.n + E.TLn - 1) / E.TLn;
+  ProfScope ps(&E, "fluid_ic");
+  hipLaunchKernelGGL(fluid_ic_kernel<T>, dim3((E.n * E.n + 255) / 256, c.B), dim3(256), (size_t)nv * 4 * sizeof(T), E.stream,
+                     E.n, nv, (T)c.Lx, (T)c.Lx, vort, E.yreal.as<T>());
+  hipLaunchKernelGGL((fluid_fft_fast_kernel<T, -1, true>), dim3(gt, c.B), dim3(FL_NTH), E.lds_n, E.stream, d, E.yreal.p,
+                     E.tmpc.as<Z>());
+  hipLaunchKernelGGL((fluid_fft_slow_kernel<T, -1, false>), dim3(gt, c.B), dim3(FL_NTH), E.lds_n, E.stream, d,
+                     E.tmpc.as<Z>(), y_out, (T)1);
+  PDEC_HIP(hipGetLastError());
+  return PDEC_OK;
+}
+
 // the vortex table in the environment's dtype (fp32: rounded once from the caller's doubles), the initialiser, the 2-D FFT
 template <class T>
 static int fluid_ic_t(FluidEnv& E, const double* vortices, int nv, void* y_out) {
-  typedef C2<T> Z;
-  const pdec_env_cfg& c = E.cfg;
-  const size_t cnt = (size_t)c.B * nv * 4, vb = cnt * sizeof(T);
+  const size_t cnt = (size_t)E.cfg.B * nv * 4, vb = cnt * sizeof(T);
   std::vector<T> vt;
   const void* src = vortices;
   if (!std::is_same<T, double>::value) {
@@ -1659,16 +1731,8 @@ static int fluid_ic_t(FluidEnv& E, const double* vortices, int nv, void* y_out) 
   }
   if (E.icv.bytes < vb) PDEC_HIP(E.icv.alloc(vb));
   PDEC_HIP(hipMemcpyAsync(E.icv.p, src, vb, hipMemcpyHostToDevice, E.stream));
-  const FluidDev<T> d = fluid_dev<T>(E);
-  const int gt = (E.n + E.TLn - 1) / E.TLn;
-  ProfScope ps(&E, "fluid_ic");
-  hipLaunchKernelGGL(fluid_ic_kernel<T>, dim3((E.n * E.n + 255) / 256, c.B), dim3(256), (size_t)nv * 4 * sizeof(T), E.stream,
-                     E.n, nv, (T)c.Lx, (T)c.Lx, E.icv.as<T>(), E.yreal.as<T>());
-  hipLaunchKernelGGL((fluid_fft_fast_kernel<T, -1, true>), dim3(gt, c.B), dim3(FL_NTH), E.lds_n, E.stream, d, E.yreal.p,
-                     E.tmpc.as<Z>());
-  hipLaunchKernelGGL((fluid_fft_slow_kernel<T, -1, false>), dim3(gt, c.B), dim3(FL_NTH), E.lds_n, E.stream, d,
-                     E.tmpc.as<Z>(), y_out, (T)1);
-  PDEC_HIP(hipGetLastError());
+  int rc = fluid_ic_launch<T>(E, E.icv.as<T>(), nv, y_out);
+  if (rc) return rc;
   PDEC_HIP(hipStreamSynchronize(E.stream));      // the host array (and vt) may be reused / freed once this returns
   return PDEC_OK;
 }
@@ -1681,4 +1745,49 @@ extern "C" int pdec_fluid_ic(pdec_handle h, const double* vortices, int nv, void
   PDEC_REQUIRE(vortices && y_out && nv >= 1 && nv <= 1024, "pdec_fluid_ic: bad arguments (1 <= nv <= 1024)");
   FluidEnv& E = static_cast<FluidEnv&>(*E0);
   return E.cfg.dtype == PDEC_F32 ? fluid_ic_t<float>(E, vortices, nv, y_out) : fluid_ic_t<double>(E, vortices, nv, y_out);
+}
+
+static FluidEnv* fluid_handle(pdec_handle h, const char* who) {
+  Env* E0 = lookup_as<Env>(h, Kind::Env);
+  if (!E0 || E0->cfg.pde_kind != PDEC_PDE_FLUID_RK4) { set_error("%s: not a fluid env handle", who); return nullptr; }
+  return static_cast<FluidEnv*>(E0);
+}
+
+// pdec_fluid_ic with the table already in device memory (doubles): the same launches, no host copy, no synchronisation.
+// An fp32 environment rounds the table once, on the device, into its own icv (the rounding of the host path's cast).
+extern "C" int pdec_fluid_ic_dev(pdec_handle h, const double* vortices_dev, int nv, void* y_out) {
+  FluidEnv* Ep = fluid_handle(h, "pdec_fluid_ic_dev");
+  if (!Ep) return PDEC_E_HANDLE;
+  PDEC_REQUIRE(vortices_dev && y_out && nv >= 1 && nv <= 1024, "pdec_fluid_ic_dev: bad arguments (1 <= nv <= 1024)");
+  FluidEnv& E = *Ep;
+  if (E.cfg.dtype != PDEC_F32) return fluid_ic_launch<double>(E, vortices_dev, nv, y_out);
+  const size_t cnt = (size_t)E.cfg.B * nv * 4;
+  if (E.icv.bytes < cnt * sizeof(float)) PDEC_HIP(E.icv.alloc(cnt * sizeof(float)));
+  hipLaunchKernelGGL(fluid_round_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, E.stream, vortices_dev, E.icv.as<float>(),
+                     cnt);
+  return fluid_ic_launch<float>(E, E.icv.as<float>(), nv, y_out);
+}
+
+template <class T>
+static int fluid_error_detection_t(FluidEnv& E, const void* y, int32_t* errored_out) {
+  const int B = E.cfg.B;
+  int rc = fluid_to_physical<T>(E, y);
+  if (rc) return rc;
+  ProfScope ps(&E, "fluid_error_detection");
+  PDEC_HIP(hipMemsetAsync(E.errbits.p, 0, sizeof(int32_t) * B, E.stream));
+  hipLaunchKernelGGL(fluid_jump_kernel<T>, dim3((E.n + FL_JUMP_ROWS - 1) / FL_JUMP_ROWS, B), dim3(FL_JUMP_NTH), 0, E.stream, E.n,
+                     E.yreal.as<T>(), E.errbits.as<int32_t>());
+  hipLaunchKernelGGL(fluid_jump_finish_kernel, dim3((B + 255) / 256), dim3(256), 0, E.stream, B, E.errbits.as<int32_t>(), errored_out);
+  PDEC_HIP(hipGetLastError());
+  return PDEC_OK;
+}
+
+// error_detection of the fluid script (scripts/Fluid/setup/FluidSetup.jl:263-273) per trajectory; see include/pdeconv.h
+extern "C" int pdec_fluid_error_detection(pdec_handle h, const void* y, int32_t* errored_out) {
+  FluidEnv* Ep = fluid_handle(h, "pdec_fluid_error_detection");
+  if (!Ep) return PDEC_E_HANDLE;
+  PDEC_REQUIRE(y && errored_out, "pdec_fluid_error_detection: null argument");
+  // (a batch stepped in parts: the parent environment has work arrays of the whole batch of its own, fluid_make)
+  return Ep->cfg.dtype == PDEC_F32 ? fluid_error_detection_t<float>(*Ep, y, errored_out)
+                                   : fluid_error_detection_t<double>(*Ep, y, errored_out);
 }

@@ -146,6 +146,55 @@ def perturb_factors(rng, n, lo, hi):
     return np.where(pick == 0, float(lo), float(hi))
 
 
+# ---- fluid members: the vortex tables of a block of episodes, and what the episode logs cost (pure host logic)
+
+def draw_block_tables(setup, rngs, L, caseno):
+    """The initial vortex tables of up to L episodes for each member: rngs[m] is member m's own init_rng, or None for a member
+    that draws none (idle, or without random inits).  Member m's e-th table is the e-th successive
+    setup.ic_vortices(caseno, rngs[m], 1) of its generator, as its solo hook draws one per episode.  Returns (tables
+    [L, M, nv, 4] -- ones where nothing was drawn --, states): states[m] = [the generator's state before the first draw, the state
+    behind draw 1, ..., behind draw L], or None."""
+    tables, states = None, []
+    for m, rng in enumerate(rngs):
+        if rng is None:
+            states.append(None)
+            continue
+        st = [rng.bit_generator.state]
+        for e in range(int(L)):
+            v = setup.ic_vortices(caseno, rng, 1)[0]
+            if tables is None:              # (the table's length is ic_vortices' own)
+                tables = np.ones((int(L), len(rngs)) + v.shape, dtype=np.float64)
+            tables[e, m] = v
+            st.append(rng.bit_generator.state)
+        states.append(st)
+    if tables is None:
+        tables = np.ones((int(L), len(rngs), 1, 4), dtype=np.float64)
+    return tables, states
+
+
+def restore_block_rngs(rngs, states, consumed):
+    """after a block: member m's generator goes back to the state behind the last table it consumed (consumed[m] of the L drawn),
+    so a member that stopped inside the block has advanced its generator exactly as far as its solo run has"""
+    for rng, st, k in zip(rngs, states, consumed):
+        if rng is not None and st is not None:
+            rng.bit_generator.state = st[int(k)]
+
+
+def episode_log_bytes(setup, T, itemsize=8):
+    """(logs, best_rows) bytes PER MEMBER of a population's per-step slots of one episode of T control steps (run._EpisodeLogs:
+    y, state and action T + 1 slots, p and reward T) and of the best episode's rows the block path keeps on the device
+    (action, p, y, reward: T slots each).  A fluid field is a complex spectrum (two reals per cell); p has the field's shape."""
+    fluid = bool(getattr(setup, "is_fluid", False))
+    y = int(np.prod(setup.y_shape)) * (2 if fluid else 1)
+    p = y if fluid else int(np.prod(getattr(setup, "p_shape", (setup.nx,))))
+    ns, A = setup.state_shape
+    a = int(np.prod(setup.action_shape))
+    r = int(setup.reward_len)
+    logs = (int(T) + 1) * (y + ns * A + a) + int(T) * (p + r)
+    best = int(T) * (a + p + y + r)
+    return logs * int(itemsize), best * int(itemsize)
+
+
 def _model(actor):
     return getattr(actor, "model", actor)
 
@@ -211,8 +260,11 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
     with _on_stream(stream):    # (the environments' own tensors are made on their stream as well)
         if y0 is None:
             small = PDEenv(setup, B=int(n_inits), dtype=dtype, device=device, stream=stream, autoreset=False)
-            y0 = torch.empty_like(small.y)
-            small.random_init(int(init_seed), 0, out=y0)
+            if getattr(setup, "is_fluid", False):   # the fluid's own initialiser: vortex tables from numpy's default_rng(init_seed)
+                y0 = setup.random_init_device(small, np.random.default_rng(int(init_seed)))
+            else:
+                y0 = torch.empty_like(small.y)
+                small.random_init(int(init_seed), 0, out=y0)
         y0 = (y0 if isinstance(y0, torch.Tensor) else torch.as_tensor(np.array(y0, copy=True))).to(device=dev, dtype=dtype).contiguous()
         K = int(y0.shape[0])
         env = None              # without a persistent rollout or a batched step loop no B = M K environment is built to hear it
@@ -284,20 +336,39 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
 
 
 class Population:
-    def __init__(self, setup, agents, hooks, stream_env, dtype=torch.float64, device="cuda:0"):
+    def __init__(self, setup, agents, hooks, stream_env, dtype=torch.float64, device="cuda:0", part_streams=None,
+                 max_log_bytes=8 << 30):
+        """part_streams: handed to the population's PDEenv (the fluid steps its batch in parts on them where it splits it).
+        max_log_bytes: the most the per-step slots of one episode (and the best-row copies of the block path) may take on the
+        device; a fluid member's are (T + 1) + T full spectra and more (episode_log_bytes)."""
         M = len(agents)
         if M < 1 or len(hooks) != M:
             _refuse("needs one hook per agent and at least one member")
         name = type(setup).__name__
-        if getattr(setup, "is_fluid", False) or getattr(setup, "is_kseg2d", False):
+        if getattr(setup, "is_kseg2d", False):
             _refuse(f"{name} is not served (its batched step, part streams and initialisers need their own check); "
-                    "KSSetup and KellerSegelSetup are")
+                    "KSSetup, KellerSegelSetup and FluidSetup are")
         if dtype != torch.float64:
             _refuse("fp64 environments only (the shape of every reference-shaped run)")
         if getattr(setup, "memory_size", 0):
             _refuse("memory_size > 0 is not on the device-episode path")
         if stream_env is None:
             _refuse("needs an explicit environment stream (make_streams)")
+        # before anything is allocated: the members must be learners of THIS setup
+        ns, A = setup.state_shape
+        for m, ag in enumerate(agents):
+            if not isinstance(ag, Agent):
+                _refuse(f"member {m}: an Agent with a PDEhook is needed")
+            pol = ag.policy
+            if getattr(pol, "mono", None) or getattr(pol, "reward_group", None) is not None:
+                continue                # (refused by name below)
+            rows, stride = pol.behavior_actor.model.dims[0], ag.trajectory.stride
+            if rows != ns or stride != A:
+                _refuse(f"member {m}: its actor reads {rows} state rows and its replay takes {stride} columns per step, but {name} "
+                        f"has {ns} state rows and {A} actuators: the member was not made for this setup")
+            if getattr(setup, "is_fluid", False) and stride > 256:
+                _refuse(f"member {m}: {stride} actuators per step, and the device-episode path serves at most 256 "
+                        f"(run.device_episodes_ok); of {name}'s experiments Fluid_8 and Fluid_16 are served, Fluid_32 is not")
         self.setup, self.agents, self.hooks, self.M = setup, list(agents), list(hooks), M
         probe = PDEenv(setup, B=1, dtype=dtype, device=device, stream=stream_env, autoreset=False)
         a0 = agents[0]
@@ -341,10 +412,18 @@ class Population:
         self.stream_env, self.stream_upd = stream_env, a0.trajectory.stream
         if self.stream_env.cuda_stream == self.stream_upd.cuda_stream:
             _refuse("the environment and the networks need two different streams")
-        self.env = PDEenv(setup, B=M, dtype=dtype, device=device, stream=stream_env, autoreset=False)
+        T = _episode_steps(setup)
+        per_logs, per_best = episode_log_bytes(setup, T, 8)
+        need = M * (per_logs + per_best)
+        if need > int(max_log_bytes):
+            _refuse(f"the per-step slots of one episode of {T} steps take {M * per_logs} bytes for {M} members and the best "
+                    f"episode's rows of the block path {M * per_best} more: {need} bytes in all, above max_log_bytes = "
+                    f"{int(max_log_bytes)}; at most {int(max_log_bytes) // (per_logs + per_best)} members fit")
+        self.is_fluid = bool(getattr(setup, "is_fluid", False))
+        self.env = PDEenv(setup, B=M, dtype=dtype, device=device, stream=stream_env, autoreset=False, part_streams=part_streams)
         self.lib = lib = self.env.lib
-        _lib.check(lib.pdec_env_set_member_layout(self.env.handle, 1))
-        ns, A = setup.state_shape
+        if not self.is_fluid:       # (the fluid step is per trajectory as it stands: no pairing of trajectories to re-arrange)
+            _lib.check(lib.pdec_env_set_member_layout(self.env.handle, 1))
         self.cols = A
         pol0, tr0 = a0.policy, a0.trajectory
         with _on_stream(self.stream_upd):
@@ -532,7 +611,7 @@ class Population:
             for m, (ag, hk) in enumerate(zip(self.agents, self.hooks)):
                 if hk.collect_history:
                     _refuse(f"member {m}: collect_history needs every episode's rows on the host; run it with episodes_per_sync=1")
-                if hk.error_detection_given:
+                if hk.error_detection_given and not self._own_error_detection(hk):
                     _refuse(f"member {m}: a hook with an error_detection callable is settled on the host every episode; run it "
                             "with episodes_per_sync=1")
                 if (ag.policy.reset_stage == POST_EPISODE_STAGE) != (self.agents[0].policy.reset_stage == POST_EPISODE_STAGE):
@@ -559,6 +638,15 @@ class Population:
             hk(POST_EXPERIMENT_STAGE, ag, env)
         return self.hooks
 
+    def _ic_case(self):
+        """generate_random_init's case (FluidSetup.jl:386-394): ic(4) in evaluation, ic(3) in training"""
+        return 4 if self.setup.evaluation else 3
+
+    def _fluid_ic(self, table, out):
+        """pdec_fluid_ic_dev on the environment's stream: `out` [M, ...] from the device table [M, nv, 4] (kept alive by the
+        caching allocator's stream order: it was made with the environment's stream current)"""
+        _lib.check(self.lib.pdec_fluid_ic_dev(self.env.handle, _lib.ptr(table), int(table.shape[-2]), _lib.ptr(out)))
+
     def _pre_episode(self, active):
         """env.reset(), agent PRE_EPISODE (the dummy pop), hook PRE_EPISODE (random inits: one launch for all members); the
         rows of idle members are restored afterwards"""
@@ -572,14 +660,21 @@ class Population:
         rnd = [m for m in np.flatnonzero(active) if self.hooks[m].use_random_init]
         with _on_stream(self.stream_env):
             if rnd:
-                nblk = (env.random_init_coefficients() + 3) // 4
-                seeds = torch.tensor([self.hooks[m].init_seed if m in rnd else 0 for m in range(M)], dtype=torch.int64)
-                offs = torch.tensor([self.hooks[m]._init_off if m in rnd else 0 for m in range(M)], dtype=torch.int64)
-                so = torch.stack([seeds, offs]).to(env.device, non_blocking=False)
                 drawn = torch.empty_like(env.y)
-                _lib.check(lib.pdec_env_random_init_members(env.handle, _lib.ptr(so[0]), _lib.ptr(so[1]), _lib.ptr(drawn)))
-                for m in rnd:
-                    self.hooks[m]._init_off += nblk
+                if self.is_fluid:
+                    # every member's own vortex table from its own generator, as its solo hook draws it
+                    # (FluidSetup.random_init_device); one upload, one initialiser launch at B = M
+                    tables, _ = draw_block_tables(self.setup, [self.hooks[m].init_rng if m in rnd else None for m in range(M)], 1,
+                                                  self._ic_case())
+                    self._fluid_ic(torch.from_numpy(tables[0]).to(env.device), drawn)
+                else:
+                    nblk = (env.random_init_coefficients() + 3) // 4
+                    seeds = torch.tensor([self.hooks[m].init_seed if m in rnd else 0 for m in range(M)], dtype=torch.int64)
+                    offs = torch.tensor([self.hooks[m]._init_off if m in rnd else 0 for m in range(M)], dtype=torch.int64)
+                    so = torch.stack([seeds, offs]).to(env.device, non_blocking=False)
+                    _lib.check(lib.pdec_env_random_init_members(env.handle, _lib.ptr(so[0]), _lib.ptr(so[1]), _lib.ptr(drawn)))
+                    for m in rnd:
+                        self.hooks[m]._init_off += nblk
                 mask = torch.zeros(M, dtype=torch.bool)
                 mask[rnd] = True
                 mask = mask.to(env.device)
@@ -700,7 +795,14 @@ class Population:
         tm["settle_s"] += t3 - t2
 
     # ---- blocks of episodes (run(stops, episodes_per_sync > 1)): the episode boundary on the device
-    def _open_episode(self, any_random):
+    def _own_error_detection(self, hk):
+        """is the hook's error_detection FluidSetup.error_detection of this population's own setup (what make_hook() sets)?  The
+        block path then runs its device form (pdec_fluid_error_detection) behind every episode's close launch"""
+        f = hk.error_detection
+        return (self.is_fluid and getattr(f, "__self__", None) is self.setup
+                and getattr(f, "__func__", None) is getattr(type(self.setup), "error_detection", None))
+
+    def _open_episode(self, any_random, table=None):
         """_pre_episode with the members masked by the device columns ACTIVE (rows) and use_random_init / init seed / init offset
         (book) instead of host lists: env.reset(), the random fields of all members in one launch, idle members keep y and state"""
         env, lib = self.env, self.lib
@@ -711,9 +813,12 @@ class Population:
         env.reset()
         with _on_stream(self.stream_env):
             if any_random:
-                seeds, offs = self._book[:, BK_INIT_SEED].contiguous(), self._book[:, BK_INIT_OFF].contiguous()
                 drawn = torch.empty_like(env.y)
-                _lib.check(lib.pdec_env_random_init_members(env.handle, _lib.ptr(seeds), _lib.ptr(offs), _lib.ptr(drawn)))
+                if self.is_fluid:       # this episode's slice of the block's vortex tables
+                    self._fluid_ic(table, drawn)
+                else:
+                    seeds, offs = self._book[:, BK_INIT_SEED].contiguous(), self._book[:, BK_INIT_OFF].contiguous()
+                    _lib.check(lib.pdec_env_random_init_members(env.handle, _lib.ptr(seeds), _lib.ptr(offs), _lib.ptr(drawn)))
                 mask = act & (self._book[:, BK_RANDOM_INIT] != 0)
                 y0 = torch.where(mask.view((M,) + (1,) * (env.y.dim() - 1)), drawn, env.y0)
                 env.y0 = y0
@@ -751,7 +856,7 @@ class Population:
         rows = np.zeros((M, ROW), dtype=np.int64)
         book = np.zeros((M, BOOK), dtype=np.int64)
         rows[:, GAMMA:ETA_C + 1] = self._hyper_rows()[:, :4].copy().view(np.int64)
-        nblk = (env.random_init_coefficients() + 3) // 4
+        nblk = 0 if self.is_fluid else (env.random_init_coefficients() + 3) // 4     # (fluid: INIT_OFF / INIT_INC carry 0)
         as_bits = lambda v: int(np.array([v], dtype=np.float64).view(np.int64)[0])      # noqa: E731
         for m, (ag, hk) in enumerate(zip(self.agents, self.hooks)):
             pol, tr = ag.policy, ag.trajectory
@@ -762,19 +867,33 @@ class Population:
             st = stops[m]
             kind, lim = (0, st.episode) if type(st) is StopAfterEpisode else (1, st.step)
             book[m, :BK_FIRED] = (hk.ep, hk.min_best_episode, int(bool(hk.collect_NNA)), has, as_bits(cmp), as_bits(hk.bestreward),
-                                  hk.bestepisode, kind, st.cur, lim, int(bool(hk.use_random_init)), hk.init_seed, hk._init_off, nblk)
+                                  hk.bestepisode, kind, st.cur, lim, int(bool(hk.use_random_init)), hk.init_seed, 0 if self.is_fluid else hk._init_off, nblk)
         _lib.check(lib.pdec_population_bp_sel(self._h, rows.ctypes.data_as(C.c_void_p), 0))
         start = rows.copy()
         with _on_stream(s_upd):
             self.rows.copy_(torch.from_numpy(rows))
             self._book.copy_(torch.from_numpy(book))
         any_random = bool(book[:, BK_RANDOM_INIT].any())
+        tables = rngs = rng_states = None
+        if self.is_fluid:
+            # the vortex tables of the whole block from the members' own generators (one upload); the generators are set back
+            # to what each member consumed when the block is settled.  err[e, m]: error_detection behind episode e's close
+            if any_random:
+                rngs = [hk.init_rng if (active[m] and hk.use_random_init) else None for m, hk in enumerate(self.hooks)]
+                tab, rng_states = draw_block_tables(self.setup, rngs, L, self._ic_case())
+                with _on_stream(s_env):
+                    tables = torch.from_numpy(tab).to(env.device)
+            detect = any(self._own_error_detection(self.hooks[m]) for m in np.flatnonzero(active))
+            with _on_stream(s_env):
+                if getattr(self, "_err", None) is None or self._err.shape[0] < L:
+                    self._err = torch.zeros((L, M), dtype=torch.int32, device=env.device)
+                self._err.zero_()
         reset_post = int(self.agents[0].policy.reset_stage == POST_EPISODE_STAGE)
         ysz, ssz = env.y[0].numel(), env.state[0].numel()
         ev_act, ev_env = _Event(lib), _Event(lib)
         for e in range(L):
             _join(s_upd, s_env)
-            self._open_episode(any_random)
+            self._open_episode(any_random, tables[e] if tables is not None else None)
             with _on_stream(s_env):
                 logs.y[0].copy_(env.y)
                 logs.state[0].copy_(env.state)
@@ -808,15 +927,25 @@ class Population:
                     la[0, 0].numel(), lp[0, 0].numel(), ly[0, 0].numel(), lr[0, 0].numel()))
             _lib.check(lib.pdec_population_copy_actors(self._h, P(self._which)))
             _lib.check(lib.pdec_population_episode_close(self._h, 1, P(self._book), *close))
+            if self.is_fluid and detect:
+                # on the environment's stream, behind the close launch (which wrote env.y) and before the next initialiser
+                s_env.wait_stream(s_upd)
+                _lib.check(lib.pdec_fluid_error_detection(env.handle, P(env.y), P(self._err[e])))
+        if self.is_fluid:
+            s_upd.wait_stream(s_env)
         with _on_stream(s_upd):
-            pack = torch.cat([self.rows.view(-1), self._book.view(-1), self._elog[:L].reshape(-1)])
+            parts = [self.rows.view(-1), self._book.view(-1), self._elog[:L].reshape(-1)]
+            if self.is_fluid:
+                parts.append(self._err[:L].reshape(-1).to(torch.int64))
+            pack = torch.cat(parts)
             t1 = time.perf_counter()
             host = pack.cpu().numpy()                                          # the one read-back of the block
         t2 = time.perf_counter()
         s_env.wait_stream(s_upd)
         rows_out = host[:M * ROW].reshape(M, ROW).copy()
         book_out = host[M * ROW:M * (ROW + BOOK)].reshape(M, BOOK)
-        elog = host[M * (ROW + BOOK):].reshape(L, M, ELOG)
+        elog = host[M * (ROW + BOOK):M * (ROW + BOOK) + L * M * ELOG].reshape(L, M, ELOG)
+        err = host[M * (ROW + BOOK) + L * M * ELOG:].reshape(L, M) if self.is_fluid else None
         # ---- settle every member for the whole block: the schedule of each episode at its logged number of steps, with the
         # boundary movements between them, must end at the device's counters
         pol0, tr0 = self.agents[0].policy, self.agents[0].trajectory
@@ -852,6 +981,9 @@ class Population:
                 r = float(rewards[e, m])
                 if elog[e, m, EL_STEPS] == T and hk.ep >= hk.min_best_episode:
                     hk.rewards_compare.append(r)
+                # PDEhook.end_episode: an episode that ended early and is errored, noted before ep advances
+                if err is not None and elog[e, m, EL_STEPS] < T and err[e, m] and self._own_error_detection(hk):
+                    hk.errored_episodes.append(hk.ep)
                 hk.rewards.append(r)
                 hk.ep += 1
             if hk.ep != int(bk[BK_EP]):
@@ -859,12 +991,15 @@ class Population:
             hk.bestreward = float(bk[BK_BESTREWARD:BK_BESTREWARD + 1].view(np.float64)[0])
             hk.bestepisode = int(bk[BK_BESTEPISODE])
             stops[m].cur = int(bk[BK_STOP_CUR])
-            hk._init_off = int(bk[BK_INIT_OFF])
+            if not self.is_fluid:
+                hk._init_off = int(bk[BK_INIT_OFF])
             best_e = np.flatnonzero(elog[:, m, EL_NEW_BEST])
             if best_e.size and hk.collect_bestDF:
                 changed.append((m, int(elog[best_e[-1], m, EL_STEPS])))
             if not rows_out[m, ACTIVE]:
                 active[m] = False
+        if rngs is not None:
+            restore_block_rngs(rngs, rng_states, ran.sum(axis=0))
         if changed:                                             # the best episodes' rows, through the hook's own row path
             with _on_stream(s_upd):
                 ii = torch.as_tensor([m for m, _ in changed], device=env.device)

@@ -209,6 +209,18 @@ class FluidSetup:
         y_y = (torch.roll(w, 1, dims=-1) - w).abs()
         return bool(max(float(y_x.max()), float(y_y.max())) > 10.0)
 
+    def error_detection_device(self, env, y=None):
+        """error_detection per trajectory on the device (pdec_fluid_error_detection: the library's own inverse transform, one
+        reduction kernel): a bool tensor [B] for `y` (default env.y) in the environment's layout, enqueued on the environment's
+        stream without a read-back.  Uses the work arrays of `env`'s sensing, so not beside a step of `env` on another stream."""
+        import torch
+        from ..env import _on_stream
+        y = env.y if y is None else y
+        with _on_stream(env.stream):
+            out = torch.empty(env.B, dtype=torch.int32, device=env.device)
+            _lib.check(env.lib.pdec_fluid_error_detection(env.handle, _lib.ptr(y), _lib.ptr(out)))
+            return out != 0
+
     def make_hook(self, **kw):
         """the training hook of the fluid script (FluidSetup.jl:373-377): PDEhook with this setup's error_detection"""
         from ..hook import PDEhook

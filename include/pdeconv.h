@@ -179,6 +179,22 @@ int pdec_kseg2d_env_create(pdec_handle* h, const pdec_env_cfg* cfg, int ny, int 
  * = fft2 of the sum over nv vortices (9 periodic images each).  vortices: HOST [B][nv][4] = (x0, y0, a0, U_max), the
  * random draws of ic(3)/ic(4) made by the caller (scripts/Fluid/setup/FluidSetup.jl:386-394 generate_random_init). */
 int pdec_fluid_ic(pdec_handle h, const double* vortices, int nv, void* y_out);
+/* The same with the table already in DEVICE memory (doubles, [B][nv][4]): the launches of pdec_fluid_ic on the
+ * environment's stream, no host copy and no synchronisation, so it can stand between two episodes that are enqueued in
+ * one go.  An fp32 environment rounds the table once on the device.  y_out is bit for bit what pdec_fluid_ic writes for
+ * the same table.  The table must stay valid until the stream has passed the call. */
+int pdec_fluid_ic_dev(pdec_handle h, const double* vortices_dev, int nv, void* y_out);
+
+/* error_detection of the fluid script (scripts/Fluid/setup/FluidSetup.jl:263-273) per trajectory, on the device:
+ * w = real(ifft2(y[b])) through the library's own inverse passes (the sensing's), then errored_out[b] (device, int32 [B])
+ * = 1 when the maximum over all cells of |w[i][j] - w[i-1][j]| and |w[i][j] - w[i][j-1]| (periodic along both axes)
+ * exceeds 10, else 0.  The maximum propagates NaN, as the host function's does: errored_out[b] = 1 exactly when some
+ * difference is above 10 (+inf included) and no difference is NaN.  A spectrum with a non-finite entry therefore yields 0
+ * (its w is NaN wherever the entry reaches, and NaN > 10 is false).
+ * Runs on the environment's stream and uses the environment's work arrays (the ones featurize and the step's sensing
+ * use), so it must not overlap a step, featurize, reward or initialiser call of the same environment on another stream;
+ * y itself is only read.  An environment that steps its batch in parts serves the whole batch here from its own arrays. */
+int pdec_fluid_error_detection(pdec_handle h, const void* y, int32_t* errored_out);
 
 /* prepare_action(; env): p[B][N] from action[B][A]      (KSSetup.jl:231-245) */
 int pdec_actuate(pdec_handle h, const void* action, void* p_out);

@@ -1,0 +1,48 @@
+// Stand-alone host check of the two device entry points of csrc/fluid.hip (pdec_fluid_ic_dev, pdec_fluid_error_detection) under
+// AddressSanitizer / UBSan, on a machine without a GPU.  No environment can be made there, so what runs is the entry points'
+// handle look-up with every combination of arguments a confused caller might pass: each call must return an error code, set
+// pdec_last_error and write none of its outputs.  The argument checks behind a valid handle and the launches themselves need
+// a GPU and are the GPU tests' (tests/test_gpu_fluid_dev_entries.py).
+//
+//   cd distributedconvrl-pde-control_amd/csrc && make            # the other objects, as usual
+//   hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -Xarch_host -fsanitize=address,undefined \
+//         -Xarch_host -fno-sanitize-recover=all -c fluid.hip -o /tmp/fluid_san.o
+//   clang++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I../../include \
+//         -c ../../tools/fluid_entries_sanitize.cpp -o /tmp/san_main.o
+//   hipcc -fsanitize=address,undefined --offload-arch=gfx950 /tmp/san_main.o /tmp/fluid_san.o $(ls *.o | grep -v '^fluid.o$') \
+//         -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib -o /tmp/fluid_entries_sanitize && /tmp/fluid_entries_sanitize
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+#include "pdeconv.h"
+
+static int failures = 0;
+static void refused(const char* what, int rc) {
+  const char* msg = pdec_last_error();
+  if (rc == 0 || !msg || !*msg) {
+    std::printf("NOT refused: %s (rc %d)\n", what, rc);
+    ++failures;
+  } else {
+    std::printf("refused (%d): %s -- %s\n", rc, what, msg);
+  }
+}
+
+int main() {
+  double table[4] = {0.5, 0.5, 0.05, 1.0};
+  double y[8] = {0};
+  int32_t flags[2] = {0, 0};
+  const pdec_handle none = 0, stale = 0x7fffffffu;
+  refused("ic_dev, handle 0", pdec_fluid_ic_dev(none, table, 1, y));
+  refused("ic_dev, stale handle", pdec_fluid_ic_dev(stale, table, 1, y));
+  refused("ic_dev, null table", pdec_fluid_ic_dev(none, nullptr, 1, y));
+  refused("ic_dev, nv = 0", pdec_fluid_ic_dev(none, table, 0, y));
+  refused("ic_dev, nv = 1025", pdec_fluid_ic_dev(none, table, 1025, y));
+  refused("error_detection, handle 0", pdec_fluid_error_detection(none, y, flags));
+  refused("error_detection, stale handle", pdec_fluid_error_detection(stale, y, flags));
+  refused("error_detection, null y", pdec_fluid_error_detection(none, nullptr, flags));
+  refused("error_detection, null flags", pdec_fluid_error_detection(none, y, nullptr));
+  if (flags[0] || flags[1] || y[0] != 0.0) { std::printf("a refused call wrote its output\n"); ++failures; }
+  std::printf(failures ? "FAILED\n" : "OK\n");
+  return failures ? 1 : 0;
+}

@@ -1,16 +1,17 @@
 """Throughput of a Population (population.py) against the same members run one after another.
 
-For KS22 and KS200 at each M: env-steps/s of the population (host clock around whole episodes, ending in a synchronise), the
+For KS22, KS200 and the fluid (fluid8: Fluid_8 on the reference's 128 x 128 grid, --te for shorter episodes) at each M: env-steps/s of the population (host clock around whole episodes, ending in a synchronise), the
 host time per episode split into its phases (Population.timing: issue = initialisers and every enqueue up to the read-back,
 readback = the wait for the device, settle = the members' host bookkeeping and the boundary launches), and at M <= 8 the same
-members as M solo run() calls back to back.
+members as M solo run() calls back to back (the fluid: at every M).
 With --episodes-per-sync 1,8 every mode gets its own population of the same members; after one untimed round the modes alternate
 inside each of --rounds rounds (a region = one pop.run of --episodes episodes), and a row per mode reports the median (min - max)
 of env-steps/s over the rounds and the host phases per block (a block = one read-back; at 1 every episode is a block).
 Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this script.
 
     python tools/population_probe.py [--setups ks22,ks200] [--members 1,8,32,128,256,320] [--episodes 3] [--out probe.json]
-                                     [--episodes-per-sync 1,8] [--rounds 5]"""
+                                     [--episodes-per-sync 1,8] [--rounds 5]
+    python tools/population_probe.py --setups fluid8 --members 1,4,16 --episodes-per-sync 1,4 --episodes 3 --rounds 5 [--te 2.0]"""
 import argparse
 import importlib
 import json
@@ -25,16 +26,25 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pkg = importlib.import_module("distributedconvrl-pde-control_amd")
 
 
+def make_setup(name, te=None):
+    if name == "fluid8":
+        return pkg.FluidSetup.Fluid_8(**({} if te is None else dict(te=te)))
+    return getattr(pkg.KSSetup, {"ks22": "KS22", "ks200": "KS200"}[name])()
+
+
 def members(setup, seeds, s_upd):
     ags = [pkg.create_agent(setup=setup, B=1, rng=np.random.default_rng(s), noise_seed=s, stream=s_upd) for s in seeds]
-    hks = [pkg.PDEhook(min_best_episode=1, use_random_init=True, init_seed=s) for s in seeds]
+    if getattr(setup, "is_fluid", False):       # the fluid script's hook: its error_detection, every member's own generator
+        hks = [setup.make_hook(min_best_episode=1, use_random_init=True, init_seed=s, init_rng=np.random.default_rng(s)) for s in seeds]
+    else:
+        hks = [pkg.PDEhook(min_best_episode=1, use_random_init=True, init_seed=s) for s in seeds]
     for a in ags:
         a.policy.act_noise = setup.act_noise
     return ags, hks
 
 
-def probe(name, M, episodes, modes=(1,), rounds=1):
-    setup = getattr(pkg.KSSetup, {"ks22": "KS22", "ks200": "KS200"}[name])()
+def probe(name, M, episodes, modes=(1,), rounds=1, te=None):
+    setup = make_setup(name, te)
     s_env, s_upd = pkg.make_streams((-1, 0))
     pops, walls = {}, {E: [] for E in modes}
     for E in modes:
@@ -66,7 +76,7 @@ def probe(name, M, episodes, modes=(1,), rounds=1):
                    issue_ms=1e3 * tm["issue_s"] / blocks, readback_wait_ms=1e3 * tm["readback_s"] / blocks,
                    settle_ms=1e3 * tm["settle_s"] / blocks)
         rows.append(row)
-    if M <= 8:
+    if M <= 8 or name == "fluid8":
         envs = [pkg.PDEenv(setup, B=1, dtype=torch.float64, stream=s_env) for _ in range(M)]
         sa, sh = members(setup, list(range(M)), s_upd)
         for a, h, e in zip(sa, sh, envs):
@@ -92,12 +102,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--episodes-per-sync", default="1", help="comma list of modes, alternated inside every round")
     ap.add_argument("--rounds", type=int, default=1, help="timed rounds behind the one untimed round")
+    ap.add_argument("--te", type=float, default=None, help="fluid8: episode length in time units (default: the script's 6.0)")
     a = ap.parse_args()
     modes = tuple(int(x) for x in a.episodes_per_sync.split(","))
     rows = []
     for name in a.setups.split(","):
         for M in (int(x) for x in a.members.split(",")):
-            for r in probe(name, M, a.episodes, modes, a.rounds):
+            for r in probe(name, M, a.episodes, modes, a.rounds, a.te):
                 print(json.dumps(r), flush=True)
                 rows.append(r)
     if a.out:
