@@ -21,7 +21,9 @@ class KellerSegel2DSetup:
                  nna_scale=2.0, nna_scale_critic=17.0, drop_middle_layer=True, gamma=0.99, rho=0.995,
                  batch_size=3, start_steps=-1, update_after=1, update_freq=1, update_loops=20,
                  learning_rate=0.0005, learning_rate_critic=0.001, act_limit=1.0, act_noise=1.2,
-                 trajectory_length=100_000, memory_size=0):
+                 trajectory_length=100_000, memory_size=0, actuators_to_sensors=None):
+        """actuators_to_sensors (1-based sensor numbers, row-major over the Sy x Sx sensor grid): an arbitrary actuator list in
+        place of the `border` rule; their boxes must not overlap (pdec_kseg2d_env_create refuses that)"""
         self.nx, self.ny = int(nx), int(ny)
         self.Lx = 0.1 * self.nx if Lx is None else float(Lx)          # dx = 0.1 as in the 1-D script (:39)
         self.dx = self.Lx / self.nx
@@ -34,6 +36,9 @@ class KellerSegel2DSetup:
         by = min(bx, (self.Sy - 1) // 2) if border_y is None else int(border_y)
         ix, iy = np.arange(bx, self.Sx - bx), np.arange(by, self.Sy - by)
         self.actuators_to_sensors = (iy[:, None] * self.Sx + ix[None, :]).reshape(-1) + 1     # 1-based, like the reference
+        if actuators_to_sensors is not None:
+            from .ks import check_actuators_to_sensors
+            self.actuators_to_sensors = check_actuators_to_sensors(actuators_to_sensors, self.Sx * self.Sy, "KellerSegel2DSetup")
         self.te, self.t0, self.dt = te, t0, dt
         self.oversampling = int(substeps)
         self.max_value, self.check_max_value, self.agent_power = max_value, check_max_value, agent_power

@@ -21,7 +21,7 @@ import numpy as np
 class KSeg2DConfig:
     def __init__(self, nx=100, ny=5, Lx=10.0, sensor_x=None, sensor_y=None, border_x=2, border_y=None,
                  half_window=2, dt=0.006, te=8.0, agent_power=10.0, window_size=3, temporal_steps=2,
-                 action_punish=0.0, delta_action_punish=0.0, max_value=20.0, substeps=32):
+                 action_punish=0.0, delta_action_punish=0.0, max_value=20.0, substeps=32, a2s=None):
         self.nx, self.ny, self.Lx = int(nx), int(ny), float(Lx)
         self.dx = self.Lx / self.nx                       # square cells: dy = dx
         self.hw = int(half_window)
@@ -35,6 +35,9 @@ class KSeg2DConfig:
         iy = np.arange(self.border_y, self.Sy - self.border_y)
         # sensor s = iy * Sx + ix (row-major over the sensor grid); 0-based actuator -> sensor map
         self.a2s = (iy[:, None] * self.Sx + ix[None, :]).reshape(-1)
+        if a2s is not None:                               # an arbitrary actuator list, 1-based sensor numbers like the reference's
+            self.a2s = np.asarray(a2s, dtype=np.int64).reshape(-1) - 1
+            assert len(self.a2s) and self.a2s.min() >= 0 and self.a2s.max() < self.Sx * self.Sy
         self.dt, self.te, self.agent_power = dt, te, agent_power
         self.window_size, self.temporal_steps = window_size, temporal_steps
         self.action_punish, self.delta_action_punish = action_punish, delta_action_punish
