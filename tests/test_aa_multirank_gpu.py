@@ -296,7 +296,7 @@ def test_bench_c4_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["PDEC_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C4", "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--batch", "8", "--nx", "64", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--batch", "8", "--nx", "64", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 2 and d["n_ranks_observed"] == 2 and d["config"]["global_batch"] == 16
@@ -310,7 +310,7 @@ def test_bench_c5_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["PDEC_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C5", "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "2", "--nx", "128", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--batch", "2", "--nx", "128", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 2 and d["n_ranks_observed"] == 2 and d["config"]["global_batch"] == 4 and d["dtype"] == "f64"
@@ -342,13 +342,13 @@ def test_self_launcher_kills_its_ranks_at_the_deadline():
 
 
 def test_bench_8gpu_line_carries_config_c3_as_a_variant():
-    """`bench.py --gpus 8` appends BASELINE.json configs[2] (KS N = 1024, 512 trajectories per GPU, gradient all-reduce) as
+    """`bench.py --gpus 8 --full` appends BASELINE.json configs[2] (KS N = 1024, 512 trajectories per GPU, gradient all-reduce) as
     variants.C3, run on the same ranks with the reducer the headline verified.  Here the same code path with two ranks on the one
     GPU (PDEC_BENCH_C3_VARIANT=1 switches it on below 8 ranks), small batch: the line keeps its headline and gains the variant."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(PDEC_BENCH_BACKEND="gloo", PDEC_BENCH_C3_VARIANT="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "4", "--batch", "32",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 64 and "config C2" not in d["config"]["workload"]   # custom batch

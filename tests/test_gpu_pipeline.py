@@ -469,17 +469,25 @@ def test_a_request_for_the_deleted_bf16_split_passes_is_an_error(pkg, monkeypatc
 def test_bench_times_exactly_steps_and_dumps_the_last_step(tmp_path):
     """`bench.py --steps K --dump-outputs DIR`: exactly K timed steps, in one block, ms_per_step = that block / K; the arrays
     of the last timed step land in DIR as float32 / float64 .npy files, and a second run with the same arguments computes
-    the same arrays"""
+    the same arrays.  The first run is a plain one: its line carries the headline and nothing that takes launches or CPU
+    runs of its own; the second adds `--full`, which brings those figures and leaves the timed path and its arrays alone"""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     dumps = []
-    for run in ("a", "b"):
+    extras = {"roofline", "kernels_ms_per_step", "kernels_ms_per_step_in_pipeline", "splits_env_steps_per_s", "cpu_baseline",
+              "cpu_baseline_c1"}
+    for run, more in (("a", []), ("b", ["--full", "--cpu-seconds", "0.5"])):
         out = tmp_path / run
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "7", "--warmup", "3", "--batch", "64",
-                            "--no-cpu-baseline", "--no-variants", "--dump-outputs", str(out)], env=env, capture_output=True,
-                           text=True, timeout=600)
+                            "--dump-outputs", str(out)] + more, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        if more:
+            assert extras <= set(d) and d["roofline"]["kernel"] and d["cpu_baseline"]["value"] > 0, sorted(d)
+        else:
+            assert not (extras | {"variants"}) & set(d), sorted(d)
+        assert d["metric"].startswith("env-steps/sec") and d["unit"] == "env-steps/s" and d["higher_is_better"] and d["dtype"] == "f32"
+        assert d["value"] == pytest.approx(64 / (d["ms_per_step"] * 1e-3), rel=1e-9)      # env-steps of one step / its time
         assert d["steps"] == 7 and d["repeats"] == 1 and len(d["repeat_ms_per_step"]) == 1
         assert abs(d["ms_per_step"] - d["repeat_ms_per_step"][0]) < 1e-5 and d["checks"]["finite"]
         names = set(d["dump_outputs"]["arrays"])

@@ -9,7 +9,7 @@ def mk(**over):
     ns = types.SimpleNamespace(gpus=1, steps=None, warmup=None, batch=None, nx=None, no_cpu_baseline=True, config="C2", split_update=False,
         no_variants=True, deadline_s=1500.0, integrator="cnab2", no_overlap=False, overlap="auto", issue="auto", no_graph=False, replay=False,
         replay_steps=64, lag=2, dp_sync="policy", collective="auto", two_layer=False, episode_steps=51, cpu_seconds=12.0, repeats=0,
-        launch_check=False, quick=True)
+        launch_check=False, quick=True, full=True)
     for k, v in over.items(): setattr(ns, k, v)
     bench.fill_defaults(ns)
     return ns
