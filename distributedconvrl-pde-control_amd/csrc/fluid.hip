@@ -1082,6 +1082,12 @@ struct FluidEnv : Env {
   ~FluidEnv() override {
     for (int i = 0; i < MAXPART; ++i) half[i].reset();
   }
+  int actuate(const void* action, void* p_out) override;
+  int featurize(const void* y, const void* state_prev, void* state_out, const void* action = nullptr) override;
+  int reward(const void* y, const void* action, const void* action_prev, void* r_out) override;
+  int pde_step(const void* y_in, const void* p, void* y_out, int32_t* done) override;
+  int rhs_eval(const void* y, const void* p, void* out) override;
+  int env_step(const StepArgs& a) override;
 };
 
 // does the persistent x-pass (fluid_k2p_kernel) serve this environment?  Decided once: K1 writes W in the layout K2 reads.
@@ -1399,7 +1405,6 @@ static int fluid_feat_launch(FluidEnv& E, const void* action, const void* action
   return PDEC_OK;
 }
 
-static FluidEnv& as_fluid(Env& E) { return static_cast<FluidEnv&>(E); }
 static bool is_f32(const FluidEnv& E) { return E.cfg.dtype == PDEC_F32; }
 
 template <class T>
@@ -1420,13 +1425,12 @@ static int fluid_actuate_t(FluidEnv& E, const void* action, void* p_out) {
   return PDEC_OK;
 }
 
-int fluid_actuate(Env& E0, const void* action, void* p_out) {
-  FluidEnv& E = as_fluid(E0);
-  return is_f32(E) ? fluid_actuate_t<float>(E, action, p_out) : fluid_actuate_t<double>(E, action, p_out);
+int FluidEnv::actuate(const void* action, void* p_out) {
+  return is_f32(*this) ? fluid_actuate_t<float>(*this, action, p_out) : fluid_actuate_t<double>(*this, action, p_out);
 }
 
-int fluid_featurize(Env& E0, const void* y, const void* state_prev, void* state_out, const void* action) {
-  FluidEnv& E = as_fluid(E0);
+int FluidEnv::featurize(const void* y, const void* state_prev, void* state_out, const void* action) {
+  FluidEnv& E = *this;
   int rc = is_f32(E) ? fluid_dots<float>(E, y) : fluid_dots<double>(E, y);
   if (rc) return rc;
   // (action: the memory rows only)
@@ -1434,16 +1438,16 @@ int fluid_featurize(Env& E0, const void* y, const void* state_prev, void* state_
   return fluid_feat_launch<double>(E, action, nullptr, state_prev, state_out, nullptr, nullptr);
 }
 
-int fluid_reward(Env& E0, const void* y, const void* action, const void* action_prev, void* r_out) {
-  FluidEnv& E = as_fluid(E0);
+int FluidEnv::reward(const void* y, const void* action, const void* action_prev, void* r_out) {
+  FluidEnv& E = *this;
   int rc = is_f32(E) ? fluid_dots<float>(E, y) : fluid_dots<double>(E, y);
   if (rc) return rc;
   if (is_f32(E)) return fluid_feat_launch<float>(E, action, action_prev, nullptr, nullptr, r_out, nullptr);
   return fluid_feat_launch<double>(E, action, action_prev, nullptr, nullptr, r_out, nullptr);
 }
 
-int fluid_rhs_eval(Env& E0, const void* y, const void* p, void* out) {
-  FluidEnv& E = as_fluid(E0);
+int FluidEnv::rhs_eval(const void* y, const void* p, void* out) {
+  FluidEnv& E = *this;
   if (is_f32(E)) return fluid_rhs_launch<float>(E, y, p, nullptr, nullptr, out, 0, 0.0, 0.0);
   return fluid_rhs_launch<double>(E, y, p, nullptr, nullptr, out, 0, 0.0, 0.0);
 }
@@ -1469,9 +1473,8 @@ static int fluid_pde_step_t(FluidEnv& E, const void* y_in, const void* p, void* 
   return PDEC_OK;
 }
 
-int fluid_pde_step(Env& E0, const void* y_in, const void* p, void* y_out, int32_t* done) {
-  FluidEnv& E = as_fluid(E0);
-  return is_f32(E) ? fluid_pde_step_t<float>(E, y_in, p, y_out, done) : fluid_pde_step_t<double>(E, y_in, p, y_out, done);
+int FluidEnv::pde_step(const void* y_in, const void* p, void* y_out, int32_t* done) {
+  return is_f32(*this) ? fluid_pde_step_t<float>(*this, y_in, p, y_out, done) : fluid_pde_step_t<double>(*this, y_in, p, y_out, done);
 }
 
 template <class T>
@@ -1489,9 +1492,8 @@ static int fluid_env_step_t(FluidEnv& E, const void* y_in, const void* action, c
   return fluid_feat_launch<T>(E, action, action_prev, state_prev, state_out, reward_out, done);   // :220-222
 }
 
-int fluid_env_step(Env& E0, const void* y_in, const void* action, const void* action_prev, const void* state_prev,
-                   void* y_out, void* p_out, void* state_out, void* reward_out, int32_t* done) {
-  FluidEnv& E = as_fluid(E0);
+int FluidEnv::env_step(const StepArgs& a) {
+  FluidEnv& E = *this;
   if (E.nparts >= 2 && !E.prof) {
     // the parts of the batch side by side: every argument is batch-major, so a part is a pointer offset.  (Per-kernel
     // timing passes, pdec_prof_enable, take the whole batch on one stream.)
@@ -1514,9 +1516,10 @@ int fluid_env_step(Env& E0, const void* y_in, const void* action, const void* ac
       FluidEnv& H = *E.half[hh];
       H.stream = hh == 0 ? E.stream : E.ps.st[hh];
       H.term_out = E.term_out ? (char*)E.term_out + (size_t)b0 * A * ts : nullptr;
-      const int rc = fluid_env_step(H, off(y_in, b0 * nn * 2 * ts), off(action, b0 * A * na * ts), off(action_prev, b0 * A * na * ts),
-                                    off(state_prev, b0 * A * ns * ts), offm(y_out, b0 * nn * 2 * ts), offm(p_out, b0 * nn * 2 * ts),
-                                    offm(state_out, b0 * A * ns * ts), offm(reward_out, b0 * A * ts), done ? done + b0 : nullptr);
+      const int rc = H.env_step(StepArgs{off(a.y_in, b0 * nn * 2 * ts), nullptr, off(a.action, b0 * A * na * ts),
+                                         off(a.action_prev, b0 * A * na * ts), off(a.state_prev, b0 * A * ns * ts),
+                                         offm(a.y_out, b0 * nn * 2 * ts), offm(a.p_out, b0 * nn * 2 * ts),
+                                         offm(a.state_out, b0 * A * ns * ts), offm(a.reward_out, b0 * A * ts), a.done ? a.done + b0 : nullptr});
       if (rc) { rc_part = rc; break; }              // (the part streams are joined below on this path too)
       b0 += H.cfg.B;
     }
@@ -1525,8 +1528,8 @@ int fluid_env_step(Env& E0, const void* y_in, const void* action, const void* ac
     PDEC_HIP(ej);
     return PDEC_OK;
   }
-  if (is_f32(E)) return fluid_env_step_t<float>(E, y_in, action, action_prev, state_prev, y_out, p_out, state_out, reward_out, done);
-  return fluid_env_step_t<double>(E, y_in, action, action_prev, state_prev, y_out, p_out, state_out, reward_out, done);
+  if (is_f32(E)) return fluid_env_step_t<float>(E, a.y_in, a.action, a.action_prev, a.state_prev, a.y_out, a.p_out, a.state_out, a.reward_out, a.done);
+  return fluid_env_step_t<double>(E, a.y_in, a.action, a.action_prev, a.state_prev, a.y_out, a.p_out, a.state_out, a.reward_out, a.done);
 }
 
 }  // namespace pdec

@@ -71,7 +71,7 @@ __device__ __forceinline__ C2<T> c2(V2<T> v) { return mk<T>(v.x, v.y); }
 
 // Right-hand side of TWO adjacent cells at once (x = cell i, y = cell i+1 of a row), one species per vector: every
 // operation is element-wise over the pair, so for fp32 the whole expression is packed VOP3P math (v_pk_add/mul/fma_f32,
-// two cells per instruction).  Same discretisation as the 1-D kernel kseg_rhs (env.hip) with the constants folded:
+// two cells per instruction).  Same discretisation as the 1-D kernel kseg_rhs (kseg.hip) with the constants folded:
 // Lap = ((w + e) + (s + n) - 4c)/dx^2, grad u . grad v = ((e-w)_u (e-w)_v + (n-s)_u (n-s)_v) / (4 dx^2),
 // u' = Lap u + u (1 - 5.6 Lap v - u) - 5.6 grad u . grad v,  v' = Lap v - v + u + p
 template <class T>
@@ -333,6 +333,12 @@ struct Kseg2dEnv : Env {
   PartStreams ps;                                    // common.hpp: the caller's or library-made streams, fork / join events
   int part_streams() const override;
   int set_part_streams(const hipStream_t* s, int n) override;
+  int actuate(const void* action, void* p_out) override;
+  int featurize(const void* y, const void* state_prev, void* state_out, const void* action = nullptr) override;
+  int reward(const void* y, const void* action, const void* action_prev, void* r_out) override;
+  int pde_step(const void* y_in, const void* p, void* y_out, int32_t* done) override;
+  int rhs_eval(const void* y, const void* p, void* out) override;
+  int env_step(const StepArgs& a) override;
 };
 
 static Kseg2dEnv& as_k2(Env& E) { return static_cast<Kseg2dEnv&>(E); }
@@ -530,59 +536,47 @@ static int k2_probe(Kseg2dEnv& E, int nb, int reps, int iters, double* us) {
 }
 #endif
 
-#define K2_DISPATCH(fn, ...) (E.cfg.dtype == PDEC_F64 ? fn<double>(E, __VA_ARGS__) : fn<float>(E, __VA_ARGS__))
+#define K2_DISPATCH(fn, ...) (cfg.dtype == PDEC_F64 ? fn<double>(*this, __VA_ARGS__) : fn<float>(*this, __VA_ARGS__))
 
-int kseg2d_actuate(Env& E0, const void* action, void* p_out) {
-  Kseg2dEnv& E = as_k2(E0);
-  return K2_DISPATCH(k2_actuate, action, p_out);
-}
-
-int kseg2d_featurize(Env& E0, const void* y, const void* state_prev, void* state_out) {
-  Kseg2dEnv& E = as_k2(E0);
+int Kseg2dEnv::actuate(const void* action, void* p_out) { return K2_DISPATCH(k2_actuate, action, p_out); }
+int Kseg2dEnv::featurize(const void* y, const void* state_prev, void* state_out, const void*) {      // (no action memory on the 2-D grid)
   return K2_DISPATCH(k2_sense, y, nullptr, nullptr, state_prev, state_out, nullptr, nullptr);
 }
-
-int kseg2d_reward(Env& E0, const void* y, const void* action, const void* action_prev, void* r_out) {
-  Kseg2dEnv& E = as_k2(E0);
+int Kseg2dEnv::reward(const void* y, const void* action, const void* action_prev, void* r_out) {
   return K2_DISPATCH(k2_sense, y, action, action_prev, nullptr, nullptr, r_out, nullptr);
 }
-
-int kseg2d_rhs_eval(Env& E0, const void* y, const void* p, void* out) {
-  Kseg2dEnv& E = as_k2(E0);
-  return E.cfg.dtype == PDEC_F64 ? k2_launch_rk4<double, 1, 1>(E, y, p, out, nullptr, 0)
-                                 : k2_launch_rk4<float, 1, 1>(E, y, p, out, nullptr, 0);
+int Kseg2dEnv::rhs_eval(const void* y, const void* p, void* out) {
+  return cfg.dtype == PDEC_F64 ? k2_launch_rk4<double, 1, 1>(*this, y, p, out, nullptr, 0)
+                               : k2_launch_rk4<float, 1, 1>(*this, y, p, out, nullptr, 0);
 }
-
-int kseg2d_pde_step(Env& E0, const void* y_in, const void* p, void* y_out, int32_t* done) {
-  Kseg2dEnv& E = as_k2(E0);
+int Kseg2dEnv::pde_step(const void* y_in, const void* p, void* y_out, int32_t* done) {
   PDEC_REQUIRE(y_in != y_out, "kseg2d: y_out must not alias y_in");
   return K2_DISPATCH(k2_integrate, y_in, p, nullptr, y_out, done);
 }
 
-int kseg2d_env_step(Env& E0, const void* y_in, const void* action, const void* action_prev, const void* state_prev,
-                    void* y_out, void* p_out, void* state_out, void* reward_out, int32_t* done) {
-  Kseg2dEnv& E = as_k2(E0);
+int Kseg2dEnv::env_step(const StepArgs& a) {
+  Kseg2dEnv& E = *this;
   const size_t ts = dtype_size(E.cfg.dtype);
-  void* ph = p_out;
+  void* ph = a.p_out;
   if (!ph) {
     const size_t need = (size_t)E.cfg.B * E.ny * E.nx * ts;
     if (E.pbuf.bytes < need) PDEC_HIP(E.pbuf.alloc(need));
     ph = E.pbuf.p;
   }
-  int32_t* dn = done;
+  int32_t* dn = a.done;
   if (!dn && E.term_out) {
     if (E.done_tmp.bytes < sizeof(int32_t) * E.cfg.B) PDEC_HIP(E.done_tmp.alloc(sizeof(int32_t) * E.cfg.B));
     dn = E.done_tmp.as<int32_t>();
   }
   int rc;
-  if ((rc = kseg2d_actuate(E0, action, ph))) return rc;                                 // src/PDEenv.jl:199
-  PDEC_REQUIRE(y_in != y_out, "kseg2d: y_out must not alias y_in");
+  if ((rc = actuate(a.action, ph))) return rc;                                 // src/PDEenv.jl:199
+  PDEC_REQUIRE(a.y_in != a.y_out, "kseg2d: y_out must not alias y_in");
   // fp64 (HBM-bound): the forcing is synthesised in the kernel from the action table; fp32: reading the p field
   // measured faster than the two-level gather (PDEC_KSEG2D_GATHER=0/1 overrides)
   static const char* gv = getenv("PDEC_KSEG2D_GATHER");
   const bool gather = gv ? gv[0] == '1' : E.cfg.dtype == PDEC_F64;
-  if ((rc = K2_DISPATCH(k2_integrate, y_in, ph, gather ? action : nullptr, y_out, dn))) return rc;   // :216-218 (zeroes done)
-  if ((rc = K2_DISPATCH(k2_sense, y_out, action, action_prev, state_prev, state_out, reward_out, dn))) return rc;   // :220-222
+  if ((rc = K2_DISPATCH(k2_integrate, a.y_in, ph, gather ? a.action : nullptr, a.y_out, dn))) return rc;   // :216-218 (zeroes done)
+  if ((rc = K2_DISPATCH(k2_sense, a.y_out, a.action, a.action_prev, a.state_prev, a.state_out, a.reward_out, dn))) return rc;   // :220-222
   if (E.term_out && dn) {
     const int nA = E.cfg.B * E.cfg.A;
     if (E.cfg.dtype == PDEC_F64)

@@ -218,13 +218,11 @@ __global__ void randn_kernel(T* __restrict__ dst, size_t n, uint64_t seed, uint6
     if (q == 0) *ctr_next = offset + ctr_inc;
   }
   if (q * 4 >= n) return;
-  const uint64_t ctr = offset + q;
-  uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-  philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-  const double s = 1.0 / 4294967296.0;
+  uint32_t c[4];
+  noise_block(c, seed, offset + q);
   for (int h = 0; h < 2; ++h) {
-    const double u1 = ((double)c[2 * h] + 0.5) * s, u2 = ((double)c[2 * h + 1] + 0.5) * s;
-    const double rad = sqrt(-2.0 * log(u1)), ang = 6.283185307179586 * u2;
+    double rad, ang;
+    noise_polar(c, h, rad, ang);
     const size_t i = q * 4 + 2 * h;
     if (i < n) dst[i] = (T)(rad * cos(ang));
     if (i + 1 < n) dst[i + 1] = (T)(rad * sin(ang));
@@ -1157,14 +1155,7 @@ __device__ __forceinline__ T* small_act_body(const SmallActArgs& g, const T* __r
     const int c = i / no, f = i - c * no;
     T v = xin[f * cols + c];
     if (g.learning && f < g.nrows) {
-      const uint64_t ctr = offset + (uint64_t)(i >> 2);
-      uint32_t ph[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-      philox4x32(ph, (uint32_t)g.seed, (uint32_t)(g.seed >> 32));
-      const int h = (i >> 1) & 1;
-      const double sc = 1.0 / 4294967296.0;
-      const double u1 = ((double)ph[2 * h] + 0.5) * sc, u2 = ((double)ph[2 * h + 1] + 0.5) * sc;
-      const double rad = sqrt(-2.0 * log(u1)), ang = 6.283185307179586 * u2;
-      const T z = (T)((i & 1) ? rad * sin(ang) : rad * cos(ang));
+      const T z = (T)noise_normal(g.seed, offset, i);
       v += z * an;
     }
     v = v < -lim ? -lim : (v > lim ? lim : v);

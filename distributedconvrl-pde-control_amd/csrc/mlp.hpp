@@ -163,6 +163,29 @@ __device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t 
   }
 }
 
+// ---- the exploration-noise stream (seed, offset): Philox block `offset + (i >> 2)` holds the normals 4 (i >> 2) .. + 3, two
+// Box-Muller pairs (cos, sin) from its halves.  Every acting path draws through these pieces, so that the step loop, the
+// persistent rollouts and randn + act see the same numbers element for element.
+__device__ __forceinline__ void noise_block(uint32_t (&ph)[4], uint64_t seed, uint64_t ctr) {
+  ph[0] = (uint32_t)ctr; ph[1] = (uint32_t)(ctr >> 32); ph[2] = 0u; ph[3] = 0u;
+  philox4x32(ph, (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+// Box-Muller radius and angle of half h (0 / 1) of a block
+__device__ __forceinline__ void noise_polar(const uint32_t (&ph)[4], int h, double& rad, double& ang) {
+  const double sc = 1.0 / 4294967296.0;
+  const double u1 = ((double)ph[2 * h] + 0.5) * sc, u2 = ((double)ph[2 * h + 1] + 0.5) * sc;
+  rad = sqrt(-2.0 * log(u1)); ang = 6.283185307179586 * u2;
+}
+// normal number i of the stream (I: the index type of the caller, kept so that its index arithmetic stays what it was)
+template <class I>
+__device__ __forceinline__ double noise_normal(uint64_t seed, uint64_t offset, I i) {
+  uint32_t ph[4];
+  noise_block(ph, seed, offset + (uint64_t)(i >> 2));
+  double rad, ang;
+  noise_polar(ph, (int)((i >> 1) & 1), rad, ang);
+  return (i & 1) ? rad * sin(ang) : rad * cos(ang);
+}
+
 // kernel-side view of the beta powers: read `cur` (every thread that needs it), one thread of the grid writes `next`
 struct BpArgs {
   const double* cur;

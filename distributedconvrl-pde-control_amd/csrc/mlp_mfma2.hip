@@ -718,14 +718,7 @@ __global__ __launch_bounds__(256) void policy_act2_kernel(Net2 n, const float* _
   if (!valid || q != 0) return;
   if (tanh_out) o = tanhf(o);
   if (learning) {
-    const uint64_t ctr = offset + (uint64_t)(c >> 2);
-    uint32_t ph[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-    philox4x32(ph, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const int hsel = (c >> 1) & 1;
-    const double sc = 1.0 / 4294967296.0;
-    const double u1 = ((double)ph[2 * hsel] + 0.5) * sc, u2 = ((double)ph[2 * hsel + 1] + 0.5) * sc;
-    const double rad = sqrt(-2.0 * log(u1)), ang = 6.283185307179586 * u2;
-    const float z = (float)((c & 1) ? rad * sin(ang) : rad * cos(ang));
+    const float z = (float)noise_normal(seed, offset, c);
     o += z * act_noise;
   }
   out[c] = fminf(fmaxf(o, -lim), lim);

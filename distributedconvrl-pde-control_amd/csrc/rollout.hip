@@ -100,15 +100,13 @@ extern "C" int pdec_rollout(pdec_handle henv, pdec_handle hactor, int T, void* y
   const int ns = env_ns(c), cols = c.B * (c.mono ? 1 : c.A), na = A->dims[A->L];
   PDEC_REQUIRE(A->dims[0] == (c.mono ? c.S : ns) && cols * na == c.B * c.A * env_na(c),
                "pdec_rollout: actor shape %d -> %d does not match the state/action matrices", A->dims[0], na);
-  if (ks_rollout_supported(*E, *A)) {
-    // KS: the whole loop in ONE persistent launch -- the trajectories stay in registers / LDS between steps and the actor is
-    // evaluated in the kernel (csrc/env.hip: ks_rollout_kernel); reward_sum accumulates, the logs are written per step
-    return ks_rollout_persistent(*E, *A, T, y, state, action, act_noise, act_limit, learning, seed, offset, reward_sum, log_y,
-                                 log_p, log_action, log_reward, done_any, done_step);
-  }
-  if (kseg_rollout_supported(*E, *A))     // 1-D Keller-Segel: likewise one launch (csrc/env.hip: kseg_rollout_kernel)
-    return kseg_rollout_persistent(*E, *A, T, y, state, action, act_noise, act_limit, learning, seed, offset, reward_sum, log_y,
-                                   log_p, log_action, log_reward, done_any, done_step);
+  const RollSpec spec{T, learning, act_noise, act_limit, seed, offset};
+  const RollPtrs ptrs{y, state, action, reward_sum, log_y, log_p, log_action, log_reward, done_any, done_step};
+  // KS: the whole loop in ONE persistent launch -- the trajectories stay in registers / LDS between steps and the actor is
+  // evaluated in the kernel (csrc/ks_rollout.hip: ks_rollout_kernel); reward_sum accumulates, the logs are written per step
+  if (ks_rollout_supported(*E, *A)) return ks_rollout_persistent(*E, *A, spec, ptrs);
+  // 1-D Keller-Segel: likewise one launch (csrc/kseg.hip: kseg_rollout_kernel)
+  if (kseg_rollout_supported(*E, *A)) return kseg_rollout_persistent(*E, *A, spec, ptrs);
   return rollout_step_loop(henv, E, T, y, state, action, reward_sum, log_y, log_p, log_action, log_reward, done_any, done_step,
                            [&](int t, const void* s, void* a) {
                              return pdec_policy_act_rng(hactor, s, cols, act_noise, act_limit, learning, seed,
@@ -141,8 +139,8 @@ extern "C" int pdec_rollout_members(pdec_handle henv, const pdec_handle* actors,
     if (nets[m]->dims != nets[0]->dims || nets[m]->acts != nets[0]->acts || nets[m]->dtype != nets[0]->dtype)
       return PDEC_OK;      // differing shapes: not served (the caller refuses or loops over solo rollouts)
   if (rollout_members_supported(*E, nets)) {
-    int rc = rollout_members_persistent(*E, nets, per_member, T, y, state, action, act_limit, reward_sum, log_y, log_p, log_action,
-                                        log_reward, done_any, done_step);
+    int rc = rollout_members_persistent(*E, nets, per_member, T, act_limit,
+                                        RollPtrs{y, state, action, reward_sum, log_y, log_p, log_action, log_reward, done_any, done_step});
     if (rc == PDEC_OK) *served = 1;
     return rc;
   }

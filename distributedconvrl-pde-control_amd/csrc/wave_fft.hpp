@@ -9,7 +9,7 @@
 // next in-lane radix-E butterfly.  No LDS, no barriers.  The forward transform leaves mode
 //     k = qd + Q * (perm(lane) + 64 e),  perm = (l>>4) + 4((l>>2)&3) + 16(l&3)  (E = 4)   or   bitrev6(l)  (E = 2)
 // in slot (qd, e); the inverse (decimation in time) consumes that order and returns natural order, so a
-// forward -> pointwise -> inverse chain never reorders data.  Same scheme as FftWave256 in env.hip, generalised
+// forward -> pointwise -> inverse chain never reorders data.  Same scheme as FftWave256 in ks_engines.hpp, generalised
 // to the 2-D fluid's line lengths (768 / 512 / 384 / 256 / 128) and to fp64.  WaveFft<T, ...> is the transform of C2<T>;
 // WaveFftD<...> = WaveFft<double, ...>.
 #pragma once

@@ -227,7 +227,7 @@ class TrainPipeline:
         self.stop_events = (self.rpart is not None and Ev is _Event and not self.serial
                             and os.environ.get("PDEC_STOP_EVENTS", "1") != "0")
         # The PDE step beside the fused 3-layer passes.  Round 2: its register form (92 VGPRs) could not share a SIMD with two
-        # waves of the 222-VGPR critic pass, so the pipeline asked for the 64-VGPR form (csrc/env.hip, SHARE) at priority 3.
+        # waves of the 222-VGPR critic pass, so the pipeline asked for the 64-VGPR form (csrc/ks_step.hip, SHARE) at priority 3.
         # Round 3: the passes are bounded to 208 allocated VGPRs (2 x 208 + 96 = 512), the register form fits beside them, and
         # at its own priority 1 it takes less from the passes: 117.7 -> 111.4 us per control step (r03bc).  PDEC_SHARE=1 asks for
         # the 64-VGPR form again.

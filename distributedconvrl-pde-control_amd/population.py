@@ -91,7 +91,7 @@ def python_max_state(values):
 # ---- evaluation: every member's actor scored on the SAME held-out initial fields, in one launch where the library serves it
 
 def member_workgroups(M, K):
-    """The workgroups of the KS member rollout (csrc/env.hip: ks_rollout_kernel, member form) for M members of K trajectories:
+    """The workgroups of the KS member rollout (csrc/ks_rollout.hip: ks_rollout_kernel, member form) for M members of K trajectories:
     a list of (member, pair, b0, has1).  Workgroup w serves member w // ceil(K / 2), pair w % ceil(K / 2): the trajectories
     b0 = member * K + 2 * pair and, where has1, b0 + 1 -- the pairing of a solo launch on K trajectories, so the two
     trajectories that share a complex FFT always belong to one member."""

@@ -1,4 +1,4 @@
-"""The case table of test_gpu_ks_geometry.py: geometries of the Kuramoto-Sivashinsky environment (csrc/env.hip: ks_env_step_kernel,
+"""The case table of test_gpu_ks_geometry.py: geometries of the Kuramoto-Sivashinsky environment (csrc/ks_step.hip: ks_env_step_kernel,
 ks_rollout_kernel, ksfd_env_step_kernel, ksfd_wave_step_kernel, sense_kernel and their shared pieces sense_dots, actuate_cell(s),
 actuate_consecutive, reward_traj / reward_pair, featurize_traj / featurize_pair, block_max, write_terminal, and the band tables
 Wd / Cnt / sn0 / an0 / fmap / gsum of pdec_env_create) away from the three shipped layouts (KS22: 8 sensors every 24 cells, KS200:
@@ -82,7 +82,7 @@ BLOWUP_PATCH = 40.0              # trajectory 1's last three cells
 # rollouts: the actor is [ns, H, 1] relu / tanh.  H = 20 where ks_rollout_lds stays under 64 KiB with it in both dtypes
 # (perm_oddA_256 in fp64: 63.4 KB), 8 where only the narrower actor fits (A = S = 64 or 48 with window 5; 128 threads: the
 # activation planes are 4 max(dims) nthreads elements)
-RO_W = 32                        # csrc/env.hip: the widest layer of the in-kernel actor
+RO_W = 32                        # csrc/roll_actor.hpp: the widest layer of the in-kernel actor
 ROLL_H = {"narrow_256": 8, "narrower_256": 8, "dense_192": 8, "sparse_240": 8}
 ROLL_H_DEFAULT = 20
 ROLL_MUST_SERVE = ["perm_oddA_256", "narrow_256", "irregular_256", "dense_192", "sparse_240"]
@@ -161,7 +161,7 @@ def blowup_inputs(case, B=5):
 
 # ------------------------------------------------------------------ the host rules, restated
 ENGINES = {256: "FftWave256", 1024: "FftWave1024", 192: "FftFixed192", 240: "FftFixed240", 600: "FftFixed600"}
-_FFT_BUFFERS = {"FftWave256": 1, "FftWave1024": 2, "FftGeneric": 3, "FftFixed192": 3, "FftFixed240": 3, "FftFixed600": 3}
+_FFT_BUFFERS = {"FftWave256": 1, "FftWave1024": 2, "FftR4": 2, "FftGeneric": 3, "FftFixed192": 3, "FftFixed240": 3, "FftFixed600": 3}
 
 
 def nthreads(nx, integrator="cnab2"):
@@ -249,8 +249,16 @@ def geometry(G, Ga, a2s, case, prec="f64"):
         lds_bytes=lds)
 
 
+def with_engine(geo, case, prec, engine):
+    """the geometry of a spectral row under PDEC_KS_LDS_FFT=1 ("FftR4", 256 / 1024 cells) or PDEC_KS_GENERIC_FFT=1 ("FftGeneric"):
+    the work-group stays, the transform buffers (ENG::lds_complex) change"""
+    N, ts = _get(case).nx, 8 if prec == "f64" else 4
+    assert geo["engine"] in ("FftWave256", "FftWave1024") and geo["nthreads"] == N // 4
+    return dict(geo, engine=engine, lds_bytes=geo["lds_bytes"] + (_FFT_BUFFERS[engine] - _FFT_BUFFERS[geo["engine"]]) * N * 2 * ts)
+
+
 def ks_rollout_lds(geo, tsize, dims):
-    """ks_rollout_lds of csrc/env.hip for an actor of layer sizes `dims` (geo of the same dtype)"""
+    """rollout_lds (KS) of csrc/roll_actor.hpp for an actor of layer sizes `dims` (geo of the same dtype)"""
     image = (sum((d + 1) * RO_W for d in dims[:-1]) + 3) // 4 * 4
     return geo["lds_bytes"] + (2 * geo["A"] * geo["ns"] + 4 * geo["A"] + image + 4 * max(dims) * geo["nthreads"]) * tsize + 16
 

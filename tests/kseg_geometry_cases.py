@@ -1,5 +1,5 @@
-"""The case table of test_gpu_kseg_geometry.py: geometries of the 1-D Keller-Segel environment (csrc/env.hip:
-kseg_env_step_kernel, kseg_rollout_kernel, sense_dots, actuate_cell, featurize_traj, reward_traj, block_max, write_terminal and the
+"""The case table of test_gpu_kseg_geometry.py: geometries of the 1-D Keller-Segel environment (csrc/kseg.hip:
+kseg_env_step_kernel, kseg_rollout_kernel; csrc/env_sense.hpp: sense_dots, actuate_cell, featurize_traj, reward_traj, block_max, write_terminal and the
 band construction of pdec_env_create) away from the one shipped point (100 cells, 20 sensors every 5 cells, actuators on sensors
 3..18, window 3, temporal_steps 2), plus a plain-Python restatement of the host rules that decide what a geometry reaches
 (work-group size, band widths, sense_dots' grouping, the LDS bill of the persistent rollout).  Imports numpy only, so
@@ -67,7 +67,7 @@ BLOWUP_REWARD_MAX = 0.5          # max_value of the "reward" form: tame rewards 
 # rollouts (test 3d): the actor is [ns, ROLL_H, 1] relu / tanh; served: does the persistent launch take (case, dtype size)
 ROLL_H = 20
 ROLLOUT = ["wrap_nx100", "fmap_w3_nx100", "roll_nx320", "nx1024"]
-RO_W = 32                        # csrc/env.hip: the widest layer of the in-kernel actor
+RO_W = 32                        # csrc/roll_actor.hpp: the widest layer of the in-kernel actor
 
 
 # ------------------------------------------------------------------ builders
@@ -183,7 +183,7 @@ def geometry(G, Ga, a2s, case):
 
 
 def rollout_lds(geo, tsize, dims=None):
-    """kseg_lds_bytes + kseg_rollout_lds of csrc/env.hip for an actor of layer sizes `dims`"""
+    """kseg_lds_bytes of csrc/kseg.hip + rollout_lds (Keller-Segel) of csrc/roll_actor.hpp for an actor of layer sizes `dims`"""
     N, S, A, ns = geo["nthreads"] - geo["dead_lanes"], geo["S"], geo["A"], geo["ns"]
     dims = [ns, ROLL_H, 1] if dims is None else dims
     step = (2 * (N + 2) + 2 * A + 2 * S + 16 * S + 16) * tsize

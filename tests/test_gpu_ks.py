@@ -171,7 +171,7 @@ def test_host_pointer_wrapper(pkg):
 def test_rk4_fd_variant_matches_its_oracle(pkg, prec, tol, integ, nx, monkeypatch):
     """north-star variant: RK4 + periodic 5-point FD (stencils of KSSetup.jl:55-59); rhs, do_step and the fused
     (env)(action) against oracle/ks.py rhs_fd / do_step_rk4_fd (relative to max|value|).  nx = 256: the fused step runs in
-    its one-wave-per-trajectory form (four cells per lane, neighbours by lane exchange, csrc/env.hip: ksfd_wave_step_kernel);
+    its one-wave-per-trajectory form (four cells per lane, neighbours by lane exchange, csrc/ksfd.hip: ksfd_wave_step_kernel);
     it must also agree with the general one-cell-per-thread form (PDEC_KSFD_LDS=1) to round-off.  nx = 64 / 100 / 1024: the
     work-group sizes of ksfd_env_step_kernel (nt = ceil(N / 64) 64) without a dead lane, with 28 and with all 16 waves, at the
     cell size of the 240-cell row (Lx = nx 200 / 240), where the explicit step is stable."""

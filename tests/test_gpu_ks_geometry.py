@@ -1,5 +1,5 @@
-"""The Kuramoto-Sivashinsky kernels (csrc/env.hip: ks_env_step_kernel with every FFT engine, its SIMD-sharing form, ks_rollout_kernel
-in its solo and member forms, ksfd_env_step_kernel, ksfd_wave_step_kernel, sense_kernel, and the band tables pdec_env_create builds)
+"""The Kuramoto-Sivashinsky kernels (csrc/ks_step.hip: ks_env_step_kernel with every FFT engine, its SIMD-sharing form; ks_rollout.hip:
+ks_rollout_kernel in its solo and member forms; ksfd.hip: ksfd_env_step_kernel, ksfd_wave_step_kernel; env.hip: sense_kernel, and the band tables pdec_env_create builds)
 against oracle/ks.py over the geometries of ks_geometry_cases.py: both actuation branches of every engine, A != S, odd A,
 permuted and repeated actuators_to_sensors, bands narrower than sense_dots' unrolled body, cells no actuator reaches, every
 grouping of sense_dots, the global agent with A != S, the temporal stack, all three blow-up tests, punishments and the disturbance
@@ -44,6 +44,15 @@ Worst deviation / bound over all rows on an MI355X, the row with the largest rat
            action, reward      1.1e-16, 6.7e-16 / 2e-11           6.0e-8, 4.8e-7 / 2e-5
            reward_sum          1.8e-15 / 2e-11                    9.5e-7 / 2e-5
   reward partials (fp32)       8.5e-7 / 5.2e-6 perm_oddA_256
+  engine switches (PDEC_KS_LDS_FFT=1: FftR4, PDEC_KS_GENERIC_FFT=1: FftGeneric; perm_oddA_256 and subset_1024, the bounds above)
+  fused    p                   1.8e-15 / 6.4e-12 perm_oddA_256 R4   6.5e-7 / 6.8e-5  perm_oddA_256 R4
+           y                   2.8e-15 / 1.0e-11 perm_oddA_256 R4   1.2e-6 / 3.0e-5  perm_oddA_256 R4
+           state               6.9e-18 / 1.6e-16 subset_1024 R4     4.3e-9 / 2.8e-8  subset_1024 R4
+           reward              4.4e-16 / 8.2e-15 perm_oddA_256 R4   2.8e-7 / 3.4e-6  perm_oddA_256 generic
+           vs pieces: p 0 / 0, y 0 / 0 (bit for bit), state 6.9e-18 / 5.6e-9, reward 2.2e-16 / 6.0e-8
+  rollout  served by ks_rollout_kernel on perm_oddA_256 in fp32 only (the other six rows exceed 64 KiB of LDS with the larger
+           transform buffers and run as the step loop, bit for bit): first action 3.0e-8 / 2e-6, y 6.3e-7 / 2e-5,
+           p 4.8e-7 / 2e-4, action 6.0e-8, reward 2.4e-7, reward_sum 3.6e-7 / 2e-5 (R4; generic: no larger)
 No quantity exceeded its bound and no kernel or table had to change."""
 import ctypes as C
 
@@ -155,11 +164,8 @@ def test_pieces_match_the_oracle(pkg, case, prec):
 
 
 # ------------------------------------------------------------------ b. the fused step, three control steps
-@pytest.mark.parametrize("case,prec", ROWS, ids=IDS)
-def test_fused_step_matches_the_oracle_and_the_pieces(pkg, case, prec):
-    """three control steps, each teacher-forced: the oracle starts every step from the device's own previous field, so chaos
-    does not accumulate.  p, y, reward, state, done and the terminal columns; state and reward at the device's new field; and the
-    fused step against the stand-alone pieces at the same inputs"""
+def _fused_step_body(pkg, case, prec, tag=""):
+    """the body of test_fused_step_matches_the_oracle_and_the_pieces (tag: what the printed line adds to the row's name)"""
     from oracle import ks
     dt = _dt(prec)
     c = kc.CASES[case]
@@ -206,11 +212,34 @@ def test_fused_step_matches_the_oracle_and_the_pieces(pkg, case, prec):
             ok &= _err(worst, "state_vs_pieces", _jl(env.state[b]), _jl(st_pc[b]), ts)
             ok &= _err(worst, "reward_vs_pieces", _np(env.reward[b]), _np(r_pc[b]), tr)
         a_prev = act[t]
-    print(f"[ks-geometry fused {case} {prec}] (worst, bound):", worst)
+    print(f"[ks-geometry fused {case} {prec}{tag}] (worst, bound):", worst)
     assert ok, worst
     if c.temporal_steps > 1:       # the stack really shifted: the older block is the fresh block of the step before
         assert _same(env.state[:, :, c.window_size:], st_in[:, :, :c.window_size]) and not _same(env.state[:, :, :c.window_size], st_in[:, :, :c.window_size])
     env.close(), pieces.close()
+
+
+@pytest.mark.parametrize("case,prec", ROWS, ids=IDS)
+def test_fused_step_matches_the_oracle_and_the_pieces(pkg, case, prec):
+    """three control steps, each teacher-forced: the oracle starts every step from the device's own previous field, so chaos
+    does not accumulate.  p, y, reward, state, done and the terminal columns; state and reward at the device's new field; and the
+    fused step against the stand-alone pieces at the same inputs"""
+    _fused_step_body(pkg, case, prec)
+
+
+# the two engines that only a switch reaches (README, the table of switches): radix-4 through LDS at 256 / 1024 cells, and the
+# generic engine on a grid that has a compile-time one.  These two rows are the only grids on which the switches select anything.
+SWITCHES = {"PDEC_KS_LDS_FFT": "FftR4", "PDEC_KS_GENERIC_FFT": "FftGeneric"}
+SWITCH_ROWS = [(sw, n, p) for sw in SWITCHES for n in ("perm_oddA_256", "subset_1024") for p in ("f64", "f32")]
+SWITCH_IDS = [f"{sw}-{n}-{p}" for sw, n, p in SWITCH_ROWS]
+
+
+@pytest.mark.parametrize("switch,case,prec", SWITCH_ROWS, ids=SWITCH_IDS)
+def test_fused_step_under_the_engine_switches(pkg, monkeypatch, switch, case, prec):
+    """test_fused_step_matches_the_oracle_and_the_pieces with the engine of the switch (read when the environments are created),
+    held to the same bounds as the default engines"""
+    monkeypatch.setenv(switch, "1")
+    _fused_step_body(pkg, case, prec, tag=f" {switch}=1")
 
 
 def test_simd_sharing_form_with_odd_a(pkg):
@@ -317,19 +346,16 @@ def _launches(env, label):
     return n.value
 
 
-@pytest.mark.parametrize("case,prec", ROWS, ids=IDS)
-def test_rollout_equals_the_step_loop_or_is_not_served(pkg, monkeypatch, case, prec):
-    """ks_rollout_kernel on every row the restated ks_rollout_shape_ok serves: 6 steps with learning = True, noise 0.3, against the
-    per-step loop pdec_policy_act_rng -> (env)(action) of the same Philox stream -- logged rows, reward_sum and done_step, with
-    test_rollout_equals_step_by_step_loop's bounds.  With odd A one column pair of the policy loop straddles the two packed
-    trajectories and its noise element shares a Box-Muller pair across them.  A row that is not served (temporal stack, "reward"
-    check, mono, finite differences, more than 64 KiB) must be refused by the library as well: pdec_rollout_members reports
-    served = 0 and enqueues nothing, and the per-actuator rows then run as the enqueued step loop, bit for bit."""
+def _rollout_body(pkg, monkeypatch, case, prec, engine=None):
+    """the body of test_rollout_equals_the_step_loop_or_is_not_served (engine: the one a switch selects instead of the grid's own;
+    its transform buffers enter the restated shape rule)"""
     monkeypatch.setenv("PDEC_ROLLOUT_PERSISTENT", "1")
     L = pkg._lib
     dt, T, noise, seed = _dt(prec), 6, 0.3, 99
     c = kc.CASES[case]
     setup, cfg, g = _row(pkg, case, prec)
+    if engine:
+        g = kc.with_engine(g, case, prec, engine)
     served = kc.rollout_served(g, case, prec)
     ns, A = setup.state_shape
     y0 = _cast(kc.inputs(case, B, seed=3)[0], prec)
@@ -389,7 +415,7 @@ def test_rollout_equals_the_step_loop_or_is_not_served(pkg, monkeypatch, case, p
             ok &= _err(worst, "p", d(out["p"][t], rows[t][1]), 0, 2e-4 * sc)
             ok &= _err(worst, "action", d(out["action"][t], rows[t][2]), 0, 2e-5 * sc)
             ok &= _err(worst, "reward", d(out["reward"][t], rows[t][3]), 0, 2e-5 * sc)
-        print(f"[ks-geometry rollout {case} {prec}] H = {kc.roll_h(case)} (worst, bound):", worst)
+        print(f"[ks-geometry rollout {case} {prec}{' ' + engine if engine else ''}] H = {kc.roll_h(case)} (worst, bound):", worst)
         assert ok, worst
     else:
         assert _same(env.y, ref_env.y) and _same(env.state, ref_env.state) and _same(env.action, ref_env.action)
@@ -398,6 +424,26 @@ def test_rollout_equals_the_step_loop_or_is_not_served(pkg, monkeypatch, case, p
             for k, name in enumerate(("y", "p", "action", "reward")):
                 assert _same(out[name][t], rows[t][k]), (t, name)
     env.close(), ref_env.close()
+
+
+@pytest.mark.parametrize("case,prec", ROWS, ids=IDS)
+def test_rollout_equals_the_step_loop_or_is_not_served(pkg, monkeypatch, case, prec):
+    """ks_rollout_kernel on every row the restated ks_rollout_shape_ok serves: 6 steps with learning = True, noise 0.3, against the
+    per-step loop pdec_policy_act_rng -> (env)(action) of the same Philox stream -- logged rows, reward_sum and done_step, with
+    test_rollout_equals_step_by_step_loop's bounds.  With odd A one column pair of the policy loop straddles the two packed
+    trajectories and its noise element shares a Box-Muller pair across them.  A row that is not served (temporal stack, "reward"
+    check, mono, finite differences, more than 64 KiB) must be refused by the library as well: pdec_rollout_members reports
+    served = 0 and enqueues nothing, and the per-actuator rows then run as the enqueued step loop, bit for bit."""
+    _rollout_body(pkg, monkeypatch, case, prec)
+
+
+@pytest.mark.parametrize("switch,case,prec", SWITCH_ROWS, ids=SWITCH_IDS)
+def test_rollout_under_the_engine_switches(pkg, monkeypatch, switch, case, prec):
+    """test_rollout_equals_the_step_loop_or_is_not_served with the engine of the switch: ks_rollout_kernel<T, FftR4 | FftGeneric>
+    where the larger transform buffers leave the launch under 64 KiB (perm_oddA_256 in fp32), the step loop on that engine
+    elsewhere -- and the library's verdict must be the restated one either way"""
+    monkeypatch.setenv(switch, "1")
+    _rollout_body(pkg, monkeypatch, case, prec, engine=SWITCHES[switch])
 
 
 @pytest.mark.parametrize("prec", ["f64", "f32"])

@@ -1,4 +1,4 @@
-"""The 1-D Keller-Segel kernels (csrc/env.hip: kseg_env_step_kernel<T, 0 | 1 | 2>, kseg_rollout_kernel<T, MEM, NT>, sense_kernel,
+"""The 1-D Keller-Segel kernels (csrc/kseg.hip: kseg_env_step_kernel<T, 0 | 1 | 2>, kseg_rollout_kernel<T, MEM, NT>; csrc/env.hip: sense_kernel,
 and the band tables pdec_env_create builds) against oracle/keller_segel.py over the geometries of kseg_geometry_cases.py -- the
 work-group sizes 64 .. 1024, overlapping actuator boxes, window wrap, permuted actuators, the fmap gather with two species, deep
 temporal stacks, one sense_dots group, punishments, the midpoint integrator, all three blow-up tests and both member forms of the
@@ -385,7 +385,7 @@ def test_member_rollout_equals_the_solo_rollouts(pkg, monkeypatch, case, prec):
         env.close()
     # the launch itself, by the library's own label: pdec_rollout_members on an environment of this test, profiled.  The label
     # "kseg_rollout_members" is kseg_rollout_launch's member branch, which picks kseg_rollout_kernel<T, true, 256> up to 256
-    # threads and <T, true, 1024> above (csrc/env.hip); a kernel trace of this test names both instantiations
+    # threads and <T, true, 1024> above (csrc/kseg.hip); a kernel trace of this test names both instantiations
     L = pkg._lib
     env = pkg.PDEenv(setup, B=M * K, dtype=dt, y0=y0.repeat(M, 1, 1), autoreset=False)
     L.check(env.lib.pdec_prof_reset(env.handle))
