@@ -37,7 +37,19 @@ small launch behind every env step adds the step's per-trajectory mean reward to
 the others, so recorded steps and graphs carry it), and the episode's last step, which is eager, snapshots the parameters
 its acting kernel read, writes the episode's row and makes the hook's best-episode decision without a read-back.
 `random_init` draws a new initial field for every episode at its (eager) first step, on the env stream, before the acting
-kernel reads it."""
+kernel reads it.
+
+Greedy held-out evaluation (opt-in, `eval_every`; needs the ledger): behind the last step of every eval_every-th episode the
+snapshot of that step is rolled out without noise on an environment of its own from K fixed held-out fields, and the ledger
+scores it on the device -- per trajectory b, from the rollout's reward_sum [K][R] and done_step [K]: ret_b = (sum_a (double)
+reward_sum[b][a]) / R in a order, blew_b = done_step[b] >= 0; score = (sum_b ret_b) / K in b order, NaN when any blew_b is set or
+any ret_b is not finite (population.score_members' rule; `eval_score` restates it on the host).  Enqueued at the (eager) last
+step, never inside a capture or a recorded step:
+
+    env stream:   [wait eval_{n-1} done] -> pdec_ledger_eval_load (staging -> evaluation actor) -> event
+    eval stream:  wait event -> reset the evaluation env to eval_y0 -> pdec_rollout -> pdec_ledger_eval_close -> done event
+
+With eval_stream=None the eval stream is the env stream (behind the episode's last env step, no events)."""
 import ctypes as C
 import os
 
@@ -96,11 +108,29 @@ class _Ledger:
             pass
 
 
+def eval_score(reward_sum, done_step):
+    """(ret [K] float64, blew [K] bool, score) of one greedy evaluation from a rollout's host arrays reward_sum [K, R] and
+    done_step [K], in the order of arithmetic of the device (module docstring; csrc/ledger.hip: ledger_eval_close_kernel)"""
+    rs = np.asarray(reward_sum)
+    K, R = rs.shape
+    ret = np.zeros(K)
+    for a in range(R):
+        ret = ret + rs[:, a].astype(np.float64)
+    ret = ret / float(R)
+    blew = np.asarray(done_step).reshape(K) >= 0
+    s = 0.0
+    for v in ret:
+        s += float(v)
+    bad = bool(blew.any()) or not bool(np.isfinite(ret).all())
+    return ret, blew, (float("nan") if bad else s / float(K))
+
+
 class TrainPipeline:
     def __init__(self, env, agent, lag=2, episode_steps=51, stream_env=None, stream_upd=None, use_graphs=True,
                  chunks=(24, 6, 1), use_replay=False, noise_seed=1234, kick_env_after_critic=None, stream_ar=None,
                  ar_off_chain=None, log_episodes=0, min_best_episode=0, random_init=False, init_seed=0, init_rng=None,
-                 init_rank=(0, 1)):
+                 init_rank=(0, 1), eval_every=0, eval_inits=8, eval_seed=0, eval_y0=None, eval_capacity=64, eval_stream=None,
+                 best_by="train"):
         """env: PDEenv on `stream_env`; agent: create_agent(..., stream=stream_upd).  lag: the update of step k trains on
         the transition of step k - lag (>= 1).  episode_steps: lock-stepped episodes of that many control steps (0: one
         endless episode): the last transition is terminal (done = time >= te, src/PDEenv.jl:227) and the next step starts
@@ -119,7 +149,22 @@ class TrainPipeline:
         random_init: every episode starts from a new field -- KS / Keller-Segel / 2-D Keller-Segel: env.random_init(init_seed,
         off), episode e of rank r of W (init_rank = (r, W)) drawing from off = (e W + r) * n with n = B ceil(nc / 4) the
         counters of one call, so W ranks of B trajectories draw together what one rank of W B draws ((0, 1): PDEhook's
-        advance); the fluid: setup.random_init_device(env, init_rng).  A field given to reset_from() is used as it is."""
+        advance); the fluid: setup.random_init_device(env, init_rng).  A field given to reset_from() is used as it is.
+
+        eval_every = N > 0: greedy held-out evaluation (module docstring) behind the last step of every episode whose 1-based
+        number is a multiple of N -- one episode of episode_steps control steps, learning = 0, the policy's act_limit, on an
+        environment of its own (B = K, the training env's setup and dtype) from the fields eval_y0 [K, ...], or, None,
+        eval_inits fields drawn once as population.evaluate_actors draws its own (Philox stream (eval_seed, 0) of
+        env.random_init; the fluid: setup.random_init_device(env, np.random.default_rng(eval_seed))).  pipe.eval_y0: the
+        fields; pipe.eval_zero_score: the score of the zero action on them (an actor with all parameters 0, run once here).
+        The last eval_capacity evaluations are kept: eval_returns(), eval_scores.  eval_stream: None = the env stream, or a
+        stream that is neither the env nor the update stream (made by the same make_streams call) on which the evaluation
+        runs beside training.  best_by: "train" -- best_actor() / bestreward / bestepisode follow the training return, as
+        without evaluations -- or "eval": the hook's rule on the evaluation scores (episode >= min_best_episode, score not
+        NaN and >= every earlier such score), keeping the evaluated parameters.  Needs log_episodes > 0 (the snapshot lives
+        in the ledger), episode_steps > 0 and no active reducer."""
+        self._check_eval_args(env, agent, episode_steps, stream_env, stream_upd, log_episodes, eval_every, eval_inits, eval_y0,
+                              eval_capacity, eval_stream, best_by)
         self.env, self.agent, self.policy = env, agent, agent.policy
         self.lib = env.lib
         self.LAG = max(1, int(lag))
@@ -252,8 +297,125 @@ class TrainPipeline:
         self._captured = False
         self.n_graph_launches = self.n_eager_steps = 0
         self._setup_episodes(log_episodes, min_best_episode, random_init, init_seed, init_rng, init_rank)
+        self._setup_eval(eval_every, eval_inits, eval_seed, eval_y0, eval_capacity, eval_stream, best_by, Ev)
         self.reset_from(env.y0)
         self._keep_y0 = False
+
+    @staticmethod
+    def _check_eval_args(env, agent, episode_steps, stream_env, stream_upd, log_episodes, eval_every, eval_inits, eval_y0,
+                         eval_capacity, eval_stream, best_by):
+        """the refusals of the evaluation arguments, by name, before anything is allocated"""
+        if best_by not in ("train", "eval"):
+            raise _lib.PdecError(f"TrainPipeline(best_by={best_by!r}): 'train' or 'eval'")
+        if int(eval_every) < 0:
+            raise _lib.PdecError(f"TrainPipeline(eval_every={eval_every}): a period >= 0")
+        if int(eval_every) == 0:
+            if best_by == "eval":
+                raise _lib.PdecError("TrainPipeline(best_by='eval') needs evaluations: eval_every > 0")
+            return
+        if int(log_episodes) <= 0:
+            raise _lib.PdecError("TrainPipeline(eval_every=...) needs the episode ledger, which holds the snapshot: log_episodes > 0")
+        if int(episode_steps) <= 0:
+            raise _lib.PdecError("TrainPipeline(eval_every=...) needs episodes: episode_steps > 0")
+        reducer = agent.policy.reducer
+        if reducer is not None and reducer.active:
+            raise _lib.PdecError("TrainPipeline(eval_every=...) is not available with an active reducer: the ledger keeps no "
+                                 "snapshot there")
+        if int(eval_inits) < 1:
+            raise _lib.PdecError(f"TrainPipeline(eval_inits={eval_inits}): at least one held-out field")
+        if int(eval_capacity) < 1:
+            raise _lib.PdecError(f"TrainPipeline(eval_capacity={eval_capacity}): at least one row")
+        if eval_y0 is not None:
+            shape = tuple(eval_y0.shape) if hasattr(eval_y0, "shape") else np.shape(eval_y0)
+            if len(shape) != len(env._yshape) or shape[0] < 1 or shape[1:] != tuple(env._yshape[1:]):
+                raise _lib.PdecError(f"TrainPipeline(eval_y0=...): expected shape (K,) + {tuple(env._yshape[1:])}, got {shape}")
+        if eval_stream is not None:
+            s_upd = stream_upd if stream_upd is not None else agent.policy.behavior_critic.model.stream
+            s_env = stream_env if stream_env is not None else env.stream
+            if s_upd is not None and eval_stream.cuda_stream == s_upd.cuda_stream and (
+                    s_env is None or s_env.cuda_stream != s_upd.cuda_stream):
+                raise _lib.PdecError("TrainPipeline(eval_stream=...): the update stream cannot carry the evaluation; None (the "
+                                     "env stream) or a third stream")
+
+    def _setup_eval(self, eval_every, eval_inits, eval_seed, eval_y0, eval_capacity, eval_stream, best_by, Ev):
+        """the evaluation environment, actor, held-out fields and zero-action baseline (one synchronisation); nothing when off"""
+        self.eval_every, self.best_by = int(eval_every), best_by
+        self.n_evals = 0
+        self.eval_env = self.eval_actor = self.eval_y0 = self.eval_zero_score = None
+        self.s_eval = None
+        if self.eval_every <= 0:
+            return
+        from .env import PDEenv
+        from .nna import HipMLP
+        env, lib = self.env, self.lib
+        self.eval_capacity = int(eval_capacity)
+        self.s_eval = eval_stream if eval_stream is not None else self.s_env
+        self._eval_aside = self.s_eval.cuda_stream != self.s_env.cuda_stream
+        s = self.s_eval
+        with torch.cuda.stream(s):
+            if eval_y0 is None:
+                K = int(eval_inits)
+                ee = PDEenv(env.setup, B=K, dtype=env.dtype, device=env.device, stream=s, autoreset=False)
+                if env.is_fluid:
+                    y0 = env.setup.random_init_device(ee, np.random.default_rng(int(eval_seed)))
+                else:
+                    y0 = torch.empty_like(ee.y)
+                    ee.random_init(int(eval_seed), 0, out=y0)
+                y0 = y0.clone()
+            else:
+                y0 = (eval_y0 if isinstance(eval_y0, torch.Tensor) else torch.as_tensor(np.array(eval_y0, copy=True)))
+                y0 = y0.to(device=env.device, dtype=env.dtype).contiguous().clone()
+                K = int(y0.shape[0])
+                ee = PDEenv(env.setup, B=K, dtype=env.dtype, device=env.device, stream=s, autoreset=False)
+            self.eval_env, self.eval_y0, self.eval_K = ee, y0, K
+            m = self.actor
+            cols = K * env.setup.state_shape[1]
+            self.eval_actor = HipMLP(m.dims, m.acts, None, env.dtype, m.device, max(cols, m.max_cols), s)    # all parameters 0
+            self._eval_rsum = torch.zeros((K, env.setup.reward_len), dtype=env.dtype, device=env.device)
+            self._eval_done = torch.zeros((2, K), dtype=torch.int32, device=env.device)        # done_any, done_step
+        _lib.check(lib.pdec_ledger_eval_attach(self.ledger.h, ee.handle, self.eval_actor.handle, self.eval_capacity))
+        self.ev_eload, self.ev_edone = Ev(lib), Ev(lib)     # evaluation actor loaded (env stream) / evaluation closed (eval stream)
+        self._eval_pending = False
+        # the zero action on the same fields: the rollout of the all-zero actor the evaluation actor still is.  It also makes
+        # every lazily created buffer of the rollout path, so that the evaluations of the run enqueue and return.
+        self._eval_rollout()
+        s.synchronize()
+        self.eval_zero_score = eval_score(self._eval_rsum.cpu().numpy(), self._eval_done[1].cpu().numpy())[2]
+
+    def _eval_rollout(self):
+        """reset the evaluation env to eval_y0 and enqueue one greedy episode of the evaluation actor, on the eval stream"""
+        ee, lib = self.eval_env, self.lib
+        with torch.cuda.stream(self.s_eval):
+            ee.y.copy_(self.eval_y0)
+            _lib.check(lib.pdec_featurize(ee.handle, _lib.ptr(ee.y), None, _lib.ptr(ee.state)))
+            ee.action.zero_()
+            self._eval_rsum.zero_()
+            self._eval_done.zero_()
+            _lib.check(lib.pdec_rollout(ee.handle, self.eval_actor.handle, self.E, _lib.ptr(ee.y), _lib.ptr(ee.state),
+                                        _lib.ptr(ee.action), 0.0, float(self.policy.act_limit), 0, 0, 0,
+                                        _lib.ptr(self._eval_rsum), None, None, None, None, _lib.ptr(self._eval_done[0]),
+                                        _lib.ptr(self._eval_done[1])))
+
+    def _eval_load(self):
+        """env stream, behind the snapshot of an evaluated episode's last step: the staged parameters -> the evaluation actor"""
+        if self._eval_aside and self._eval_pending:
+            self.ev_edone.wait(self.s_env)              # the previous evaluation still reads the actor being rewritten
+        _lib.check(self.lib.pdec_ledger_eval_load(self.ledger.h))
+        if self._eval_aside:
+            self.ev_eload.record(self.s_env)
+
+    def _eval_run(self, episode):
+        """the evaluation of 1-based `episode`, on the eval stream (the env stream: behind the episode's last env step)"""
+        if self._eval_aside:
+            self.ev_eload.wait(self.s_eval)
+        self._eval_rollout()
+        with torch.cuda.stream(self.s_eval):
+            _lib.check(self.lib.pdec_ledger_eval_close(self.ledger.h, _lib.ptr(self._eval_rsum), _lib.ptr(self._eval_done[1]),
+                                                       self.n_evals, int(episode), self.min_best_episode))
+        self.n_evals += 1
+        if self._eval_aside:
+            self.ev_edone.record(self.s_eval)
+            self._eval_pending = True
 
     def _setup_episodes(self, log_episodes, min_best_episode, random_init, init_seed, init_rng, init_rank):
         env = self.env
@@ -364,6 +526,8 @@ class TrainPipeline:
         act, act_prev = self.aring[k % 3], self.aring[(k - 1) % 3]
         rew, flags, term = self.rring[k % 3], self.fring[k % 3], self.tring[k % 3]
         capturing = chunk_first or chunk_last or self._capturing
+        # greedy evaluation behind this step: the last step (eager) of an episode whose 1-based number is a multiple of eval_every
+        evaluate = last and self.eval_every > 0 and (self.n_episodes + 1) % self.eval_every == 0
         mid_wait_prev, self._mid_wait_prev = self._mid_wait_prev, False
         if not self.serial:
             if chunk_first:                       # fork: everything before this chunk is ordered before it on the env stream
@@ -402,6 +566,8 @@ class TrainPipeline:
                 if last and self.track_best:
                     # what this acting kernel read, before the actor half that waits for ev_act may rewrite it
                     L.check(lib.pdec_ledger_snapshot(self.ledger.h))
+                    if evaluate:
+                        self._eval_load()
                 if not self.serial and self.LAG >= 2:
                     self.ev_act[k % 2].record(self.s_env)
             if self.drain_between:
@@ -441,6 +607,8 @@ class TrainPipeline:
                     self.ev_act[k % 2].record(self.s_env)
                 if self._mid_waits:
                     self.ev_env[k % 2].record(self.s_env)
+            if evaluate:
+                self._eval_run(self.n_episodes)        # (behind everything step k puts on the env stream)
             if self.drain_between:                     # kernel-timing pass: nothing of the env branch overlaps the update
                 torch.cuda.synchronize()
 
@@ -775,15 +943,47 @@ class TrainPipeline:
         n = min(self.n_episodes, N)
         return [float(means[e % N]) for e in range(self.n_episodes - n, self.n_episodes)]
 
+    def _need_eval(self):
+        if self.eval_every <= 0:
+            raise _lib.PdecError("TrainPipeline: evaluations are off (eval_every=0)")
+
+    def _eval_rows(self):
+        """(ring rows oldest first, dropped) of the last min(evaluations, eval_capacity) evaluations"""
+        N = self.eval_capacity
+        n = min(self.n_evals, N)
+        return [e % N for e in range(self.n_evals - n, self.n_evals)], self.n_evals - n
+
+    def eval_returns(self):
+        """(episodes [n] int64, returns [n, K] float64, blew_up [n, K] bool, dropped): the last n = min(evaluations,
+        eval_capacity) evaluations, oldest first -- the 1-based episode each one followed, its per-trajectory returns and
+        blow-up bits -- and how many earlier ones the ring has overwritten"""
+        self._need_eval()
+        N, K = self.eval_capacity, self.eval_K
+        eps, ret, blew = np.empty(N, dtype=np.int64), np.empty((N, K)), np.empty((N, K), dtype=np.int32)
+        _lib.check(self.lib.pdec_ledger_eval_read(self.ledger.h, _lib.ptr(eps), _lib.ptr(ret), _lib.ptr(blew), None))
+        rows, dropped = self._eval_rows()
+        return eps[rows], ret[rows], blew[rows] != 0, dropped
+
+    @property
+    def eval_scores(self):
+        """score of each kept evaluation (module docstring), oldest first; NaN: a trajectory stopped or is not finite"""
+        self._need_eval()
+        sc = np.empty(self.eval_capacity)
+        _lib.check(self.lib.pdec_ledger_eval_read(self.ledger.h, None, None, None, _lib.ptr(sc)))
+        return sc[self._eval_rows()[0]]
+
     def _best(self):
-        self._need_ledger(best=True)
         v, e = C.c_double(), C.c_int64()
+        if self.best_by == "eval":
+            _lib.check(self.lib.pdec_ledger_eval_best(self.ledger.h, C.byref(v), C.byref(e)))
+            return v.value, e.value
+        self._need_ledger(best=True)
         _lib.check(self.lib.pdec_ledger_best(self.ledger.h, C.byref(v), C.byref(e)))
         return v.value, e.value
 
     @property
     def bestreward(self):
-        """PDEhook.bestreward: -1e6 until an episode has been chosen"""
+        """PDEhook.bestreward: -1e6 until an episode has been chosen (best_by="eval": the best evaluation score)"""
         return self._best()[0]
 
     @property
@@ -800,7 +1000,10 @@ class TrainPipeline:
         A = self.policy.behavior_actor
         m = A.model
         out = HipMLP(m.dims, m.acts, None, m.dtype, m.device, m.max_cols, m.stream)
-        _lib.check(self.lib.pdec_ledger_best_params(self.ledger.h, out.handle))
+        if self.best_by == "eval":
+            _lib.check(self.lib.pdec_ledger_eval_best_params(self.ledger.h, out.handle))
+        else:
+            _lib.check(self.lib.pdec_ledger_best_params(self.ledger.h, out.handle))
         import copy
         return CustomNeuralNetworkApproximator(out, copy.copy(A.optimizer))
 
@@ -809,8 +1012,12 @@ class TrainPipeline:
         self.s_upd.synchronize()
         if self.s_ar is not None:
             self.s_ar.synchronize()
+        if self.s_eval is not None:
+            self.s_eval.synchronize()
 
     def close(self):
+        if self.s_eval is not None:
+            self.s_eval.synchronize()                  # an evaluation still running reads objects this pipeline owns
         if getattr(self, "simd_sharing", False):
             self.lib.pdec_env_set_simd_sharing(self.env.handle, 0, None)
             self.simd_sharing = False

@@ -640,6 +640,36 @@ int pdec_ledger_read(pdec_handle ledger, double* returns, int32_t* blew_up, doub
 int pdec_ledger_best(pdec_handle ledger, double* value, int64_t* episode);
 int pdec_ledger_best_params(pdec_handle ledger, pdec_handle mlp);
 
+/* Greedy held-out evaluation of the training actor, scored on the device (replaces the noise-free env.rollout on a fixed set of
+ * fields that tools/pipeline_learning_probe.py ran after a training run, and PDEhook's choice of bestNNA by the noisy training
+ * return, src/PDEhook.jl:65-76, by one made on the evaluation score).  The numbers, per evaluated trajectory b of the K the
+ * evaluation environment holds, from a rollout's reward_sum [K][R] (environment's dtype) and done_step [K]:
+ *   ret_b  = (sum_a (double) reward_sum[b][a]) / R, summed in a order;   blew_b = done_step[b] >= 0
+ *   score  = (sum_b ret_b) / K, summed in b order; NaN when any blew_b is set or any ret_b is not finite
+ * (population.py: score_members' rule, so a population's evaluate() and the pipeline rank alike).
+ * pdec_ledger_eval_attach: ties an evaluation environment (B = K, any stream), an evaluation actor of the ledger's actor's layer
+ * sizes (any dtype the staged parameters promote to exactly: the actor's own, or PDEC_F64) and `capacity` rows to a ledger made
+ * with an actor; allocates rows [capacity][K] fp64 / int32, [capacity] scores and episode numbers, the evaluation state and the
+ * best-by-evaluation parameter buffer.  Once per ledger. */
+int pdec_ledger_eval_attach(pdec_handle ledger, pdec_handle eval_env, pdec_handle eval_actor, int capacity);
+/* on the TRAINING environment's stream, behind pdec_ledger_snapshot of the same step: the staged parameters -> the evaluation
+ * actor's flat parameters (Float32 -> fp64 is an exact promotion), one device kernel, no host copy, no synchronisation; the
+ * images the acting kernels derive from them are rebuilt by the evaluation actor's next acting call on its own stream.  The
+ * caller orders the streams: this call behind the previous evaluation's close, the evaluation's rollout behind this call. */
+int pdec_ledger_eval_load(pdec_handle ledger);
+/* on the EVALUATION environment's stream, behind the rollout that filled reward_sum / done_step (device): one workgroup writes
+ * row `n_eval mod capacity` (returns, bits, score, 1-based `episode`) as defined above and applies PDEhook's rule to the score --
+ * an evaluation with episode >= min_best_episode whose score is not NaN and >= every earlier such score becomes the best; its
+ * parameters are copied from the EVALUATION ACTOR (the staging buffer may already hold a later snapshot).  Nothing is read back. */
+int pdec_ledger_eval_close(pdec_handle ledger, const void* reward_sum, const int32_t* done_step, int64_t n_eval, int64_t episode,
+                           int64_t min_best_episode);
+/* host accessors (synchronise the evaluation environment's stream): all rows (any pointer may be NULL) -- episodes [capacity],
+ * returns / blew_up [capacity][K], scores [capacity] --, the best score (-1e6 before any choice) and its 1-based episode (0:
+ * none), the best parameters into an MLP of the actor's layer sizes (converted when its dtype differs) */
+int pdec_ledger_eval_read(pdec_handle ledger, int64_t* episodes, double* returns, int32_t* blew_up, double* scores);
+int pdec_ledger_eval_best(pdec_handle ledger, double* value, int64_t* episode);
+int pdec_ledger_eval_best_params(pdec_handle ledger, pdec_handle mlp);
+
 /* ---------------------------------------------------------------- HIP graphs -- */
 /* Record everything enqueued on the stream of `origin` (pdec_set_stream; not the null stream) -- library calls, and any
  * other stream that forks from it and joins it again through events -- between _begin and _end into one HIP graph;
