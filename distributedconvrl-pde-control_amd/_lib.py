@@ -52,7 +52,8 @@ SIGNATURES = {
     "pdec_fluid_env_create": [C.POINTER(Handle), C.POINTER(EnvCfg), _i, _i, _pd, _pi32, _pd, _pi32, _pi32],
     "pdec_kseg2d_env_create": [C.POINTER(Handle), C.POINTER(EnvCfg), _i, _i, _i, _pi32, _pi32, _i, _pi32],
     "pdec_fluid_ic": [Handle, _pd, _i, _vp],
-    "pdec_fluid_ic_dev": [Handle, _vp, _i, _vp], "pdec_fluid_error_detection": [Handle, _vp, _vp],
+    "pdec_fluid_ic_dev": [Handle, _vp, _i, _vp], "pdec_fluid_ic_rng": [Handle, _u64, _u64, _i, _vp, _vp],
+    "pdec_fluid_error_detection": [Handle, _vp, _vp],
     "pdec_actuate": [Handle, _vp, _vp],
     "pdec_pde_step": [Handle, _vp, _vp, _vp, _vp],
     "pdec_featurize": [Handle, _vp, _vp, _vp], "pdec_featurize_action": [Handle, _vp, _vp, _vp, _vp], "pdec_mlp_set_noise_rows": [Handle, _i],

@@ -338,8 +338,6 @@ int pdec_env_create(pdec_handle* h, const pdec_env_cfg* cfg, const double* senso
 
 int pdec_env_set_terminal_out(pdec_handle h, void* terminal_per_column) {
   GET_ENV(E, h);
-  PDEC_REQUIRE(E->cfg.pde_kind != PDEC_PDE_FLUID_RK4 || !terminal_per_column,
-               "pdec_env_set_terminal_out: not provided for the fluid environment (expand its done[B] flags)");
   E->term_out = terminal_per_column;
   return PDEC_OK;
 }

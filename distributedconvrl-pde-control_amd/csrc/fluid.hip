@@ -28,6 +28,7 @@
 // Layout: Julia ComplexF64[ny, nx] column-major = memory [nx][ny] (y fastest); square box (nx = ny = n,
 // Lx = Ly) as in every shipped script.  "fast axis" = y, "slow axis" = x.
 #include "env.hpp"
+#include "mlp.hpp"
 #include "wave_fft.hpp"
 
 #include <type_traits>
@@ -405,11 +406,15 @@ struct FeatArgs {
 };
 
 // featurize (3x3 circular window of the spa x spa sensor grid, FluidSetup.jl:219-224) + reward (:188-202)
+// term_out (pdec_env_set_terminal_out, the env step only): [B][A], 1 on every column of a trajectory whose flag of this step is
+// set -- check_max 2: the flag reduced here in LDS, behind its barrier; 1: done[b] as fluid_maxabs_kernel left it; 0: zeros.
+// Written on the reward path: the env step always has a reward_out (pdec_env_step refuses a null one).
 template <class T>
 __global__ __launch_bounds__(256) void fluid_feat_kernel(FeatArgs<T> g, const T* __restrict__ dots,
                                                          const T* __restrict__ action, const T* __restrict__ action_prev,
                                                          const T* __restrict__ state_prev, T* __restrict__ state_out,
-                                                         T* __restrict__ reward_out, int32_t* __restrict__ done) {
+                                                         T* __restrict__ reward_out, int32_t* __restrict__ done,
+                                                         T* __restrict__ term_out) {
   __shared__ int flag;
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const T* dt = dots + (size_t)b * g.S;
@@ -447,6 +452,11 @@ __global__ __launch_bounds__(256) void fluid_feat_kernel(FeatArgs<T> g, const T*
     }
     __syncthreads();
     if (done && tid == 0 && g.check_max == 2) done[b] = flag;
+    if (term_out) {
+      const int f = g.check_max == 2 ? flag : (g.check_max == 1 ? done[b] : 0);
+      const T tv = f ? (T)1 : (T)0;
+      for (int a = tid; a < g.A; a += nt) term_out[(size_t)b * g.A + a] = tv;
+    }
   }
 }
 
@@ -1005,6 +1015,26 @@ __global__ void fluid_round_kernel(const double* __restrict__ in, float* __restr
   if (i < cnt) out[i] = (float)in[i];
 }
 
+// The random draws of ic(3) / ic(4) (src/fluid_rk4.jl:72-120) from the library's Philox stream (seed, offset): one thread per
+// (trajectory b, vortex v) = counter offset + b nv + v, its words w0..w3, u_i = (w_i + 0.5) 2^-32 (random_init_kernel's
+// convention); row (x0, y0, a0, U) = (u0 Lx, u1 Ly, a0, 2 u3 - 1), a0 = a_base (case 3) or a_base (0.5 + u2) (case 4).
+// tab: the environment's table [B][nv][4]; copy: the caller's, or null.
+__global__ void fluid_vortex_draw_kernel(int total, int vary_a, double Lx, double Ly, double a_base, uint64_t seed, uint64_t offset,
+                                         double* __restrict__ tab, double* __restrict__ copy) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const uint64_t ctr = offset + (uint64_t)i;
+  uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
+  philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  double u[4];
+  for (int q = 0; q < 4; ++q) u[q] = ((double)c[q] + 0.5) * (1.0 / 4294967296.0);
+  const double row[4] = {u[0] * Lx, u[1] * Ly, vary_a ? a_base * (0.5 + u[2]) : a_base, 2.0 * u[3] - 1.0};
+  for (int q = 0; q < 4; ++q) {
+    tab[(size_t)4 * i + q] = row[q];
+    if (copy) copy[(size_t)4 * i + q] = row[q];
+  }
+}
+
 // error_detection (scripts/Fluid/setup/FluidSetup.jl:263-273) on w = real(ifft2(y)) [B][n][n]: the largest |w[r][i] - w[r-1][i]|
 // and |w[r][i] - w[r][i-1]|, periodic along both axes.  grid (ceil(n / FL_JUMP_ROWS), B): a workgroup walks its rows downwards,
 // a thread keeps the row above in a register (one halo row per tile) and takes its left neighbour from the lane beside it
@@ -1055,7 +1085,7 @@ struct FluidEnv : Env {
   int n = 0, p = 0, nl = 0, TL = 0, TLn = 0, BH = 0, BW = 0, nb1 = 0;
   FftPlan plp, pln;
   DevBuf k, twp, twn, sbox, sorg, abox, aorg, a2s_d, blkptr, blkidx;
-  DevBuf W, W2, fs, acc, yreal, tmpc, dots, phat, icv, errbits;
+  DevBuf W, W2, fs, acc, yreal, tmpc, dots, phat, icv, icd, errbits, yflag;
   size_t lds_p = 0, lds_n = 0;
   int wave_E = 0, wave_Q = 0;     // != 0: the one-line-per-wave transforms serve the padded length p
   int wave_LB = 6;                // 5: one line per HALF wave (p = 192, 64)
@@ -1396,11 +1426,11 @@ static FeatArgs<T> feat_args(const FluidEnv& E) {
 
 template <class T>
 static int fluid_feat_launch(FluidEnv& E, const void* action, const void* action_prev, const void* state_prev,
-                             void* state_out, void* reward_out, int32_t* done) {
+                             void* state_out, void* reward_out, int32_t* done, void* term_out = nullptr) {
   ProfScope ps(&E, "fluid_feat");
   hipLaunchKernelGGL(fluid_feat_kernel<T>, dim3(E.cfg.B), dim3(256), 0, E.stream, feat_args<T>(E), E.dots.as<T>(),
                      (const T*)action, (const T*)action_prev, (const T*)state_prev, (T*)state_out,
-                     (T*)reward_out, done);
+                     (T*)reward_out, done, (T*)term_out);
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
 }
@@ -1485,11 +1515,13 @@ static int fluid_env_step_t(FluidEnv& E, const void* y_in, const void* action, c
   if ((rc = fluid_actuate_t<T>(E, action, ph))) return rc;                              // src/PDEenv.jl:199
   if ((rc = fluid_pde_step_t<T>(E, y_in, ph, y_out, nullptr))) return rc;               // :216-218
   if ((rc = fluid_dots<T>(E, y_out))) return rc;
+  // (terminal rows without a done array: check_max_value "y" leaves its flags in a slot of the environment's own)
+  if (!done && E.term_out && E.cfg.check_max_value == 1) done = E.yflag.as<int32_t>();
   if (done && E.cfg.check_max_value != 2) {
     if (E.cfg.check_max_value == 1) { if ((rc = fluid_done_y<T>(E, y_out, done))) return rc; }
     else PDEC_HIP(hipMemsetAsync(done, 0, sizeof(int32_t) * E.cfg.B, E.stream));
   }
-  return fluid_feat_launch<T>(E, action, action_prev, state_prev, state_out, reward_out, done);   // :220-222
+  return fluid_feat_launch<T>(E, action, action_prev, state_prev, state_out, reward_out, done, E.term_out);   // :220-222
 }
 
 int FluidEnv::env_step(const StepArgs& a) {
@@ -1636,6 +1668,8 @@ static int fluid_make(std::unique_ptr<FluidEnv>& out, const pdec_env_cfg& c, int
   // that the device entry points only enqueue
   PDEC_HIP(E->errbits.alloc(Bz * sizeof(int32_t)));
   PDEC_HIP(E->icv.alloc(Bz * 50 * 4 * ts));
+  // the flag slot of the terminal rows under check_max_value "y" (every child of a split batch needs its own): made here too
+  PDEC_HIP(E->yflag.alloc(Bz * sizeof(int32_t)));
   if ((rc = (c.dtype == PDEC_F32 ? fluid_set_attrs<float>(*E) : fluid_set_attrs<double>(*E)))) return rc;
   out = std::move(E);
   return PDEC_OK;
@@ -1649,6 +1683,9 @@ extern "C" int pdec_fluid_env_create(pdec_handle* h, const pdec_env_cfg* cfg, in
   std::unique_ptr<FluidEnv> E;
   int rc = fluid_make(E, *cfg, BH, BW, sensor_boxes, sensor_origin, actuator_boxes, actuator_origin, a2s);
   if (rc) return rc;
+  // pdec_fluid_ic_rng's table of doubles (50 vortices, ic(4)), on the environment the caller holds only -- the initialisers serve
+  // a split batch from the parent's own arrays --: made here, so that the calls of a run only enqueue
+  PDEC_HIP(E->icd.alloc((size_t)cfg->B * 50 * 4 * sizeof(double)));
   // part-batch children for the fused env step where a part still fills the chip (padded 512-point grids and up): two by
   // default; PDEC_FLUID_SPLIT=0 off, 1 / 2 two parts, 3 / 4 that many
   static const char* sp = getenv("PDEC_FLUID_SPLIT");
@@ -1758,17 +1795,39 @@ static FluidEnv* fluid_handle(pdec_handle h, const char* who) {
 
 // pdec_fluid_ic with the table already in device memory (doubles): the same launches, no host copy, no synchronisation.
 // An fp32 environment rounds the table once, on the device, into its own icv (the rounding of the host path's cast).
-extern "C" int pdec_fluid_ic_dev(pdec_handle h, const double* vortices_dev, int nv, void* y_out) {
-  FluidEnv* Ep = fluid_handle(h, "pdec_fluid_ic_dev");
-  if (!Ep) return PDEC_E_HANDLE;
-  PDEC_REQUIRE(vortices_dev && y_out && nv >= 1 && nv <= 1024, "pdec_fluid_ic_dev: bad arguments (1 <= nv <= 1024)");
-  FluidEnv& E = *Ep;
+static int fluid_ic_from_dev(FluidEnv& E, const double* vortices_dev, int nv, void* y_out) {
   if (E.cfg.dtype != PDEC_F32) return fluid_ic_launch<double>(E, vortices_dev, nv, y_out);
   const size_t cnt = (size_t)E.cfg.B * nv * 4;
   if (E.icv.bytes < cnt * sizeof(float)) PDEC_HIP(E.icv.alloc(cnt * sizeof(float)));
   hipLaunchKernelGGL(fluid_round_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, E.stream, vortices_dev, E.icv.as<float>(),
                      cnt);
   return fluid_ic_launch<float>(E, E.icv.as<float>(), nv, y_out);
+}
+
+extern "C" int pdec_fluid_ic_dev(pdec_handle h, const double* vortices_dev, int nv, void* y_out) {
+  FluidEnv* Ep = fluid_handle(h, "pdec_fluid_ic_dev");
+  if (!Ep) return PDEC_E_HANDLE;
+  PDEC_REQUIRE(vortices_dev && y_out && nv >= 1 && nv <= 1024, "pdec_fluid_ic_dev: bad arguments (1 <= nv <= 1024)");
+  return fluid_ic_from_dev(*Ep, vortices_dev, nv, y_out);
+}
+
+// ic(3) / ic(4) with the draws made on the device: fluid_vortex_draw_kernel into the environment's own table (allocated with the
+// environment), then the launches of pdec_fluid_ic_dev on it; see include/pdeconv.h
+extern "C" int pdec_fluid_ic_rng(pdec_handle h, uint64_t seed, uint64_t offset, int caseno, double* vortices_out, void* y_out) {
+  FluidEnv* Ep = fluid_handle(h, "pdec_fluid_ic_rng");
+  if (!Ep) return PDEC_E_HANDLE;
+  PDEC_REQUIRE(caseno == 3 || caseno == 4, "pdec_fluid_ic_rng: caseno %d (3: 30 vortices, training; 4: 50, evaluation)", caseno);
+  PDEC_REQUIRE(y_out, "pdec_fluid_ic_rng: null y_out");
+  FluidEnv& E = *Ep;
+  const int nv = caseno == 3 ? 30 : 50, total = E.cfg.B * nv;
+  PDEC_REQUIRE(E.icd.bytes >= (size_t)total * 4 * sizeof(double), "pdec_fluid_ic_rng: internal: table too small");
+  {
+    ProfScope ps(&E, "fluid_vortex_draw");
+    hipLaunchKernelGGL(fluid_vortex_draw_kernel, dim3((total + 255) / 256), dim3(256), 0, E.stream, total, caseno == 4 ? 1 : 0,
+                       E.cfg.Lx, E.cfg.Lx, E.cfg.Lx / 20, seed, offset, E.icd.as<double>(), vortices_out);
+    PDEC_HIP(hipGetLastError());
+  }
+  return fluid_ic_from_dev(E, E.icd.as<double>(), nv, y_out);
 }
 
 template <class T>

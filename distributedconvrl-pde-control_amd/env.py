@@ -276,19 +276,30 @@ class PDEenv:
         _lib.check(self.lib.pdec_rhs_eval(self._h, _lib.ptr(y), _lib.ptr(p), _lib.ptr(out)))
         return out
 
-    def random_init(self, seed, offset, out=None):
+    def random_init(self, seed, offset, out=None, vortices_out=None):
         """generate_random_init() of the KS, Keller-Segel and 2-D Keller-Segel setups on the device (pdec_env_random_init;
         scripts/KS/setup/KSSetup.jl:288-298, scripts/Keller-Segel/setup/KellerSegelSetup.jl:373-384, and its 2-D form in
         setups/keller_segel2d.py): fills `out` (default: a new tensor shaped like env.y) from the Philox stream
-        (seed, offset) and returns the number of counters consumed"""
+        (seed, offset) and returns the number of counters consumed.  The fluid: ic(4) of an evaluation setup, else ic(3)
+        (FluidSetup.jl:386-394), the vortex table drawn on the device (pdec_fluid_ic_rng: one counter per vortex) and copied
+        to `vortices_out` (float64 device tensor [B, nv, 4]) when given."""
         out = torch.empty_like(self.y) if out is None else out
-        _lib.check(self.lib.pdec_env_random_init(self._h, int(seed), int(offset), _lib.ptr(out)))
+        if vortices_out is not None and not self.is_fluid:
+            raise _lib.PdecError("PDEenv.random_init(vortices_out=...): only the fluid environment draws a vortex table")
+        if self.is_fluid:
+            _lib.check(self.lib.pdec_fluid_ic_rng(self._h, int(seed), int(offset), 4 if self.setup.evaluation else 3,
+                                                  _lib.ptr(vortices_out), _lib.ptr(out)))
+        else:
+            _lib.check(self.lib.pdec_env_random_init(self._h, int(seed), int(offset), _lib.ptr(out)))
         self._last_random_init = out
         return self.B * ((self.random_init_coefficients() + 3) // 4)
 
     def random_init_coefficients(self):
-        """sine coefficients per trajectory of random_init (each takes one uniform of the Philox stream)"""
+        """sine coefficients per trajectory of random_init (each takes one uniform of the Philox stream); the fluid: the four
+        uniforms of each of its nv vortices"""
         st = self.setup
+        if self.is_fluid:
+            return 4 * (50 if st.evaluation else 30)
         if getattr(st, "is_kseg2d", False):
             return 2 * (int(np.ceil(st.Lx / 3)) + int(np.ceil(st.ny * st.dx / 3)))
         return 8 if st.y_shape == (st.nx,) else 2 * int(np.ceil(st.Lx / 3))

@@ -149,7 +149,9 @@ class TrainPipeline:
         random_init: every episode starts from a new field -- KS / Keller-Segel / 2-D Keller-Segel: env.random_init(init_seed,
         off), episode e of rank r of W (init_rank = (r, W)) drawing from off = (e W + r) * n with n = B ceil(nc / 4) the
         counters of one call, so W ranks of B trajectories draw together what one rank of W B draws ((0, 1): PDEhook's
-        advance); the fluid: setup.random_init_device(env, init_rng).  A field given to reset_from() is used as it is.
+        advance); the fluid draws the same way (n = B nv, pdec_fluid_ic_rng) unless an init_rng is given: then
+        setup.random_init_device(env, init_rng), the host's table.  A field given to reset_from() is used as it is.
+        A fluid environment must have the networks' dtype; its steps are never captured (use_graphs resolves to False).
 
         eval_every = N > 0: greedy held-out evaluation (module docstring) behind the last step of every episode whose 1-based
         number is a multiple of N -- one episode of episode_steps control steps, learning = 0, the policy's act_limit, on an
@@ -163,6 +165,14 @@ class TrainPipeline:
         without evaluations -- or "eval": the hook's rule on the evaluation scores (episode >= min_best_episode, score not
         NaN and >= every earlier such score), keeping the evaluated parameters.  Needs log_episodes > 0 (the snapshot lives
         in the ledger), episode_steps > 0 and no active reducer."""
+        # pdec_policy_act_rng_dev reads the state ring in the actor's type: a fluid environment of another dtype cannot step.
+        # Refused by name at the first run() / capture(), not here: an object of that combination may be constructed and asked
+        # for its episode-start draw (tests/test_gpu_pipeline_episodes.py::test_random_inits_fluid does).
+        self._dtype_refusal = None
+        if getattr(env, "is_fluid", False) and env.dtype != agent.policy.behavior_actor.model.dtype:
+            self._dtype_refusal = (f"TrainPipeline: the fluid environment ({env.dtype}) and the networks "
+                                   f"({agent.policy.behavior_actor.model.dtype}) must have one dtype: the acting kernel reads "
+                                   "the environment's state ring in the actor's type")
         self._check_eval_args(env, agent, episode_steps, stream_env, stream_upd, log_episodes, eval_every, eval_inits, eval_y0,
                               eval_capacity, eval_stream, best_by)
         self.env, self.agent, self.policy = env, agent, agent.policy
@@ -191,7 +201,10 @@ class TrainPipeline:
         # a recorded step / a graph holds POINTERS: policy.update must hand the ring tensors through unchanged, which it
         # does only when no dtype conversion makes a temporary (`.to(dt).contiguous()` is the identity then)
         self._batch_aliases = env.dtype == self.policy.behavior_critic.model.dtype
-        self.use_graphs = bool(use_graphs) and not self.use_replay and not self.multi_rank and self._batch_aliases
+        # (the fluid step forks its batch onto part streams and takes milliseconds: its steps are issued eagerly / from the
+        # recorded calls, never from a captured graph)
+        self.use_graphs = (bool(use_graphs) and not self.use_replay and not self.multi_rank and self._batch_aliases
+                           and not env.is_fluid)
         self.chunks = tuple(sorted({int(c) for c in chunks if c == 1 or c % PERIOD == 0} | {1}, reverse=True))
         setup, B = env.setup, env.B
         ns, A = setup.state_shape
@@ -433,7 +446,7 @@ class TrainPipeline:
             self.ledger = _Ledger(self.lib, env.handle, self.actor.handle if self.track_best else 0, self.log_episodes)
         self.random_init = bool(random_init)
         self.init_seed = int(init_seed)
-        self.init_rng = init_rng if init_rng is not None else np.random.default_rng(0)
+        self.init_rng = init_rng          # the fluid: None = the device draw of env.random_init, else random_init_device(env, rng)
         r, W = (int(v) for v in init_rank)
         if not 0 <= r < W:
             raise _lib.PdecError(f"TrainPipeline(init_rank={tuple(init_rank)}): rank r of W needs 0 <= r < W")
@@ -442,7 +455,7 @@ class TrainPipeline:
         self._init_ep = 0
         if self.random_init:
             if env.is_fluid:
-                if not hasattr(env.setup, "random_init_device"):
+                if init_rng is not None and not hasattr(env.setup, "random_init_device"):
                     raise _lib.PdecError("TrainPipeline(random_init=True): the setup has no random_init_device")
             elif not getattr(env.setup, "device_random_init", True):
                 raise _lib.PdecError("TrainPipeline(random_init=True): the setup has no device initialiser")
@@ -453,7 +466,7 @@ class TrainPipeline:
         """a new initial field into env.y0 and its features into state0, on the env stream (the first step of an episode)"""
         env = self.env
         with torch.cuda.stream(self.s_env):
-            if env.is_fluid:
+            if env.is_fluid and self.init_rng is not None:
                 env.y0.copy_(env.setup.random_init_device(env, self.init_rng))
             else:
                 r, W = self.init_rank
@@ -782,6 +795,8 @@ class TrainPipeline:
     def capture(self):
         """record the chunk graphs (needs >= 3 warm-up steps behind it so that every lazily created buffer exists and
         the update has transitions to train on); advances the run by len(chunks) periods of eager-equivalent steps"""
+        if self._dtype_refusal:
+            raise _lib.PdecError(self._dtype_refusal)
         self._check_key()
         if not self.use_graphs or self._captured:
             return
@@ -894,6 +909,8 @@ class TrainPipeline:
     def run(self, n):
         """issue n control steps (asynchronous: returns when they are enqueued)"""
         n = int(n)
+        if self._dtype_refusal:
+            raise _lib.PdecError(self._dtype_refusal)
         self._check_key()
         while n > 0:
             k = self.tick

@@ -184,6 +184,16 @@ int pdec_fluid_ic(pdec_handle h, const double* vortices, int nv, void* y_out);
  * one go.  An fp32 environment rounds the table once on the device.  y_out is bit for bit what pdec_fluid_ic writes for
  * the same table.  The table must stay valid until the stream has passed the call. */
 int pdec_fluid_ic_dev(pdec_handle h, const double* vortices_dev, int nv, void* y_out);
+/* ic(3) (caseno 3: nv = 30, training) / ic(4) (caseno 4: nv = 50, evaluation) with the random draws made on the device from
+ * the library's Philox4x32-10 stream (seed, offset) instead of by the caller; any other caseno is refused.  One kernel, one
+ * thread per (trajectory b, vortex v): counter offset + b nv + v, its four words w0..w3, u_i = (w_i + 0.5) 2^-32 in double
+ * (pdec_env_random_init's convention); table row (x0, y0, a0, U) = (u0 Lx, u1 Ly, a0, 2 u3 - 1) with a0 = Lx / 20 (case 3)
+ * or (Lx / 20) (0.5 + u2) (case 4).  One call consumes B nv counters, so W environments of B trajectories at offsets
+ * o + r B nv draw what one of W B draws at o.  The table [B][nv][4] of doubles lives in a device buffer allocated with the
+ * environment (no allocation, host copy or synchronisation in the call) and is also copied to vortices_out when that is not
+ * NULL (DEVICE pointer); then the launches of pdec_fluid_ic_dev on the environment's stream (an fp32 environment rounds the
+ * table once on the device): y_out is bit for bit pdec_fluid_ic_dev of that table. */
+int pdec_fluid_ic_rng(pdec_handle h, uint64_t seed, uint64_t offset, int caseno, double* vortices_out, void* y_out);
 
 /* error_detection of the fluid script (scripts/Fluid/setup/FluidSetup.jl:263-273) per trajectory, on the device:
  * w = real(ifft2(y[b])) through the library's own inverse passes (the sensing's), then errored_out[b] (device, int32 [B])
@@ -219,7 +229,11 @@ int pdec_env_step(pdec_handle h, const void* y_in, const void* action, const voi
 /* Optional extra output of pdec_env_step for the batched DDPG update: terminal_per_column
  * [B][A] (mono: [B][1]) of the plan's dtype, 1.0 on every actuator column of a trajectory that
  * blew up in this step (the `terminal` trace RL.jl fills per actuator, src/PDEagent.jl:284-288),
- * 0.0 otherwise.  NULL (default) disables it.  The pointer is read at each later pdec_env_step. */
+ * 0.0 otherwise.  NULL (default) disables it.  The pointer is read at each later pdec_env_step.
+ * The fluid environment writes the rows in its sensing launch (no further launch): the flag of check_max_value 2 as that
+ * launch reduces it, the flag of check_max_value 1 as the spectrum test left it (in a slot of the environment's own when
+ * done is NULL), zeros when the test is off; a batch stepped in parts writes each part's slice.  The rows go out with the
+ * rewards: pdec_env_step refuses a NULL reward_out, so every accepted step writes them. */
 int pdec_env_set_terminal_out(pdec_handle h, void* terminal_per_column);
 /* RHS evaluation for known-answer tests: out = f(y, p)    (KellerSegelSetup.jl:213-232) */
 int pdec_rhs_eval(pdec_handle h, const void* y, const void* p, void* out);
