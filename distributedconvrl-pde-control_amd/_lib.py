@@ -148,6 +148,7 @@ DEBUG_SIGNATURES = {
     "pdec_debug_small_update_kernel": [Handle, Handle, Handle, Handle, _i, _i, _d, _i, C.c_char_p, _i, C.POINTER(_i64)],
     "pdec_debug_batched_update_route": [Handle, Handle, Handle, Handle, _i, _i, C.c_char_p, _i, C.POINTER(_i64)],
     "pdec_debug_act_members_plan": [Handle, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i64)],
+    "pdec_debug_fluid_plan": [Handle, _pi32],
 }
 _RESTYPES = {"pdec_last_error": C.c_char_p}
 

@@ -692,7 +692,10 @@ __global__ __launch_bounds__(64 * TC >> (6 - LB)) void fluid_k2w_kernel(FluidDev
 //     barriers are raw (s_waitcnt lgkmcnt(0); s_barrier) -- __syncthreads() would drain the prefetch.
 //     (First cut: two field regions, outputs stored straight from the transform's registers -- 16-byte pieces of 64 different
 //     lines per instruction: 9.4 M partial-line writes per launch cost 23-34 us that no amount of overlap hid.)
-// Same arithmetic per column as K2w (bit-identical W2).
+// Same arithmetic per column as K2w, in the same order.  W2 is bit-identical to K2w's where the compiler contracts the two kernels'
+// multiply-adds alike: measured so in fp64 at n = 256 and 512 and in fp32 at n = 256; NOT in fp32 at n = 512
+// (<float,4,3,..>: 392 fused multiply-add lanes in K2w, 398 in K2p), where the right-hand sides differ by 1.6e-7 of max |rhs|
+// (2.6 units of 2^-24; tests/test_gpu_fluid_geometry.py holds both to the oracle and the difference to 16 units).
 __device__ __forceinline__ void k2p_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 template <int N>
 __device__ __forceinline__ void k2p_wait_but() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
@@ -1358,13 +1361,19 @@ static int fluid_integrate_wave(FluidEnv& Ev, const FluidDev<T>& d, void* f, con
 // (A HIP graph of the whole sub-step loop -- 8 K = 320 kernel nodes at the reference's own shape, one trajectory on the 128^2
 // grid -- was measured and dropped: 232 against 260 env-steps/s eager.  That loop is not launch-bound: its kernels run
 // 17-48 workgroups of ~10 us each on 256 CUs, HISTORY.md.)
-template <class T>
-static int fluid_integrate(FluidEnv& E, void* f, const void* phat) {
+// does fluid_integrate take the fused form (fluid_integrate_wave)?  Asked for by size or by PDEC_FLUID_FUSE, and served only where
+// a one-line-per-wave plan exists (line pairs: n >= 256); a grid that asks and has none takes the plain loop.
+static bool fluid_fused(const FluidEnv& E) {
   // measured (B = 16): n = 256: 650 -> 701 env-steps/s fused; n = 512: 76.6 -> 74.5 (the fused waves run six transforms
   // each and the stage's streaming phase no longer overlaps other waves' transforms) -> fused below 512 only
   static const char* fuse_env = getenv("PDEC_FLUID_FUSE");     // 1 / 0 force it on / off
   const bool fuse = fuse_env ? fuse_env[0] == '1' : (E.n >= 256 && E.n < 512);
-  if (fuse && E.n >= 256) {
+  return fuse && E.n >= 256 && E.wave_E != 0 && E.wave_LB == 6;
+}
+
+template <class T>
+static int fluid_integrate(FluidEnv& E, void* f, const void* phat) {
+  if (fluid_fused(E)) {
     const FluidDev<T> d = fluid_dev<T>(E);
     if (E.wave_E == 4 && E.wave_Q == 3) return fluid_integrate_wave<T, 4, 3, 6>(E, d, f, phat);
     if (E.wave_E == 4 && E.wave_Q == 2) return fluid_integrate_wave<T, 4, 2, 6>(E, d, f, phat);
@@ -1578,8 +1587,10 @@ static int fluid_make(std::unique_ptr<FluidEnv>& out, const pdec_env_cfg& c, int
   PDEC_REQUIRE(c.B >= 1 && n >= 8 && n % 4 == 0 && c.K >= 1, "pdec_fluid_env_create: bad sizes B=%d N=%d K=%d", c.B, n, c.K);
   PDEC_REQUIRE(c.S >= 1 && c.A >= 1 && c.sensors_per_axis >= 1 && c.sensors_per_axis * c.sensors_per_axis == c.S,
                "pdec_fluid_env_create: S must equal sensors_per_axis^2");
-  PDEC_REQUIRE(c.window >= 1 && (c.window & 1) && c.window <= c.sensors_per_axis && c.temporal_steps >= 1 && !c.mono,
-               "pdec_fluid_env_create: window must be odd and <= sensors_per_axis; no mono variant");
+  // (a window wider than the sensor grid is served: circshift wraps any shift (FluidSetup.jl:219-224), and fluid_feat_kernel
+  // reduces every offset modulo sensors_per_axis -- the window then visits a sensor more than once)
+  PDEC_REQUIRE(c.window >= 1 && (c.window & 1) && c.temporal_steps >= 1 && !c.mono,
+               "pdec_fluid_env_create: window must be odd; no mono variant");
   PDEC_REQUIRE(BH >= 1 && BW >= 1 && BH <= n && BW <= n, "pdec_fluid_env_create: bad box %dx%d", BH, BW);
   PDEC_REQUIRE(c.memory_size >= 0 && c.memory_size <= 64, "pdec_fluid_env_create: memory_size %d out of range", c.memory_size);
   PDEC_REQUIRE(c.Lx > 0 && c.dt > 0, "pdec_fluid_env_create: Lx and dt must be positive");
@@ -1852,4 +1863,18 @@ extern "C" int pdec_fluid_error_detection(pdec_handle h, const void* y, int32_t*
   // (a batch stepped in parts: the parent environment has work arrays of the whole batch of its own, fluid_make)
   return Ep->cfg.dtype == PDEC_F32 ? fluid_error_detection_t<float>(*Ep, y, errored_out)
                                    : fluid_error_detection_t<double>(*Ep, y, errored_out);
+}
+
+// Unit-test entry: the dispatch decisions of this environment, by the host code that dispatches; see include/pdeconv_debug.h
+extern "C" int pdec_debug_fluid_plan(pdec_handle h, int32_t* out12) {
+  FluidEnv* Ep = fluid_handle(h, "pdec_debug_fluid_plan");
+  if (!Ep) return PDEC_E_HANDLE;
+  PDEC_REQUIRE(out12, "pdec_debug_fluid_plan: null out12");
+  const FluidEnv& E = *Ep;
+  const bool k2p = k2p_eligible(E);
+  const int wave = E.wave_E != 0;
+  const int32_t plan[12] = {E.p, E.nl, E.TL, E.TLn, E.wave_E, E.wave_Q, wave ? E.wave_LB : 0, wave && E.n >= 256 ? 1 : 0,
+                            k2p ? 1 : 0, fluid_fused(E) ? 1 : 0, E.nparts, k2p ? E.cfg.B * (E.p / 8) : 0};
+  for (int i = 0; i < 12; ++i) out12[i] = plan[i];
+  return PDEC_OK;
 }

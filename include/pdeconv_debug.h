@@ -66,6 +66,15 @@ int pdec_debug_batched_update_route(pdec_handle actor, pdec_handle critic, pdec_
 int pdec_debug_act_members_plan(pdec_handle actor, int state_dtype, int cols_per_member, int* tile_cols, int* tiles,
                                 int64_t* lds_bytes);
 
+/* Unit-test entry (no reference counterpart): the dispatch decisions of a fluid environment (pdec_fluid_env_create), with the env
+ * switches as the process read them -- host code only, launches nothing.  out12 = { p (padded line length), nl (lines between the
+ * two inverse passes), TL, TLn (lines per LDS tile of the padded / the n x n passes), wave_E, wave_Q, wave_LB (the one-line-per-wave
+ * plan WaveFft<E, Q, LB> serving p; 0, 0, 0: the LDS-tile kernels serve it), pair (fluid_k1w_kernel takes a line and its mirror
+ * per wave), k2p (the persistent x-pass fluid_k2p_kernel, W tile-major), fused (do_step takes fluid_integrate_wave), nparts (parts
+ * the fused env step splits the batch into; 0: unsplit), x-pass tiles (B p / 8 workgroup tiles of fluid_k2p_kernel; 0 without it) }.
+ * Computed by the host code that dispatches (csrc/fluid.hip fluid_make, k2p_eligible, fluid_fused). */
+int pdec_debug_fluid_plan(pdec_handle env, int32_t* out12);
+
 #ifdef __cplusplus
 }
 #endif
