@@ -115,7 +115,7 @@ int rollout_members_persistent(Env& E, const std::vector<const Mlp*>& actors, in
   const int rct = roll_tab_upload(E, actors);
   if (rct) return rct;
   const RollMembers pm{E.roll_tab.as<const void*>(), K, A.dtype == PDEC_F32 ? 1 : 0};
-  const RollSpec greedy{T, 0, 0.0, act_limit, 0, 0};
+  const RollSpec greedy{T, 0, 0.0, act_limit, 0, 0, E.control_from};
   return E.cfg.pde_kind == PDEC_PDE_KS_CNAB2 ? ks_rollout_persistent(E, A, greedy, ptrs, &pm) : kseg_rollout_persistent(E, A, greedy, ptrs, &pm);
 }
 
@@ -213,7 +213,7 @@ int pdec_env_create(pdec_handle* h, const pdec_env_cfg* cfg, const double* senso
     E->lds_bytes = ks_lds_bytes(c, E->engine);
     PDEC_REQUIRE(E->lds_bytes <= 160 * 1024, "KS kernel needs %zu B of LDS (> 160 KiB)", E->lds_bytes);
     // per-mode constants, scripts/KS/setup/KSSetup.jl:115-123,131-135
-    std::vector<double> c1(N), c2(N), c3(N), c4(N), g(N), dh(2 * N), tw(2 * N), dist(N);
+    std::vector<double> c1(N), c2(N), c3(N), c4(N), g(N), dh(2 * N), dh1(2 * N), tw(2 * N), dist(N), dist1(N);
     const double hh = c.dt / c.K, dt2 = hh / 2, dt32 = 3 * hh / 2, dx = c.Lx / N;
     for (int k = 0; k < N; ++k) {
       double kx = k < N / 2 ? k : (k == N / 2 ? 0 : k - N);
@@ -223,7 +223,8 @@ int pdec_env_create(pdec_handle* h, const pdec_env_cfg* cfg, const double* senso
       c1[k] = Ainv * Bc; c2[k] = Ainv * dt32; c3[k] = Ainv * dt2; c4[k] = Ainv * hh; g[k] = -0.5 * al;
       tw[2 * k] = cos(2 * M_PI * k / N);
       tw[2 * k + 1] = -sin(2 * M_PI * k / N);
-      dist[k] = c.mu * cos(2 + M_PI + (dx * (k + 1)) / (c.Lx / 2));  // KSSetup.jl:155
+      dist1[k] = cos(2 + M_PI + (dx * (k + 1)) / (c.Lx / 2));        // KSSetup.jl:155
+      dist[k] = c.mu * dist1[k];
     }
     for (int k = 0; k < N; ++k) {  // O(N^2) host DFT, setup time only
       double re = 0, im = 0;
@@ -235,6 +236,16 @@ int pdec_env_create(pdec_handle* h, const pdec_env_cfg* cfg, const double* senso
         }
       dh[2 * k] = hh * re;
       dh[2 * k + 1] = hh * im;
+      // the same spectrum at mu = 1, scaled per trajectory in the kernels (pdec_env_set_disturbance): made here, so that the
+      // setter stores a pointer and nothing else
+      double re1 = 0, im1 = 0;
+      for (int n = 0; n < N; ++n) {
+        long long ph = ((long long)k * n) % N;
+        re1 += dist1[n] * tw[2 * ph];
+        im1 += dist1[n] * tw[2 * ph + 1];
+      }
+      dh1[2 * k] = hh * re1;
+      dh1[2 * k + 1] = hh * im1;
     }
     int rc;
     if ((rc = upload_converted(E->c1, c1.data(), N, c.dtype))) return rc;
@@ -243,6 +254,7 @@ int pdec_env_create(pdec_handle* h, const pdec_env_cfg* cfg, const double* senso
     if ((rc = upload_converted(E->c4, c4.data(), N, c.dtype))) return rc;
     if ((rc = upload_converted(E->g, g.data(), N, c.dtype))) return rc;
     if ((rc = upload_converted(E->dhat, dh.data(), 2 * N, c.dtype))) return rc;
+    if ((rc = upload_converted(E->dhat1, dh1.data(), 2 * N, c.dtype))) return rc;
     if ((rc = upload_converted(E->tw, tw.data(), 2 * N, c.dtype))) return rc;
   } else if (c.pde_kind == PDEC_PDE_KS_RK4_FD) {
     PDEC_REQUIRE(c.n_species == 1, "KS has one species");
@@ -359,6 +371,29 @@ int pdec_env_set_member_layout(pdec_handle h, int on) {
                "pdec_env_set_member_layout: the 1-D KS and Keller-Segel environments only (pde kind %d)", k);
   PDEC_REQUIRE(!on || !E->rsum_out, "pdec_env_set_member_layout: per-pair reward partials are set (pdec_env_set_reward_partials_out)");
   E->member = on != 0;
+  return PDEC_OK;
+}
+
+int pdec_env_set_disturbance(pdec_handle h, const void* mu_per_trajectory) {
+  GET_ENV(E, h);
+  const pdec_env_cfg& c = E->cfg;
+  if (mu_per_trajectory) {
+    PDEC_REQUIRE(c.pde_kind != PDEC_PDE_FLUID_RK4, "pdec_env_set_disturbance: the fluid has no disturbance term (KS environments only)");
+    PDEC_REQUIRE(c.pde_kind != PDEC_PDE_KSEG_RK4 && c.pde_kind != PDEC_PDE_KSEG2D_RK4,
+                 "pdec_env_set_disturbance: Keller-Segel has no disturbance term (KS environments only)");
+    PDEC_REQUIRE(c.pde_kind == PDEC_PDE_KS_CNAB2 || c.pde_kind == PDEC_PDE_KS_RK4_FD, "pdec_env_set_disturbance: pde kind %d is not a KS environment",
+                 c.pde_kind);
+    PDEC_REQUIRE(!c.mono, "pdec_env_set_disturbance: the global/mono agent's step has no disturbance term (KSglobalSetup.jl:167); "
+                          "per-actuator agents only");
+  }
+  E->mu_b = mu_per_trajectory;
+  return PDEC_OK;
+}
+
+int pdec_env_set_control_from(pdec_handle h, int n0) {
+  GET_ENV(E, h);
+  PDEC_REQUIRE(n0 >= 0, "pdec_env_set_control_from: n0 = %d is negative", n0);
+  E->control_from = n0;
   return PDEC_OK;
 }
 

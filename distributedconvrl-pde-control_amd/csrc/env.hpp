@@ -27,6 +27,8 @@ struct EnvDev {
   // KS CNAB2 per-mode constants
   const T *c1, *c2, *c3, *c4, *g;
   const C2<T>* dhat;     // h * fft(mu cos(...))
+  const C2<T>* dhat1;    // the same table at mu = 1 (pdec_env_set_disturbance: scaled per trajectory by mu_b)
+  const T* mu_b;         // optional [B]: per-trajectory disturbance amplitude in the place of cfg.mu (pdec_env_set_disturbance)
   const C2<T>* tw;       // exp(-2 pi i k/N)
   FftPlan fft;
   LaunchSync sync;       // pdec_set_launch_sync (SYNC instantiations of the fused KS step only)
@@ -64,7 +66,7 @@ struct StepArgs {
 
 struct Env : Object {
   pdec_env_cfg cfg;
-  DevBuf Gs, sn0, GaC, an0, gsum, a2s, fmap, c1, c2, c3, c4, g, dhat, tw;
+  DevBuf Gs, sn0, GaC, an0, gsum, a2s, fmap, c1, c2, c3, c4, g, dhat, dhat1, tw;
   int Wd = 0, Cnt = 0;
   DevBuf stage;  // staging for the _host wrappers
   DevBuf roll;   // ping-pong buffers of pdec_rollout
@@ -75,6 +77,8 @@ struct Env : Object {
   float* rsum_out = nullptr;
   bool share_simd = false;   // pdec_env_set_simd_sharing: launch the 64-VGPR form of the fused KS step
   bool member = false;       // pdec_env_set_member_layout: one KS trajectory per workgroup, the B = 1 launch's arithmetic
+  const void* mu_b = nullptr;   // pdec_env_set_disturbance: caller-owned device array [B] of the environment's dtype
+  int control_from = 0;         // pdec_env_set_control_from: the rollouts act from this step on (zero action before it)
   FftPlan fft;
   int nthreads = 64;
   KsEngine engine = KsEngine::Generic;   // PDEC_PDE_KS_CNAB2 only
@@ -121,6 +125,7 @@ EnvDev<T> make_dev(const Env& E) {
   e.rsum_out = E.rsum_out;
   e.c1 = E.c1.as<T>(); e.c2 = E.c2.as<T>(); e.c3 = E.c3.as<T>(); e.c4 = E.c4.as<T>(); e.g = E.g.as<T>();
   e.dhat = E.dhat.as<C2<T>>(); e.tw = E.tw.as<C2<T>>();
+  e.dhat1 = E.dhat1.as<C2<T>>(); e.mu_b = static_cast<const T*>(E.mu_b);
   e.fft = E.fft;
   e.member = E.member ? 1 : 0;
   return e;
@@ -152,7 +157,7 @@ size_t ksfd_lds_bytes(const pdec_env_cfg& c);
 // PDEC_E_INVALID without touching anything when it is not.
 struct Mlp;
 struct RollMembers;
-struct RollSpec { int steps, learning; double act_noise, act_limit; uint64_t seed, offset; };      // what the launch does
+struct RollSpec { int steps, learning; double act_noise, act_limit; uint64_t seed, offset; int control_from = 0; };      // what the launch does
 struct RollPtrs {       // its arrays as they cross the C ABI (pdec_rollout)
   void *y, *state, *action, *reward_sum, *log_y, *log_p, *log_action, *log_reward;
   int32_t *done_any, *done_step;

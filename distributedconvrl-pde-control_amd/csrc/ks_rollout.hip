@@ -62,14 +62,17 @@ __global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, 
   }
   C2<T> U[KS_MPT], Nn[KS_MPT], Ck[KS_MPT], v[KS_MPT];
   T kc1[KS_MPT], kc2[KS_MPT], kc3[KS_MPT], kg[KS_MPT], kc4[KS_MPT];
-  C2<T> kd[KS_MPT];
+  C2<T> kd[KS_MPT];      // (m0 + i m1) * dhat: the disturbance of both packed trajectories, each at its amplitude (ks_step.hip)
+  const C2<T>* __restrict__ dtab = e.mu_b ? e.dhat1 : e.dhat;
+  const T m0 = e.mu_b ? e.mu_b[b0] : (T)1, m1 = e.mu_b ? e.mu_b[has1 ? b1 : b0] : (T)1;
 #pragma unroll
   for (int j = 0; j < KS_MPT; ++j) {      // per-mode constants (mode layout of the engine) and the initial fields
     const int k = eng.mode_index(j);
     const bool ok = k < N;
     kc1[j] = ok ? e.c1[k] : (T)0; kc2[j] = ok ? e.c2[k] : (T)0; kc3[j] = ok ? e.c3[k] : (T)0;
     kc4[j] = ok ? e.c4[k] : (T)0; kg[j] = ok ? e.g[k] : (T)0;
-    kd[j] = ok ? e.dhat[k] : mk<T>(0, 0);
+    const C2<T> d = ok ? dtab[k] : mk<T>(0, 0);
+    kd[j] = mk<T>(m0 * d.x - m1 * d.y, m0 * d.y + m1 * d.x);
     const int n = eng.phys_index(j);
     U[j] = n < N ? mk<T>(g.y[o0 + n], has1 ? g.y[o1 + n] : (T)0) : mk<T>(0, 0);
   }
@@ -78,13 +81,18 @@ __global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, 
   __syncthreads();
 
   for (int t = 0; t < g.steps; ++t) {
-    // ---- policy (src/PDEagent.jl:183-207): one pair of adjacent columns of the [2][A] column space per thread
+    // ---- policy (src/PDEagent.jl:183-207): one pair of adjacent columns of the [2][A] column space per thread.  Before step
+    // control_from (pdec_env_set_control_from; plotting.jl:55-60) the action is zero: no actor, no noise, no reward summed
+    const bool ctl = t >= g.control_from;
     for (int q0 = 0; q0 < A; q0 += nt) {
       const int q = q0 + tid;
       if (q < A) {
         const int idx0 = 2 * q;
-        for (int i = 0; i < ns; ++i) hb[(size_t)i * nt + tid] = T2{stl[(size_t)idx0 * ns + i], stl[(size_t)(idx0 + 1) * ns + i]};
-        const T2 o2 = ro_actor_pair<T>(actor, wl, hb, tid, nt);
+        T2 o2 = T2{(T)0, (T)0};
+        if (ctl) {
+          for (int i = 0; i < ns; ++i) hb[(size_t)i * nt + tid] = T2{stl[(size_t)idx0 * ns + i], stl[(size_t)(idx0 + 1) * ns + i]};
+          o2 = ro_actor_pair<T>(actor, wl, hb, tid, nt);
+        }
         uint64_t cprev = ~0ull;
         double rad = 0, ang = 0;
         uint32_t ph[4];
@@ -92,7 +100,7 @@ __global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, 
         for (int s = 0; s < 2; ++s) {
           const int idx = idx0 + s, r = idx / A, a = idx - r * A;
           T o = s == 0 ? o2.x : o2.y;
-          if (!MEM && g.learning && (r == 0 || has1)) {
+          if (!MEM && ctl && g.learning && (r == 0 || has1)) {
             const uint64_t c = (uint64_t)(r == 0 ? b0 : b1) * A + a;          // global column = element of the noise stream
             if ((c >> 2) != cprev) {
               noise_block(ph, g.seed, g.offset + (uint64_t)t * ((cols + 3) / 4) + (c >> 2));
@@ -149,7 +157,7 @@ __global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, 
     eng.template run<-1>(v);
 #pragma unroll
     for (int j = 0; j < KS_MPT; ++j)
-      Ck[j] = mk<T>(kc4[j] * v[j].x + (kd[j].x - kd[j].y), kc4[j] * v[j].y + (kd[j].x + kd[j].y));
+      Ck[j] = mk<T>(kc4[j] * v[j].x + kd[j].x, kc4[j] * v[j].y + kd[j].y);
     // ---- do_step (KSSetup.jl:130-160): Nn = G fft(u^2), u_hat = fft(u), K CNAB2 sub-steps, y+ = real(ifft(u_hat))
 #pragma unroll
     for (int j = 0; j < KS_MPT; ++j) v[j] = mk<T>(U[j].x * U[j].x, U[j].y * U[j].y);
@@ -212,8 +220,10 @@ __global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, 
     }
     __syncthreads();
     for (int a = tid; a < A; a += nt) {
-      rsum[a] += rnow[a];
-      rsum[A + a] += rnow[A + a];
+      if (ctl) {
+        rsum[a] += rnow[a];
+        rsum[A + a] += rnow[A + a];
+      }
       if (g.log_reward) {
         g.log_reward[((size_t)t * e.B + b0) * A + a] = rnow[a];
         if (has1) g.log_reward[((size_t)t * e.B + b1) * A + a] = rnow[A + a];

@@ -20,7 +20,10 @@ namespace pdec {
 // SHARE (pdec_env_set_simd_sharing; fp32 single-wave engine only): the 64-VGPR form of the kernel, see below
 // SYNC (pdec_set_launch_sync; single-workgroup launches of the reference's own shapes): wait for the producer of the action
 // before anything is read, signal behind the last store -- a separate instantiation, so that the batched kernels keep their code
-template <class T, class ENG, bool FUSED, bool SHARE = false, bool SYNC = false>
+// MU (pdec_env_set_disturbance): the disturbance amplitude per trajectory -- likewise instantiations of their own: in the one code
+// path for both cases the register form of <float, FftWave256> took 98 VGPRs instead of 96 and its SIMD-sharing form spilled 20
+// instead of 15, and those two budgets are what lets the step run beside the update passes
+template <class T, class ENG, bool FUSED, bool SHARE = false, bool SYNC = false, bool MU = false>
 __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kernel(EnvDev<T> e, const T* __restrict__ y_in, const T* __restrict__ p_in,
                                    const T* __restrict__ action, const T* __restrict__ action_prev,
                                    const T* __restrict__ state_prev, T* __restrict__ y_out,
@@ -52,6 +55,12 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
   const int b0 = e.member ? (int)blockIdx.x : 2 * (int)blockIdx.x, b1 = b0 + 1;
   const bool has1 = !e.member && b1 < e.B;
   const size_t o0 = (size_t)b0 * N, o1 = (size_t)b1 * N;
+  // disturbance (KSSetup.jl:155): cfg.mu, baked into the table dhat -- or, with pdec_env_set_disturbance, an amplitude per trajectory
+  // on the table at mu = 1.  m0, m1 are uniform over the workgroup; a trajectory alone in it (the last of an odd batch, the member
+  // layout) fills the empty slot with its own amplitude, as its B = 1 launch does with cfg.mu
+  const C2<T>* __restrict__ dtab = MU ? e.dhat1 : e.dhat;
+  T m0 = 1, m1 = 1;
+  if constexpr (MU) { m0 = e.mu_b[b0]; m1 = e.mu_b[has1 ? b1 : b0]; }
 
   if (FUSED) {
     for (int a = tid; a < e.A; a += nt) {
@@ -112,10 +121,11 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
   for (int j = 0; j < KS_MPT; ++j) {
     const int k = eng.mode_index(j);
     if (k < N) {
-      const C2<T> d = e.dhat[k];
+      const C2<T> d = dtab[k];
       const T c4 = e.c4[k];
-      // (1+i)*dhat: the same real disturbance enters both packed trajectories
-      Ck[j] = mk<T>(c4 * v[j].x + (d.x - d.y), c4 * v[j].y + (d.x + d.y));
+      // (1+i)*dhat: the same real disturbance enters both packed trajectories; MU: (m0 + i m1) * dhat1, each at its amplitude
+      if constexpr (MU) Ck[j] = mk<T>(c4 * v[j].x + (m0 * d.x - m1 * d.y), c4 * v[j].y + (m0 * d.y + m1 * d.x));
+      else Ck[j] = mk<T>(c4 * v[j].x + (d.x - d.y), c4 * v[j].y + (d.x + d.y));
       kc1[j] = e.c1[k];
       kc2[j] = e.c2[k];
       kc3[j] = e.c3[k];
@@ -294,15 +304,17 @@ int ks_launch_step(Env& E, bool fused, const StepArgs& a, const LaunchSync& sync
     e.sync = sync;
     with_ks_engine<T>(E.engine, [&](auto tag) {
       using ENG = typename decltype(tag)::type;
-      auto kern = fused ? ks_env_step_kernel<T, ENG, true> : ks_env_step_kernel<T, ENG, false>;
+      const bool mu = E.mu_b != nullptr;      // pdec_env_set_disturbance: the MU instantiation of whichever form is launched
+      auto kern = fused ? (mu ? ks_env_step_kernel<T, ENG, true, false, false, true> : ks_env_step_kernel<T, ENG, true>)
+                        : (mu ? ks_env_step_kernel<T, ENG, false, false, false, true> : ks_env_step_kernel<T, ENG, false>);
       size_t lds = E.lds_bytes;
       if constexpr (sizeof(T) == 4 && ks_is_single_wave(decltype(tag)::kind))   // SHARE: the 64-VGPR form + its lane-private
         if (fused && E.share_simd) {                                           // constant slots (8 float4 per lane, 16-byte aligned)
-          kern = ks_env_step_kernel<T, ENG, true, true>;
+          kern = mu ? ks_env_step_kernel<T, ENG, true, true, false, true> : ks_env_step_kernel<T, ENG, true, true>;
           lds += 16 + 8 * 16 * 64;
         }
       if constexpr (sizeof(T) == 8 && ks_is_fixed_plan(decltype(tag)::kind))    // SYNC (launch_step has checked the rest)
-        if (synced) kern = ks_env_step_kernel<T, ENG, true, false, true>;
+        if (synced) kern = mu ? ks_env_step_kernel<T, ENG, true, false, true, true> : ks_env_step_kernel<T, ENG, true, false, true>;
       if (timed) {
         PDEC_TIMED_LAUNCH(&E, "ks_env_step", kern, grid, block, lds, PDEC_STEP_KERNEL_ARGS(T, e, a));
         return;

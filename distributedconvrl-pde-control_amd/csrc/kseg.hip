@@ -182,10 +182,11 @@ __global__ void __launch_bounds__(NT) kseg_rollout_kernel(EnvDev<T> e, RollActor
   for (int t = 0; t < g.steps; ++t) {
     // ---- policy (src/PDEagent.jl:183-207): the A actuator columns share the weights (per-actuator agents); one thread per
     // (actuator, output unit) and layer, k-ordered accumulation like the oracle's W * x + b
+    const bool ctl = t >= g.control_from;     // pdec_env_set_control_from: zero action, no noise, no reward summed before it
     {
       const T* in = stl;
       int istride = ns, off = 0;
-      for (int l = 0; l < actor.L; ++l) {
+      for (int l = 0; ctl && l < actor.L; ++l) {
         const int din = actor.dims[l], dout = actor.dims[l + 1], fn = actor.acts[l];
         T* out = hb + (size_t)(l & 1) * A * RO_W;
         const T* Wt = wl + off;
@@ -200,8 +201,8 @@ __global__ void __launch_bounds__(NT) kseg_rollout_kernel(EnvDev<T> e, RollActor
         off += (din + 1) * RO_W;
       }
       for (int a = tid; a < A; a += nt) {
-        T o = in[a * RO_W];
-        if (!MEM && g.learning) {
+        T o = ctl ? in[a * RO_W] : (T)0;
+        if (!MEM && ctl && g.learning) {
           const uint64_t c = (uint64_t)b * A + a;                          // global column = element of the noise stream
           o += (T)noise_normal(g.seed, g.offset + (uint64_t)t * ((cols + 3) / 4), c) * g.act_noise;
         }
@@ -256,7 +257,7 @@ __global__ void __launch_bounds__(NT) kseg_rollout_kernel(EnvDev<T> e, RollActor
     { T* sw = stl; stl = stn; stn = sw; }
     __syncthreads();
     for (int a = tid; a < A; a += nt) {
-      rsum[a] += rnow[a];
+      if (ctl) rsum[a] += rnow[a];
       if (g.log_reward) g.log_reward[((size_t)t * e.B + b) * A + a] = rnow[a];
     }
     __syncthreads();

@@ -83,7 +83,8 @@ __global__ void ksfd_env_step_kernel(EnvDev<T> e, const T* __restrict__ y_in, co
     p = p_in[yo + n];
   }
   // forcing = actuation + disturbance mu cos(2 + pi + x/(Lx/2)), x = dx (n+1)   (KSSetup.jl:36,155)
-  const T force = p + (live ? e.dist_mu * (T)cos(2.0 + 3.14159265358979323846 + (double)e.dx * (n + 1) / ((double)e.dx * N / 2)) : (T)0);
+  const T mu = e.mu_b ? e.mu_b[b] : e.dist_mu;      // pdec_env_set_disturbance: this trajectory's amplitude
+  const T force = p + (live ? mu * (T)cos(2.0 + 3.14159265358979323846 + (double)e.dx * (n + 1) / ((double)e.dx * N / 2)) : (T)0);
   const T i2dx = (T)0.5 / e.dx, idx2 = (T)1 / (e.dx * e.dx), idx4 = idx2 * idx2;
   if (MODE == 2) {
     const T f = ksfd_rhs<T>(u, force, su, n, N, i2dx, idx2, idx4, live);
@@ -199,13 +200,14 @@ __global__ void __launch_bounds__(64) ksfd_wave_step_kernel(EnvDev<T> e, const T
     actp[a] = action_prev[(size_t)b * e.A + a];
   }
   __syncthreads();
+  const T mu = e.mu_b ? e.mu_b[b] : e.dist_mu;      // pdec_env_set_disturbance: this trajectory's amplitude
 #pragma unroll
   for (int c = 0; c < CPL; ++c) {
     const int n = n0 + c;
     const T p = actuate_cell<T>(e, act, n);
     if (p_out) p_out[yo + n] = p;
     // forcing = actuation + disturbance mu cos(2 + pi + x/(Lx/2)), x = dx (n+1)   (KSSetup.jl:36,155)
-    force[c] = p + e.dist_mu * (T)cos(2.0 + 3.14159265358979323846 + (double)e.dx * (n + 1) / ((double)e.dx * N / 2));
+    force[c] = p + mu * (T)cos(2.0 + 3.14159265358979323846 + (double)e.dx * (n + 1) / ((double)e.dx * N / 2));
   }
   const T i2dx = (T)0.5 / e.dx, idx2 = (T)1 / (e.dx * e.dx), idx4 = idx2 * idx2, h = e.hstep;
   for (int it = 0; it < e.K; ++it) {

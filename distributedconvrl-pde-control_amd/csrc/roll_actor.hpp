@@ -28,6 +28,7 @@ struct RollArgs {
   T* reward_sum;                           // optional [B][A]: += every step's reward
   T *log_y, *log_p, *log_action, *log_reward;   // optional [steps][B][...]
   int32_t *done_any, *done_step;           // optional [B]
+  int control_from;                        // pdec_env_set_control_from: steps t < control_from take the zero action, unrewarded
 };
 
 template <class T>
@@ -144,7 +145,7 @@ inline RollActor make_roll_actor(const Mlp& A) {
 template <class T>
 RollArgs<T> make_roll_args(const RollSpec& s, const RollPtrs& p) {
   return RollArgs<T>{s.steps, s.learning, (T)s.act_noise, (T)s.act_limit, s.seed, s.offset, (T*)p.y, (T*)p.state, (T*)p.action,
-                     (T*)p.reward_sum, (T*)p.log_y, (T*)p.log_p, (T*)p.log_action, (T*)p.log_reward, p.done_any, p.done_step};
+                     (T*)p.reward_sum, (T*)p.log_y, (T*)p.log_p, (T*)p.log_action, (T*)p.log_reward, p.done_any, p.done_step, s.control_from};
 }
 // dynamic LDS of a rollout workgroup: the step kernel's (E.lds_bytes) + state, rewards, the actor image and its activation
 // planes (KS: [2][rows] column pairs per thread; Keller-Segel: [2][A][RO_W])

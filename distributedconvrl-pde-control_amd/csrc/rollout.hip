@@ -55,13 +55,17 @@ static int rollout_step_loop(pdec_handle henv, Env* E, int T, void* y, void* sta
   if (done_step) PDEC_HIP(hipMemsetAsync(done_step, 0xFF, sizeof(int32_t) * c.B, E->stream));
   int cur = 0;
   for (int t = 0; t < T; ++t) {
-    int rc = act(t, (const void*)sb[cur], (void*)ab[cur ^ 1]);
+    // before step control_from (pdec_env_set_control_from) the zero action in the place of the acting call, unrewarded
+    const bool ctl = t >= E->control_from;
+    int rc = PDEC_OK;
+    if (ctl) rc = act(t, (const void*)sb[cur], (void*)ab[cur ^ 1]);
+    else PDEC_HIP(hipMemsetAsync(ab[cur ^ 1], 0, nact, E->stream));
     if (rc) return rc;
     rc = pdec_env_step(henv, yb[cur], ab[cur ^ 1], ab[cur], sb[cur], yb[cur ^ 1], pb, sb[cur ^ 1], rb, db);
     if (rc) return rc;
     cur ^= 1;
     const size_t nrew = nr / ts;
-    if (reward_sum) {
+    if (reward_sum && ctl) {
       if (c.dtype == PDEC_F64)
         hipLaunchKernelGGL(rollout_accum_kernel<double>, dim3((unsigned)((nrew + 255) / 256)), dim3(256), 0, E->stream, nrew,
                            (const double*)rb, (double*)reward_sum);
@@ -100,7 +104,7 @@ extern "C" int pdec_rollout(pdec_handle henv, pdec_handle hactor, int T, void* y
   const int ns = env_ns(c), cols = c.B * (c.mono ? 1 : c.A), na = A->dims[A->L];
   PDEC_REQUIRE(A->dims[0] == (c.mono ? c.S : ns) && cols * na == c.B * c.A * env_na(c),
                "pdec_rollout: actor shape %d -> %d does not match the state/action matrices", A->dims[0], na);
-  const RollSpec spec{T, learning, act_noise, act_limit, seed, offset};
+  const RollSpec spec{T, learning, act_noise, act_limit, seed, offset, E->control_from};
   const RollPtrs ptrs{y, state, action, reward_sum, log_y, log_p, log_action, log_reward, done_any, done_step};
   // KS: the whole loop in ONE persistent launch -- the trajectories stay in registers / LDS between steps and the actor is
   // evaluated in the kernel (csrc/ks_rollout.hip: ks_rollout_kernel); reward_sum accumulates, the logs are written per step

@@ -139,6 +139,8 @@ class PDEenv:
         self.steps, self.time = 0, 0.0
         self.autoreset = (self.B > 1) if autoreset is None else bool(autoreset)
         self._state0 = torch.empty(self._sshape, **kw)
+        self.mu = None                  # set_disturbance: the per-trajectory amplitudes the library reads (kept alive here)
+        self._control_from = 0
         self.reset()
 
     # ---- helpers
@@ -389,15 +391,39 @@ class PDEenv:
         _lib.check(self.lib.pdec_env_set_simd_sharing(self.handle, 1 if on else 0, C.byref(eff)))
         return bool(eff.value)
 
+    def set_disturbance(self, mu):
+        """Per-trajectory amplitude of the KS disturbance mu cos(2 + pi + x / (Lx / 2)) (KSSetup.jl:155) in the place of the
+        setup's scalar mu (pdec_env_set_disturbance): `mu` a tensor or array [B], converted once to the environment's dtype and
+        device and kept alive by this object (env.mu; writing into it changes what later steps read), or None to return to
+        setup.mu.  Trajectory b then steps as an environment created at mu[b] would.  KS setups with per-actuator agents
+        only; resets and autoreset leave it alone (it belongs to the batch slot, not to the episode)."""
+        if mu is None:
+            _lib.check(self.lib.pdec_env_set_disturbance(self._h, None))
+            self.mu = None
+            return
+        with _on_stream(self.stream):
+            t = mu if isinstance(mu, torch.Tensor) else torch.as_tensor(np.array(mu, dtype=np.float64, copy=True))
+            if t.dim() != 1 or int(t.shape[0]) != self.B:
+                raise _lib.PdecError(f"PDEenv.set_disturbance: expected {self.B} amplitudes (one per trajectory), got shape "
+                                     f"{tuple(t.shape)}")
+            t = t.to(device=self.device, dtype=self.dtype).contiguous().clone()
+        _lib.check(self.lib.pdec_env_set_disturbance(self._h, _lib.ptr(t)))
+        self.mu = t
+
     # ---- T control steps without returning to the host (SURVEY.md §8f row F2)
-    def rollout(self, actor, T, act_noise=0.0, act_limit=1.0, learning=False, seed=0, offset=0, log=False):
+    def rollout(self, actor, T, act_noise=0.0, act_limit=1.0, learning=False, seed=0, offset=0, log=False, control_from=0):
         """for t in 1:T; action = policy(env); env(action); end  (src/PDEagent.jl:175-209 + src/PDEenv.jl:195-241)
         enqueued in ONE library call: actor forward (+ exploration noise when `learning`), clamp, fused env step,
         device-side reward accumulation and -- with log=True -- the per-step rows PDEhook records
         (src/PDEhook.jl:54-62).  `actor` is a HipMLP of the environment's dtype on the environment's stream.
         Returns device tensors: reward_sum [B, A], done_step [B] (first step that raised `done`, -1 = none) and the logs
-        y [T, ...], p, action, reward.  env.y / state / action / steps / time advance by T steps."""
+        y [T, ...], p, action, reward.  env.y / state / action / steps / time advance by T steps.
+        control_from = n0 > 0 (plot_heat's p_t_action, src/plotting.jl:55-60): the steps t < n0 take the zero action -- no
+        actor, no noise -- and reward_sum adds the steps t >= n0 only; logs and done_step cover all T steps."""
         T = int(T)
+        if int(control_from) != self._control_from:
+            _lib.check(self.lib.pdec_env_set_control_from(self._h, int(control_from)))
+            self._control_from = int(control_from)
         kw = dict(dtype=self.dtype, device=self.device)
         with _on_stream(self.stream):
             out = dict(reward_sum=torch.zeros((self.B, self.setup.reward_len), **kw),

@@ -231,7 +231,7 @@ def act_members_tiles(C, maxw, itemsize):
 
 
 def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, dtype=torch.float64, stream=None, act_limit=1.0,
-                    log=False, device="cuda:0"):
+                    log=False, device="cuda:0", mu=None, control_from=0):
     """One greedy evaluation episode of each of M actors (HipMLPs or approximators of ONE shape) from the same K initial fields:
     `y0` [K, ...] in the environment's memory layout, or -- None -- n_inits fields drawn once with env.random_init from the
     Philox stream (init_seed, 0).  `steps` defaults to one episode (te / dt + 1, as testrun).  The environment of
@@ -245,12 +245,27 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
     Returns episode_reward [M, K] (mean over actuators of the summed reward, PDEhook's figure), reward_sum [M, K, A],
     done_step [M, K] (device tensors), score [M] (numpy; NaN: a trajectory blew up or is not finite), order (best first, NaN
     last, ties by index), one_launch, workgroups (of the one launch; None otherwise), batched (True: the one step loop of the
-    2-D setups; False on the other two routes) and with log=True the rows y, p, action, reward [T, M, K, ...]."""
-    models = [_model(a) for a in actors]
-    M = len(models)
+    2-D setups; False on the other two routes) and with log=True the rows y, p, action, reward [T, M, K, ...].
+    Robustness (scripts/KS/KS200_disturbed/KS200_disturbed.jl at batch scale; KS setups): `mu`, a sequence of n_mu disturbance
+    amplitudes, evaluates every actor at every amplitude on the same K fields -- the environment has B = M * n_mu * K
+    trajectories, member m's block laid out [n_mu][K], each (member, amplitude) block of K trajectories its own entry of the
+    launch's actor table (so KS is still ONE launch, and a block's numbers are bit for bit those of the call with that single
+    amplitude) -- and `control_from` = n0 leaves the first n0 steps uncontrolled and unrewarded (PDEenv.rollout).  The result
+    then carries episode_reward [M, n_mu, K], reward_sum [M, n_mu, K, A], done_step [M, n_mu, K], score [M, n_mu] (the NaN rule
+    per (member, amplitude)), mu (numpy) and order by the mean of score over the amplitudes (NaN if any of them is NaN); the
+    log rows are [T, M, n_mu, K, ...].  mu=None: the shapes above, setup.mu everywhere."""
+    members = [_model(a) for a in actors]
+    M = len(members)
     if M < 1:
         raise _lib.PdecError("evaluate_actors: needs at least one actor")
-    for m, md in enumerate(models):
+    mus = None if mu is None else [float(x) for x in np.asarray(mu, dtype=np.float64).reshape(-1)]
+    if mus is not None and not mus:
+        raise _lib.PdecError("evaluate_actors: mu is empty")
+    n_mu = 1 if mus is None else len(mus)
+    control_from = int(control_from)
+    models = [md for md in members for _ in range(n_mu)]       # one entry per (member, amplitude) block of K trajectories
+    M_members, M = M, M * n_mu
+    for m, md in enumerate(members):
         if list(md.dims) != list(models[0].dims) or list(md.acts) != list(models[0].acts):
             raise _lib.PdecError(f"evaluate_actors: member {m}'s actor shape {list(md.dims)} / activations differ from member 0's "
                                  f"{list(models[0].dims)}: all members must have the same shape")
@@ -271,6 +286,10 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
         if _has_persistent_rollout(setup) or _has_batched_rollout(setup):
             env = PDEenv(setup, B=M * K, dtype=dtype, device=device, y0=y0.repeat((M,) + (1,) * (y0.dim() - 1)), stream=stream,
                          autoreset=False)
+            if mus is not None:
+                env.set_disturbance(torch.tensor(mus, dtype=torch.float64).repeat_interleave(K).repeat(M_members))
+            if control_from:
+                _lib.check(env.lib.pdec_env_set_control_from(env.handle, control_from))
     B = M * K
     s_env = stream if stream is not None else torch.cuda.current_stream(dev)
     others = {}
@@ -310,10 +329,13 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
             small.set_y0(y0)
         cols = K * setup.state_shape[1]
         parts = []
-        for md in models:
-            actor = md if (md.dtype == small.dtype and md.max_cols >= cols) else md.clone(dtype=small.dtype, max_cols=cols)
+        for v, md in enumerate(models):
+            if v % n_mu == 0:
+                actor = md if (md.dtype == small.dtype and md.max_cols >= cols) else md.clone(dtype=small.dtype, max_cols=cols)
+            if mus is not None:
+                small.set_disturbance(torch.full((K,), mus[v % n_mu], dtype=torch.float64))
             small.reset()
-            parts.append(small.rollout(actor, T, act_limit=act_limit, learning=False, log=log))
+            parts.append(small.rollout(actor, T, act_limit=act_limit, learning=False, log=log, control_from=control_from))
         with _on_stream(stream):
             out = {k: torch.cat([p_[k] for p_ in parts], dim=0 if k in ("reward_sum", "done_step") else 1)
                    for k in (("reward_sum", "done_step") + (("y", "p", "action", "reward") if log else ()))}
@@ -325,6 +347,17 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
                 res[k] = out[k].view((T, M, K) + tuple(out[k].shape[2:]))
         host = (res["episode_reward"].double().cpu().numpy(), res["done_step"].cpu().numpy())     # (waits for the stream)
     res["score"], res["order"] = score_members(*host)
+    if mus is not None:
+        with _on_stream(stream):
+            for k in ("reward_sum", "done_step", "episode_reward"):
+                res[k] = res[k].view((M_members, n_mu) + tuple(res[k].shape[1:]))
+            for k in ("y", "p", "action", "reward"):
+                if k in res:
+                    res[k] = res[k].view((T, M_members, n_mu) + tuple(res[k].shape[2:]))
+        res["score"] = res["score"].reshape(M_members, n_mu)
+        res["mu"] = np.asarray(mus, dtype=np.float64)
+        mean = res["score"].mean(axis=1)                  # NaN if any amplitude's score is
+        res["order"] = sorted(range(M_members), key=lambda m: (bool(np.isnan(mean[m])), -mean[m] if not np.isnan(mean[m]) else 0.0, m))
     res["one_launch"], res["batched"] = one, batched
     is_ks = one and tuple(setup.y_shape) == (setup.nx,)      # (served: a setup with a persistent rollout, so no 2-D one)
     res["workgroups"] = (len(member_workgroups(M, K)) if is_ks else B) if one else None

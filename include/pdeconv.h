@@ -552,6 +552,25 @@ int pdec_env_random_init_members(pdec_handle env, const uint64_t* seeds, const u
  * trajectory per workgroup instead of two per complex FFT, so trajectory b's outputs are bit for bit those of a B = 1 step
  * on its inputs, whatever the other trajectories hold (the 1-D Keller-Segel step already runs one per workgroup). */
 int pdec_env_set_member_layout(pdec_handle env, int on);
+/* Robustness runs (scripts/KS/KS200_disturbed/KS200_disturbed.jl:16: an agent trained at mu = 0, evaluated at mu = 0.02): the
+ * amplitude of the KS disturbance mu cos(2 + pi + x / (Lx / 2)) (KSSetup.jl:155) per trajectory instead of the creation-time
+ * scalar cfg.mu.  mu_per_trajectory: a device array [B] of the environment's dtype, owned by the caller and read by every later
+ * step or rollout launch on the environment's stream (the call itself stores the pointer and neither copies nor synchronises,
+ * so launches recorded or captured afterwards follow later writes to the array); NULL returns to cfg.mu.  Trajectory b then steps
+ * as an environment created with cfg.mu = mu[b] steps it: CNAB2 adds mu[b] h fft(cos(...)) -- the table at mu = 1, made at
+ * creation, scaled per packed pair -- and the finite-difference steps add mu[b] cos(...) to the forcing, where an array of equal
+ * values is bit for bit the scalar.  It belongs to the batch slot, not to the episode: pdec_env_autoreset leaves it alone.
+ * Served for the KS environments with per-actuator agents (PDEC_PDE_KS_CNAB2 with every FFT engine, both step forms, the member
+ * layout and the persistent rollouts; PDEC_PDE_KS_RK4_FD with both integrators).  Refused for the global/mono agent
+ * (KSglobalSetup.jl:167 has no such term), for 1-D and 2-D Keller-Segel and for the fluid.  The acting-only closures
+ * (pdec_actuate, pdec_featurize, pdec_reward) do not depend on it. */
+int pdec_env_set_disturbance(pdec_handle env, const void* mu_per_trajectory);
+/* Delayed control (src/plotting.jl:55-60, plot_heat(p_t_action = ...): uncontrolled until t = p_t_action, then the actor
+ * engages), a sticky setting read by pdec_rollout and pdec_rollout_members in all their forms; n0 = 0 (the default) is off.
+ * For the steps t < n0 the action is exactly zero -- no actor evaluation, no exploration noise -- and reward_sum adds only the
+ * steps t >= n0 (the uncontrolled prefix is the same whatever the actor).  The noise numbering per step is unchanged, so the
+ * steps t >= n0 draw what they draw with n0 = 0; the log rows, done_any and done_step cover all T steps. */
+int pdec_env_set_control_from(pdec_handle env, int n0);
 
 /* ---------------------------------------------------------------- populations of single-trajectory learners
  * M independent reference-shaped DDPG learners (B = 1, small-batch update with device-side sampling, glue launch) whose

@@ -173,6 +173,16 @@ function set_simd_sharing(h::UInt64, on::Bool)
     eff[] != 0
 end
 
+# robustness runs (scripts/KS/KS200_disturbed/KS200_disturbed.jl): the amplitude of the KS disturbance per trajectory -- mu a device
+# array [B] of the environment's dtype (device_upload) that the caller keeps alive, C_NULL returns to cfg.mu -- and the control
+# step from which rollout! / rollout_members! engage the actor (plot_heat's p_t_action; zero action and no reward before it)
+function set_disturbance(h::UInt64, mu::Ptr{Cvoid})
+    check(ccall((:pdec_env_set_disturbance, LIB), Cint, (UInt64, Ptr{Cvoid}), h, mu))
+end
+function set_control_from(h::UInt64, n0::Integer)
+    check(ccall((:pdec_env_set_control_from, LIB), Cint, (UInt64, Cint), h, n0))
+end
+
 # 2-D fluid: gaussians[i] are the `sparse` thresholded bumps of scripts/Fluid/setup/FluidSetup.jl:139-161, passed as
 # the dense BW x BH box around the periodic support of each (boxes [S][BW][BH], origin (j0, i0), 0-based)
 function fluid_env_create(cfg::EnvCfg, BH, BW, sensor_boxes, sensor_origin, actuator_boxes, actuator_origin, a2s)
