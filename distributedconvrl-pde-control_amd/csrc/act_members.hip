@@ -5,7 +5,7 @@
 // it is ONE sequence at B = M K: member m's block of C = K A state columns is driven by member m's actor, taken from the
 // pointer table the environment owns (Env::roll_tab), and the env step that follows serves all M K trajectories at once.
 //
-// Arithmetic: small_act_body's (mlp.hip), which is gemm_kernel's -- per output element acc = 0, acc += (T)W[j][k] x[k] in
+// Arithmetic: small_act_body's (act.hip), which is gemm_kernel's -- per output element acc = 0, acc += (T)W[j][k] x[k] in
 // ascending k, + (T)b[j], apply_act<T>, and after the last layer the clamp to +-act_limit -- so a member's actions are bit for
 // bit those of pdec_policy_act_rng (greedy) on its block alone through either of those two routes.  Greedy only: the
 // exploration noise of the solo call is numbered by global column, a member's stream is not defined.

@@ -1,4 +1,7 @@
-// mlp.hpp -- the MLP object shared by mlp.hip (generic path) and mlp_mfma.hip (fp32 MFMA path)
+// mlp.hpp -- the MLP object, what every acting path and every ADAM kernel share (activations, the exploration-noise stream, the
+// beta powers) and the table of a fused DDPG kernel family.  For every file that holds an Mlp*: mlp.hip (generic path), ddpg.hip
+// (DDPG passes and their routing), act.hip (acting), mlp_mfma.hip / mlp_mfma2.hip (the two fused families), and the rollout,
+// replay, ledger, communicator and population files
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -48,85 +51,12 @@ struct Mlp : Object {
 
   Mlp() : Object(Kind::Mlp) {}
   int init(int dtype, int L, const int32_t* dims, const int32_t* acts, int max_cols);
-  template <class T>
+  // in the net's dtype (mlp.hip)
   int pack(const void* s1, int n1, int l1, const void* s2, int n2, int l2, int cols);
-  template <class T>
   int forward(int cols);
-  template <class T>
   int backward(const void* dy, int ldy, int cols, bool want_dw, bool want_dx, double grad_scale);
   template <class T>
   T* dy_buf(int) { return dy.as<T>(); }
-};
-
-// ---- populations (pdec_population_create, population.py): M independent single-trajectory learners whose per-step launches
-// are ONE launch of M workgroups each.  Workgroup m reads member m's pointers from a device table (PopMember) and its counters
-// from row m of a device int64 table that the host writes once per episode and reads back once per episode.
-#define POP_ROW 16
-enum PopSlot {
-  POP_USTEP = 0,    // policy.update_step
-  POP_NSA,          // trajectory.n_sa
-  POP_NRT,          // trajectory.n_rt
-  POP_NOISE,        // policy._noise_off (Philox counters of the exploration noise)
-  POP_SAMPLE,       // policy._sample_off (Philox counters of the minibatch draws)
-  POP_HALT,         // the member's episode halt flag (low 32 bits; pdec_set_episode_halt's protocol)
-  POP_ACTIVE,       // 1: the member runs this episode (0: its stop condition has fired)
-  POP_BPA,          // slot of the actor's / critic's double-buffered ADAM beta powers (Mlp::bp_sel)
-  POP_BPC,
-  POP_NOISE_AMP,    // act_noise, act_limit (bit patterns of doubles)
-  POP_LIMIT,
-};
-// a member's own hyper-parameters (bit patterns of doubles), read by the small update's prologue (sm_member_begin) when
-// pdec_population_set_member_hyper is on; with it off the launch-wide values of pdec_population_create hold and the slots are
-// not read.  Slot 15 stays free.
-enum PopHyperSlot {
-  POP_GAMMA = 11,   // policy.y
-  POP_RHO,          // policy.rho_effective
-  POP_ETA_A,        // behaviour actor's / critic's ADAM step size
-  POP_ETA_C,
-};
-// ---- a member's book (pdec_population_episode_close, csrc/pop_book.hip): what its PDEhook and its stop condition hold between
-// two episodes, so that the episode boundary needs no host.  A caller-owned device table int64 [M][POP_BOOK] beside the rows,
-// doubles as bit patterns; population.py mirrors the names (tests/test_population_blocks_host.py compares them).
-#define POP_BOOK 16
-enum PopBookSlot {
-  PBK_EP = 0,        // hook.ep: index of the episode that is running (the close increments it)
-  PBK_MIN_BEST,      // hook.min_best_episode
-  PBK_COLLECT_NNA,   // hook.collect_NNA (0 / 1)
-  PBK_CMP_HAS,       // 1: rewards_compare is not empty
-  PBK_CMP,           // Python's max(rewards_compare) (double): the first element unless a later one compared greater
-  PBK_BESTREWARD,    // hook.bestreward (double)
-  PBK_BESTEPISODE,   // hook.bestepisode
-  PBK_STOP_KIND,     // 0: StopAfterEpisode, 1: StopAfterEpisodeWithMinSteps
-  PBK_STOP_CUR,      // the stop object's cur
-  PBK_STOP_LIMIT,    // its episode / step
-  PBK_RANDOM_INIT,   // hook.use_random_init (0 / 1)
-  PBK_INIT_SEED,     // hook.init_seed
-  PBK_INIT_OFF,      // hook._init_off: Philox offset of the member's NEXT initial field
-  PBK_INIT_INC,      // ceil(coefficients / 4): what one drawn field consumes
-  PBK_FIRED,         // phase 0 -> phase 1 of one close: the stop condition fired in this episode
-  PBK_SPARE,
-};
-// the episode log of a block, int64 [E][M][POP_ELOG]: one entry per member and episode
-#define POP_ELOG 4
-enum PopElogSlot {
-  PEL_REWARD = 0,    // the episode reward (double)
-  PEL_STEPS,         // executed control steps n (0: the member was idle)
-  PEL_NEW_BEST,      // 1: the episode is the member's new best
-  PEL_RAN,           // 1: the member ran this episode
-};
-struct PopMember {
-  const void* actor_p;                         // behaviour actor parameters (acting)
-  float *ts, *ta, *tr, *tt;                     // replay traces: state, action, reward, terminal
-  uint64_t noise_seed, sample_seed;
-  float *Ap, *Ag, *Am, *Av, *Apt, *Cp, *Cg, *Cm, *Cv, *Cpt;   // the small update's learner state
-  double *bpA, *bpC;                            // [2][2] beta powers
-  float* losses;                                // [2]
-};
-// one destination of pdec_population_clone: member `dst` takes over member `src`'s learner; bp*: the CURRENT beta-power slots
-// (Mlp::bp_sel) of the two members' actors / critics, rows_*: the replay rows that go along (0: the destination keeps its replay)
-struct PopClone {
-  int src, dst, bpa_src, bpc_src, bpa_dst, bpc_dst;
-  long long rows_sa, rows_rt;
 };
 
 // the activations of a Dense layer, as every forward pass of the library applies them (gemm_kernel's epilogue, the acting kernels)
@@ -143,13 +73,19 @@ __device__ __forceinline__ float apply_act<float>(float z, int act) {
   return z;
 }
 
-// ---- acting for few columns (mlp.hip: small_act_kernel) and its member form (act_members.hip: act_members_kernel)
+static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ---- acting for few columns (act.hip: small_act_kernel) and its member form (act_members.hip: act_members_kernel)
 #define SMALL_ACT_MAXL 4                 // layers the two kernels take
 #define SMALL_ACT_LDS (48 * 1024)        // bytes of LDS they allow themselves: two activation buffers [widest layer][columns]
 int mlp_maxw(const Mlp* M);              // the widest layer, input included
-// would pdec_policy_act_rng on `cols` states of M take a fused MFMA acting kernel (act_route: ACT_FUSED3 / ACT_FUSED2)?  Those sum
-// in another order than small_act_kernel / gemm_kernel do.
-bool act_route_is_fused(const Mlp* M, int cols);
+// what serves pdec_policy_act_rng for `cols` states where no fused family does (act.hip)
+enum ActRoute { ACT_GENERIC = 0, ACT_SMALL };
+ActRoute act_route(const Mlp* M, int cols);
+// n normals of the stream (seed, offset) into dst on o's stream (mlp.hip: randn_kernel); ctr_cur != null: the device-resident
+// counter of pdec_policy_act_rng_dev, see FusedFamily::policy_act
+int launch_randn(Object* o, void* dst, size_t n, int dtype, uint64_t seed, uint64_t offset, const uint64_t* ctr_cur,
+                 uint64_t* ctr_next, uint64_t ctr_inc);
 
 // Philox4x32-10 counter-based generator (the exploration noise that replaces randn(rng), src/PDEagent.jl:201)
 __device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t k1) {
@@ -219,72 +155,55 @@ int reward_group_route(Mlp* C, const void* r, int Bu, int quirk, CriticRoute* ou
 template <int N>
 using tile_c = std::integral_constant<int, N>;
 
-// mlp_mfma.hip: fused fp32 MFMA DDPG passes (3-layer actor/critic pairs)
 struct AdamPolyak {
   double eta, b1, b2, eps, rho;
 };
-bool fused_supported(const Mlp* A, const Mlp* C);
+// ---- a fused DDPG kernel family: fp32 MFMA passes, apply and acting kernels for one class of actor / critic pairs.  Two exist:
+// fused3_family (mlp_mfma.hip: 3-layer pairs on padded weight images) and fused2_family (mlp_mfma2.hip: the reference-shaped
+// 2-layer nets [ns, h, 1] / [ns+1, H, 1] on the flat parameters).  ddpg.hip and act.hip pick one through the selectors below and
+// call through the table; null = the generic path.
+struct FusedFamily {
+  bool (*pair_ok)(const Mlp* A, const Mlp* C);   // the passes serve this actor / critic pair
+  bool (*net_ok)(const Mlp* M);                  // adam_polyak serves this net
+  bool (*act_ok)(const Mlp* M, int cols);        // policy_act serves `cols` states of this actor
+  int apply_min_bu;                              // pdec_ddpg_update_async applies ADAM + Polyak in the finish launch from this batch on
+  // apply != nullptr: the slab reduction also performs ADAM on the network, Polyak into its target and refreshes
+  // the padded weight images (single-GPU path: no all-reduce between gradient and update)
+  int (*critic_grads)(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const void* a, const void* r, const void* t,
+                      const void* sn, int Bu, double gamma, int quirk, double grad_scale, void* loss_dev,
+                      const AdamPolyak* apply, const void* loss_add);
+  int (*actor_grads)(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
+                     const AdamPolyak* apply);
+  int (*adam_polyak)(Mlp* M, Mlp* Mt, const AdamPolyak& ap);
+  // ctr_cur != null: the noise offset is *ctr_cur (+ offset) and one thread writes *ctr_next = that + ctr_inc
+  int (*policy_act)(Mlp* A, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
+                    uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc);
+  // kernel name and dynamic LDS bytes of the pass / acting launch the functions above would make (nothing is launched)
+  int (*describe)(const Mlp* A, const Mlp* C, bool actor_pass, char* name, int name_len, int64_t* lds);
+  int (*act_describe)(const Mlp* A, char* name, int name_len, int64_t* lds);
+};
+extern const FusedFamily fused3_family, fused2_family;
+// the family that serves a pair's passes / a net's apply / an acting call, asked in the order 3-layer, 2-layer (ddpg.hip)
+const FusedFamily* fused_family_of_pair(const Mlp* A, const Mlp* C);
+const FusedFamily* fused_family_of_net(const Mlp* M);
+const FusedFamily* fused_family_of_act(const Mlp* M, int cols);
+// would pdec_policy_act_rng on `cols` states of M take a fused MFMA acting kernel?  Those sum in another order than
+// small_act_kernel / gemm_kernel do.
+inline bool act_route_is_fused(const Mlp* M, int cols) { return fused_family_of_act(M, cols) != nullptr; }
+
+// features of the 3-layer image, not of "a family" (mlp_mfma.hip): the net predicate (stop / reduce events, reward partials) and
+// the flat parameters of the published image the next acting kernel reads (fw_pub[pub]), enqueued on `stream`
 bool fused_net_supported(const Mlp* M);
-// apply != nullptr: the slab reduction also performs ADAM on the network, Polyak into its target and refreshes
-// the padded weight images (single-GPU path: no all-reduce between gradient and update)
-int fused_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const void* a, const void* r, const void* t,
-                       const void* sn, int Bu, double gamma, int quirk, double grad_scale, void* loss_dev,
-                       const AdamPolyak* apply, const void* loss_add = nullptr);
-int fused_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
-                      const AdamPolyak* apply);
-int fused_adam_polyak(Mlp* M, Mlp* Mt, const AdamPolyak& ap);
-// flat parameters of the published image the next acting kernel reads (fw_pub[pub]), enqueued on `stream`
 int fused_unpack_published(Mlp* A, float* flat_out, hipStream_t stream);
-// ctr_cur != null: the noise offset is *ctr_cur (+ offset) and one thread writes *ctr_next = that + ctr_inc
-int fused_policy_act(Mlp* A, const void* state, int cols, double act_noise, double act_limit, int learning,
-                     uint64_t seed, uint64_t offset, void* actions_out, const uint64_t* ctr_cur = nullptr,
-                     uint64_t* ctr_next = nullptr, uint64_t ctr_inc = 0);
-
-// kernel name and dynamic LDS bytes of the pass / acting launch the functions above would make (nothing is launched)
-int fused_describe(const Mlp* A, const Mlp* C, bool actor_pass, char* name, int name_len, int64_t* lds);
-int fused_act_describe(const Mlp* A, char* name, int name_len, int64_t* lds);
-
-// mlp_mfma2.hip: the same passes for the reference-shaped 2-layer nets [ns, h, 1] / [ns+1, H, 1] (flat parameters, no image)
 // mean of r[0..n) in a fixed order, one block; *out = device scalar owned by C (mlp_mfma2.hip)
 int launch_rmean(Mlp* C, const float* r, int n, float** out);
-bool fused2_supported(const Mlp* A, const Mlp* C);
-bool fused2_net_supported(const Mlp* M);
-bool fused2_act_supported(const Mlp* A, int cols);
-int fused2_policy_act(Mlp* A, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
-                      uint64_t offset, void* actions_out, const uint64_t* ctr_cur = nullptr, uint64_t* ctr_next = nullptr,
-                      uint64_t ctr_inc = 0);
-int fused2_adam_polyak(Mlp* M, Mlp* Mt, const AdamPolyak& ap);
-int fused2_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const void* a, const void* r, const void* t,
-                        const void* sn, int Bu, double gamma, int quirk, double grad_scale, void* loss_dev,
-                        const AdamPolyak* apply, const void* loss_add = nullptr);
-int fused2_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
-                       const AdamPolyak* apply);
-
-int fused2_describe(const Mlp* A, const Mlp* C, bool actor_pass, char* name, int name_len, int64_t* lds);
-int fused2_act_describe(const Mlp* A, char* name, int name_len, int64_t* lds);
-
-struct Population : Object {
-  int M = 0, cols = 0, dtype = PDEC_F64;
-  std::vector<Mlp*> A, C, At, Ct;
-  DevBuf tab;                        // PopMember [M]
-  DevBuf clones;                     // PopClone [M] (pdec_population_clone)
-  DevBuf snap;                       // float* [M][2]: the hooks' best / current actor parameters (pdec_population_set_actor_copies)
-  std::vector<Mlp*> snap_nets;       // (their objects: a copy makes their derived images stale)
-  long long* rows = nullptr;         // [M][POP_ROW] (the caller's device buffer)
-  long long cap = 0, cap1 = 0, after = 0, freq = 1, start_steps = 0;
-  int stride = 0, loops = 1, Bu = 1, quirk = 0;
-  double gamma = 0.99, rho = 1.0, eta_a = 0, eta_c = 0;   // member 0's at creation: they select the kernel, and hold for
-  int member_hyper = 0;                                    // every member unless member_hyper (pdec_population_set_member_hyper)
-  Population() : Object(Kind::Population) {}
-};
 
 }  // namespace pdec
 
-// the population behind handle h at an entry point (the GET_MLP of populations; here because mlp.hip and mlp_small.hip
-// both have population entry points)
-#define GET_POP(P, h)                                                           \
-  pdec::Population* P = pdec::lookup_as<pdec::Population>(h, pdec::Kind::Population); \
-  if (!P) {                                                                     \
-    pdec::set_error("%s: bad handle", __func__);                                \
-    return PDEC_E_HANDLE;                                                       \
+// the network behind handle h at an entry point
+#define GET_MLP(M, h)                                            \
+  pdec::Mlp* M = pdec::lookup_as<pdec::Mlp>(h, pdec::Kind::Mlp); \
+  if (!M) {                                                      \
+    pdec::set_error("%s: not an mlp handle", __func__);          \
+    return PDEC_E_HANDLE;                                        \
   }

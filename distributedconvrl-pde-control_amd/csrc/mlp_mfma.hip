@@ -1013,7 +1013,7 @@ bool fused_net_supported(const Mlp* M) {
   return mt == 9 || mt == 2 || mt == 1;
 }
 
-bool fused_supported(const Mlp* A, const Mlp* C) {
+static bool fused_supported(const Mlp* A, const Mlp* C) {
   if (fused_disabled()) return false;
   if (A->dtype != PDEC_F32 || C->dtype != PDEC_F32) return false;
   if (A->L != 3 || C->L != 3) return false;
@@ -1245,6 +1245,12 @@ int fused_unpack_published(Mlp* A, float* flat_out, hipStream_t stream) {
   return PDEC_OK;
 }
 
+// a 3-layer fp32 actor whose published image the fused acting kernel reads, at any number of columns
+#define FUSED3_ACT_MAX_H 31
+static bool fused_act_ok(const Mlp* M, int) {
+  return fused_net_supported(M) && M->dims[M->L] == 1 && M->dims[1] <= FUSED3_ACT_MAX_H;
+}
+
 // tiles and dynamic LDS bytes of the acting kernel of a fused 3-layer actor, or the refusal
 static int fused_act_plan(const Mlp* A, int* mta, size_t* lds) {
   *mta = mt_of(A->dims[1]);
@@ -1255,8 +1261,8 @@ static int fused_act_plan(const Mlp* A, int* mta, size_t* lds) {
   return PDEC_OK;
 }
 
-int fused_policy_act(Mlp* A, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
-                     uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc) {
+static int fused_policy_act(Mlp* A, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
+                            uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc) {
   int rc = ensure_prepped(A);
   if (rc) return rc;
   FNet f = fnet_of(A);
@@ -1285,7 +1291,7 @@ int fused_policy_act(Mlp* A, const void* state, int cols, double act_noise, doub
   return PDEC_OK;
 }
 
-int fused_act_describe(const Mlp* A, char* name, int name_len, int64_t* lds_out) {
+static int fused_act_describe(const Mlp* A, char* name, int name_len, int64_t* lds_out) {
   int mta = 0;
   size_t lds = 0;
   if (int rc = fused_act_plan(A, &mta, &lds)) return rc;
@@ -1297,15 +1303,15 @@ int fused_act_describe(const Mlp* A, char* name, int name_len, int64_t* lds_out)
 }
 
 // ADAM(M) + Polyak(Mt <- M) + image refresh from the gradient buffer (after an external all-reduce)
-int fused_adam_polyak(Mlp* M, Mlp* Mt, const AdamPolyak& ap) {
+static int fused_adam_polyak(Mlp* M, Mlp* Mt, const AdamPolyak& ap) {
   int rc;
   if ((rc = ensure_prepped(M)) || (Mt && (rc = ensure_prepped(Mt)))) return rc;
   return launch_finish(M, Mt, nullptr, 0, mt_of(M->dims[1]), 1.0, 0, 1, 0, nullptr, &ap);
 }
 
-int fused_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const void* a, const void* r, const void* t,
-                       const void* sn, int Bu, double gamma, int quirk, double grad_scale, void* loss_dev,
-                       const AdamPolyak* apply, const void* loss_add) {
+static int fused_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const void* a, const void* r, const void* t,
+                              const void* sn, int Bu, double gamma, int quirk, double grad_scale, void* loss_dev,
+                              const AdamPolyak* apply, const void* loss_add) {
   int rc;
   if ((rc = ensure_prepped(C)) || (rc = ensure_prepped(At)) || (rc = ensure_prepped(Ct))) return rc;
   const int mt = mt_of(C->dims[1]), mta = mt_of(A->dims[1]);
@@ -1338,7 +1344,7 @@ int fused_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const vo
 
 // what fused_critic_grads / fused_actor_grads would launch for this pair (pdec_debug_batched_update_route): through the same
 // visitor and the same lds_bytes<> as launch_critic / launch_actor
-int fused_describe(const Mlp* A, const Mlp* C, bool actor_pass, char* name, int name_len, int64_t* lds) {
+static int fused_describe(const Mlp* A, const Mlp* C, bool actor_pass, char* name, int name_len, int64_t* lds) {
   if (int rc = split_refused()) return rc;
   return visit_tiles(mt_of(C->dims[1]), mt_of(A->dims[1]), [&](auto MT, auto MTA) {
     constexpr int mt_ = decltype(MT)::value, mta_ = decltype(MTA)::value;
@@ -1348,8 +1354,8 @@ int fused_describe(const Mlp* A, const Mlp* C, bool actor_pass, char* name, int 
   });
 }
 
-int fused_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
-                      const AdamPolyak* apply) {
+static int fused_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
+                             const AdamPolyak* apply) {
   int rc;
   if ((rc = ensure_prepped(C)) || (rc = ensure_prepped(A)) || (apply && At && (rc = ensure_prepped(At)))) return rc;
   const int mt = mt_of(C->dims[1]), mta = mt_of(A->dims[1]);
@@ -1369,5 +1375,13 @@ int fused_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double gra
   (void)C;
   return launch_finish(A, apply ? At : nullptr, A->fslab.as<float>(), grid, mta, grad_scale, 1, Bu, 0, loss_dev, apply);
 }
+
+// the finish launch of a pass applies ADAM + Polyak at every batch size.  (Host pass only: the device pass would emit a const
+// table as a constant of the code object, and these are addresses of host functions.)
+#ifndef __HIP_DEVICE_COMPILE__
+const FusedFamily fused3_family = {fused_supported,    fused_net_supported, fused_act_ok,      0,
+                                   fused_critic_grads, fused_actor_grads,   fused_adam_polyak, fused_policy_act,
+                                   fused_describe,     fused_act_describe};
+#endif
 
 }  // namespace pdec

@@ -776,7 +776,7 @@ static bool fused2_disabled() {
   return v == 1;
 }
 
-bool fused2_supported(const Mlp* A, const Mlp* C) {
+static bool fused2_supported(const Mlp* A, const Mlp* C) {
   if (fused2_disabled()) return false;
   if (A->dtype != PDEC_F32 || C->dtype != PDEC_F32 || A->L != 2 || C->L != 2) return false;
   const int ns = A->dims[0];
@@ -900,7 +900,7 @@ static int launch_finish2(Mlp* M, Mlp* Mt, int nslab, int MT, int nR, double gra
 }
 
 // 2-layer fp32 actor [ns, h, 1] (relu, tanh | identity), h <= 31, ns <= 48, at least a few hundred columns
-bool fused2_act_supported(const Mlp* A, int cols) {
+static bool fused2_act_supported(const Mlp* A, int cols) {
   if (fused2_disabled() || A->dtype != PDEC_F32 || A->L != 2 || A->dims[2] != 1 || cols < 256) return false;
   if (A->acts[0] != PDEC_ACT_RELU || (A->acts[1] != PDEC_ACT_TANH && A->acts[1] != PDEC_ACT_IDENTITY)) return false;
   return A->dims[0] <= 8 * K2MAX && mt2_of(A->dims[1]) <= 2;
@@ -909,8 +909,8 @@ bool fused2_act_supported(const Mlp* A, int cols) {
 template <int MTA, int KB>
 static size_t act2_lds() { return (size_t)lds2_floats(16 * MTA, 8 * KB + 4) * 4; }
 
-int fused2_policy_act(Mlp* A, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
-                      uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc) {
+static int fused2_policy_act(Mlp* A, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
+                             uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc) {
   const Net2 n = net2_of(A);
   const int mta = mt2_of(A->dims[1]), tanh_out = A->acts[1] == PDEC_ACT_TANH;
   const dim3 grid((cols + 63) / 64), block(256);
@@ -927,7 +927,7 @@ int fused2_policy_act(Mlp* A, const void* state, int cols, double act_noise, dou
   return PDEC_OK;
 }
 
-int fused2_act_describe(const Mlp* A, char* name, int name_len, int64_t* lds) {
+static int fused2_act_describe(const Mlp* A, char* name, int name_len, int64_t* lds) {
   return visit2_act(net2_of(A).kb, mt2_of(A->dims[1]), [&](auto MTA, auto KB) {
     constexpr int mta_ = decltype(MTA)::value, kb_ = decltype(KB)::value;
     snprintf(name, name_len, "policy_act2_kernel<%d,%d>", mta_, kb_);
@@ -936,9 +936,9 @@ int fused2_act_describe(const Mlp* A, char* name, int name_len, int64_t* lds) {
   });
 }
 
-bool fused2_net_supported(const Mlp* M) { return !fused2_disabled() && M->dtype == PDEC_F32 && M->L == 2; }
+static bool fused2_net_supported(const Mlp* M) { return !fused2_disabled() && M->dtype == PDEC_F32 && M->L == 2; }
 
-int fused2_adam_polyak(Mlp* M, Mlp* Mt, const AdamPolyak& ap) {
+static int fused2_adam_polyak(Mlp* M, Mlp* Mt, const AdamPolyak& ap) {
   Finish2Args g{};
   g.grads = M->grads.as<float>();
   g.apply = 1;
@@ -972,9 +972,9 @@ int launch_rmean(Mlp* C, const float* r, int n, float** out) {
   return PDEC_OK;
 }
 
-int fused2_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const void* a, const void* r, const void* t,
-                        const void* sn, int Bu, double gamma, int quirk, double grad_scale, void* loss_dev,
-                        const AdamPolyak* apply, const void* loss_add) {
+static int fused2_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const void* a, const void* r, const void* t,
+                               const void* sn, int Bu, double gamma, int quirk, double grad_scale, void* loss_dev,
+                               const AdamPolyak* apply, const void* loss_add) {
   const int mt = mt2_of(C->dims[1]), mta = mt2_of(A->dims[1]), nR = nr_of(C->dims[0]);
   int tpw = 8;
   const int grid = grid2_of(Bu, &tpw);
@@ -999,8 +999,8 @@ int fused2_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, const v
   return launch_finish2(C, apply ? Ct : nullptr, grid, mt, nR, grad_scale, 0, Bu, quirk, loss_dev, apply, loss_add);
 }
 
-int fused2_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
-                       const AdamPolyak* apply) {
+static int fused2_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
+                              const AdamPolyak* apply) {
   const int mt = mt2_of(C->dims[1]), mta = mt2_of(A->dims[1]), nRa = nr_of(A->dims[0]);
   int tpw = 8;
   const int grid = grid2_of(Bu, &tpw);
@@ -1017,7 +1017,7 @@ int fused2_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double gr
 
 // what fused2_critic_grads / fused2_actor_grads would launch for this pair (pdec_debug_batched_update_route): the networks go
 // into the arguments as they do there, then the same visitor and the same LDS check as launch2
-int fused2_describe(const Mlp* A, const Mlp* C, bool actor_pass, char* name, int name_len, int64_t* lds) {
+static int fused2_describe(const Mlp* A, const Mlp* C, bool actor_pass, char* name, int name_len, int64_t* lds) {
   Fused2Args g{};
   g.C = net2_of(C); g.A = net2_of(A);
   return visit2_pass(g, mt2_of(C->dims[1]), mt2_of(A->dims[1]), [&](auto MT, auto MTA, auto KB) {
@@ -1029,6 +1029,14 @@ int fused2_describe(const Mlp* A, const Mlp* C, bool actor_pass, char* name, int
     return (int)PDEC_OK;
   });
 }
+
+// below FUSED2_APPLY_MIN_BU columns the passes are the same kernels and ADAM / Polyak are launches of their own
+#define FUSED2_APPLY_MIN_BU 64
+#ifndef __HIP_DEVICE_COMPILE__        // (a host table: see fused3_family, mlp_mfma.hip)
+const FusedFamily fused2_family = {fused2_supported,    fused2_net_supported, fused2_act_supported, FUSED2_APPLY_MIN_BU,
+                                   fused2_critic_grads, fused2_actor_grads,   fused2_adam_polyak,   fused2_policy_act,
+                                   fused2_describe,     fused2_act_describe};
+#endif
 
 }  // namespace pdec
 

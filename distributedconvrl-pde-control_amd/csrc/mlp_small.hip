@@ -10,7 +10,7 @@
 // waves share the CU's L1, so a barrier orders them), activations in LDS.  fp32 like the reference's networks, ADAM
 // arithmetic in fp64 like Flux (see finish_param in mlp_mfma.hip).
 #include "common.hpp"
-#include "mlp.hpp"
+#include "population.hpp"
 
 namespace pdec {
 

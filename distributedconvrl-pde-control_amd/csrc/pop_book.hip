@@ -3,10 +3,10 @@
 //
 // Between two episodes of a member the host does a handful of scalar rules: PDEhook's POST_EPISODE bookkeeping
 // (src/PDEhook.jl:65-97), the stop condition (src/StopCondition.jl:6-40), the agent's POST_EPISODE push and PRE_EPISODE pop
-// (src/PDEagent.jl:215-252, :291-314).  Here they run on the member's book (enum PopBookSlot, mlp.hpp) and its counter row, so a
+// (src/PDEagent.jl:215-252, :291-314).  Here they run on the member's book (enum PopBookSlot, population.hpp) and its counter row, so a
 // block of episodes is enqueued without a read-back between them.
 #include "common.hpp"
-#include "mlp.hpp"
+#include "population.hpp"
 
 namespace pdec {
 

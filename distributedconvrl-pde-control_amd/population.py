@@ -27,13 +27,13 @@ from .pipeline import _Event
 from .run import (StopAfterEpisode, StopAfterEpisodeWithMinSteps, _EpisodeLogs, _add_episode_reward, _episode_schedule,
                   _episode_steps, _episode_time, _executed_steps, _join, _stop_fired, device_episodes_ok)
 
-# a member's row of the device counter table: POP_ROW and enum PopSlot of csrc/mlp.hpp (tests/test_host_logic.py compares them)
+# a member's row of the device counter table: POP_ROW and enum PopSlot of csrc/population.hpp (tests/test_host_logic.py compares them)
 ROW = 16
 USTEP, NSA, NRT, NOISE, SAMPLE, HALT, ACTIVE, BPA, BPC, NOISE_AMP, LIMIT = range(11)
-# a member's own gamma, rho and ADAM step sizes (bit patterns of doubles): enum PopHyperSlot of csrc/mlp.hpp; slot 15 is free
+# a member's own gamma, rho and ADAM step sizes (bit patterns of doubles): enum PopHyperSlot of csrc/population.hpp; slot 15 is free
 GAMMA, RHO, ETA_A, ETA_C = range(11, 15)
 # a member's book -- what its hook and its stop condition hold between two episodes -- and the episode log of a block:
-# POP_BOOK / enum PopBookSlot and POP_ELOG / enum PopElogSlot of csrc/mlp.hpp (tests/test_population_blocks_host.py compares them)
+# POP_BOOK / enum PopBookSlot and POP_ELOG / enum PopElogSlot of csrc/population.hpp (tests/test_population_blocks_host.py compares them)
 BOOK = 16
 (BK_EP, BK_MIN_BEST, BK_COLLECT_NNA, BK_CMP_HAS, BK_CMP, BK_BESTREWARD, BK_BESTEPISODE, BK_STOP_KIND, BK_STOP_CUR, BK_STOP_LIMIT,
  BK_RANDOM_INIT, BK_INIT_SEED, BK_INIT_OFF, BK_INIT_INC, BK_FIRED, BK_SPARE) = range(BOOK)

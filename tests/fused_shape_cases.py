@@ -88,7 +88,6 @@ def read_constants(csrc=CSRC):
     m3 = open(os.path.join(csrc, "mlp_mfma.hip")).read()
     m2 = open(os.path.join(csrc, "mlp_mfma2.hip")).read()
     blocks = open(os.path.join(csrc, "mfma_blocks.hpp")).read()
-    mlp = open(os.path.join(csrc, "mlp.hip")).read()
 
     def define(src, name):
         return int(re.search(rf"^#define {name} (\d+)\b", src, flags=re.M).group(1))
@@ -101,8 +100,8 @@ def read_constants(csrc=CSRC):
          "T2": xlist(m2, "FUSED2_TILES"), "A2": [t[0] for t in xlist(m2, "FUSED2_ACT_TILES")],
          "KB2": [t[0] for t in xlist(m2, "FUSED2_KBS")]}
     k["ACT2_MIN_COLS"] = int(re.search(r"bool fused2_act_supported\(.*?cols < (\d+)\)", m2, flags=re.S).group(1))
-    k["APPLY2_MIN_BU"] = int(re.search(r"rt == ROUTE_FUSED2 && Bu >= (\d+)", mlp).group(1))
-    k["ACT3_MAX_H"] = int(re.search(r"bool fused_act_ok\(.*?dims\[1\] <= (\d+)", mlp, flags=re.S).group(1))
+    k["APPLY2_MIN_BU"] = define(m2, "FUSED2_APPLY_MIN_BU")
+    k["ACT3_MAX_H"] = define(m3, "FUSED3_ACT_MAX_H")
     return k
 
 

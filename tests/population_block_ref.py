@@ -3,7 +3,7 @@ statement per rule.  tests/test_population_blocks_host.py checks it against the 
 tests/test_gpu_population_blocks.py checks the launch against it, bit for bit."""
 import numpy as np
 
-# slots of a member's counter row, its book and the episode log (csrc/mlp.hpp: PopSlot, PopBookSlot, PopElogSlot)
+# slots of a member's counter row, its book and the episode log (csrc/population.hpp: PopSlot, PopBookSlot, PopElogSlot)
 USTEP, NSA, NRT, NOISE, SAMPLE, HALT, ACTIVE = range(7)
 (EP, MIN_BEST, COLLECT_NNA, CMP_HAS, CMP, BESTREWARD, BESTEPISODE, STOP_KIND, STOP_CUR, STOP_LIMIT, RANDOM_INIT, INIT_SEED,
  INIT_OFF, INIT_INC, FIRED, SPARE) = range(16)

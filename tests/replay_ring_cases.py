@@ -1,5 +1,5 @@
 """The case table of test_gpu_replay_ring.py: the trajectory glue of csrc/replay.hip (replay_push2_kernel, replay_push_rt_kernel,
-replay_sample_kernel, autoreset_kernel), the same pushes inside csrc/mlp.hip's step_glue_kernel and the slot table of
+replay_sample_kernel, autoreset_kernel), the same pushes inside csrc/act.hip's step_glue_kernel and the slot table of
 csrc/mlp_small.hip, at the seams of the two rings -- away from the one geometry the shipped runs use (ns = na = 1, stride = A = 8,
 a capacity that is a multiple of the push).  Imports neither torch nor numpy (numpy only inside the functions that draw data), so
 test_replay_ring_table.py can hold the table against its claims on a machine without a GPU.

@@ -1,5 +1,5 @@
 """GPU tests of the trajectory glue at its seams: csrc/replay.hip (replay_push2_kernel, replay_push_rt_kernel, replay_sample_kernel,
-autoreset_kernel), the pushes of csrc/mlp.hip's step_glue_kernel and the slot table of csrc/mlp_small.hip, every row of
+autoreset_kernel), the pushes of csrc/act.hip's step_glue_kernel and the slot table of csrc/mlp_small.hip, every row of
 replay_ring_cases.py against the plain model of replay_ring_ref.py.  These kernels copy, cast fp64 -> fp32 and do integer
 arithmetic, so every comparison is exact (np.array_equal; NaN positions by mask where NaNs are planted).
 test_replay_ring_table.py holds the table's claims and shows that each comparison rejects the mistake it is there for."""

@@ -767,10 +767,10 @@ def test_executed_steps_rule(pkg):
 
 
 def test_population_slot_table_equals_the_device_enum(pkg):
-    """population.py's ROW and slot names are POP_ROW and enum PopSlot of csrc/mlp.hpp, in order"""
+    """population.py's ROW and slot names are POP_ROW and enum PopSlot of csrc/population.hpp, in order"""
     import importlib
     pop = importlib.import_module(pkg.__name__ + ".population")
-    hpp = open(os.path.join(ROOT, "distributedconvrl-pde-control_amd", "csrc", "mlp.hpp")).read()
+    hpp = open(os.path.join(ROOT, "distributedconvrl-pde-control_amd", "csrc", "population.hpp")).read()
     assert pop.ROW == int(re.search(r"#define POP_ROW (\d+)", hpp).group(1))
     body = re.sub(r"//.*", "", re.search(r"enum PopSlot \{(.*?)\};", hpp, re.S).group(1))
     names = [n.strip() for n in body.split(",") if n.strip()]

@@ -231,9 +231,9 @@ def test_block_length_against_stepping_the_stop_classes(pkg, kind):
 
 def test_book_slot_tables_equal_the_device_enums(pkg):
     """population.py's BOOK / BK_* and ELOG / EL_* are POP_BOOK / enum PopBookSlot and POP_ELOG / enum PopElogSlot of
-    csrc/mlp.hpp, in order; so are the restatement's; row slot 15 stays free"""
+    csrc/population.hpp, in order; so are the restatement's; row slot 15 stays free"""
     _, _, pop = _mods(pkg)
-    hpp = open(os.path.join(ROOT, "distributedconvrl-pde-control_amd", "csrc", "mlp.hpp")).read()
+    hpp = open(os.path.join(ROOT, "distributedconvrl-pde-control_amd", "csrc", "population.hpp")).read()
     for enum, define, prefix, mine, size in (("PopBookSlot", "POP_BOOK", "PBK_", "BK_", pop.BOOK), ("PopElogSlot", "POP_ELOG", "PEL_", "EL_", pop.ELOG)):
         assert size == int(re.search(r"#define %s (\d+)" % define, hpp).group(1))
         body = re.sub(r"//.*", "", re.search(r"enum %s \{(.*?)\};" % enum, hpp, re.S).group(1))

@@ -1,4 +1,4 @@
-"""Host rules of population sweeps (population.py): the hyper-parameter slots of the row table against csrc/mlp.hpp, the exploit
+"""Host rules of population sweeps (population.py): the hyper-parameter slots of the row table against csrc/population.hpp, the exploit
 plan and its perturbation.  No GPU."""
 import importlib
 import os
@@ -30,7 +30,7 @@ def _enum(hpp, name):
 
 
 def test_hyper_slots_equal_the_device_enum(pop):
-    hpp = open(os.path.join(ROOT, "distributedconvrl-pde-control_amd", "csrc", "mlp.hpp")).read()
+    hpp = open(os.path.join(ROOT, "distributedconvrl-pde-control_amd", "csrc", "population.hpp")).read()
     slots, hyper = _enum(hpp, "PopSlot"), _enum(hpp, "PopHyperSlot")
     assert hyper == dict(POP_GAMMA=11, POP_RHO=12, POP_ETA_A=13, POP_ETA_C=14)
     assert [pop.GAMMA, pop.RHO, pop.ETA_A, pop.ETA_C] == [hyper[k] for k in ("POP_GAMMA", "POP_RHO", "POP_ETA_A", "POP_ETA_C")]
