@@ -6,6 +6,7 @@ mono/global agent: one column per env).  The reference pushes A columns per step
 CircularArraySARTTrajectory and samples `batch_size` of them per update
 (src/PDEagent.jl:254-340); the batched run pushes B*A columns per step in [b][a] order, so
 the next-state of column i sits at i + B*A (the reference's `inds .+ number_actuators`)."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -210,6 +211,32 @@ class CircularArraySARTTrajectory:
                     terminal=self.terminal[i_rt], next_state=self.state[i_sn])
 
 
+def noise_scale_buffer(scale, n, device, who, out=None, stream=None):
+    """the float64 device tensor of a noise scale (pdec_mlp_set_noise_scale) from a host array or a device tensor of n values
+    (n = None: any length >= 1).  Host values are checked -- finite, not negative, the right length --; a device tensor is
+    checked for its length only and copied device to device without a host wait.  out: write INTO this tensor (on `stream`)
+    instead of making a new one, so that a pointer handed out earlier stays valid."""
+    if isinstance(scale, torch.Tensor) and scale.is_cuda:
+        if scale.dim() != 1 or (n is not None and int(scale.shape[0]) != n) or scale.shape[0] < 1:
+            raise ValueError(f"{who}: expected {'>= 1' if n is None else n} amplitudes in a 1-D array, got shape {tuple(scale.shape)}")
+        src = scale
+    else:
+        a = np.array(scale.cpu() if isinstance(scale, torch.Tensor) else scale, dtype=np.float64, copy=True)
+        if a.ndim != 1 or (n is not None and a.shape[0] != n) or a.shape[0] < 1:
+            raise ValueError(f"{who}: expected {'>= 1' if n is None else n} amplitudes in a 1-D array, got shape {a.shape}")
+        bad = np.flatnonzero(~np.isfinite(a) | (a < 0))
+        if bad.size:
+            raise ValueError(f"{who}: amplitudes must be finite and >= 0; entry {int(bad[0])} is {float(a[bad[0]])!r}"
+                             f" ({bad.size} of {a.shape[0]} entries are not)")
+        src = torch.from_numpy(a)
+    ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+    with ctx:
+        if out is None:
+            out = torch.empty(src.shape[0], dtype=torch.float64, device=device)
+        out.copy_(src)
+    return out
+
+
 class CustomDDPGPolicy:
     """src/PDEagent.jl:121-209, 342-418"""
 
@@ -262,6 +289,7 @@ class CustomDDPGPolicy:
         self._acting = {}                                 # dtype -> promoted acting copy of the actor
         self._noise = None
         self._actions = None
+        self.noise_scale = None                           # set_noise_scale: float64 device tensor [n] of per-entry amplitudes
         self._set_noise_rows(m)
 
     def set_reward_interleave(self, interleave):
@@ -281,6 +309,26 @@ class CustomDDPGPolicy:
         if self.memory_size:
             _lib.check(self.lib.pdec_mlp_set_noise_rows(model.handle, model.dims[-1] - self.memory_size))
 
+    def set_noise_scale(self, scale, cols_per_entry=None):
+        """Exploration amplitude per trajectory in the place of self.act_noise (pdec_mlp_set_noise_scale): `scale` a host array
+        or a device tensor of n values, or None to return to the scalar.  Column c of every acting call of this policy then adds
+        randn * scale[c // cols_per_entry] (cols_per_entry: number_actuators by default, so entry b is trajectory b), and a call
+        must have n * cols_per_entry columns.  The policy owns a float64 device copy (self.noise_scale) and keeps it alive;
+        writing into that tensor changes what later calls read.  Host values are checked: finite and not negative."""
+        m = self.behavior_actor.model
+        if scale is None:
+            self.noise_scale = None
+            for model in [m] + list(self._acting.values()):
+                model.set_noise_scale(None)
+            return
+        cpe = self.number_actuators if cols_per_entry is None else cols_per_entry
+        if int(cpe) != cpe or int(cpe) < 1:
+            raise ValueError(f"set_noise_scale: cols_per_entry must be an integer >= 1 (got {cols_per_entry!r})")
+        self.noise_scale = noise_scale_buffer(scale, None, m.device, "CustomDDPGPolicy.set_noise_scale")
+        self._noise_scale_cpe = int(cpe)
+        for model in [m] + list(self._acting.values()):
+            model.set_noise_scale(self.noise_scale, self._noise_scale_cpe)
+
     @property
     def rho_effective(self):
         """the Polyak factor the update kernels receive (see quirk_frozen_targets)"""
@@ -295,6 +343,8 @@ class CustomDDPGPolicy:
         if key not in self._acting:
             self._acting[key] = m.clone(dtype=dtype, max_cols=max(cols, 1))
             self._set_noise_rows(self._acting[key])
+            if self.noise_scale is not None:
+                self._acting[key].set_noise_scale(self.noise_scale, self._noise_scale_cpe)
         else:
             _lib.check(self.lib.pdec_mlp_copy(self._acting[key].handle, m.handle))
         return self._acting[key]

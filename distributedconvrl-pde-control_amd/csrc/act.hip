@@ -14,20 +14,25 @@ using namespace pdec;
 // the activation -- the order of gemm_kernel's epilogue --, the Philox / Box-Muller draw of randn_kernel for element
 // column * outputs + row, then v += noise * act_noise and the clamp of act_noise_clamp_kernel.
 // (SMALL_ACT_MAXL: mlp.hpp)
-struct SmallActArgs {
+// AN: what carries the amplitude -- the launch scalar, or NoiseScale (pdec_mlp_set_noise_scale; a kernel family of its own, so
+// that the scalar kernels keep their arguments and their code)
+template <class AN>
+struct SmallActArgsT {
   int L, cols, maxw, learning, nrows;
   int dims[SMALL_ACT_MAXL + 1], acts[SMALL_ACT_MAXL], woff[SMALL_ACT_MAXL], boff[SMALL_ACT_MAXL];
   const void* p;
-  double act_noise, lim;
+  AN act_noise;
+  double lim;
   uint64_t seed, offset;
   const uint64_t* ctr_cur;
   uint64_t* ctr_next;
   uint64_t ctr_inc;
 };
+using SmallActArgs = SmallActArgsT<double>;
 // the kernel's body; returns the LDS buffer that holds the finished actions as element i = column * outputs + row (what `out`
 // receives), for a caller that goes on with them inside the same launch (step_glue_kernel)
-template <class T, class TP>
-__device__ __forceinline__ T* small_act_body(const SmallActArgs& g, const T* __restrict__ state, T* __restrict__ out,
+template <class T, class TP, class AN>
+__device__ __forceinline__ T* small_act_body(const SmallActArgsT<AN>& g, const T* __restrict__ state, T* __restrict__ out,
                                              unsigned char* smem) {
   T* X0 = reinterpret_cast<T*>(smem);
   T* X1 = X0 + (size_t)g.maxw * g.cols;
@@ -60,12 +65,16 @@ __device__ __forceinline__ T* small_act_body(const SmallActArgs& g, const T* __r
     T* t = xin; xin = xout; xout = t;
   }
   const int no = g.dims[g.L];
-  const T an = (T)g.act_noise, lim = (T)g.lim;
+  constexpr bool NS = std::is_same<AN, NoiseScale>::value;
+  T an = 0;
+  if constexpr (!NS) an = (T)g.act_noise;
+  const T lim = (T)g.lim;
   for (int i = tid; i < no * cols; i += 256) {       // i = column * outputs + row: the element index of the noise stream
     const int c = i / no, f = i - c * no;
     T v = xin[f * cols + c];
     if (g.learning && f < g.nrows) {
       const T z = (T)noise_normal(g.seed, offset, i);
+      if constexpr (NS) an = noise_amp<T>(g.act_noise, c);
       v += z * an;
     }
     v = v < -lim ? -lim : (v > lim ? lim : v);
@@ -74,8 +83,8 @@ __device__ __forceinline__ T* small_act_body(const SmallActArgs& g, const T* __r
   }
   return xout;
 }
-template <class T, class TP>
-__global__ __launch_bounds__(256) void small_act_kernel(SmallActArgs g, const T* __restrict__ state, T* __restrict__ out) {
+template <class T, class TP, class AN = double>
+__global__ __launch_bounds__(256) void small_act_kernel(SmallActArgsT<AN> g, const T* __restrict__ state, T* __restrict__ out) {
   extern __shared__ __align__(16) unsigned char small_act_smem[];
   (void)small_act_body<T, TP>(g, state, out, small_act_smem);
 }
@@ -86,14 +95,15 @@ __global__ __launch_bounds__(256) void small_act_kernel(SmallActArgs g, const T*
 //   start policy), PRE_ACT push of the next step's (state, action) (:254-274; replay_push2_kernel: skipped once the episode has
 //   ended).  Same arithmetic and the same stores as the three launches; each of them was ~5 us of launch latency on the chain
 //   act -> push -> update / env step -> push of the reference-shaped loop.
-struct StepGlueArgs {
+template <class AN>
+struct StepGlueArgsT {
   float *tr, *tt;              // POST_ACT push: reward / terminal traces, capacity cap_rt, first slot start_rt, n_rt values (0: none)
   const void* r;
   const int32_t* done;
   int cols_per_traj, force;
   long long cap_rt, start_rt, n_rt;
   int act_mode;                // 0: no acting, 1: the actor, 2: the zero action
-  SmallActArgs act;
+  SmallActArgsT<AN> act;
   const void* state;           // [cols][ns] of the environment's type: acting input and the PRE_ACT push's state rows
   void* out;                   // [cols][na]
   float *ts, *ta;              // PRE_ACT push: state / action traces, capacity cap_sa rows, first row start_sa, n_sa rows (0: none)
@@ -110,11 +120,12 @@ struct StepGlueArgs {
   long long d_noise, start_steps;
   size_t r_bytes, s_bytes, o_bytes;
 };
-template <class T, class TP>
-__global__ __launch_bounds__(256) void step_glue_kernel(StepGlueArgs g_in) {
+using StepGlueArgs = StepGlueArgsT<double>;
+template <class T, class TP, class AN = double>
+__global__ __launch_bounds__(256) void step_glue_kernel(StepGlueArgsT<AN> g_in) {
   extern __shared__ __align__(16) unsigned char small_act_smem[];
   const int tid = threadIdx.x;
-  StepGlueArgs g = g_in;
+  StepGlueArgsT<AN> g = g_in;
   long long* mrow = nullptr;
   bool macting = false;
   if (g.pm) {                         // population member blockIdx.x: the solo call's arguments from its table entries
@@ -123,7 +134,8 @@ __global__ __launch_bounds__(256) void step_glue_kernel(StepGlueArgs g_in) {
     mrow = g.rows + (size_t)mb * POP_ROW;
     g.tr = pm.tr; g.tt = pm.tt; g.ts = pm.ts; g.ta = pm.ta;
     g.act.p = pm.actor_p; g.act.seed = pm.noise_seed; g.act.offset = (uint64_t)mrow[POP_NOISE];
-    g.act.act_noise = __longlong_as_double(mrow[POP_NOISE_AMP]); g.act.lim = __longlong_as_double(mrow[POP_LIMIT]);
+    if constexpr (std::is_same<AN, double>::value) g.act.act_noise = __longlong_as_double(mrow[POP_NOISE_AMP]);   // (members: scalar only)
+    g.act.lim = __longlong_as_double(mrow[POP_LIMIT]);
     g.start_rt = mrow[POP_NRT] % g.cap_rt;
     g.start_sa = mrow[POP_NSA] % g.cap_sa;
     if (g.r) g.r = static_cast<const char*>(g.r) + mb * g.r_bytes;
@@ -206,8 +218,9 @@ static bool small_act_ok(const Mlp* M, int dtype, int cols) {
 }
 
 // the fields of SmallActArgs that depend on the network
-static SmallActArgs small_act_args(const Mlp* M, int cols) {
-  SmallActArgs g{};
+template <class AN = double>
+static SmallActArgsT<AN> small_act_args(const Mlp* M, int cols) {
+  SmallActArgsT<AN> g{};
   g.L = M->L; g.cols = cols;
   g.maxw = mlp_maxw(M);
   for (int l = 0; l <= M->L; ++l) g.dims[l] = M->dims[l];
@@ -216,9 +229,11 @@ static SmallActArgs small_act_args(const Mlp* M, int cols) {
   return g;
 }
 
-static int small_act(Mlp* M, int dtype, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
-                     uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc) {
-  SmallActArgs g = small_act_args(M, cols);
+template <class AN>
+static int small_act_launch(Mlp* M, int dtype, const void* state, int cols, AN act_noise, double act_limit, int learning,
+                            uint64_t seed, uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next,
+                            uint64_t ctr_inc) {
+  SmallActArgsT<AN> g = small_act_args<AN>(M, cols);
   g.learning = learning;
   g.p = M->params.p;
   g.act_noise = act_noise; g.lim = act_limit; g.seed = seed; g.offset = offset;
@@ -226,21 +241,28 @@ static int small_act(Mlp* M, int dtype, const void* state, int cols, double act_
   const size_t lds = small_act_lds(M, dtype, cols);
   ProfScope ps(M, "small_act");
   if (dtype == PDEC_F64 && M->dtype == PDEC_F32)
-    hipLaunchKernelGGL((small_act_kernel<double, float>), dim3(1), dim3(256), lds, M->stream, g, (const double*)state, (double*)actions_out);
+    hipLaunchKernelGGL((small_act_kernel<double, float, AN>), dim3(1), dim3(256), lds, M->stream, g, (const double*)state, (double*)actions_out);
   else if (dtype == PDEC_F64)
-    hipLaunchKernelGGL((small_act_kernel<double, double>), dim3(1), dim3(256), lds, M->stream, g, (const double*)state, (double*)actions_out);
+    hipLaunchKernelGGL((small_act_kernel<double, double, AN>), dim3(1), dim3(256), lds, M->stream, g, (const double*)state, (double*)actions_out);
   else
-    hipLaunchKernelGGL((small_act_kernel<float, float>), dim3(1), dim3(256), lds, M->stream, g, (const float*)state, (float*)actions_out);
+    hipLaunchKernelGGL((small_act_kernel<float, float, AN>), dim3(1), dim3(256), lds, M->stream, g, (const float*)state, (float*)actions_out);
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;
 }
+static int small_act(Mlp* M, int dtype, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
+                     uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc) {
+  if (M->noise_scale)
+    return small_act_launch(M, dtype, state, cols, noise_scale_of(M), act_limit, learning, seed, offset, actions_out, ctr_cur,
+                            ctr_next, ctr_inc);
+  return small_act_launch(M, dtype, state, cols, act_noise, act_limit, learning, seed, offset, actions_out, ctr_cur, ctr_next, ctr_inc);
+}
 
 // launch(step_glue_kernel<T, TP>) of the (state dtype, parameter dtype) pair; the caller brings its own launch call
-template <class F>
+template <class AN = double, class F>
 static void step_glue_dispatch(int state_dtype, int param_dtype, F&& launch) {
-  if (state_dtype == PDEC_F64 && param_dtype == PDEC_F32) launch(step_glue_kernel<double, float>);
-  else if (state_dtype == PDEC_F64) launch(step_glue_kernel<double, double>);
-  else launch(step_glue_kernel<float, float>);
+  if (state_dtype == PDEC_F64 && param_dtype == PDEC_F32) launch(step_glue_kernel<double, float, AN>);
+  else if (state_dtype == PDEC_F64) launch(step_glue_kernel<double, double, AN>);
+  else launch(step_glue_kernel<float, float, AN>);
 }
 
 ActRoute pdec::act_route(const Mlp* M, int cols) { return small_act_ok(M, M->dtype, cols) ? ACT_SMALL : ACT_GENERIC; }
@@ -255,6 +277,7 @@ extern "C" {
 static int policy_act_rng_impl(pdec_handle actor, Mlp* M, const void* state, int cols, double act_noise, double act_limit,
                                int learning, uint64_t seed, uint64_t offset, void* actions_out, const uint64_t* ctr_cur,
                                uint64_t* ctr_next, uint64_t ctr_inc) {
+  if (learning) PDEC_REQUIRE_NOISE_COLS(M, cols, "pdec_policy_act_rng");
   if (const FusedFamily* fam = fused_family_of_act(M, cols))
     return fam->policy_act(M, state, cols, act_noise, act_limit, learning, seed, offset, actions_out, ctr_cur, ctr_next, ctr_inc);
   if (act_route(M, cols) == ACT_SMALL)
@@ -289,6 +312,7 @@ int pdec_policy_act_rng_as(pdec_handle actor, int state_dtype, const void* state
   *served = 0;
   if (!small_act_ok(M, state_dtype, cols) || M->dtype == state_dtype) return PDEC_OK;
   PDEC_REQUIRE(state && actions_out, "pdec_policy_act_rng_as: null");
+  if (learning) PDEC_REQUIRE_NOISE_COLS(M, cols, "pdec_policy_act_rng_as");
   *served = 1;
   return small_act(M, state_dtype, state, cols, act_noise, act_limit, learning, seed, offset, actions_out, nullptr, nullptr, 0);
 }
@@ -328,20 +352,7 @@ int pdec_step_glue(pdec_handle actor, pdec_handle trajectory_handle, int dtype, 
                "pdec_step_glue: bad PRE_ACT push");
   PDEC_REQUIRE(act_mode == 0 || (actions_out && (act_mode == 2 || (state && cols >= 1))), "pdec_step_glue: bad acting arguments");
   PDEC_REQUIRE(act_mode == 0 || !n_sa || n_sa == cols, "pdec_step_glue: the PRE_ACT push takes the acting call's columns");
-  StepGlueArgs g{};
-  g.tr = (float*)reward_trace; g.tt = (float*)terminal_trace; g.r = reward; g.done = done_flags;
-  g.cols_per_traj = cols_per_traj; g.force = force_terminal; g.cap_rt = capacity; g.start_rt = start_rt; g.n_rt = n_rt;
-  g.act_mode = act_mode; g.state = state; g.out = actions_out;
-  g.ts = (float*)state_trace; g.ta = (float*)action_trace; g.ns = M->dims[0]; g.na = M->dims[M->L];
-  g.cap_sa = capacity_rows; g.start_sa = start_sa; g.n_sa = n_sa;
-  g.halt = o->halt;
-  g.sync = M->sync;
-  M->sync = LaunchSync{};
-  g.act = small_act_args(M, cols);
-  g.act.learning = 1;
-  g.act.p = M->params.p;
-  g.act.act_noise = act_noise; g.act.lim = act_limit; g.act.seed = seed; g.act.offset = offset;
-  const size_t lds = act_mode == 1 ? small_act_lds(M, dtype, cols) : 16;
+  if (act_mode == 1) PDEC_REQUIRE_NOISE_COLS(M, cols, "pdec_step_glue");
   hipEvent_t ev = nullptr;
   if (done_event) {
     ev = pdec::event_native(done_event);
@@ -349,10 +360,29 @@ int pdec_step_glue(pdec_handle actor, pdec_handle trajectory_handle, int dtype, 
   }
   *served = 1;
   ProfScope ps(M, "step_glue");
-  // (done_event rides on the launch as the completion event of its dispatch packet, like pdec_mlp_set_stop_event's)
-  step_glue_dispatch(dtype, M->dtype, [&](auto kern) { hipExtLaunchKernelGGL(kern, dim3(1), dim3(256), lds, M->stream, nullptr, ev, 0, g); });
-  PDEC_HIP(hipGetLastError());
-  return PDEC_OK;
+  // by what carries the amplitude: the call's scalar, or the array set on the actor (a kernel family of its own)
+  auto launch = [&](auto amp) -> int {
+    using AN = decltype(amp);
+    StepGlueArgsT<AN> g{};
+    g.tr = (float*)reward_trace; g.tt = (float*)terminal_trace; g.r = reward; g.done = done_flags;
+    g.cols_per_traj = cols_per_traj; g.force = force_terminal; g.cap_rt = capacity; g.start_rt = start_rt; g.n_rt = n_rt;
+    g.act_mode = act_mode; g.state = state; g.out = actions_out;
+    g.ts = (float*)state_trace; g.ta = (float*)action_trace; g.ns = M->dims[0]; g.na = M->dims[M->L];
+    g.cap_sa = capacity_rows; g.start_sa = start_sa; g.n_sa = n_sa;
+    g.halt = o->halt;
+    g.sync = M->sync;
+    M->sync = LaunchSync{};
+    g.act = small_act_args<AN>(M, cols);
+    g.act.learning = 1;
+    g.act.p = M->params.p;
+    g.act.act_noise = amp; g.act.lim = act_limit; g.act.seed = seed; g.act.offset = offset;
+    const size_t lds = act_mode == 1 ? small_act_lds(M, dtype, cols) : 16;
+    // (done_event rides on the launch as the completion event of its dispatch packet, like pdec_mlp_set_stop_event's)
+    step_glue_dispatch<AN>(dtype, M->dtype, [&](auto kern) { hipExtLaunchKernelGGL(kern, dim3(1), dim3(256), lds, M->stream, nullptr, ev, 0, g); });
+    PDEC_HIP(hipGetLastError());
+    return PDEC_OK;
+  };
+  return act_mode == 1 && M->noise_scale ? launch(noise_scale_of(M)) : launch(act_noise);
 }
 
 int pdec_population_glue(pdec_handle pop, int phase, const void* reward, const int32_t* done_flags, const void* state,
@@ -407,6 +437,18 @@ int pdec_policy_act_rng_dev(pdec_handle actor, const void* state, int cols, doub
                            c + (M->nc_sel ^ 1), inc);
   if (rc) return rc;
   flip(M->nc_sel);
+  return PDEC_OK;
+}
+
+int pdec_mlp_set_noise_scale(pdec_handle actor, const double* scale_dev, int64_t n, int cols_per_entry) {
+  GET_MLP(M, actor);
+  if (!scale_dev) {
+    M->noise_scale = nullptr; M->noise_scale_n = 0; M->noise_scale_cpe = 1;
+    return PDEC_OK;
+  }
+  PDEC_REQUIRE(n >= 1 && cols_per_entry >= 1 && n * cols_per_entry <= INT32_MAX, "pdec_mlp_set_noise_scale: %lld entries x %d columns",
+               (long long)n, cols_per_entry);
+  M->noise_scale = scale_dev; M->noise_scale_n = n; M->noise_scale_cpe = cols_per_entry;
   return PDEC_OK;
 }
 

@@ -157,13 +157,20 @@ size_t ksfd_lds_bytes(const pdec_env_cfg& c);
 // PDEC_E_INVALID without touching anything when it is not.
 struct Mlp;
 struct RollMembers;
-struct RollSpec { int steps, learning; double act_noise, act_limit; uint64_t seed, offset; int control_from = 0; };      // what the launch does
+struct RollSpec {       // what the launch does
+  int steps, learning;
+  double act_noise, act_limit;
+  uint64_t seed, offset;
+  int control_from = 0;
+  const double* noise_scale = nullptr;      // pdec_mlp_set_noise_scale on the actor, for a learning launch (null: act_noise)
+  int noise_cpe = 1;
+};
 struct RollPtrs {       // its arrays as they cross the C ABI (pdec_rollout)
   void *y, *state, *action, *reward_sum, *log_y, *log_p, *log_action, *log_reward;
   int32_t *done_any, *done_step;
 };
-bool ks_rollout_supported(const Env& E, const Mlp& A);
-bool kseg_rollout_supported(const Env& E, const Mlp& A);
+bool ks_rollout_supported(const Env& E, const Mlp& A, bool noise_tab = false);     // noise_tab: rollout_lds (roll_actor.hpp)
+bool kseg_rollout_supported(const Env& E, const Mlp& A, bool noise_tab = false);
 // pm != null: the member form (A = member 0's actor, the shape all members share; the caller has checked the shape)
 int ks_rollout_persistent(Env& E, const Mlp& A, const RollSpec& spec, const RollPtrs& ptrs, const RollMembers* pm = nullptr);
 int kseg_rollout_persistent(Env& E, const Mlp& A, const RollSpec& spec, const RollPtrs& ptrs, const RollMembers* pm = nullptr);

@@ -15,8 +15,11 @@ namespace pdec {
 // MEM: the member form -- workgroup w serves pair w % ceil(K/2) of member w / ceil(K/2), i.e. the trajectories
 // m K + 2 pair (+ 1 while 2 pair + 1 < K): the pairing a solo launch on B = K trajectories makes, so both trajectories of a
 // complex FFT (and of a thread's column pair) belong to ONE member and a member's arithmetic is that of its solo rollout.
-template <class T, class ENG, bool MEM>
-__global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, RollActor actor, RollArgs<T> g, RollMembers pm) {
+// AN = NoiseScale (pdec_mlp_set_noise_scale; solo form): the amplitude of each of the workgroup's [2][A] columns, entry
+// (b A + a) / cols_per_entry of the array, is read into LDS once, behind the activation planes.
+template <class T, class ENG, bool MEM, class AN = T>
+__global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, RollActor actor, RollArgs<T, AN> g, RollMembers pm) {
+  constexpr bool NS = std::is_same<AN, NoiseScale>::value;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int N = e.N, tid = threadIdx.x, nt = blockDim.x, A = e.A, ns = e.ns;
   set_wave_prio(e.prio);
@@ -59,6 +62,14 @@ __global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, 
     act[a] = g.action[(size_t)b0 * A + a];
     act[A + a] = has1 ? g.action[(size_t)b1 * A + a] : (T)0;
     rsum[a] = rsum[A + a] = 0;
+  }
+  T* namp = nullptr;                      // [2][A] (NS)
+  if constexpr (NS) {
+    namp = reinterpret_cast<T*>(hb + (size_t)2 * actor.rows * nt);
+    for (int a = tid; a < A; a += nt) {
+      namp[a] = noise_amp<T>(g.act_noise, (size_t)b0 * A + a);
+      namp[A + a] = has1 ? noise_amp<T>(g.act_noise, (size_t)b1 * A + a) : (T)0;
+    }
   }
   C2<T> U[KS_MPT], Nn[KS_MPT], Ck[KS_MPT], v[KS_MPT];
   T kc1[KS_MPT], kc2[KS_MPT], kc3[KS_MPT], kg[KS_MPT], kc4[KS_MPT];
@@ -108,7 +119,10 @@ __global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, 
             }
             // the odd element shares the Box-Muller pair of its even neighbour
             if (s == 0 || (c & 1) == 0) noise_polar(ph, (int)((c >> 1) & 1), rad, ang);
-            o += (T)((c & 1) ? rad * sin(ang) : rad * cos(ang)) * g.act_noise;
+            T amp;
+            if constexpr (NS) amp = namp[idx];
+            else amp = g.act_noise;
+            o += (T)((c & 1) ? rad * sin(ang) : rad * cos(ang)) * amp;
           }
           o = o < -g.act_limit ? -g.act_limit : (o > g.act_limit ? g.act_limit : o);
           actp[idx] = act[idx];
@@ -259,14 +273,17 @@ __global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, 
 }
 
 // ------------------------------------------------------------------ host side
-bool ks_rollout_supported(const Env& E, const Mlp& A) { return A.dtype == E.cfg.dtype && rollout_shape_ok(E, A, true); }
+bool ks_rollout_supported(const Env& E, const Mlp& A, bool noise_tab) {
+  return A.dtype == E.cfg.dtype && rollout_shape_ok(E, A, true, noise_tab);
+}
 
 // pm = null: the solo form.  Member form: A is member 0's actor (the shape all members share), the grid M ceil(K / 2)
 int ks_rollout_persistent(Env& E, const Mlp& A, const RollSpec& spec, const RollPtrs& ptrs, const RollMembers* pm) {
-  if (!pm && !ks_rollout_supported(E, A)) { set_error("ks_rollout_persistent: configuration not covered"); return PDEC_E_INVALID; }
+  const bool ntab = roll_noise_tab(spec, pm);
+  if (!pm && !ks_rollout_supported(E, A, ntab)) { set_error("ks_rollout_persistent: configuration not covered"); return PDEC_E_INVALID; }
   const pdec_env_cfg& c = E.cfg;
   const RollActor ra = make_roll_actor(A);
-  const size_t lds = rollout_lds(E, A, true);
+  const size_t lds = rollout_lds(E, A, true, ntab);
   const dim3 grid(pm ? (c.B / pm->K) * ((pm->K + 1) / 2) : (c.B + 1) / 2), block(E.nthreads);
   ProfScope ps(&E, pm ? "ks_rollout_members" : "ks_rollout");
   by_dtype(c.dtype, [&](auto t) {
@@ -275,7 +292,10 @@ int ks_rollout_persistent(Env& E, const Mlp& A, const RollSpec& spec, const Roll
     const RollArgs<T> g = make_roll_args<T>(spec, ptrs);
     with_ks_engine<T>(E.engine, [&](auto tag) {
       using ENG = typename decltype(tag)::type;
-      if (pm) hipLaunchKernelGGL((ks_rollout_kernel<T, ENG, true>), grid, block, lds, E.stream, e, ra, g, *pm);
+      if (ntab)
+        hipLaunchKernelGGL((ks_rollout_kernel<T, ENG, false, NoiseScale>), grid, block, lds, E.stream, e, ra,
+                           (make_roll_args<T, NoiseScale>(spec, ptrs)), RollMembers{});
+      else if (pm) hipLaunchKernelGGL((ks_rollout_kernel<T, ENG, true>), grid, block, lds, E.stream, e, ra, g, *pm);
       else hipLaunchKernelGGL((ks_rollout_kernel<T, ENG, false>), grid, block, lds, E.stream, e, ra, g, RollMembers{});
     });
   });

@@ -142,9 +142,11 @@ __global__ void kseg_env_step_kernel(EnvDev<T> e, const T* __restrict__ y_in, co
 // of step t) as the acting kernel's, so the launch tracks the step-by-step loop to the actor's summation order.
 // MEM: the member form -- trajectory b (one workgroup) takes the actor of member b / K from the table.  NT: the largest
 // workgroup the instantiation is launched with (1024: any; the member form has a 256-thread instantiation, whose register
-// budget holds the fp64 loop without spills).
-template <class T, bool MEM, int NT>
-__global__ void __launch_bounds__(NT) kseg_rollout_kernel(EnvDev<T> e, RollActor actor, RollArgs<T> g, RollMembers pm) {
+// budget holds the fp64 loop without spills).  AN = NoiseScale (pdec_mlp_set_noise_scale; solo form): the amplitude of each of
+// the trajectory's A columns, entry (b A + a) / cols_per_entry of the array, is read into LDS once, behind the activations.
+template <class T, bool MEM, int NT, class AN = T>
+__global__ void __launch_bounds__(NT) kseg_rollout_kernel(EnvDev<T> e, RollActor actor, RollArgs<T, AN> g, RollMembers pm) {
+  constexpr bool NS = std::is_same<AN, NoiseScale>::value;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int N = e.N, tid = threadIdx.x, nt = blockDim.x, b = blockIdx.x, A = e.A, ns = e.ns;
   T* su = reinterpret_cast<T*>(smem_raw);  // [N+2]
@@ -173,6 +175,9 @@ __global__ void __launch_bounds__(NT) kseg_rollout_kernel(EnvDev<T> e, RollActor
   for (int a = tid; a < A; a += nt) {
     act[a] = g.action[(size_t)b * A + a];
     rsum[a] = 0;
+  }
+  if constexpr (NS) {                      // [A] behind the activations
+    for (int a = tid; a < A; a += nt) hb[(size_t)2 * A * RO_W + a] = noise_amp<T>(g.act_noise, (size_t)b * A + a);
   }
   T u = live ? g.y[yo + 2 * n] : (T)0, v = live ? g.y[yo + 2 * n + 1] : (T)0;
   int flag = 0, first = -1;
@@ -204,7 +209,8 @@ __global__ void __launch_bounds__(NT) kseg_rollout_kernel(EnvDev<T> e, RollActor
         T o = ctl ? in[a * RO_W] : (T)0;
         if (!MEM && ctl && g.learning) {
           const uint64_t c = (uint64_t)b * A + a;                          // global column = element of the noise stream
-          o += (T)noise_normal(g.seed, g.offset + (uint64_t)t * ((cols + 3) / 4), c) * g.act_noise;
+          if constexpr (NS) o += (T)noise_normal(g.seed, g.offset + (uint64_t)t * ((cols + 3) / 4), c) * hb[(size_t)2 * A * RO_W + a];
+          else o += (T)noise_normal(g.seed, g.offset + (uint64_t)t * ((cols + 3) / 4), c) * g.act_noise;
         }
         o = o < -g.act_limit ? -g.act_limit : (o > g.act_limit ? g.act_limit : o);
         actp[a] = act[a];
@@ -293,18 +299,24 @@ int kseg_launch_step(Env& E, int mode, const StepArgs& a) {
 }
 
 // ---- persistent rollout
-bool kseg_rollout_supported(const Env& E, const Mlp& A) { return A.dtype == E.cfg.dtype && rollout_shape_ok(E, A, false); }
+bool kseg_rollout_supported(const Env& E, const Mlp& A, bool noise_tab) {
+  return A.dtype == E.cfg.dtype && rollout_shape_ok(E, A, false, noise_tab);
+}
 int kseg_rollout_persistent(Env& E, const Mlp& A, const RollSpec& spec, const RollPtrs& ptrs, const RollMembers* pm) {
-  if (!pm && !kseg_rollout_supported(E, A)) { set_error("kseg_rollout_persistent: configuration not covered"); return PDEC_E_INVALID; }
+  const bool ntab = roll_noise_tab(spec, pm);
+  if (!pm && !kseg_rollout_supported(E, A, ntab)) { set_error("kseg_rollout_persistent: configuration not covered"); return PDEC_E_INVALID; }
   const RollActor ra = make_roll_actor(A);
-  const size_t lds = rollout_lds(E, A, false);
+  const size_t lds = rollout_lds(E, A, false, ntab);
   const dim3 grid(E.cfg.B), block(E.nthreads);
   ProfScope ps(&E, pm ? "kseg_rollout_members" : "kseg_rollout");
   by_dtype(E.cfg.dtype, [&](auto t) {
     using T = decltype(t);
     const EnvDev<T> e = make_dev<T>(E);
     const RollArgs<T> g = make_roll_args<T>(spec, ptrs);
-    if (pm && E.nthreads <= 256) hipLaunchKernelGGL((kseg_rollout_kernel<T, true, 256>), grid, block, lds, E.stream, e, ra, g, *pm);
+    if (ntab)
+      hipLaunchKernelGGL((kseg_rollout_kernel<T, false, 1024, NoiseScale>), grid, block, lds, E.stream, e, ra,
+                         (make_roll_args<T, NoiseScale>(spec, ptrs)), RollMembers{});
+    else if (pm && E.nthreads <= 256) hipLaunchKernelGGL((kseg_rollout_kernel<T, true, 256>), grid, block, lds, E.stream, e, ra, g, *pm);
     else if (pm) hipLaunchKernelGGL((kseg_rollout_kernel<T, true, 1024>), grid, block, lds, E.stream, e, ra, g, *pm);
     else hipLaunchKernelGGL((kseg_rollout_kernel<T, false, 1024>), grid, block, lds, E.stream, e, ra, g, RollMembers{});
   });

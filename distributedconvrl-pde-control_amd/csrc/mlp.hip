@@ -198,14 +198,15 @@ __global__ void cast_copy_kernel(TD* __restrict__ dst, const TS* __restrict__ sr
 
 // actions[c][f] = clamp(H[f][c] + noise[c][f]*act_noise, +-lim)
 // (noise on the first nrows outputs only: the action-memory rows stay noise-free, src/PDEagent.jl:201)
-template <class T>
+// AN: what carries the amplitude -- the launch scalar, or NoiseScale (pdec_mlp_set_noise_scale)
+template <class T, class AN = T>
 __global__ void act_noise_clamp_kernel(const T* __restrict__ H, const T* __restrict__ noise, int cols, int n, int nrows,
-                                       T act_noise, T lim, T* __restrict__ out) {
+                                       AN act_noise, T lim, T* __restrict__ out) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= cols) return;
   for (int f = 0; f < n; ++f) {
     T v = H[(size_t)f * cols + c];
-    if (noise && f < nrows) v += noise[(size_t)c * n + f] * act_noise;
+    if (noise && f < nrows) v += noise[(size_t)c * n + f] * noise_amp<T>(act_noise, c);
     v = v < -lim ? -lim : (v > lim ? lim : v);
     out[(size_t)c * n + f] = v;
   }
@@ -638,6 +639,7 @@ int pdec_policy_act(pdec_handle actor, const void* state, const void* noise, int
                     double act_limit, void* actions_out) {
   GET_MLP(M, actor);
   PDEC_REQUIRE(state && actions_out, "pdec_policy_act: null");
+  if (noise) PDEC_REQUIRE_NOISE_COLS(M, cols, "pdec_policy_act");
   int rc = M->pack(state, M->dims[0], 0, nullptr, 0, 0, cols);
   if (rc) return rc;
   rc = M->forward(cols);
@@ -645,7 +647,13 @@ int pdec_policy_act(pdec_handle actor, const void* state, const void* noise, int
   const int no = M->dims[M->L], nrows = M->noise_rows < 0 ? no : M->noise_rows;
   dim3 grid(cdiv(cols, 256)), block(256);
   ProfScope ps(M, "act_noise_clamp");
-  if (M->dtype == PDEC_F64)
+  if (noise && M->noise_scale && M->dtype == PDEC_F64)
+    hipLaunchKernelGGL((act_noise_clamp_kernel<double, NoiseScale>), grid, block, 0, M->stream, M->H[M->L].as<double>(),
+                       (const double*)noise, cols, no, nrows, noise_scale_of(M), act_limit, (double*)actions_out);
+  else if (noise && M->noise_scale)
+    hipLaunchKernelGGL((act_noise_clamp_kernel<float, NoiseScale>), grid, block, 0, M->stream, M->H[M->L].as<float>(),
+                       (const float*)noise, cols, no, nrows, noise_scale_of(M), (float)act_limit, (float*)actions_out);
+  else if (M->dtype == PDEC_F64)
     hipLaunchKernelGGL((act_noise_clamp_kernel<double>), grid, block, 0, M->stream, M->H[M->L].as<double>(), (const double*)noise,
                        cols, no, nrows, act_noise, act_limit, (double*)actions_out);
   else

@@ -34,6 +34,9 @@ struct Mlp : Object {
   DevBuf noise_ctr;                  // uint64 [2]: double-buffered exploration-noise counter of pdec_policy_act_rng_dev
   int nc_sel = 0;
   int noise_rows = -1;   // pdec_mlp_set_noise_rows: exploration noise on the first rows of the output only (-1: all)
+  const double* noise_scale = nullptr;   // pdec_mlp_set_noise_scale: the caller's device array of amplitudes (null: the call's scalar)
+  int64_t noise_scale_n = 0;             // its entries; an acting call then has noise_scale_n * noise_scale_cpe columns
+  int noise_scale_cpe = 1;
   std::vector<DevBuf> H;             // activations, feature-major [dims[l]][cols]
   DevBuf dz[2];                      // ping-pong dL/dz buffers [maxdim][cols]
   DevBuf dy;                         // dL/dy of the output layer [dims[L]][cols]
@@ -122,6 +125,25 @@ __device__ __forceinline__ double noise_normal(uint64_t seed, uint64_t offset, I
   return (i & 1) ? rad * sin(ang) : rad * cos(ang);
 }
 
+// ---- the exploration amplitude of a column as a kernel receives it: the launch scalar (the default instantiations, whose text
+// and arguments are what they were before the array existed), or NoiseScale -- entry c / cols_per_entry of the device array of
+// pdec_mlp_set_noise_scale, converted to the kernel's type as the scalar is ((T)act_noise: an array of equal values is the
+// scalar call bit for bit)
+struct NoiseScale {
+  const double* scale;
+  int cols_per_entry;
+};
+template <class T, class S, class I>
+__device__ __forceinline__ T noise_amp(S a, I) { return (T)a; }
+template <class T, class I>
+__device__ __forceinline__ T noise_amp(NoiseScale s, I c) { return (T)s.scale[c / s.cols_per_entry]; }
+inline NoiseScale noise_scale_of(const Mlp* M) { return NoiseScale{M->noise_scale, M->noise_scale_cpe}; }
+// an acting call of `cols` columns against the array set on M (none set: fine)
+#define PDEC_REQUIRE_NOISE_COLS(M, cols, who)                                                                                  \
+  PDEC_REQUIRE(!(M)->noise_scale || (long long)(cols) == (long long)(M)->noise_scale_n * (M)->noise_scale_cpe,                 \
+               "%s: %d columns, but the noise scale set on the actor serves %lld entries x %d columns = %lld", who, (int)(cols), \
+               (long long)(M)->noise_scale_n, (M)->noise_scale_cpe, (long long)(M)->noise_scale_n * (M)->noise_scale_cpe)
+
 // kernel-side view of the beta powers: read `cur` (every thread that needs it), one thread of the grid writes `next`
 struct BpArgs {
   const double* cur;
@@ -175,7 +197,8 @@ struct FusedFamily {
   int (*actor_grads)(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
                      const AdamPolyak* apply);
   int (*adam_polyak)(Mlp* M, Mlp* Mt, const AdamPolyak& ap);
-  // ctr_cur != null: the noise offset is *ctr_cur (+ offset) and one thread writes *ctr_next = that + ctr_inc
+  // ctr_cur != null: the noise offset is *ctr_cur (+ offset) and one thread writes *ctr_next = that + ctr_inc.  With an array set
+  // on A (pdec_mlp_set_noise_scale) the launch takes the kernel's NoiseScale instantiation and act_noise is not read
   int (*policy_act)(Mlp* A, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
                     uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc);
   // kernel name and dynamic LDS bytes of the pass / acting launch the functions above would make (nothing is launched)

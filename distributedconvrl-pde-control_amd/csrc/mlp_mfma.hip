@@ -922,11 +922,11 @@ __global__ __launch_bounds__(FIN_THREADS) void fused_finish_kernel(FinishArgs g_
 // actions = clamp(actor(state) + randn * act_noise, +-act_limit)  (src/PDEagent.jl:183-207) in ONE launch on the
 // same MFMA building blocks as the update passes (16 columns per wave, layer outputs chained as B operands);
 // exploration noise from the same Philox counter stream as pdec_randn (element index = column), so both
-// paths draw identical numbers.
+// paths draw identical numbers.  AN: what carries the amplitude -- the launch scalar, or NoiseScale (pdec_mlp_set_noise_scale).
 #define ACT_THREADS 256
-template <int MTA>
+template <int MTA, class AN = float>
 __global__ __launch_bounds__(ACT_THREADS) void policy_act_fused_kernel(FNet f, const float* __restrict__ state, int cols, int ns,
-                                                                      float act_noise, float lim, int learning, int tanh_out,
+                                                                      AN act_noise, float lim, int learning, int tanh_out,
                                                                       uint64_t seed, uint64_t offset, float* __restrict__ out,
                                                                       const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc,
                                                                       int prio) {
@@ -963,7 +963,7 @@ __global__ __launch_bounds__(ACT_THREADS) void policy_act_fused_kernel(FNet f, c
   if (tanh_out) o = tanhf(o);
   if (learning) {
     const float z = (float)noise_normal(seed, offset, c);
-    o += z * act_noise;
+    o += z * noise_amp<float>(act_noise, c);
   }
   out[c] = fminf(fmaxf(o, -lim), lim);
 }
@@ -1278,11 +1278,14 @@ static int fused_policy_act(Mlp* A, const void* state, int cols, double act_nois
   const int prio = env_prio("PDEC_PRIO_ACT", 3);
   const dim3 grid((cols + 63) / 64), block(ACT_THREADS);
   rc = visit_act_tiles(mta, [&](auto MTA) {
-    auto kern = policy_act_fused_kernel<decltype(MTA)::value>;
-#define ACT_ARGS f, (const float*)state, cols, A->dims[0], (float)act_noise, (float)act_limit, learning, tanh_out, seed, offset, \
-                 (float*)actions_out, ctr_cur, ctr_next, ctr_inc, prio
-    if (A->prof) PDEC_TIMED_LAUNCH(A, "policy_act_fused", kern, grid, block, lds, ACT_ARGS);
-    else hipLaunchKernelGGL(kern, grid, block, lds, A->stream, ACT_ARGS);
+#define ACT_ARGS(an) f, (const float*)state, cols, A->dims[0], an, (float)act_limit, learning, tanh_out, seed, offset, \
+                     (float*)actions_out, ctr_cur, ctr_next, ctr_inc, prio
+    auto go = [&](auto kern, auto an) {
+      if (A->prof) PDEC_TIMED_LAUNCH(A, "policy_act_fused", kern, grid, block, lds, ACT_ARGS(an));
+      else hipLaunchKernelGGL(kern, grid, block, lds, A->stream, ACT_ARGS(an));
+    };
+    if (A->noise_scale) go(policy_act_fused_kernel<decltype(MTA)::value, NoiseScale>, noise_scale_of(A));
+    else go(policy_act_fused_kernel<decltype(MTA)::value>, (float)act_noise);
 #undef ACT_ARGS
     return (int)PDEC_OK;
   });

@@ -19,10 +19,12 @@ struct RollMembers {
   int K;                       // trajectories per member
   int f32;                     // the parameters are Float32 whatever the environment's dtype (promoted while the image is filled)
 };
-template <class T>
+// AN: what carries the exploration amplitude -- the launch scalar, or NoiseScale (pdec_mlp_set_noise_scale)
+template <class T, class AN = T>
 struct RollArgs {
   int steps, learning;
-  T act_noise, act_limit;
+  AN act_noise;
+  T act_limit;
   uint64_t seed, offset;
   T *y, *state, *action;                   // in / out: [B][N], [B][A][ns], [B][A]
   T* reward_sum;                           // optional [B][A]: += every step's reward
@@ -142,22 +144,31 @@ inline RollActor make_roll_actor(const Mlp& A) {
   for (int l = 0; l < A.L; ++l) ra.acts[l] = A.acts[l];
   return ra;
 }
-template <class T>
-RollArgs<T> make_roll_args(const RollSpec& s, const RollPtrs& p) {
-  return RollArgs<T>{s.steps, s.learning, (T)s.act_noise, (T)s.act_limit, s.seed, s.offset, (T*)p.y, (T*)p.state, (T*)p.action,
-                     (T*)p.reward_sum, (T*)p.log_y, (T*)p.log_p, (T*)p.log_action, (T*)p.log_reward, p.done_any, p.done_step, s.control_from};
+template <class T, class AN = T>
+RollArgs<T, AN> make_roll_args(const RollSpec& s, const RollPtrs& p) {
+  AN amp;
+  if constexpr (std::is_same<AN, NoiseScale>::value) amp = NoiseScale{s.noise_scale, s.noise_cpe};
+  else amp = (T)s.act_noise;
+  return RollArgs<T, AN>{s.steps, s.learning, amp, (T)s.act_limit, s.seed, s.offset, (T*)p.y, (T*)p.state, (T*)p.action,
+                         (T*)p.reward_sum, (T*)p.log_y, (T*)p.log_p, (T*)p.log_action, (T*)p.log_reward, p.done_any, p.done_step,
+                         s.control_from};
 }
+// does this launch take the kernels of the amplitude array?  (a learning solo launch with an array set on the actor)
+inline bool roll_noise_tab(const RollSpec& s, const RollMembers* pm) { return !pm && s.learning && s.noise_scale; }
 // dynamic LDS of a rollout workgroup: the step kernel's (E.lds_bytes) + state, rewards, the actor image and its activation
-// planes (KS: [2][rows] column pairs per thread; Keller-Segel: [2][A][RO_W])
-inline size_t rollout_lds(const Env& E, const Mlp& A, bool ks) {
+// planes (KS: [2][rows] column pairs per thread; Keller-Segel: [2][A][RO_W]).  noise_tab: a learning launch with the amplitude
+// array of pdec_mlp_set_noise_scale keeps each of its columns' amplitude behind the planes (KS: [2][A]; Keller-Segel: [A]); a
+// configuration that this pushes over the 64 KB bound takes the step loop.
+inline size_t rollout_lds(const Env& E, const Mlp& A, bool ks, bool noise_tab = false) {
   const pdec_env_cfg& c = E.cfg;
   const size_t image = (ro_image_elems(A.dims.data(), A.L) + 3) & ~3;
   const size_t planes = ks ? (size_t)4 * *std::max_element(A.dims.begin(), A.dims.begin() + A.L + 1) * E.nthreads : (size_t)2 * c.A * RO_W;
-  return E.lds_bytes + ((size_t)2 * c.A * env_ns(c) + (ks ? 4 : 2) * (size_t)c.A + image + planes) * dtype_size(c.dtype) + 16;
+  const size_t tab = noise_tab ? (ks ? 2 : 1) * (size_t)c.A : 0;
+  return E.lds_bytes + ((size_t)2 * c.A * env_ns(c) + (ks ? 4 : 2) * (size_t)c.A + image + planes + tab) * dtype_size(c.dtype) + 16;
 }
 // does the persistent rollout of the KS (ks) or the 1-D Keller-Segel environment serve E with an actor of A's shape?
 // (everything but the parameters' dtype: the member form reads Float32 parameters into an fp64 image)
-inline bool rollout_shape_ok(const Env& E, const Mlp& A, bool ks) {
+inline bool rollout_shape_ok(const Env& E, const Mlp& A, bool ks, bool noise_tab = false) {
   const pdec_env_cfg& c = E.cfg;
   const char* off = getenv("PDEC_ROLLOUT_PERSISTENT");
   if (off && off[0] == '0') return false;
@@ -166,6 +177,6 @@ inline bool rollout_shape_ok(const Env& E, const Mlp& A, bool ks) {
   if (A.L < 1 || A.L > 3 || A.dims[A.L] != 1 || A.dims[0] != env_ns(c)) return false;
   for (int l = 0; l <= A.L; ++l)
     if (A.dims[l] > RO_W) return false;
-  return rollout_lds(E, A, ks) <= 64 * 1024;
+  return rollout_lds(E, A, ks, noise_tab) <= 64 * 1024;
 }
 }  // namespace pdec

@@ -104,13 +104,15 @@ extern "C" int pdec_rollout(pdec_handle henv, pdec_handle hactor, int T, void* y
   const int ns = env_ns(c), cols = c.B * (c.mono ? 1 : c.A), na = A->dims[A->L];
   PDEC_REQUIRE(A->dims[0] == (c.mono ? c.S : ns) && cols * na == c.B * c.A * env_na(c),
                "pdec_rollout: actor shape %d -> %d does not match the state/action matrices", A->dims[0], na);
-  const RollSpec spec{T, learning, act_noise, act_limit, seed, offset, E->control_from};
+  const bool ntab = learning && A->noise_scale;
+  if (ntab) PDEC_REQUIRE_NOISE_COLS(A, cols, "pdec_rollout");
+  const RollSpec spec{T, learning, act_noise, act_limit, seed, offset, E->control_from, ntab ? A->noise_scale : nullptr, A->noise_scale_cpe};
   const RollPtrs ptrs{y, state, action, reward_sum, log_y, log_p, log_action, log_reward, done_any, done_step};
   // KS: the whole loop in ONE persistent launch -- the trajectories stay in registers / LDS between steps and the actor is
   // evaluated in the kernel (csrc/ks_rollout.hip: ks_rollout_kernel); reward_sum accumulates, the logs are written per step
-  if (ks_rollout_supported(*E, *A)) return ks_rollout_persistent(*E, *A, spec, ptrs);
+  if (ks_rollout_supported(*E, *A, ntab)) return ks_rollout_persistent(*E, *A, spec, ptrs);
   // 1-D Keller-Segel: likewise one launch (csrc/kseg.hip: kseg_rollout_kernel)
-  if (kseg_rollout_supported(*E, *A)) return kseg_rollout_persistent(*E, *A, spec, ptrs);
+  if (kseg_rollout_supported(*E, *A, ntab)) return kseg_rollout_persistent(*E, *A, spec, ptrs);
   return rollout_step_loop(henv, E, T, y, state, action, reward_sum, log_y, log_p, log_action, log_reward, done_any, done_step,
                            [&](int t, const void* s, void* a) {
                              return pdec_policy_act_rng(hactor, s, cols, act_noise, act_limit, learning, seed,

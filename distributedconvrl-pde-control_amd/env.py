@@ -411,7 +411,8 @@ class PDEenv:
         self.mu = t
 
     # ---- T control steps without returning to the host
-    def rollout(self, actor, T, act_noise=0.0, act_limit=1.0, learning=False, seed=0, offset=0, log=False, control_from=0):
+    def rollout(self, actor, T, act_noise=0.0, act_limit=1.0, learning=False, seed=0, offset=0, log=False, control_from=0,
+                noise_scale=None):
         """for t in 1:T; action = policy(env); env(action); end  (src/PDEagent.jl:175-209 + src/PDEenv.jl:195-241)
         enqueued in ONE library call: actor forward (+ exploration noise when `learning`), clamp, fused env step,
         device-side reward accumulation and -- with log=True -- the per-step rows PDEhook records
@@ -419,8 +420,17 @@ class PDEenv:
         Returns device tensors: reward_sum [B, A], done_step [B] (first step that raised `done`, -1 = none) and the logs
         y [T, ...], p, action, reward.  env.y / state / action / steps / time advance by T steps.
         control_from = n0 > 0 (plot_heat's p_t_action, src/plotting.jl:55-60): the steps t < n0 take the zero action -- no
-        actor, no noise -- and reward_sum adds the steps t >= n0 only; logs and done_step cover all T steps."""
+        actor, no noise -- and reward_sum adds the steps t >= n0 only; logs and done_step cover all T steps.
+        noise_scale = [B] (host array or device tensor) with learning=True: trajectory b explores at noise_scale[b] in the place of
+        act_noise (pdec_mlp_set_noise_scale, one entry per A columns), set on the actor for this call; what was set on it before
+        is restored afterwards."""
         T = int(T)
+        scale_prev = None
+        if noise_scale is not None:
+            from .agent import noise_scale_buffer
+            buf = noise_scale_buffer(noise_scale, self.B, self.device, "PDEenv.rollout(noise_scale)", stream=self.stream)
+            scale_prev = (actor.noise_scale,)
+            actor.set_noise_scale(buf, self.setup.reward_len)
         if int(control_from) != self._control_from:
             _lib.check(self.lib.pdec_env_set_control_from(self._h, int(control_from)))
             self._control_from = int(control_from)
@@ -450,6 +460,9 @@ class PDEenv:
                 _lib.ptr(out.get("y")), _lib.ptr(out.get("p")), _lib.ptr(out.get("action")), _lib.ptr(out.get("reward")),
                 _lib.ptr(out["done_any"]), _lib.ptr(out["done_step"])))
         finally:
+            if scale_prev is not None:
+                self._scale_keepalive = buf         # (the launch reads it after this call has returned)
+                actor.set_noise_scale(*(scale_prev[0] or (None,)))
             if moved:
                 _lib.check(self.lib.pdec_set_stream(actor.handle, _stream_ptr(astream)))
                 astream.wait_stream(self.stream)

@@ -43,6 +43,7 @@ class HipMLP:
         _lib.check(self.lib.pdec_mlp_create(C.byref(self._h), _lib.dtype_code(dtype), len(self.acts), d, a, None,
                                             self.max_cols))
         self.stream = stream
+        self.noise_scale = None
         if stream is not None:
             _lib.check(self.lib.pdec_set_stream(self._h, C.c_void_p(stream.cuda_stream)))
         if params is not None:
@@ -112,6 +113,20 @@ class HipMLP:
         p, n = C.c_void_p(), C.c_int()
         _lib.check(self.lib.pdec_mlp_grad_buffer(self._h, C.byref(p), C.byref(n)))
         return p.value, n.value
+
+    def set_noise_scale(self, scale, cols_per_entry=1):
+        """pdec_mlp_set_noise_scale: `scale` a contiguous float64 device tensor [n] that this object keeps alive (column c of an
+        acting call explores at scale[c // cols_per_entry] in the place of the call's act_noise), or None for the scalar.
+        self.noise_scale: (tensor, cols_per_entry) or None -- what to hand back to restore it."""
+        if scale is None:
+            _lib.check(self.lib.pdec_mlp_set_noise_scale(self._h, None, 0, 1))
+            self.noise_scale = None
+            return
+        if not (isinstance(scale, torch.Tensor) and scale.is_cuda and scale.dtype == torch.float64 and scale.dim() == 1
+                and scale.is_contiguous()):
+            raise _lib.PdecError("HipMLP.set_noise_scale: a contiguous float64 device tensor [n]")
+        _lib.check(self.lib.pdec_mlp_set_noise_scale(self._h, _lib.ptr(scale), int(scale.shape[0]), int(cols_per_entry)))
+        self.noise_scale = (scale, int(cols_per_entry))
 
     def clone(self, dtype=None, max_cols=None):
         m = HipMLP(self.dims, self.acts, None, dtype or self.dtype, self.device, max_cols or self.max_cols, self.stream)

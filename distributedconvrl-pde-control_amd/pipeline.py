@@ -130,7 +130,7 @@ class TrainPipeline:
                  chunks=(24, 6, 1), use_replay=False, noise_seed=1234, kick_env_after_critic=None, stream_ar=None,
                  ar_off_chain=None, log_episodes=0, min_best_episode=0, random_init=False, init_seed=0, init_rng=None,
                  init_rank=(0, 1), eval_every=0, eval_inits=8, eval_seed=0, eval_y0=None, eval_capacity=64, eval_stream=None,
-                 best_by="train"):
+                 best_by="train", noise_scale=None):
         """env: PDEenv on `stream_env`; agent: create_agent(..., stream=stream_upd).  lag: the update of step k trains on
         the transition of step k - lag (>= 1).  episode_steps: lock-stepped episodes of that many control steps (0: one
         endless episode): the last transition is terminal (done = time >= te, src/PDEenv.jl:227) and the next step starts
@@ -164,7 +164,10 @@ class TrainPipeline:
         runs beside training.  best_by: "train" -- best_actor() / bestreward / bestepisode follow the training return, as
         without evaluations -- or "eval": the hook's rule on the evaluation scores (episode >= min_best_episode, score not
         NaN and >= every earlier such score), keeping the evaluated parameters.  Needs log_episodes > 0 (the snapshot lives
-        in the ledger), episode_steps > 0 and no active reducer."""
+        in the ledger), episode_steps > 0 and no active reducer.
+
+        noise_scale = [B] (host array or device tensor): trajectory b explores at noise_scale[b] in the place of the policy's
+        act_noise -- see set_noise_scale.  None: the policy's scalar."""
         # pdec_policy_act_rng_dev reads the state ring in the actor's type: a fluid environment of another dtype cannot step.
         # Refused by name at the first run() / capture(), not here: an object of that combination may be constructed and asked
         # for its episode-start draw (tests/test_gpu_pipeline_episodes.py::test_random_inits_fluid does).
@@ -309,6 +312,9 @@ class TrainPipeline:
         self._recapture = False
         self._captured = False
         self.n_graph_launches = self.n_eager_steps = 0
+        self.noise_scale = None   # set_noise_scale: float64 [B] on the device, read by every acting launch
+        if noise_scale is not None:
+            self.set_noise_scale(noise_scale)
         self._setup_episodes(log_episodes, min_best_episode, random_init, init_seed, init_rng, init_rank)
         self._setup_eval(eval_every, eval_inits, eval_seed, eval_y0, eval_capacity, eval_stream, best_by, Ev)
         self.reset_from(env.y0)
@@ -838,10 +844,32 @@ class TrainPipeline:
         t0 = max(self.tick, self._first_tick + self.LAG)
         return any(t % PERIOD == pos and self._interior(t, c) for t in range(t0, t0 + PERIOD * self.E + PERIOD))
 
+    def set_noise_scale(self, values):
+        """Per-trajectory exploration amplitude: `values` [B], a host array (checked: finite, not negative) or a device tensor
+        (copied device to device, no host wait; the caller orders its producer before the env stream), or None to return to
+        policy.act_noise.  The values are written on the env stream INTO a buffer of B doubles that the pipeline owns
+        (self.noise_scale) and that the acting launch reads at column (b A + a) // A = b (pdec_mlp_set_noise_scale), so the
+        recorded steps and the captured graphs, which hold its pointer, stay valid: a schedule such as
+        pipe.set_noise_scale(0.2 * s) between episodes keeps them, where a change of policy.act_noise drops them
+        (_check_key).  Turning the array on or off does change the key.  The array is run state of the pipeline: checkpoints
+        store policy.act_noise only."""
+        if values is None:
+            if self.noise_scale is not None:
+                self.actor.set_noise_scale(None)
+                self.noise_scale = None
+            return
+        from .agent import noise_scale_buffer
+        buf = noise_scale_buffer(values, self.env.B, self.env.device, "TrainPipeline.set_noise_scale", out=self.noise_scale,
+                                 stream=self.s_env)
+        if self.noise_scale is None:
+            self.actor.set_noise_scale(buf, self.cols // self.env.B)
+            self.noise_scale = buf
+
     def _scalar_key(self):
-        """the per-step scalars that a recorded step / a captured graph holds as frozen launch arguments"""
+        """the per-step scalars that a recorded step / a captured graph holds as frozen launch arguments (with a noise scale
+        array set, a fixed marker in the place of act_noise: the launches hold the array's pointer, not its values)"""
         pol = self.policy
-        return (float(pol.act_noise), float(pol.act_limit), float(pol.behavior_actor.optimizer.eta),
+        return ("noise_scale" if self.noise_scale is not None else float(pol.act_noise), float(pol.act_limit), float(pol.behavior_actor.optimizer.eta),
                 float(pol.behavior_critic.optimizer.eta), float(pol.y), float(pol.rho_effective), int(bool(pol.quirk)),
                 pol.reward_group, bool(self.kick_env_after_critic), int(self.noise_seed))
 

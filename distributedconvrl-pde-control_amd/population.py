@@ -393,6 +393,9 @@ class Population:
             if not isinstance(ag, Agent):
                 _refuse(f"member {m}: an Agent with a PDEhook is needed")
             pol = ag.policy
+            if getattr(pol.behavior_actor.model, "noise_scale", None) is not None:
+                _refuse(f"member {m}: a noise scale array is set on its actor (set_noise_scale); a member explores at its own "
+                        "act_noise, which may differ from member to member")
             if getattr(pol, "mono", None) or getattr(pol, "reward_group", None) is not None:
                 continue                # (refused by name below)
             rows, stride = pol.behavior_actor.model.dims[0], ag.trajectory.stride

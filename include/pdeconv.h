@@ -341,6 +341,19 @@ int pdec_policy_act(pdec_handle actor, const void* state, const void* noise, int
  * actions[1:end-memory_size, :] += randn * act_noise); the clamp applies to every row.  Philox element numbering unchanged
  * (element = column * outputs + row; the memory rows' draws are skipped). */
 int pdec_mlp_set_noise_rows(pdec_handle actor, int rows);
+/* exploration amplitude per trajectory instead of one per call (src/PDEagent.jl:199-201 adds randn * act_noise with the agent's
+ * one act_noise; a batch of trajectories explores at a ladder of levels): scale_dev is a device array of n doubles that the
+ * caller keeps alive -- the pointer is stored, nothing is copied or synchronised, so a value written into the array on the acting
+ * stream serves the next launch, a recorded call and a captured graph alike.  NULL returns to the scalar.  With an array set,
+ * column c of an acting call adds z * (T)scale[c / cols_per_entry] (T: the type the kernel computes in) where it added
+ * z * (T)act_noise: an array of equal values is the scalar call bit for bit.  The call's act_noise is not read; learning = 0 still
+ * means no noise; noise rows, the clamp and the Philox element numbering are unchanged.  Served by pdec_policy_act (with noise),
+ * pdec_policy_act_rng, _rng_as, _rng_dev, pdec_step_glue and pdec_rollout with learning = 1 (in a persistent launch the global
+ * column is b A + a; the workgroup keeps its columns' amplitudes in LDS, and a configuration which that pushes over the 64 KB
+ * bound takes the step loop).  A call whose cols is not n * cols_per_entry is refused (PDEC_E_INVALID).  Not served:
+ * pdec_population_create refuses a member whose actor has an array set (members carry their amplitude in the row table); the
+ * member forms (pdec_rollout_members, pdec_policy_act_members) are greedy and do not read it. */
+int pdec_mlp_set_noise_scale(pdec_handle actor, const double* scale_dev, int64_t n, int cols_per_entry);
 int pdec_policy_act_rng(pdec_handle actor, const void* state, int cols, double act_noise, double act_limit,
                         int learning, uint64_t seed, uint64_t offset, void* actions_out);
 /* agent(env) where the environment computes in `state_dtype` and the actor keeps parameters of another type -- the reference's

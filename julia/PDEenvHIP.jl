@@ -277,6 +277,11 @@ Base.copyto!(dst::HipMLP, src::HipMLP) = check(ccall((:pdec_mlp_copy, LIB), Cint
 # memory_size > 0 (EnvCfg(memory_size = m); actions [1 + m, A]): exploration noise on the first `rows` actor outputs only,
 # as actions[1:end-memory_size, :] += randn * act_noise does (src/PDEagent.jl:201)
 set_noise_rows!(m::HipMLP, rows::Integer) = check(ccall((:pdec_mlp_set_noise_rows, LIB), Cint, (UInt64, Cint), m.h, rows))
+# exploration amplitude per trajectory: scale a device array of n Float64 (device_upload) that the caller keeps alive, C_NULL
+# returns to the call's act_noise; column c of an acting call takes scale[c ÷ cols_per_entry] (src/PDEagent.jl:199-201)
+function set_noise_scale!(m::HipMLP, scale::Ptr{Cvoid}, n::Integer, cols_per_entry::Integer)
+    check(ccall((:pdec_mlp_set_noise_scale, LIB), Cint, (UInt64, Ptr{Cdouble}, Int64, Cint), m.h, scale, n, cols_per_entry))
+end
 function Base.deepcopy(m::HipMLP)                       # PDEhook snapshots the actor (src/PDEhook.jl:37-38)
     h = Ref{UInt64}(0)
     check(ccall((:pdec_mlp_create, LIB), Cint, (Ref{UInt64}, Cint, Cint, Ptr{Int32}, Ptr{Int32}, Ptr{Cvoid}, Cint),
