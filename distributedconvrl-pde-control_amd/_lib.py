@@ -152,6 +152,7 @@ DEBUG_SIGNATURES = {
     "pdec_debug_batched_update_route": [Handle, Handle, Handle, Handle, _i, _i, C.c_char_p, _i, C.POINTER(_i64)],
     "pdec_debug_act_members_plan": [Handle, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i64)],
     "pdec_debug_fluid_plan": [Handle, _pi32],
+    "pdec_debug_fluid_wave_table": [_pi32, _i, C.POINTER(_i)],
 }
 _RESTYPES = {"pdec_last_error": C.c_char_p}
 

@@ -12,7 +12,8 @@ extern "C" {
 
 /* Unit-test entry of the register-resident wave FFT the fluid kernels are built on (csrc/wave_fft.hpp): nlines
  * lines of `len` complex doubles (device), natural order in and out, unnormalised forward (sgn < 0) / inverse
- * (sgn > 0) with FFTW's conventions (src/fluid_rk4.jl uses FFTW's fft / ifft).  len in {128,256,384,512,768}. */
+ * (sgn > 0) with FFTW's conventions (src/fluid_rk4.jl uses FFTW's fft / ifft).  len in {64,128,192,256,384,512,768}, the
+ * padded lengths of the plan table (pdec_debug_fluid_wave_table). */
 int pdec_debug_wave_fft(const void* in_dev, void* out_dev, int len, int nlines, int sgn);
 /* The same for `len` complex floats (the transform of the fp32 fluid environment); twiddles computed in fp64 and rounded
  * once.  len in {64,128,192,256,384,512,768}. */
@@ -72,8 +73,17 @@ int pdec_debug_act_members_plan(pdec_handle actor, int state_dtype, int cols_per
  * plan WaveFft<E, Q, LB> serving p; 0, 0, 0: the LDS-tile kernels serve it), pair (fluid_k1w_kernel takes a line and its mirror
  * per wave), k2p (the persistent x-pass fluid_k2p_kernel, W tile-major), fused (do_step takes fluid_integrate_wave), nparts (parts
  * the fused env step splits the batch into; 0: unsplit), x-pass tiles (B p / 8 workgroup tiles of fluid_k2p_kernel; 0 without it) }.
- * Computed by the host code that dispatches (csrc/fluid.hip fluid_make, k2p_eligible, fluid_fused). */
+ * Computed by the host code that dispatches (csrc/fluid.hip fluid_make and fluid_fused, csrc/fluid_wave.hip k2p_eligible, all
+ * three from the environment's row of the plan table below). */
 int pdec_debug_fluid_plan(pdec_handle env, int32_t* out12);
+
+/* Unit-test entry (no reference counterpart): the table of one-line-per-wave plans of the fluid environment (csrc/fluid_wave.hip
+ * fluid_wave_table), the one place that says which WaveFft<E, Q, LB> serves a padded length and which instantiations exist for
+ * it -- host code only: needs no device and no handle.  *nrows = rows of the table; out, where cap >= 14 * *nrows (else
+ * PDEC_E_INVALID with *nrows set), receives per row { p, E, Q, LB, then for fp64 and again for fp32: rhs (the un-fused right-hand
+ * side is built: 1 / 0), fused (fluid_integrate_wave with fluid_k31w_kernel), k2p (fluid_k2p_kernel), NPW, NSU (the DMA pieces per
+ * wave and output elements per thread that instantiation was built for; 0, 0 without one) }. */
+int pdec_debug_fluid_wave_table(int32_t* out, int cap, int* nrows);
 
 #ifdef __cplusplus
 }

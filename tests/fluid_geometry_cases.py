@@ -1,8 +1,9 @@
-"""The case table of test_gpu_fluid_geometry.py: geometries of the 2-D fluid environment (csrc/fluid.hip: the LDS-tile kernels
-fluid_k1/k2/k3_kernel and fluid_fft_fast/slow_kernel, the one-line-per-wave kernels fluid_k1w/k2w/k2p/k3w/k31w_kernel on the seven
-WaveFft<E, Q, LB> plans, the fused integrator fluid_integrate_wave, fluid_dots/feat/actuate_kernel) away from the grids the other
-fluid tests visit, plus a plain-Python restatement of the host rules that decide what a geometry reaches (fluid_make, pick_tile,
-k2p_eligible, fluid_fused, fluid_k2_launch, the batch parts of pdec_fluid_env_create, the LDS bytes of both kernel families).
+"""The case table of test_gpu_fluid_geometry.py: geometries of the 2-D fluid environment (csrc/fluid_lds.hip: the LDS-tile kernels
+fluid_k1/k2/k3_kernel and fluid_fft_fast/slow_kernel; csrc/fluid_wave.hip: the one-line-per-wave kernels
+fluid_k1w/k2w/k2p/k3w/k31w_kernel on the seven WaveFft<E, Q, LB> plans and the fused integrator fluid_integrate_wave;
+csrc/fluid_sense.hip: fluid_dots/feat/actuate_kernel) away from the grids the other fluid tests visit, plus a plain-Python
+restatement of the host rules that decide what a geometry reaches (fluid_make and fluid_fused of csrc/fluid.hip, pick_tile, the plan
+table fluid_wave_table with k2p_eligible and fluid_k2_launch, the batch parts of pdec_fluid_env_create, the LDS bytes of both families).
 Imports numpy only, so test_fluid_geometry_table.py holds every claim of the table against the oracle and the setup's host tables
 without a GPU; on the GPU the restated plan is held against the library's own (pdec_debug_fluid_plan) before a row runs.
 
@@ -78,7 +79,7 @@ SWITCH_CASES = {
 SWITCHES = [("PDEC_FLUID_K2P", "0"), ("PDEC_FLUID_FUSE", "1"), ("PDEC_FLUID_FUSE", "0"), ("PDEC_FLUID_LDS_FFT", "1")]
 # PDEC_FLUID_K2P=0 against the default process: fluid_k2w_kernel and fluid_k2p_kernel evaluate the same expressions in the same
 # order, so the right-hand sides are equal bit for bit (0) wherever the compiler contracts the multiply-adds of both alike -- all
-# but <float,4,3,..>, where it does not (csrc/fluid.hip above fluid_k2p_kernel).  There a result may differ by one rounding per
+# but <float,4,3,..>, where it does not (csrc/fluid_wave.hip above fluid_k2p_kernel).  There a result may differ by one rounding per
 # butterfly level: 768 = 4^4 3 has five, three transforms and the product make 16 -> 16 x 2^-24 of max |rhs| (measured: 2.6).
 K2P_VS_K2W = {("k2p0_256", "f64"): 0.0, ("k2p0_256", "f32"): 0.0, ("k2p0_512", "f64"): 0.0, ("k2p0_512", "f32"): 16 * 2.0 ** -24}
 
@@ -198,12 +199,13 @@ def reference(pkg, fluid, case):
 
 
 # ------------------------------------------------------------------ the host rules, restated
-FL_NTH, FL_TILE_ELEMS = 1024, 3072       # csrc/fluid.hip: FL_NTH, FL_NTH * FL_MAXE (TL * len <= 3072)
+FL_NTH, FL_TILE_ELEMS = 1024, 3072       # csrc/fluid.hpp: FL_NTH, FL_NTH * FL_MAXE (TL * len <= 3072)
 FL_K2_TC = 4                             # columns per workgroup of fluid_k2w_kernel
 LDS_MAX = 160 * 1024
 MAXPART = 4                              # PartStreams::MAX
+# fluid_wave_table of csrc/fluid_wave.hip; test_fluid_geometry_table.py holds both lists against the library's own table
 WAVE_PLANS = {768: (4, 3, 6), 512: (4, 2, 6), 256: (4, 1, 6), 384: (2, 3, 6), 128: (2, 1, 6), 192: (2, 3, 5), 64: (2, 1, 5)}
-K2P_BUILT = {"f64": {(9, 8), (5, 4)}, "f32": {(5, 8), (3, 4)}}     # (NPW, NSU) of the PDEC_K2P list in fluid_k2_launch
+K2P_BUILT = {"f64": {(9, 8), (5, 4)}, "f32": {(5, 8), (3, 4)}}     # (NPW, NSU) of the table's K2p columns
 PLAN_FIELDS = ("p", "nl", "TL", "TLn", "wave_E", "wave_Q", "wave_LB", "pair", "k2p", "fused", "nparts", "xtiles")
 
 

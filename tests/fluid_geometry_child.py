@@ -1,5 +1,5 @@
 """Child process of test_gpu_fluid_geometry.py::test_switch_rows_match_the_oracle: started with ONE of the documented switches set
-(PDEC_FLUID_K2P=0, PDEC_FLUID_FUSE=1, PDEC_FLUID_FUSE=0 or PDEC_FLUID_LDS_FFT=1; csrc/fluid.hip reads each once per process), it
+(PDEC_FLUID_K2P=0, PDEC_FLUID_FUSE=1, PDEC_FLUID_FUSE=0 or PDEC_FLUID_LDS_FFT=1; csrc/fluid.hip and fluid_wave.hip read each once per process), it
 runs the rows of fluid_geometry_cases.SWITCH_CASES that belong to that switch in both precisions on the inputs the parent left
 in DIR (<row>_y.npy, <row>_p.npy: complex [B, n, n]) and writes, per row and precision, <row>_<prec>_rhs.npy and / or
 <row>_<prec>_step.npy (complex128 [B, n, n]) plus meta.json: the switch as the process saw it, pdec_debug_fluid_plan of every

@@ -1,7 +1,7 @@
 """The case table of test_gpu_fluid_geometry.py (fluid_geometry_cases.py) held against the oracle and the setup's host tables.
 Runs without a GPU: it proves that every row reaches what it is there for (the kernel family, the WaveFft plan, lines per LDS
 tile, the persistent x-pass and its piece counts, the fused integrator and its fall-through, the sensing edges), that every
-instantiation the host dispatch of csrc/fluid.hip names has a row, that the inputs stay finite, tame and alive in the oracle itself
+instantiation the plan table of csrc/fluid_wave.hip builds has a row (and that the table is the one restated here), that the inputs stay finite, tame and alive in the oracle itself
 -- so the GPU test cannot pass on NaNs or on zeros -- that the inputs of the fused rows tell the self-mirror arm and the mode-4
 chain apart, and it fails by name when a purpose of the table loses its row."""
 import numpy as np
@@ -168,14 +168,57 @@ def test_every_purpose_has_its_row(geo, purpose):
 
 
 def test_the_fused_form_of_the_128_point_plan_cannot_be_reached():
-    """fluid_integrate names fluid_integrate_wave<T,2,1,6> (p = 128); the fused form needs n >= 256 and p >= n, so no geometry
-    reaches it under any switch -- the one instantiation of the dispatch without a row"""
+    """the plan table (csrc/fluid_wave.hip) builds no fluid_integrate_wave<T,2,1,6> (p = 128): the fused form needs n >= 256 and
+    p >= n, so no geometry would reach it under any switch -- the one-line-per-wave plan that FUSABLE leaves out"""
     for n in range(8, 1025, 4):
         for ifpad in (0, 1):
             c = fc._case(n, ifpad, env=("PDEC_FLUID_FUSE", "1"))
             if fc.fft_radices(n) is None or fc.fft_radices(n * 3 // 2 if ifpad else n) is None:
                 continue
             assert fc.geometry(c, "f64")["step_route"] != (2, 1, 6)
+
+
+def test_the_librarys_plan_table_is_the_restated_one(pkg):
+    """fluid_wave_table of csrc/fluid_wave.hip, read through pdec_debug_fluid_wave_table (host code: no device, no handle),
+    is WAVE_PLANS; its K2p columns are K2P_BUILT, on the rows p = 768 and p = 384 and nowhere else, each with the pieces K2pGeom
+    gives for n = 512 / n = 256; its fused column is FUSABLE; and the instantiation names of PURPOSES are its built cells,
+    one for one -- so a plan added to or dropped from the library fails here until the restated lists follow"""
+    import ctypes
+    lib = ctypes.CDLL(pkg._lib.LIB_PATH)
+    fn = lib.pdec_debug_fluid_wave_table
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    nrows = ctypes.c_int(-1)
+    assert fn(None, 0, ctypes.byref(nrows)) != 0 and nrows.value == len(fc.WAVE_PLANS)        # no room: refused, the count told
+    per = 14
+    buf = (ctypes.c_int32 * (per * nrows.value))()
+    short = (ctypes.c_int32 * (per * nrows.value))()
+    assert fn(short, per * nrows.value - 1, ctypes.byref(nrows)) != 0 and not any(short)      # one number short: nothing written
+    assert fn(buf, len(buf), ctypes.byref(nrows)) == 0 and nrows.value == len(fc.WAVE_PLANS)
+    rows = [list(buf[per * i:per * (i + 1)]) for i in range(nrows.value)]
+    assert len({r[0] for r in rows}) == len(rows) and {r[0]: tuple(r[1:4]) for r in rows} == fc.WAVE_PLANS
+    k2p_rows = {768: 512, 384: 256}                                                           # p: the padded grid's n
+    ctype = {"f64": "double", "f32": "float"}
+    names = set()
+    for r in rows:
+        p, plan = r[0], tuple(r[1:4])
+        cells = dict(zip(fc.PRECS, (r[4:9], r[9:14])))
+        for prec, (rhs, fused, k2p, npw, nsu) in cells.items():
+            assert rhs == 1, (p, prec)                                                        # all seven plans of K1w, K2w and K3w
+            assert fused == int(plan in FUSABLE), (p, prec)
+            assert k2p == int(p in k2p_rows) and (bool(k2p) or (npw, nsu) == (0, 0)), (p, prec)
+            if k2p:
+                n = k2p_rows[p]
+                assert (npw, nsu) == fc.k2p_geom(n + 1, n, prec)[1:3] and (npw, nsu) in fc.K2P_BUILT[prec], (p, prec)
+                names.add("fluid_k2p_kernel<%s,%d,%d,%d,%d>" % (ctype[prec], plan[0], plan[1], npw, nsu))
+        assert cells["f64"][:3] == cells["f32"][:3]                                           # the names with T: both dtypes
+        names.add("fluid_rhs_launch_wave<T,%d,%d,%d>" % plan)
+        names.add("fluid_k2w_kernel<T,%d,%d,%d,%d>" % (plan[0], plan[1], fc.FL_K2_TC, plan[2]))
+        if cells["f64"][1]:
+            names.add("fluid_integrate_wave<T,%d,%d,%d>" % plan)
+    for prec in fc.PRECS:
+        assert {tuple(r[7:9] if prec == "f64" else r[12:14]) for r in rows if r[0] in k2p_rows} == fc.K2P_BUILT[prec]
+    assert names == {k for k in PURPOSES if "<" in k}
 
 
 # ------------------------------------------------------------------ the setup's tables are the oracle's

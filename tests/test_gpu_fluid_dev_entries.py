@@ -1,4 +1,4 @@
-"""The two device entry points a fluid population stands on (csrc/fluid.hip): pdec_fluid_ic_dev, the episode initialiser from a
+"""The two device entry points a fluid population stands on (csrc/fluid_sense.hip): pdec_fluid_ic_dev, the episode initialiser from a
 vortex table that is already in device memory, against pdec_fluid_ic bit for bit; and pdec_fluid_error_detection, the fluid
 script's error_detection (scripts/Fluid/setup/FluidSetup.jl:263-273) per trajectory, against oracle.fluid.error_detection with
 FluidSetup.error_detection as the second witness.

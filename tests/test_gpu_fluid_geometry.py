@@ -1,4 +1,4 @@
-"""The 2-D fluid kernels (csrc/fluid.hip) against oracle/fluid.py over the geometries of fluid_geometry_cases.py, in fp64 and fp32:
+"""The 2-D fluid kernels (csrc/fluid_lds.hip, fluid_wave.hip, fluid_sense.hip) against oracle/fluid.py over the geometries of fluid_geometry_cases.py, in fp64 and fp32:
 the LDS-tile kernels with 8, 4 and 2 lines per tile (radix-5 stages among them, and the fall-through of a grid that asks for the
 fused integrator and has no wave plan), the fused integrator on un-padded grids (self-mirrored Nyquist line), with K = 1 and
 K = 3 and with several x-pass tiles per workgroup, do_step on the half-wave plans and with the persistent x-pass at n = 512,
@@ -127,7 +127,7 @@ def test_switch_rows_match_the_oracle(pkg, tmp_path, var, value):
     """PDEC_FLUID_K2P=0: fluid_k2w_kernel<T,2,3,4,6> and <T,4,3,4,6>; PDEC_FLUID_FUSE=1: fluid_k31w_kernel<T,4,3,6> and <T,4,2,6>;
     PDEC_FLUID_FUSE=0: the plain loop at n = 256; PDEC_FLUID_LDS_FFT=1: the LDS-tile kernels at the wave lengths (TL 16, 8, 4).
     The child's plan, rhs and do_step against the table and the oracle; under PDEC_FLUID_K2P=0 the right-hand side also equals
-    this process's (fluid_k2p_kernel) bit for bit wherever csrc/fluid.hip states that of W2 (fluid_geometry_cases.K2P_VS_K2W)."""
+    this process's (fluid_k2p_kernel) bit for bit wherever csrc/fluid_wave.hip states that of W2 (fluid_geometry_cases.K2P_VS_K2W)."""
     from oracle import fluid
     rows = fc.switch_rows(var, value)
     assert rows

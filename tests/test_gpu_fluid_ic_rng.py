@@ -1,5 +1,5 @@
 """pdec_fluid_ic_rng: ic(3) / ic(4) of the fluid with the vortex table drawn on the device from the library's Philox stream
-(csrc/fluid.hip: fluid_vortex_draw_kernel, then the launches of pdec_fluid_ic_dev).
+(csrc/fluid_sense.hip: fluid_vortex_draw_kernel, then the launches of pdec_fluid_ic_dev).
 
 The table against the host restatement (tests/fluid_ic_ref.py on oracle.rng.words) within 1e-15 absolute -- its entries are single
 fp64 products or sums of values in (0, 1.5), the margin allows a fused multiply-add --; the field bit for bit pdec_fluid_ic_dev

@@ -1,4 +1,4 @@
-"""Per-column terminal rows of the fluid env step (pdec_env_set_terminal_out on PDEC_PDE_FLUID_RK4; csrc/fluid.hip:
+"""Per-column terminal rows of the fluid env step (pdec_env_set_terminal_out on PDEC_PDE_FLUID_RK4; csrc/fluid_sense.hip:
 fluid_feat_kernel): rows [B][A] = 1 on every column of a trajectory whose done flag of the step is set, under every
 check_max_value mode, with and without a done array, with the batch split into parts; everything else the step writes bit for
 bit what it writes without the buffer.

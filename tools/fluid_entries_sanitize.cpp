@@ -1,4 +1,4 @@
-// Stand-alone host check of the two device entry points of csrc/fluid.hip (pdec_fluid_ic_dev, pdec_fluid_error_detection) under
+// Stand-alone host check of the two device entry points of csrc/fluid_sense.hip (pdec_fluid_ic_dev, pdec_fluid_error_detection) under
 // AddressSanitizer / UBSan, on a machine without a GPU.  No environment can be made there, so what runs is the entry points'
 // handle look-up with every combination of arguments a confused caller might pass: each call must return an error code, set
 // pdec_last_error and write none of its outputs.  The argument checks behind a valid handle and the launches themselves need
@@ -6,10 +6,10 @@
 //
 //   cd distributedconvrl-pde-control_amd/csrc && make            # the other objects, as usual
 //   hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -Xarch_host -fsanitize=address,undefined \
-//         -Xarch_host -fno-sanitize-recover=all -c fluid.hip -o /tmp/fluid_san.o
+//         -Xarch_host -fno-sanitize-recover=all -c fluid_sense.hip -o /tmp/fluid_san.o
 //   clang++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I../../include \
 //         -c ../../tools/fluid_entries_sanitize.cpp -o /tmp/san_main.o
-//   hipcc -fsanitize=address,undefined --offload-arch=gfx950 /tmp/san_main.o /tmp/fluid_san.o $(ls *.o | grep -v '^fluid.o$') \
+//   hipcc -fsanitize=address,undefined --offload-arch=gfx950 /tmp/san_main.o /tmp/fluid_san.o $(ls *.o | grep -v '^fluid_sense.o$') \
 //         -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib -o /tmp/fluid_entries_sanitize && /tmp/fluid_entries_sanitize
 #include <cstdint>
 #include <cstdio>
