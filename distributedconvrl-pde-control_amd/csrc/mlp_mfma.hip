@@ -136,19 +136,52 @@ template <int N>
 __device__ __forceinline__ void dma_wait_but() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-// h = relu(W1 x + b1): x given as KT register rows (lane holds x[4t+q][col])
+// Live extents of a net inside its padded image (wave-uniform, computed once per kernel).  The image is zero outside
+// [H][K0] and [H][H] (prep_fused_kernel writes 0 there, finish_param writes live elements only) and the activations are
+// zero in the same rows, so an MFMA on a k-step or a tile beyond these counts adds exact zeros: it is not issued.
+//   kt = ceil(K0 / 4) k-steps of the first layer hold an input row (the bias enters through the accumulator, not a ones row)
+//   mo = ceil(H / 16) tiles hold a hidden unit; tiles(H) = ceil((H + 1) / 16) counts the bias / output-gradient row of the
+//        GRADIENT image too, so mo is MT or MT - 1: only the LAST tile of a net can be dead (H a multiple of 16)
+// full (PDEC_FUSED_FULL_ROWS=1, tests only): the padded extents, i.e. every MFMA on zero rows and tiles is issued as well --
+// the bit-identity reference (tests/test_gpu_fused_live_rows.py).
+struct LiveRows {
+  int kt, mo;
+};
+template <int MT>
+__device__ __forceinline__ LiveRows live_rows(int K0, int H, int full) {
+  LiveRows v;
+  v.kt = full ? KXP / 4 : (K0 + 3) >> 2;
+  v.mo = full ? MT : (H + 15) >> 4;
+  return v;
+}
+
+// h = relu(W1 x + b1): x given as KT register rows (lane holds x[4t+q][col]).  k-steps t >= lv.kt are skipped, a last tile
+// at or beyond lv.mo is zero without an MFMA.  One uniform branch around a whole k-step for all tiles: the MFMAs of a k-step
+// are independent of each other, and every accumulator still takes its k-steps in the order t = 0, 1, ...
 template <int MT, int KT>
-__device__ __forceinline__ void layer_in(f32x4 (&h)[MT], const float (&x)[KT], const SmallLds& s, int lr, int q) {
+__device__ __forceinline__ void layer_in(f32x4 (&h)[MT], const float (&x)[KT], const SmallLds& s, int lr, int q, LiveRows lv) {
+  const bool last = MT - 1 < lv.mo;           // the one tile that can be dead
 #pragma unroll
   for (int mo = 0; mo < MT; ++mo) {
     const float* b = s.b1 + 16 * mo + 4 * q;
-    f32x4 acc = {b[0], b[1], b[2], b[3]};
-#pragma unroll
-    for (int t = 0; t < KT; ++t) acc = mfma4(s.W1[(16 * mo + lr) * LDW1 + 4 * t + q], x[t], acc);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = fmaxf(acc[r], 0.f);
-    h[mo] = acc;
+    h[mo] = f32x4{b[0], b[1], b[2], b[3]};
   }
+  auto kstep = [&](int t) {
+#pragma unroll
+    for (int mo = 0; mo < MT - 1; ++mo) h[mo] = mfma4(s.W1[(16 * mo + lr) * LDW1 + 4 * t + q], x[t], h[mo]);
+    if (last) h[MT - 1] = mfma4(s.W1[(16 * (MT - 1) + lr) * LDW1 + 4 * t + q], x[t], h[MT - 1]);
+  };
+  static_assert(KT == 4, "layer_in: four k-steps (KXP input rows)");
+  kstep(0);                                   // K0 >= 1
+  if (lv.kt > 1) {
+    kstep(1);
+    if (lv.kt > 2) {
+      kstep(2);
+      if (lv.kt > 3) kstep(3);
+    }
+  }
+  if (!last) h[MT - 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  relu_<MT>(h);
 }
 
 // out = W in (+ bias): W image row-major [..][ldw] in LDS, 4 consecutive k per ds_read_b128.
@@ -223,6 +256,41 @@ __device__ __forceinline__ void layer_hh(f32x4 (&out)[MTO], const f32x4 (&in)[MT
                                          const float* bias, int lr, int q) {
   layer_hh_part<MTO, MTI, BIAS, 0, MTO>(out, in, W, ldw, bias, lr, q);
 }
+// layer_hh for the ACTOR-sized products (MTA x MTA tiles): output tiles and k-tiles at or beyond `live` = LiveRows::mo of that
+// net are skipped, dead output tiles are zero.  With every tile live (and always at one tile) it is layer_hh itself, instruction
+// for instruction; otherwise one chain per live tile over the live k-tiles, in layer_hh's order m = 0, 1, ...  The critic's
+// MT x MT chains do not come through here.
+template <int MTO, int MTI, bool BIAS>
+__device__ __forceinline__ void layer_hh_live(f32x4 (&out)[MTO], const f32x4 (&in)[MTI], const float* W, int ldw,
+                                              const float* bias, int lr, int q, int live) {
+  static_assert(MTO == MTI, "layer_hh_live: square hidden layers");
+  if (MTO == 1 || live >= MTO) {
+    layer_hh<MTO, MTI, BIAS>(out, in, W, ldw, bias, lr, q);
+    return;
+  }
+#pragma unroll
+  for (int mo = 0; mo < MTO; ++mo) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (mo < live) {
+      if (BIAS) {
+        const float* b = bias + 16 * mo + 4 * q;
+        acc = f32x4{b[0], b[1], b[2], b[3]};
+      }
+      const float* wrow = W + (16 * mo + lr) * ldw + 4 * q;
+#pragma unroll
+      for (int m = 0; m < MTI; ++m) {
+        if (m < live) {
+          const f32x4 wv = *reinterpret_cast<const f32x4*>(wrow + 16 * m);
+          acc = mfma4(wv[0], in[m][0], acc);
+          acc = mfma4(wv[1], in[m][1], acc);
+          acc = mfma4(wv[2], in[m][2], acc);
+          acc = mfma4(wv[3], in[m][3], acc);
+        }
+      }
+    }
+    out[mo] = acc;
+  }
+}
 
 struct FusedArgs {
   FNet A, C, At, Ct;          // A/At unused fields are ignored by the actor pass
@@ -235,6 +303,7 @@ struct FusedArgs {
   int nrpart;
   const float* rbar_dev;      // != null: batch-mean reward already reduced by launch_rmean (batches beyond 32768 columns)
   int prio;                   // wave priority of the pass (PDEC_PRIO_MFMA, default 0)
+  int full_rows;              // != 0 (PDEC_FUSED_FULL_ROWS=1, tests only): MFMAs over the padded extents, see LiveRows
   unsigned long long* stamps; // diagnostic only (PDEC_STAMPS=1): [gridDim.x][16] s_memtime at phase boundaries
 
 
@@ -290,6 +359,7 @@ __global__ __launch_bounds__(FTHREADS) __attribute__((amdgpu_num_vgpr(112))) voi
   const int ns = g.ns, na = g.na, K0 = ns + na;
   const int col = blockIdx.x * FCOLS + w * 16 + lr;
   const bool valid = col < g.Bu;
+  const LiveRows LAt = live_rows<MTA>(ns, g.At.H, g.full_rows), LC = live_rows<MT>(K0, g.C.H, g.full_rows);   // (Ct is C's shape)
   set_wave_prio(g.prio);
 
 
@@ -353,15 +423,15 @@ __global__ __launch_bounds__(FTHREADS) __attribute__((amdgpu_num_vgpr(112))) voi
   float tgt;
   {
     f32x4 ha1[MTA], ha2[MTA];
-    layer_in<MTA, 4>(ha1, x, SA, lr, q);
-    layer_hh<MTA, MTA, true>(ha2, ha1, saW2, LDWa, SA.b2, lr, q);
+    layer_in<MTA, 4>(ha1, x, SA, lr, q, LAt);
+    layer_hh_live<MTA, MTA, true>(ha2, ha1, saW2, LDWa, SA.b2, lr, q, LAt.mo);
     relu_<MTA>(ha2);
     const float an = tanhf(head<MTA>(ha2, SA.w3, SA.b3[0], q));      // na == 1
 #pragma unroll
     for (int t = 0; t < 4; ++t)
       if (4 * t + q == ns) x[t] = valid ? an : 0.f;
     f32x4 h1[MT], h2[MT];
-    layer_in<MT, 4>(h1, x, SCt, lr, q);
+    layer_in<MT, 4>(h1, x, SCt, lr, q, LC);
     dma_wait_but<N_SC>();                                 // the target critic's W2 has landed
     lds_barrier();
     layer_hh<MT, MT, true>(h2, h1, Wreg, LDW, SCt.b2, lr, q);
@@ -378,7 +448,7 @@ __global__ __launch_bounds__(FTHREADS) __attribute__((amdgpu_num_vgpr(112))) voi
 #pragma unroll
   for (int t = 0; t < 4; ++t) x[t] = xq[t];
   f32x4 h1[MT], h2[MT];
-  layer_in<MT, 4>(h1, x, SC, lr, q);
+  layer_in<MT, 4>(h1, x, SC, lr, q, LC);
   dma_wait();
   lds_barrier();
   layer_hh<MT, MT, true>(h2, h1, Wreg, LDW, SC.b2, lr, q);
@@ -523,6 +593,7 @@ __global__ __launch_bounds__(FTHREADS) __attribute__((amdgpu_num_vgpr(112))) voi
   const int ns = g.ns;
   const int col = blockIdx.x * FCOLS + w * 16 + lr;
   const bool valid = col < g.Bu;
+  const LiveRows LA = live_rows<MTA>(ns, g.A.H, g.full_rows), LC = live_rows<MT>(ns + g.na, g.C.H, g.full_rows);
   set_wave_prio(g.prio);
 
   // copy schedule as in the critic pass: small blocks, then the per-column input loaded AND consumed, then the long copy
@@ -541,15 +612,15 @@ __global__ __launch_bounds__(FTHREADS) __attribute__((amdgpu_num_vgpr(112))) voi
   dma_even<NB, NW>(Wreg, g.C.w + g.C.oW2, w, l);      // lands behind the actor forward and the critic's first layer
   lds_barrier();
   f32x4 ha1[MTA], ha2[MTA];
-  layer_in<MTA, 4>(ha1, xs, SA, lr, q);
-  layer_hh<MTA, MTA, true>(ha2, ha1, saW2, LDWa, SA.b2, lr, q);
+  layer_in<MTA, 4>(ha1, xs, SA, lr, q, LA);
+  layer_hh_live<MTA, MTA, true>(ha2, ha1, saW2, LDWa, SA.b2, lr, q, LA.mo);
   relu_<MTA>(ha2);
   const float aout = tanhf(head<MTA>(ha2, SA.w3, SA.b3[0], q));
   float x[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) x[t] = (4 * t + q == ns) ? (valid ? aout : 0.f) : xs[t];
   f32x4 h1[MT], h2[MT];
-  layer_in<MT, 4>(h1, x, SC, lr, q);
+  layer_in<MT, 4>(h1, x, SC, lr, q, LC);
   unsigned long long relu1 = 0;         // bit 4 m + r = [h1[m][r] > 0]: all the backward pass needs of h1
 #pragma unroll
   for (int m = 0; m < MT; ++m)
@@ -596,7 +667,7 @@ __global__ __launch_bounds__(FTHREADS) __attribute__((amdgpu_num_vgpr(112))) voi
   const float dza3 = da * (1.f - aout * aout);
   f32x4 dza2[MTA], dza1[MTA];
   head_bwd<MTA>(dza2, ha2, SA.w3, dza3, q);
-  layer_hh<MTA, MTA, false>(dza1, dza2, saW2T, LDWa, nullptr, lr, q);
+  layer_hh_live<MTA, MTA, false>(dza1, dza2, saW2T, LDWa, nullptr, lr, q, LA.mo);
 #pragma unroll
   for (int m = 0; m < MTA; ++m)
 #pragma unroll
@@ -929,7 +1000,7 @@ __global__ __launch_bounds__(ACT_THREADS) void policy_act_fused_kernel(FNet f, c
                                                                       AN act_noise, float lim, int learning, int tanh_out,
                                                                       uint64_t seed, uint64_t offset, float* __restrict__ out,
                                                                       const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc,
-                                                                      int prio) {
+                                                                      int prio, int full_rows) {
   extern __shared__ __align__(16) float smem[];
   if (ctr_cur) {       // noise counter kept on the device (pdec_policy_act_rng_dev): read it, one thread writes the advanced value
     offset += *ctr_cur;
@@ -955,8 +1026,9 @@ __global__ __launch_bounds__(ACT_THREADS) void policy_act_fused_kernel(FNet f, c
   dma_wait();
   __syncthreads();
   f32x4 h1[MTA], h2[MTA];
-  layer_in<MTA, 4>(h1, x, SA, lr, q);
-  layer_hh<MTA, MTA, true>(h2, h1, saW2, LDWa, SA.b2, lr, q);
+  const LiveRows LA = live_rows<MTA>(ns, f.H, full_rows);
+  layer_in<MTA, 4>(h1, x, SA, lr, q, LA);
+  layer_hh_live<MTA, MTA, true>(h2, h1, saW2, LDWa, SA.b2, lr, q, LA.mo);
   relu_<MTA>(h2);
   float o = head<MTA>(h2, SA.w3, SA.b3[0], q);
   if (!valid || q != 0) return;
@@ -993,6 +1065,13 @@ static int visit_act_tiles(int mta, F&& f) {
 #undef X
   set_error("fused act: no instantiation for %d actor tiles", mta);
   return PDEC_E_INVALID;
+}
+
+// tests only, read per launch: the passes and the acting kernel issue every MFMA of the padded extents (LiveRows; the
+// bit-identity reference of the live-row form)
+static int fused_full_rows() {
+  const char* e = getenv("PDEC_FUSED_FULL_ROWS");
+  return (e && e[0] == '1') ? 1 : 0;
 }
 
 static bool fused_disabled() {
@@ -1276,10 +1355,11 @@ static int fused_policy_act(Mlp* A, const void* state, int cols, double act_nois
   if ((rc = fused_act_plan(A, &mta, &lds))) return rc;
   const int tanh_out = A->acts[2] == PDEC_ACT_TANH;
   const int prio = env_prio("PDEC_PRIO_ACT", 3);
+  const int full_rows = fused_full_rows();
   const dim3 grid((cols + 63) / 64), block(ACT_THREADS);
   rc = visit_act_tiles(mta, [&](auto MTA) {
 #define ACT_ARGS(an) f, (const float*)state, cols, A->dims[0], an, (float)act_limit, learning, tanh_out, seed, offset, \
-                     (float*)actions_out, ctr_cur, ctr_next, ctr_inc, prio
+                     (float*)actions_out, ctr_cur, ctr_next, ctr_inc, prio, full_rows
     auto go = [&](auto kern, auto an) {
       if (A->prof) PDEC_TIMED_LAUNCH(A, "policy_act_fused", kern, grid, block, lds, ACT_ARGS(an));
       else hipLaunchKernelGGL(kern, grid, block, lds, A->stream, ACT_ARGS(an));
@@ -1326,6 +1406,7 @@ static int fused_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, c
   g.Bu = Bu; g.ns = A->dims[0]; g.na = 1; g.gamma = (float)gamma; g.quirk = quirk;
   g.slab = C->fslab.as<float>();
   g.prio = env_prio("PDEC_PRIO_MFMA", 2);
+  g.full_rows = fused_full_rows();
   if (quirk && C->rpart_ext) {         // the producer of r left one partial sum per workgroup
     g.rpart = C->rpart_ext; g.nrpart = C->rpart_n;
   } else if (quirk && C->rbar_ext) {   // reduced by the producer of r on its own stream (pdec_reward_mean): nothing to sum here
@@ -1369,6 +1450,7 @@ static int fused_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, dou
   g.s = (const float*)s; g.Bu = Bu; g.ns = A->dims[0]; g.na = 1;
   g.slab = A->fslab.as<float>();
   g.prio = env_prio("PDEC_PRIO_MFMA", 2);
+  g.full_rows = fused_full_rows();
   // the actor pass is launched on the critic's stream object for profiling labels but must follow
   // ADAM(C); both handles share one stream in every caller (checked by the dispatcher)
   rc = visit_tiles(mt, mta, [&](auto MT, auto MTA) {
