@@ -7,50 +7,12 @@
 namespace pdec {
 
 // ------------------------------------------------------------------ stand-alone closures
-// MODE 0: prepare_action, 1: featurize, 2: reward
+// MODE 0: prepare_action, 1: featurize, 2: reward (env_sense.hpp: sense_traj)
 template <class T, int MODE>
 __global__ void sense_kernel(EnvDev<T> e, const T* __restrict__ y, const T* __restrict__ action,
                              const T* __restrict__ action_prev, const T* __restrict__ state_prev,
                              T* __restrict__ out) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  const int N = e.N, tid = threadIdx.x, nt = blockDim.x, b = blockIdx.x;
-  T* sy = reinterpret_cast<T*>(smem_raw);  // [2][N]
-  T* act = sy + 2 * N;
-  T* actp = act + e.A;
-  T* dots = actp + e.A;
-  T* part = dots + 2 * e.S;
-  if (MODE == 0 || MODE == 2) {     // row 0 of every action column (KSSetup.jl:176,241: action[1, i]); na = 1 without action memory
-    for (int a = tid; a < e.A; a += nt) {
-      act[a] = action[((size_t)b * e.A + a) * e.na];
-      actp[a] = MODE == 2 ? action_prev[((size_t)b * e.A + a) * e.na] : (T)0;
-    }
-    __syncthreads();
-  }
-  if (MODE == 0) {
-    for (int n = tid; n < N; n += nt) out[(size_t)b * N + n] = actuate_cell<T>(e, act, n);
-    return;
-  }
-  const int sp = e.n_species;
-  for (int i = tid; i < sp * N; i += nt) {
-    // y[sp, N] column-major: (species, cell) at cell*sp + species
-    const int n = i / sp, r = i - n * sp;
-    sy[r * N + n] = y[(size_t)b * sp * N + i];
-  }
-  if (sp == 1)
-    for (int n = tid; n < N; n += nt) sy[N + n] = 0;
-  __syncthreads();
-  sense_dots<T>(e, [&](int r, int n) { return sy[r * N + n]; }, dots, part, tid, nt);
-  if (MODE == 1) {
-    const size_t sw = e.mono ? (size_t)e.S : (size_t)e.A * e.ns;
-    if (e.mem > 0)
-      featurize_traj_mem<T>(e, dots, state_prev ? state_prev + b * sw : nullptr, action ? action + (size_t)b * e.A * e.na : nullptr,
-                            out + b * sw, tid, nt);
-    else
-      featurize_traj<T>(e, dots, state_prev ? state_prev + b * sw : nullptr, out + b * sw, tid, nt);
-  } else {
-    const int rw = e.mono ? 1 : e.A;
-    reward_traj<T>(e, dots, act, actp, out + (size_t)b * rw, tid, nt);
-  }
+  sense_traj<T, MODE>(e, blockIdx.x, y, action, action_prev, state_prev, out);
 }
 
 // terminal flag per actuator column from the per-trajectory blow-up flags (composed env step; the fused kernels write it themselves)
@@ -61,8 +23,6 @@ __global__ void terminal_from_done_kernel(const int32_t* __restrict__ done, int 
 }
 
 // ------------------------------------------------------------------ host side
-static size_t sense_lds_bytes(const pdec_env_cfg& c) { return (2 * (size_t)c.N + 2 * c.A + 2 * c.S + 16 * c.S) * dtype_size(c.dtype); }
-
 // the step of the environment's PDE (mode 0: fused env step, 1: integrate only, 2: right-hand side only)
 static int launch_step(Env& E, int mode, const StepArgs& a) {
   const pdec_env_cfg& c = E.cfg;
@@ -125,7 +85,7 @@ static int launch_sense(Env& E, int mode, const void* y, const void* action, con
   by_dtype(E.cfg.dtype, [&](auto t) {
     using T = decltype(t);
     const auto kern = mode == 0 ? sense_kernel<T, 0> : (mode == 1 ? sense_kernel<T, 1> : sense_kernel<T, 2>);
-    hipLaunchKernelGGL(kern, dim3(E.cfg.B), dim3(128), sense_lds_bytes(E.cfg), E.stream, make_dev<T>(E), (const T*)y, (const T*)action,
+    hipLaunchKernelGGL(kern, dim3(E.cfg.B), dim3(PDEC_SENSE_THREADS), sense_lds_bytes(E.cfg), E.stream, make_dev<T>(E), (const T*)y, (const T*)action,
                        (const T*)action_prev, (const T*)state_prev, (T*)out);
   });
   PDEC_HIP(hipGetLastError());

@@ -307,4 +307,55 @@ __device__ __forceinline__ void write_terminal(const EnvDev<T>& e, int b, bool f
   for (int a = tid; a < cpt; a += nt) e.term_out[(size_t)b * cpt + a] = flag ? (T)1 : (T)0;
 }
 
+// ------------------------------------------------------------------ the stand-alone closures of trajectory b
+// MODE 0: prepare_action, 1: featurize, 2: reward.  The body of sense_kernel (env.hip) and of the episode clock's masked
+// sensing launch (episode_clock.hip); both run 128 threads per trajectory -- sense_dots splits a sensor's window over nt / S
+// groups, so the sums depend on that size -- with sense_lds_bytes of dynamic LDS.
+#define PDEC_SENSE_THREADS 128
+inline size_t sense_lds_bytes(const pdec_env_cfg& c) { return (2 * (size_t)c.N + 2 * c.A + 2 * c.S + 16 * c.S) * dtype_size(c.dtype); }
+
+template <class T, int MODE>
+__device__ __forceinline__ void sense_traj(const EnvDev<T>& e, int b, const T* __restrict__ y, const T* __restrict__ action,
+                                           const T* __restrict__ action_prev, const T* __restrict__ state_prev, T* __restrict__ out) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const int N = e.N, tid = threadIdx.x, nt = blockDim.x;
+  T* sy = reinterpret_cast<T*>(smem_raw);  // [2][N]
+  T* act = sy + 2 * N;
+  T* actp = act + e.A;
+  T* dots = actp + e.A;
+  T* part = dots + 2 * e.S;
+  if (MODE == 0 || MODE == 2) {     // row 0 of every action column (KSSetup.jl:176,241: action[1, i]); na = 1 without action memory
+    for (int a = tid; a < e.A; a += nt) {
+      act[a] = action[((size_t)b * e.A + a) * e.na];
+      actp[a] = MODE == 2 ? action_prev[((size_t)b * e.A + a) * e.na] : (T)0;
+    }
+    __syncthreads();
+  }
+  if (MODE == 0) {
+    for (int n = tid; n < N; n += nt) out[(size_t)b * N + n] = actuate_cell<T>(e, act, n);
+    return;
+  }
+  const int sp = e.n_species;
+  for (int i = tid; i < sp * N; i += nt) {
+    // y[sp, N] column-major: (species, cell) at cell*sp + species
+    const int n = i / sp, r = i - n * sp;
+    sy[r * N + n] = y[(size_t)b * sp * N + i];
+  }
+  if (sp == 1)
+    for (int n = tid; n < N; n += nt) sy[N + n] = 0;
+  __syncthreads();
+  sense_dots<T>(e, [&](int r, int n) { return sy[r * N + n]; }, dots, part, tid, nt);
+  if (MODE == 1) {
+    const size_t sw = e.mono ? (size_t)e.S : (size_t)e.A * e.ns;
+    if (e.mem > 0)
+      featurize_traj_mem<T>(e, dots, state_prev ? state_prev + b * sw : nullptr, action ? action + (size_t)b * e.A * e.na : nullptr,
+                            out + b * sw, tid, nt);
+    else
+      featurize_traj<T>(e, dots, state_prev ? state_prev + b * sw : nullptr, out + b * sw, tid, nt);
+  } else {
+    const int rw = e.mono ? 1 : e.A;
+    reward_traj<T>(e, dots, act, actp, out + (size_t)b * rw, tid, nt);
+  }
+}
+
 }  // namespace pdec

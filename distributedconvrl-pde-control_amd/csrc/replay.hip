@@ -9,6 +9,7 @@
 #include "common.hpp"
 #include "env.hpp"
 #include "mlp.hpp"
+#include "random_init.hpp"
 
 namespace pdec {
 
@@ -131,58 +132,18 @@ __global__ void autoreset_kernel(ResetArgs g) {
 // Uniform k of trajectory b: word k % 4 of the Philox block (seed; counter offset + b * nblk + k / 4), u = (word + 0.5) / 2^32,
 // a = 2 u - 1 (Julia draws from its global RNG, so only the distribution can be reproduced; the oracle restates THIS stream).
 // One workgroup per trajectory; memory [N][n_species] (species fastest = Julia y[n_species, nx]).
-#define RI_MAXC 64
+// The body is random_init_row (random_init.hpp), which the episode clock's boundary launch shares.
 template <class T>
 __global__ void random_init_kernel(T* __restrict__ y, int N, int nsp, int nsin, double dx, double fdiv, double base, double l2_target,
                                    uint64_t seed, uint64_t offset, const uint64_t* __restrict__ mseed = nullptr,
                                    const uint64_t* __restrict__ moff = nullptr) {
   __shared__ double a[RI_MAXC];
-  __shared__ double red[256];
-  const int b = blockIdx.x, tid = threadIdx.x, nc = nsp * nsin, nblk = (nc + 3) / 4;
+  __shared__ double red[RI_THREADS];
+  const int b = blockIdx.x, nblk = (nsp * nsin + 3) / 4;
   // per-member streams (pdec_env_random_init_members): trajectory b draws what a B = 1 call with (mseed[b], moff[b]) draws
   const uint64_t cb = mseed ? 0 : (uint64_t)b;
   if (mseed) { seed = mseed[b]; offset = moff[b]; }
-  if (tid == 0) {
-    double nrm = 0;
-    for (int blk = 0; blk < nblk; ++blk) {
-      const uint64_t ctr = offset + cb * nblk + blk;
-      uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-      philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-      for (int i = 0; i < 4 && 4 * blk + i < nc; ++i) {
-        const double v = 2.0 * (((double)c[i] + 0.5) * (1.0 / 4294967296.0)) - 1.0;
-        a[4 * blk + i] = v;
-        nrm += v * v;
-      }
-    }
-    nrm = sqrt(nrm);
-    for (int i = 0; i < nc; ++i) a[i] /= nrm;
-  }
-  __syncthreads();
-  double scale = 1.0;
-  if (l2_target > 0) {      // KS: rescale to |y0|_2 = 30 (one species)
-    double acc = 0;
-    for (int j = tid; j < N; j += blockDim.x) {
-      const double x = (j + 1) * dx;
-      double v = 0;
-      for (int i = 1; i <= nsin; ++i) v += a[i - 1] * sin(i * x / fdiv);
-      acc += v * v;
-    }
-    red[tid] = acc;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-      if (tid < s) red[tid] += red[tid + s];
-      __syncthreads();
-    }
-    scale = l2_target / sqrt(red[0]);
-  }
-  for (int j = tid; j < N; j += blockDim.x) {
-    const double x = (j + 1) * dx;
-    for (int sp = 0; sp < nsp; ++sp) {
-      double v = 0;
-      for (int i = 1; i <= nsin; ++i) v += a[sp * nsin + i - 1] * sin(i * x / fdiv);
-      y[((size_t)b * N + j) * nsp + sp] = (T)(base + v * scale);
-    }
-  }
+  random_init_row<T>(y, b, N, nsp, nsin, dx, fdiv, base, l2_target, seed, offset + cb * nblk, a, red);
 }
 
 // The 2-D Keller-Segel setup (setups/keller_segel2d.py generate_random_init: KellerSegelSetup.jl:373-384 with the sine sums
@@ -452,17 +413,13 @@ int pdec_env_random_init_members(pdec_handle henv, const uint64_t* seeds, const 
   if (!E) { set_error("pdec_env_random_init_members: bad handle"); return PDEC_E_HANDLE; }
   PDEC_REQUIRE(y0_out && seeds && offsets, "pdec_env_random_init_members: null");
   const pdec_env_cfg& c = E->cfg;
-  int nsp, nsin;
-  double fdiv, base, l2;
-  const double two_pi = 6.283185307179586;
-  if (c.pde_kind == PDEC_PDE_KS_CNAB2 || c.pde_kind == PDEC_PDE_KS_RK4_FD) {
-    nsp = 1; nsin = 8; fdiv = two_pi; base = 0.0; l2 = 30.0;
-  } else if (c.pde_kind == PDEC_PDE_KSEG_RK4) {
-    nsp = 2; nsin = (int)ceil(c.Lx / 3.0); fdiv = two_pi * (c.Lx / 22.0); base = 1.0; l2 = 0.0;
-  } else {
+  RandomInitSpec ri;
+  if (!random_init_spec(c, &ri)) {
     set_error("pdec_env_random_init_members: the 1-D KS and Keller-Segel setups only");
     return PDEC_E_INVALID;
   }
+  const int nsp = ri.nsp, nsin = ri.nsin;
+  const double fdiv = ri.fdiv, base = ri.base, l2 = ri.l2;
   PDEC_REQUIRE(nsp * nsin <= RI_MAXC, "pdec_env_random_init_members: %d sine coefficients exceed the kernel's table", nsp * nsin);
   const double dx = c.Lx / c.N;
   ProfScope ps(E, "env_random_init");
@@ -481,13 +438,9 @@ int pdec_env_random_init(pdec_handle henv, uint64_t seed, uint64_t offset, void*
   if (!E) { set_error("pdec_env_random_init: bad handle"); return PDEC_E_HANDLE; }
   PDEC_REQUIRE(y0_out, "pdec_env_random_init: null");
   const pdec_env_cfg& c = E->cfg;
-  int nsp, nsin;
-  double fdiv, base, l2;
   const double two_pi = 6.283185307179586;
-  if (c.pde_kind == PDEC_PDE_KS_CNAB2 || c.pde_kind == PDEC_PDE_KS_RK4_FD) {
-    nsp = 1; nsin = 8; fdiv = two_pi; base = 0.0; l2 = 30.0;                                  // KSSetup.jl:288-298
-  } else if (c.pde_kind == PDEC_PDE_KSEG_RK4) {
-    nsp = 2; nsin = (int)ceil(c.Lx / 3.0); fdiv = two_pi * (c.Lx / 22.0); base = 1.0; l2 = 0.0;   // KellerSegelSetup.jl:373-384
+  RandomInitSpec ri{};
+  if (random_init_spec(c, &ri)) {                 // the 1-D setups: launched below
   } else if (c.pde_kind == PDEC_PDE_KSEG2D_RK4) {
     const int nx = c.N, ny = c.Ny;
     const double dx = c.Lx / nx, Ly = ny * dx;
@@ -510,6 +463,8 @@ int pdec_env_random_init(pdec_handle henv, uint64_t seed, uint64_t offset, void*
     set_error("pdec_env_random_init: KS, Keller-Segel and 2-D Keller-Segel only (the fluid initialiser is pdec_fluid_ic)");
     return PDEC_E_INVALID;
   }
+  const int nsp = ri.nsp, nsin = ri.nsin;
+  const double fdiv = ri.fdiv, base = ri.base, l2 = ri.l2;
   PDEC_REQUIRE(nsp * nsin <= RI_MAXC, "pdec_env_random_init: %d sine coefficients exceed the kernel's table", nsp * nsin);
   const double dx = c.Lx / c.N;
   ProfScope ps(E, "env_random_init");

@@ -49,7 +49,15 @@ step, never inside a capture or a recorded step:
     env stream:   [wait eval_{n-1} done] -> pdec_ledger_eval_load (staging -> evaluation actor) -> event
     eval stream:  wait event -> reset the evaluation env to eval_y0 -> pdec_rollout -> pdec_ledger_eval_close -> done event
 
-With eval_stream=None the eval stream is the env stream (behind the episode's last env step, no events)."""
+With eval_stream=None the eval stream is the env stream (behind the episode's last env step, no events).
+
+Per-trajectory episodes (opt-in, episodes="per_trajectory"; csrc/episode_clock.hip): the episode boundary is decided on the device.
+pdec_epclock_step right behind pdec_env_step -- on the ring slots of step k: rring, fring, tring, aring[k % 3], ybuf[(k+1) % 2],
+sring[(k+1) % 6] -- ends the episode of every trajectory whose blow-up flag is raised or whose own clock has reached
+episode_steps, in that step: terminal row, log entry, restart field and its features, zero action_prev (a ring of two buffers the
+clock writes and the next env step reads).  The host schedules as for episode_steps = 0: only step 0 is a first step, there is no
+last step, every other step is interior -- the same launch sequence, recorded and captured.  The batch-mean reward of the reward
+broadcast is taken by pdec_reward_mean behind the clock, on the rows it has sanitised; the env step's reward partials are not armed."""
 import ctypes as C
 import os
 
@@ -94,6 +102,21 @@ class _TorchEvent:
         stream.wait_event(self.ev)
 
 
+class _Clock:
+    """the episode clock of a pipeline (pdec_epclock_create), released with it"""
+
+    def __init__(self, lib, env_handle, episode_steps, capacity, random_init, seed, rank, world):
+        self.lib, self.h = lib, _lib.Handle()
+        _lib.check(lib.pdec_epclock_create(C.byref(self.h), env_handle, int(episode_steps), int(capacity), int(bool(random_init)),
+                                           int(seed), int(rank), int(world)))
+
+    def __del__(self):
+        try:
+            self.lib.pdec_destroy(self.h)
+        except Exception:
+            pass
+
+
 class _Ledger:
     """the episode ledger of a pipeline (pdec_ledger_create), released with it"""
 
@@ -130,7 +153,7 @@ class TrainPipeline:
                  chunks=(24, 6, 1), use_replay=False, noise_seed=1234, kick_env_after_critic=None, stream_ar=None,
                  ar_off_chain=None, log_episodes=0, min_best_episode=0, random_init=False, init_seed=0, init_rng=None,
                  init_rank=(0, 1), eval_every=0, eval_inits=8, eval_seed=0, eval_y0=None, eval_capacity=64, eval_stream=None,
-                 best_by="train", noise_scale=None):
+                 best_by="train", noise_scale=None, episodes="lockstep", stagger=False):
         """env: PDEenv on `stream_env`; agent: create_agent(..., stream=stream_upd).  lag: the update of step k trains on
         the transition of step k - lag (>= 1).  episode_steps: lock-stepped episodes of that many control steps (0: one
         endless episode): the last transition is terminal (done = time >= te, src/PDEenv.jl:227) and the next step starts
@@ -167,7 +190,22 @@ class TrainPipeline:
         in the ledger), episode_steps > 0 and no active reducer.
 
         noise_scale = [B] (host array or device tensor): trajectory b explores at noise_scale[b] in the place of the policy's
-        act_noise -- see set_noise_scale.  None: the policy's scalar."""
+        act_noise -- see set_noise_scale.  None: the policy's scalar.
+
+        episodes = "per_trajectory": every trajectory keeps its own episode clock on the device (csrc/episode_clock.hip;
+        DESIGN.md 3.5).  One boundary call behind every env step ends the episode of trajectory b IN that step when its blow-up
+        flag is raised or its clock reaches episode_steps: the row's transition is terminal, its return is logged, and the
+        trajectory restarts from row b of env.y0 -- or, with random_init, from row b of env.random_init(init_seed, off) at
+        off = (n W + r) B ceil(nc / 4), n the number of episodes b has finished: the field the lock-stepped pipeline draws for
+        its episode n (the host-issued step 0 draws episode 0 through _draw_init).  The other trajectories go on.  The host
+        schedules as for episode_steps = 0 -- step 0 is the only first step, every later one is interior -- so capture() and
+        the recorded calls cover every step and chunks need not fit an episode.  stagger=True starts the clock of trajectory
+        b at floor(b E / B): the time-outs spread evenly over the E phases of an episode (the first episode of b is shorter by
+        that much and is logged with the steps it really took).  log_episodes = C > 0 is then the log capacity PER TRAJECTORY
+        (finished_episodes(), episodes_finished); episode_returns() / rewards belong to the lock-stepped mode.  reset_from()
+        sets every clock back to its initial value and drops the running returns.  The 1-D environments with per-actuator
+        agents and memory_size = 0 only; not with use_replay, an active reducer, evaluations or best-actor tracking (score
+        actors with population.evaluate_actors between run() calls)."""
         # pdec_policy_act_rng_dev reads the state ring in the actor's type: a fluid environment of another dtype cannot step.
         # Refused by name at the first run() / capture(), not here: an object of that combination may be constructed and asked
         # for its episode-start draw (tests/test_gpu_pipeline_episodes.py::test_random_inits_fluid does).
@@ -176,6 +214,8 @@ class TrainPipeline:
             self._dtype_refusal = (f"TrainPipeline: the fluid environment ({env.dtype}) and the networks "
                                    f"({agent.policy.behavior_actor.model.dtype}) must have one dtype: the acting kernel reads "
                                    "the environment's state ring in the actor's type")
+        self._check_episode_mode(env, agent, episodes, stagger, episode_steps, use_replay, eval_every, min_best_episode, best_by)
+        self.per_traj, self.stagger = episodes == "per_trajectory", bool(stagger)
         self._check_eval_args(env, agent, episode_steps, stream_env, stream_upd, log_episodes, eval_every, eval_inits, eval_y0,
                               eval_capacity, eval_stream, best_by)
         self.env, self.agent, self.policy = env, agent, agent.policy
@@ -228,6 +268,9 @@ class TrainPipeline:
             self.rbar = [torch.zeros(1, dtype=torch.float32, device=dev) for _ in range(3)]  # batch-mean reward of step k
             self.azero = torch.zeros(env._ashape, **kw)                                    # action0 of a fresh episode
             self.state0 = empty(env._sshape, **kw)
+            # per-trajectory episodes: action_prev of step k, written by the clock of step k - 1 (the action ring slot is the
+            # transition's action and keeps its values where a trajectory restarts)
+            self.aprev = [torch.zeros(env._ashape, **kw) for _ in range(2)] if self.per_traj else None
         # the reference's reward broadcast (quirk) needs the batch-mean reward: reduced on the env stream
         # right behind the env step instead of by every workgroup of the critic pass
         # (not with reward groups: the critic call reduces the group means itself, CustomDDPGPolicy.reward_group)
@@ -237,8 +280,10 @@ class TrainPipeline:
         self.reward_interleave = 1 if self.use_replay else A
         # ... and for the fused KS step + 3-layer fused critic without any extra launch: the env step leaves one reward sum
         # per workgroup, the critic pass adds them
+        # (per-trajectory episodes: the partials are summed before the clock sanitises the rows of blown-up trajectories and
+        # cannot be corrected afterwards -- the mean is taken by pdec_reward_mean behind the clock)
         self.rpart, self.n_rpart = None, 0
-        if self.pre_rbar:
+        if self.pre_rbar and not self.per_traj:
             npart = C.c_int()
             probe = torch.zeros(B, dtype=torch.float32, device=dev)
             ok = self.lib.pdec_env_set_reward_partials_out(env.handle, _lib.ptr(probe), C.byref(npart)) == 0
@@ -319,6 +364,37 @@ class TrainPipeline:
         self._setup_eval(eval_every, eval_inits, eval_seed, eval_y0, eval_capacity, eval_stream, best_by, Ev)
         self.reset_from(env.y0)
         self._keep_y0 = False
+
+    @staticmethod
+    def _check_episode_mode(env, agent, episodes, stagger, episode_steps, use_replay, eval_every, min_best_episode, best_by):
+        """the refusals of episodes="per_trajectory", by name, before anything is allocated"""
+        if episodes not in ("lockstep", "per_trajectory"):
+            raise _lib.PdecError(f"TrainPipeline(episodes={episodes!r}): 'lockstep' or 'per_trajectory'")
+        if episodes == "lockstep":
+            if stagger:
+                raise _lib.PdecError("TrainPipeline(stagger=True) needs episodes='per_trajectory': lock-stepped episodes share one clock")
+            return
+        who = "TrainPipeline(episodes='per_trajectory')"
+        setup = env.setup
+        if getattr(env, "is_fluid", False):
+            raise _lib.PdecError(f"{who}: the fluid environment is not covered (its step is a launch sequence with its own sensing)")
+        if getattr(setup, "is_kseg2d", False):
+            raise _lib.PdecError(f"{who}: the 2-D Keller-Segel environment is not covered (its step is a launch sequence with its "
+                                 "own sensing)")
+        if int(getattr(setup, "memory_size", 0)) > 0:
+            raise _lib.PdecError(f"{who}: memory_size > 0 is not covered")
+        if getattr(setup, "mono", False):
+            raise _lib.PdecError(f"{who}: the global agent (mono) is not covered")
+        if use_replay:
+            raise _lib.PdecError(f"{who}: use_replay=True is not covered (the replay route pushes lock-stepped episodes)")
+        reducer = agent.policy.reducer
+        if reducer is not None and reducer.active:
+            raise _lib.PdecError(f"{who}: not available with an active reducer")
+        if int(eval_every) > 0 or int(min_best_episode) > 0 or best_by == "eval":
+            raise _lib.PdecError(f"{who}: eval_every, min_best_episode and best_by='eval' are not available -- there is no common "
+                                 "episode end to snapshot at; score actors with evaluate_actors between run() calls")
+        if int(episode_steps) <= 0:
+            raise _lib.PdecError(f"{who} needs episodes: episode_steps > 0")
 
     @staticmethod
     def _check_eval_args(env, agent, episode_steps, stream_env, stream_upd, log_episodes, eval_every, eval_inits, eval_y0,
@@ -440,9 +516,10 @@ class TrainPipeline:
         env = self.env
         self.log_episodes, self.min_best_episode = int(log_episodes), int(min_best_episode)
         self.ledger, self.track_best, self.n_episodes = None, False, 0
+        self.clock = self.clock0 = None
         if self.log_episodes < 0:
             raise _lib.PdecError(f"TrainPipeline(log_episodes={log_episodes}): a capacity >= 0")
-        if self.log_episodes > 0:
+        if self.log_episodes > 0 and not self.per_traj:
             if self.E <= 0:
                 raise _lib.PdecError("TrainPipeline(log_episodes=...) needs episodes: episode_steps > 0")
             if self.multi_rank and self.min_best_episode != 0:
@@ -467,6 +544,10 @@ class TrainPipeline:
                 raise _lib.PdecError("TrainPipeline(random_init=True): the setup has no device initialiser")
             if env.y0.data_ptr() == env.y.data_ptr():
                 env.y0 = env.y0.clone()
+        if self.per_traj:
+            self.clock = _Clock(self.lib, env.handle, self.E, max(1, self.log_episodes), self.random_init, self.init_seed, r, W)
+            B = env.B
+            self.clock0 = np.array([(b * self.E) // B if self.stagger else 0 for b in range(B)], dtype=np.int32)
 
     def _draw_init(self):
         """a new initial field into env.y0 and its features into state0, on the env stream (the first step of an episode)"""
@@ -505,6 +586,8 @@ class TrainPipeline:
         self._keep_y0 = True          # (random_init: this episode starts from y0, the next ones draw again)
         if self.ledger is not None and self.tick > self.ep_start:
             _lib.check(self.lib.pdec_ledger_discard(self.ledger.h))      # the cut episode is not logged
+        if self.clock is not None:                                       # (nor are the cut episodes of the clock)
+            _lib.check(self.lib.pdec_epclock_set(self.clock.h, _lib.ptr(self.clock0)))
         with torch.cuda.stream(self.s_env):
             if y0.data_ptr() != env.y0.data_ptr():
                 env.y0.copy_(y0)
@@ -542,7 +625,7 @@ class TrainPipeline:
         first, last = self._first_last(k)
         y_in, y_out = self.ybuf[k % 2], self.ybuf[(k + 1) % 2]
         s_in, s_out = self.sring[k % PERIOD], self.sring[(k + 1) % PERIOD]
-        act, act_prev = self.aring[k % 3], self.aring[(k - 1) % 3]
+        act, act_prev = self.aring[k % 3], (self.aprev[k % 2] if self.per_traj else self.aring[(k - 1) % 3])
         rew, flags, term = self.rring[k % 3], self.fring[k % 3], self.tring[k % 3]
         capturing = chunk_first or chunk_last or self._capturing
         # greedy evaluation behind this step: the last step (eager) of an episode whose 1-based number is a multiple of eval_every
@@ -607,6 +690,12 @@ class TrainPipeline:
                     L.check(lib.pdec_env_set_reward_partials_out(env.handle, L.ptr(self.rpart[k % 3]), None))
                 L.check(lib.pdec_env_step(env.handle, L.ptr(y_in), L.ptr(act), L.ptr(act_prev), L.ptr(s_in), L.ptr(y_out),
                                           L.ptr(self.pbuf), L.ptr(s_out), L.ptr(rew), L.ptr(flags)))
+                if self.clock is not None:
+                    # the episode boundary of every trajectory, decided on the device: the same call at every step
+                    fixed = not self.random_init
+                    L.check(lib.pdec_epclock_step(self.clock.h, L.ptr(rew), L.ptr(flags), L.ptr(term), L.ptr(act),
+                                                  L.ptr(self.aprev[(k + 1) % 2]), L.ptr(y_out), L.ptr(s_out),
+                                                  L.ptr(env.y0) if fixed else None, L.ptr(self.state0) if fixed else None))
                 if self.ledger is not None:
                     L.check(lib.pdec_ledger_step(self.ledger.h, L.ptr(rew), L.ptr(flags)))
                 if last:
@@ -736,13 +825,20 @@ class TrainPipeline:
     _first_tick = 0
     _mid_wait_prev = False    # update_{k-1} waited for env_{k-2} between its halves (so step k needs no wait at its top)
     drain_between = False
+    per_traj = False          # episodes="per_trajectory"
+
+    @property
+    def _E_host(self):
+        """the episode length the HOST schedules by: with per-trajectory episodes the boundary is the clock's, and the host
+        sees one endless episode (episode_steps = 0: step 0 is the only first step, every later one is interior)"""
+        return 0 if self.per_traj else self.E
 
     def _first_last(self, k):
         """is step k the first / the last of an episode"""
-        e = k - self.ep_start
-        if self.E <= 0:
+        e, E = k - self.ep_start, self._E_host
+        if E <= 0:
             return e == 0, False
-        return e % self.E == 0, e % self.E == self.E - 1
+        return e % E == 0, e % E == E - 1
 
     # ------------------------------------------------------------------ device replay route (row F1)
     def _replay_push(self, ev_done, s_in, act, rew, term, s_out, first, last):
@@ -806,7 +902,7 @@ class TrainPipeline:
         self._check_key()
         if not self.use_graphs or self._captured:
             return
-        if self.E > 0:
+        if self._E_host > 0:
             assert self.E > 2 * PERIOD, "episodes must be longer than two graph periods"
             self.chunks = tuple(c for c in self.chunks if c <= self.E - 2)
         while self.tick - self.LAG < self._first_tick + 2:      # lazily created buffers / first-use uploads happen eagerly
@@ -839,10 +935,11 @@ class TrainPipeline:
     def _reachable(self, c, pos):
         """is there a future tick at ring phase `pos` from which c consecutive steps are interior to an episode?  The
         pattern of (tick mod 6, episode offset) repeats after lcm(E, 6) <= 6 E ticks."""
-        if self.E <= 0:
+        E = self._E_host
+        if E <= 0:
             return True
         t0 = max(self.tick, self._first_tick + self.LAG)
-        return any(t % PERIOD == pos and self._interior(t, c) for t in range(t0, t0 + PERIOD * self.E + PERIOD))
+        return any(t % PERIOD == pos and self._interior(t, c) for t in range(t0, t0 + PERIOD * E + PERIOD))
 
     def set_noise_scale(self, values):
         """Per-trajectory exploration amplitude: `values` [B], a host array (checked: finite, not negative) or a device tensor
@@ -871,7 +968,8 @@ class TrainPipeline:
         pol = self.policy
         return ("noise_scale" if self.noise_scale is not None else float(pol.act_noise), float(pol.act_limit), float(pol.behavior_actor.optimizer.eta),
                 float(pol.behavior_critic.optimizer.eta), float(pol.y), float(pol.rho_effective), int(bool(pol.quirk)),
-                pol.reward_group, bool(self.kick_env_after_critic), int(self.noise_seed))
+                pol.reward_group, bool(self.kick_env_after_critic), int(self.noise_seed)) + (
+                    (self.env.y0.data_ptr(),) if self.per_traj else ())     # (the clock's launch holds the pointer of env.y0)
 
     def _check_key(self):
         """a noise / learning-rate schedule (or load_agent restoring act_noise) changed a frozen scalar: drop the recorded
@@ -890,11 +988,11 @@ class TrainPipeline:
         """steps k .. k+n-1 are neither the first nor the last of an episode (those run eagerly)"""
         if k - self.LAG < self._first_tick:
             return False
-        e = k - self.ep_start
-        if self.E <= 0:
+        e, E = k - self.ep_start, self._E_host
+        if E <= 0:
             return e >= 1
-        e %= self.E
-        return e >= 1 and e + n <= self.E - 1
+        e %= E
+        return e >= 1 and e + n <= E - 1
 
     def _eager(self):
         """issue step `tick` call by call.  An interior step (not the first / last of an episode) at ring phase
@@ -967,9 +1065,46 @@ class TrainPipeline:
         if best and not self.track_best:
             raise _lib.PdecError("TrainPipeline: the best actor is not tracked with an active reducer")
 
+    def _need_lockstep(self, what):
+        if self.per_traj:
+            raise _lib.PdecError(f"TrainPipeline.{what} belongs to lock-stepped episodes; with episodes='per_trajectory' every "
+                                 "trajectory ends on its own: read finished_episodes()")
+
+    def finished_episodes(self):
+        """episodes="per_trajectory": every logged episode, as a dict of flat arrays sorted by (end_step, trajectory) --
+        trajectory, episode (0-based, per trajectory), ret (float64: the ledger's arithmetic, sum over steps of the row mean),
+        length (steps it took), blew_up (bool: ended by the blow-up flag), end_step (1-based number of the control step since
+        construction that ended it) -- plus dropped: how many earlier episodes the per-trajectory rings of log_episodes
+        slots have overwritten.  Synchronises the env stream."""
+        if self.clock is None:
+            raise _lib.PdecError("TrainPipeline.finished_episodes needs episodes='per_trajectory'")
+        if self.log_episodes <= 0:
+            raise _lib.PdecError("TrainPipeline: the episode log is off (log_episodes=0)")
+        B, N = self.env.B, self.log_episodes
+        cnt = np.empty(B, dtype=np.int64)
+        ret, ln, blew, end = np.empty((B, N)), np.empty((B, N), dtype=np.int32), np.empty((B, N), dtype=np.int32), np.empty((B, N), dtype=np.int64)
+        _lib.check(self.lib.pdec_epclock_read(self.clock.h, _lib.ptr(cnt), _lib.ptr(ret), _lib.ptr(ln), _lib.ptr(blew), _lib.ptr(end)))
+        rows = [(int(end[b, e % N]), b, e) for b in range(B) for e in range(max(0, int(cnt[b]) - N), int(cnt[b]))]
+        rows.sort()
+        tb = np.array([r[1] for r in rows], dtype=np.int64)
+        te = np.array([r[2] for r in rows], dtype=np.int64)
+        sl = te % N
+        return dict(trajectory=tb, episode=te, ret=ret[tb, sl], length=ln[tb, sl], blew_up=blew[tb, sl] != 0, end_step=end[tb, sl],
+                    dropped=int(np.maximum(cnt - N, 0).sum()))
+
+    @property
+    def episodes_finished(self):
+        """episodes="per_trajectory": episodes finished so far per trajectory, int64 [B] (synchronises the env stream)"""
+        if self.clock is None:
+            raise _lib.PdecError("TrainPipeline.episodes_finished needs episodes='per_trajectory'")
+        cnt = np.empty(self.env.B, dtype=np.int64)
+        _lib.check(self.lib.pdec_epclock_read(self.clock.h, _lib.ptr(cnt), None, None, None, None))
+        return cnt
+
     def episode_returns(self):
         """(returns [n, B] float64, blew_up [n, B] bool, dropped): the last n = min(episodes, log_episodes) logged
         episodes, oldest first, and how many earlier ones the ring has overwritten"""
+        self._need_lockstep("episode_returns()")
         self._need_ledger()
         N, B = self.log_episodes, self.env.B
         ret, blew = np.empty((N, B)), np.empty((N, B), dtype=np.int32)
@@ -981,6 +1116,7 @@ class TrainPipeline:
     @property
     def rewards(self):
         """batch-mean return of each logged episode (PDEhook.rewards), the last min(episodes, log_episodes)"""
+        self._need_lockstep("rewards")
         self._need_ledger()
         N = self.log_episodes
         means = np.empty(N)

@@ -716,6 +716,36 @@ int pdec_ledger_eval_read(pdec_handle ledger, int64_t* episodes, double* returns
 int pdec_ledger_eval_best(pdec_handle ledger, double* value, int64_t* episode);
 int pdec_ledger_eval_best_params(pdec_handle ledger, pdec_handle mlp);
 
+/* ---------------------------------------------------------------- episode clock (per-trajectory episodes on the device) */
+/* A clock per trajectory of a batched 1-D environment (KS, finite-difference KS, Keller-Segel; per-actuator agents,
+ * memory_size = 0): pdec_epclock_step behind env step k decides per trajectory whether its episode ends IN this step -- its
+ * blow-up flag is raised, or its clock reaches episode_steps -- and restarts it there.  Per trajectory b, in this order:
+ *   1. blew = flags[b] != 0; where blew, non-finite entries of reward row b become 0; other rows are not touched
+ *   2. ret[b] += (sum_a (double) reward[b][a]) / R, summed in a order (pdec_ledger_step's arithmetic, on the sanitised row)
+ *   3. clock[b]++, len[b]++, total[b]++; ends = blew || clock[b] == episode_steps
+ *   4. not ended: action_prev_next[b][:] = action[b][:]; nothing else of b is written
+ *   5. ended: terminal row b = 1; log slot count[b] % capacity <- (ret[b], len[b], blew, total[b]); count[b]++; ret[b] = 0;
+ *      clock[b] = len[b] = 0; action_prev_next[b][:] = 0; y_next[b] <- the new field; state_next[b] <- its pdec_featurize row
+ *      in reset form (no previous state)
+ * The new field: row b of (y0, state0), or with random_init row b of what pdec_env_random_init(env, seed, off) draws at
+ * off = (n world + rank) B ceil(nc / 4), n = count[b] after the increment, nc the sine coefficients per trajectory -- bit for
+ * bit that call's row, and the state row bit for bit pdec_featurize's.  All counters live on the device and every argument
+ * besides the arrays is fixed at creation, so the call can be part of a recorded step or a captured graph; one or two
+ * launches on the environment's stream, one workgroup per trajectory, each writing its own trajectory's rows only.
+ * Arrays in the environment's dtype: reward / terminal [B][A], action / action_prev_next [B][A][1], y_next [B][...], state_next
+ * [B][A][ns]; flags [B] as the env step leaves them; y0 / state0 may be NULL with random_init.  Released with pdec_destroy. */
+int pdec_epclock_create(pdec_handle* clock, pdec_handle env, int episode_steps, int capacity, int random_init, uint64_t seed,
+                        int rank, int world);
+/* clock[b] = clock0[b] (host array [B], values 0 .. episode_steps - 1; NULL: zeros), len = 0, ret = 0: the running episodes
+ * are cut without a log entry; count, total and the logs stay.  Synchronises the environment's stream. */
+int pdec_epclock_set(pdec_handle clock, const int32_t* clock0);
+int pdec_epclock_step(pdec_handle clock, void* reward, const int32_t* flags, void* terminal, const void* action,
+                      void* action_prev_next, void* y_next, void* state_next, const void* y0, const void* state0);
+/* host accessor (synchronises the environment's stream; any pointer may be NULL): counts [B] episodes finished, and the log
+ * rings [B][capacity] -- episode e of trajectory b sits in slot e mod capacity: its return, its length in steps, its blow-up
+ * bit and the 1-based number of the pdec_epclock_step call that ended it */
+int pdec_epclock_read(pdec_handle clock, int64_t* counts, double* returns, int32_t* lengths, int32_t* blew_up, int64_t* end_steps);
+
 /* ---------------------------------------------------------------- HIP graphs -- */
 /* Record everything enqueued on the stream of `origin` (pdec_set_stream; not the null stream) -- library calls, and any
  * other stream that forks from it and joins it again through events -- between _begin and _end into one HIP graph;
