@@ -108,6 +108,7 @@ SIGNATURES = {
     "pdec_env_random_init_members": [Handle, _vp, _vp, _vp],
     "pdec_env_set_member_layout": [Handle, C.c_int],
     "pdec_env_set_disturbance": [Handle, _vp],
+    "pdec_env_set_faults": [Handle, _vp, _vp, _vp],
     "pdec_env_set_control_from": [Handle, C.c_int],
     "pdec_population_create": [C.POINTER(Handle), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _i, _d, _d, _i,
                                _d, _d, _i64, _i64, _i64, _vp],

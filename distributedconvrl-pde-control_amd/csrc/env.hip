@@ -8,11 +8,12 @@ namespace pdec {
 
 // ------------------------------------------------------------------ stand-alone closures
 // MODE 0: prepare_action, 1: featurize, 2: reward (env_sense.hpp: sense_traj)
-template <class T, int MODE>
-__global__ void sense_kernel(EnvDev<T> e, const T* __restrict__ y, const T* __restrict__ action,
+// FLT (pdec_env_set_faults): prepare_action with the actuator gains, featurize through the sensor faults; reward is unchanged
+template <class T, int MODE, bool FLT = false>
+__global__ void sense_kernel(EnvArg<T, FLT> e, const T* __restrict__ y, const T* __restrict__ action,
                              const T* __restrict__ action_prev, const T* __restrict__ state_prev,
                              T* __restrict__ out) {
-  sense_traj<T, MODE>(e, blockIdx.x, y, action, action_prev, state_prev, out);
+  sense_traj<T, MODE, FLT>(e, blockIdx.x, y, action, action_prev, state_prev, out);
 }
 
 // terminal flag per actuator column from the per-trajectory blow-up flags (composed env step; the fused kernels write it themselves)
@@ -34,6 +35,8 @@ static int launch_step(Env& E, int mode, const StepArgs& a) {
                     !(E.prof && E.prof_reps > 1);
     PDEC_REQUIRE(ok, "pdec_env_step: a launch sync is set (pdec_set_launch_sync) and this step is not the fused single-workgroup fp64 "
                      "KS step of 192 / 240 / 600 cells");
+    PDEC_REQUIRE(!E.faults(), "pdec_env_step: a launch sync is set (pdec_set_launch_sync) and so are fault arrays (pdec_env_set_faults): "
+                              "the synchronised step has no fault-carrying form");
   }
   switch (c.pde_kind) {
     case PDEC_PDE_KS_CNAB2: return ks_launch_step(E, fused, a, sync);
@@ -84,6 +87,13 @@ static int launch_sense(Env& E, int mode, const void* y, const void* action, con
   ProfScope ps(&E, mode == 0 ? "actuate" : (mode == 1 ? "featurize" : "reward"));
   by_dtype(E.cfg.dtype, [&](auto t) {
     using T = decltype(t);
+    if (mode != 2 && E.faults()) {
+      const auto kf = mode == 0 ? sense_kernel<T, 0, true> : sense_kernel<T, 1, true>;
+      hipLaunchKernelGGL(kf, dim3(E.cfg.B), dim3(PDEC_SENSE_THREADS),
+                         sense_lds_bytes(E.cfg), E.stream, make_dev_faults<T>(E), (const T*)y, (const T*)action, (const T*)action_prev,
+                         (const T*)state_prev, (T*)out);
+      return;
+    }
     const auto kern = mode == 0 ? sense_kernel<T, 0> : (mode == 1 ? sense_kernel<T, 1> : sense_kernel<T, 2>);
     hipLaunchKernelGGL(kern, dim3(E.cfg.B), dim3(PDEC_SENSE_THREADS), sense_lds_bytes(E.cfg), E.stream, make_dev<T>(E), (const T*)y, (const T*)action,
                        (const T*)action_prev, (const T*)state_prev, (T*)out);
@@ -347,6 +357,22 @@ int pdec_env_set_disturbance(pdec_handle h, const void* mu_per_trajectory) {
                           "per-actuator agents only");
   }
   E->mu_b = mu_per_trajectory;
+  return PDEC_OK;
+}
+
+int pdec_env_set_faults(pdec_handle h, const void* actuator_gain, const void* sensor_gain, const void* sensor_bias) {
+  GET_ENV(E, h);
+  const pdec_env_cfg& c = E->cfg;
+  if (actuator_gain || sensor_gain || sensor_bias) {
+    PDEC_REQUIRE(c.pde_kind != PDEC_PDE_FLUID_RK4, "pdec_env_set_faults: the fluid is not served (KS environments only)");
+    PDEC_REQUIRE(c.pde_kind != PDEC_PDE_KSEG2D_RK4, "pdec_env_set_faults: the 2-D Keller-Segel grid is not served (KS environments only)");
+    PDEC_REQUIRE(c.pde_kind != PDEC_PDE_KSEG_RK4, "pdec_env_set_faults: Keller-Segel is not served (KS environments only)");
+    PDEC_REQUIRE(c.pde_kind == PDEC_PDE_KS_CNAB2 || c.pde_kind == PDEC_PDE_KS_RK4_FD, "pdec_env_set_faults: pde kind %d is not a KS environment",
+                 c.pde_kind);
+    PDEC_REQUIRE(!c.mono, "pdec_env_set_faults: the global/mono agent is not served; per-actuator agents only");
+    PDEC_REQUIRE(c.memory_size == 0, "pdec_env_set_faults: memory_size %d > 0 (action memory) is not served", c.memory_size);
+  }
+  E->act_gain = actuator_gain; E->sens_gain = sensor_gain; E->sens_bias = sensor_bias;
   return PDEC_OK;
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include "common.hpp"
 #include "fft_lds.hpp"
+#include <type_traits>
 
 namespace pdec {
 
@@ -34,6 +35,20 @@ struct EnvDev {
   LaunchSync sync;       // pdec_set_launch_sync (SYNC instantiations of the fused KS step only)
   int member = 0;        // pdec_env_set_member_layout: the KS step integrates ONE trajectory per workgroup (b0 = blockIdx.x)
 };
+
+// pdec_env_set_faults: per-trajectory actuator gains [B][A], sensor gains and biases [B][S] (each may be null: healthy).  The
+// FLT instantiations of the KS kernels take EnvDevF, EnvDev with these three pointers behind it; every other kernel keeps
+// EnvDev as its argument, and with it its kernel arguments and its code
+template <class T>
+struct FaultDev {
+  const T *act_gain, *sens_gain, *sens_bias;
+};
+template <class T>
+struct EnvDevF : EnvDev<T> {
+  FaultDev<T> flt;
+};
+template <class T, bool FLT>
+using EnvArg = std::conditional_t<FLT, EnvDevF<T>, EnvDev<T>>;
 
 // The FFT engine of the spectral KS kernels (csrc/ks_engines.hpp: with_ks_engine maps an enumerator to its engine type).
 enum class KsEngine {
@@ -79,6 +94,9 @@ struct Env : Object {
   bool member = false;       // pdec_env_set_member_layout: one KS trajectory per workgroup, the B = 1 launch's arithmetic
   const void* mu_b = nullptr;   // pdec_env_set_disturbance: caller-owned device array [B] of the environment's dtype
   int control_from = 0;         // pdec_env_set_control_from: the rollouts act from this step on (zero action before it)
+  // pdec_env_set_faults: caller-owned device arrays of the environment's dtype, [B][A], [B][S], [B][S]; each may be null
+  const void *act_gain = nullptr, *sens_gain = nullptr, *sens_bias = nullptr;
+  bool faults() const { return act_gain || sens_gain || sens_bias; }
   FftPlan fft;
   int nthreads = 64;
   KsEngine engine = KsEngine::Generic;   // PDEC_PDE_KS_CNAB2 only
@@ -128,6 +146,15 @@ EnvDev<T> make_dev(const Env& E) {
   e.dhat1 = E.dhat1.as<C2<T>>(); e.mu_b = static_cast<const T*>(E.mu_b);
   e.fft = E.fft;
   e.member = E.member ? 1 : 0;
+  return e;
+}
+
+// the argument of the FLT instantiations (E.faults())
+template <class T>
+EnvDevF<T> make_dev_faults(const Env& E) {
+  EnvDevF<T> e;
+  static_cast<EnvDev<T>&>(e) = make_dev<T>(E);
+  e.flt = FaultDev<T>{static_cast<const T*>(E.act_gain), static_cast<const T*>(E.sens_gain), static_cast<const T*>(E.sens_bias)};
   return e;
 }
 

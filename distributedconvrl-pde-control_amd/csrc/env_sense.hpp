@@ -284,6 +284,25 @@ __device__ __forceinline__ void actuate_consecutive(const EnvDev<T>& e, const T*
   __syncthreads();
 }
 
+// ------------------------------------------------------------------ faults (pdec_env_set_faults), FLT instantiations only
+// The two modifications of KSSetup.jl:190-245 are made on the ARRAYS the helpers above read, so the helpers themselves serve
+// the healthy and the faulty kernels alike: the actuation reads the applied action gain[b][a] * action[a], featurize reads
+// the sensor dots gain[b][s] * dot_s + bias[b][s] (indexed by the sensor, so a window row takes its own sensor's fault; the
+// bias in units of the field, before sensor_scale).  The reward reads the commanded action and the true dots.
+template <class T>
+__device__ __forceinline__ T fault_action(const FaultDev<T>& f, int b, int A, int a, T v) {
+  return f.act_gain ? f.act_gain[(size_t)b * A + a] * v : v;
+}
+template <class T>
+__device__ __forceinline__ void fault_dots(const FaultDev<T>& f, int b, int S, const T* dots, T* out, int tid, int nt) {
+  for (int s = tid; s < S; s += nt) {
+    T v = dots[s];
+    if (f.sens_gain) v = f.sens_gain[(size_t)b * S + s] * v;
+    if (f.sens_bias) v = v + f.sens_bias[(size_t)b * S + s];
+    out[s] = v;
+  }
+}
+
 template <class T>
 __device__ __forceinline__ T block_max(T v, T* red, int tid, int nt) {
   for (int off = 32; off > 0; off >>= 1) {
@@ -314,8 +333,9 @@ __device__ __forceinline__ void write_terminal(const EnvDev<T>& e, int b, bool f
 #define PDEC_SENSE_THREADS 128
 inline size_t sense_lds_bytes(const pdec_env_cfg& c) { return (2 * (size_t)c.N + 2 * c.A + 2 * c.S + 16 * c.S) * dtype_size(c.dtype); }
 
-template <class T, int MODE>
-__device__ __forceinline__ void sense_traj(const EnvDev<T>& e, int b, const T* __restrict__ y, const T* __restrict__ action,
+// FLT: prepare_action applies the actuator gains, featurize reads the dots through the sensor faults (without action memory)
+template <class T, int MODE, bool FLT = false>
+__device__ __forceinline__ void sense_traj(const EnvArg<T, FLT>& e, int b, const T* __restrict__ y, const T* __restrict__ action,
                                            const T* __restrict__ action_prev, const T* __restrict__ state_prev, T* __restrict__ out) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int N = e.N, tid = threadIdx.x, nt = blockDim.x;
@@ -327,6 +347,7 @@ __device__ __forceinline__ void sense_traj(const EnvDev<T>& e, int b, const T* _
   if (MODE == 0 || MODE == 2) {     // row 0 of every action column (KSSetup.jl:176,241: action[1, i]); na = 1 without action memory
     for (int a = tid; a < e.A; a += nt) {
       act[a] = action[((size_t)b * e.A + a) * e.na];
+      if constexpr (FLT && MODE == 0) act[a] = fault_action<T>(e.flt, b, e.A, a, act[a]);
       actp[a] = MODE == 2 ? action_prev[((size_t)b * e.A + a) * e.na] : (T)0;
     }
     __syncthreads();
@@ -347,6 +368,12 @@ __device__ __forceinline__ void sense_traj(const EnvDev<T>& e, int b, const T* _
   sense_dots<T>(e, [&](int r, int n) { return sy[r * N + n]; }, dots, part, tid, nt);
   if (MODE == 1) {
     const size_t sw = e.mono ? (size_t)e.S : (size_t)e.A * e.ns;
+    if constexpr (FLT) {        // `part` is free behind the dots
+      fault_dots<T>(e.flt, b, e.S, dots, part, tid, nt);
+      __syncthreads();
+      featurize_traj<T>(e, part, state_prev ? state_prev + b * sw : nullptr, out + b * sw, tid, nt);
+      return;
+    }
     if (e.mem > 0)
       featurize_traj_mem<T>(e, dots, state_prev ? state_prev + b * sw : nullptr, action ? action + (size_t)b * e.A * e.na : nullptr,
                             out + b * sw, tid, nt);

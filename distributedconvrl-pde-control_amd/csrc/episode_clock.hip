@@ -135,12 +135,13 @@ __global__ void __launch_bounds__(RI_THREADS) epclock_boundary_kernel(ClockArgs<
 }
 
 // the features of the restarted trajectories' new fields (random initial fields only)
-template <class T>
-__global__ void __launch_bounds__(PDEC_SENSE_THREADS) epclock_sense_kernel(EnvDev<T> e, const int32_t* __restrict__ ended,
+// FLT (pdec_env_set_faults): through the restarted trajectory's own sensor faults, as the step would have written the state
+template <class T, bool FLT = false>
+__global__ void __launch_bounds__(PDEC_SENSE_THREADS) epclock_sense_kernel(EnvArg<T, FLT> e, const int32_t* __restrict__ ended,
                                                                           const T* __restrict__ y_next, T* __restrict__ state_next) {
   const int b = blockIdx.x;
   if (ended[b] == 0) return;
-  sense_traj<T, 1>(e, b, y_next, nullptr, nullptr, nullptr, state_next);
+  sense_traj<T, 1, FLT>(e, b, y_next, nullptr, nullptr, nullptr, state_next);
 }
 
 static EpisodeClock* get_clock(pdec_handle h, const char* fn, Env** E) {
@@ -241,7 +242,10 @@ int pdec_epclock_step(pdec_handle clock, void* reward, const int32_t* flags, voi
     g.R = K->R; g.E = K->E; g.cap = K->cap; g.arow = c.A * env_na(c); g.yrow = (int)env_y_count(c); g.srow = c.A * env_ns(c);
     g.random_init = K->random_init; g.B = K->B; g.ri = K->ri; g.seed = K->seed; g.rank = (uint64_t)K->rank; g.world = (uint64_t)K->world;
     hipLaunchKernelGGL(epclock_boundary_kernel<T>, dim3(K->B), dim3(RI_THREADS), 0, E->stream, g);
-    if (K->random_init)
+    if (K->random_init && E->faults())
+      hipLaunchKernelGGL((epclock_sense_kernel<T, true>), dim3(K->B), dim3(PDEC_SENSE_THREADS), sense_lds_bytes(c), E->stream,
+                         make_dev_faults<T>(*E), (const int32_t*)K->ended.as<int32_t>(), (const T*)y_next, (T*)state_next);
+    else if (K->random_init)
       hipLaunchKernelGGL(epclock_sense_kernel<T>, dim3(K->B), dim3(PDEC_SENSE_THREADS), sense_lds_bytes(c), E->stream, make_dev<T>(*E),
                          (const int32_t*)K->ended.as<int32_t>(), (const T*)y_next, (T*)state_next);
   });

@@ -17,8 +17,11 @@ namespace pdec {
 // complex FFT (and of a thread's column pair) belong to ONE member and a member's arithmetic is that of its solo rollout.
 // AN = NoiseScale (pdec_mlp_set_noise_scale; solo form): the amplitude of each of the workgroup's [2][A] columns, entry
 // (b A + a) / cols_per_entry of the array, is read into LDS once, behind the activation planes.
-template <class T, class ENG, bool MEM, class AN = T>
-__global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, RollActor actor, RollArgs<T, AN> g, RollMembers pm) {
+// FLT (pdec_env_set_faults): the forcing is synthesised from gain * action, staged in `rnow` (free until this step's reward is
+// written), and the state the policy reads next is featurized from gain * dot + bias, staged in `part` (free behind sense_dots):
+// no LDS beyond the healthy kernel's, so the same configurations are served.  Instantiations of their own (argument EnvDevF).
+template <class T, class ENG, bool MEM, class AN = T, bool FLT = false>
+__global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvArg<T, FLT> e, RollActor actor, RollArgs<T, AN> g, RollMembers pm) {
   constexpr bool NS = std::is_same<AN, NoiseScale>::value;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int N = e.N, tid = threadIdx.x, nt = blockDim.x, A = e.A, ns = e.ns;
@@ -138,12 +141,21 @@ __global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, 
       }
     // ---- prepare_action -> spectrum -> constant term of the CNAB2 update (KSSetup.jl:231-245, :155)
     T pa4[KS_MPT], pb4[KS_MPT];
+    const T* ap = act;          // the action the actuators apply
+    if constexpr (FLT) {
+      for (int a = tid; a < A; a += nt) {
+        rnow[a] = fault_action<T>(e.flt, b0, A, a, act[a]);
+        rnow[A + a] = has1 ? fault_action<T>(e.flt, b1, A, a, act[A + a]) : (T)0;
+      }
+      __syncthreads();
+      ap = rnow;
+    }
     {
       int n4[KS_MPT];
 #pragma unroll
       for (int j = 0; j < KS_MPT; ++j) n4[j] = eng.phys_index(j);
       if ((N & 3) == 0 && 2 * N <= 16 * e.S) {
-        actuate_consecutive<T>(e, act, act + A, part, tid, nt);
+        actuate_consecutive<T>(e, ap, ap + A, part, tid, nt);
 #pragma unroll
         for (int j = 0; j < KS_MPT; ++j) {
           pa4[j] = n4[j] < N ? part[n4[j]] : (T)0;
@@ -151,7 +163,7 @@ __global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, 
         }
         __syncthreads();      // `part` is reused by the sensor dots of this step
       } else {
-        actuate_cells<T, KS_MPT>(e, act, act + A, n4, pa4, pb4);
+        actuate_cells<T, KS_MPT>(e, ap, ap + A, n4, pa4, pb4);
       }
     }
 #pragma unroll
@@ -221,15 +233,22 @@ __global__ void __launch_bounds__(ENG::kThreads) ks_rollout_kernel(EnvDev<T> e, 
     // ---- reward (KSSetup.jl:162-178) and featurize (:190-229) from the sensor dots of the new field
     const T* Rt = reinterpret_cast<const T*>(eng.publish(U));
     sense_dots<T>(e, [&](int r, int n) { return Rt[2 * n + r]; }, dots, part, tid, nt);
+    const T* fd = dots;         // what featurize reads
+    if constexpr (FLT) {
+      fault_dots<T>(e.flt, b0, e.S, dots, part, tid, nt);
+      if (has1) fault_dots<T>(e.flt, b1, e.S, dots + e.S, part + e.S, tid, nt);
+      __syncthreads();
+      fd = part;
+    }
     if (e.fmap) {
       reward_pair<T>(e, dots, dots + e.S, act, act + A, actp, actp + A, rnow, has1 ? rnow + A : nullptr, tid, nt);
-      featurize_pair<T>(e, dots, dots + e.S, stl, has1 ? stl + A * ns : nullptr, tid, nt);
+      featurize_pair<T>(e, fd, fd + e.S, stl, has1 ? stl + A * ns : nullptr, tid, nt);
     } else {
       reward_traj<T>(e, dots, act, actp, rnow, tid, nt);
-      featurize_traj<T>(e, dots, nullptr, stl, tid, nt);
+      featurize_traj<T>(e, fd, nullptr, stl, tid, nt);
       if (has1) {
         reward_traj<T>(e, dots + e.S, act + A, actp + A, rnow + A, tid, nt);
-        featurize_traj<T>(e, dots + e.S, nullptr, stl + A * ns, tid, nt);
+        featurize_traj<T>(e, fd + e.S, nullptr, stl + A * ns, tid, nt);
       }
     }
     __syncthreads();
@@ -288,15 +307,21 @@ int ks_rollout_persistent(Env& E, const Mlp& A, const RollSpec& spec, const Roll
   ProfScope ps(&E, pm ? "ks_rollout_members" : "ks_rollout");
   by_dtype(c.dtype, [&](auto t) {
     using T = decltype(t);
-    const EnvDev<T> e = make_dev<T>(E);
     const RollArgs<T> g = make_roll_args<T>(spec, ptrs);
     with_ks_engine<T>(E.engine, [&](auto tag) {
       using ENG = typename decltype(tag)::type;
-      if (ntab)
-        hipLaunchKernelGGL((ks_rollout_kernel<T, ENG, false, NoiseScale>), grid, block, lds, E.stream, e, ra,
-                           (make_roll_args<T, NoiseScale>(spec, ptrs)), RollMembers{});
-      else if (pm) hipLaunchKernelGGL((ks_rollout_kernel<T, ENG, true>), grid, block, lds, E.stream, e, ra, g, *pm);
-      else hipLaunchKernelGGL((ks_rollout_kernel<T, ENG, false>), grid, block, lds, E.stream, e, ra, g, RollMembers{});
+      // one launch tail for the healthy and the fault-carrying kernels (pdec_env_set_faults: FLT, argument EnvDevF)
+      auto launch = [&](auto ntab_kern, auto member_kern, auto solo_kern, const auto& e) {
+        if (ntab)
+          hipLaunchKernelGGL(ntab_kern, grid, block, lds, E.stream, e, ra, (make_roll_args<T, NoiseScale>(spec, ptrs)), RollMembers{});
+        else if (pm) hipLaunchKernelGGL(member_kern, grid, block, lds, E.stream, e, ra, g, *pm);
+        else hipLaunchKernelGGL(solo_kern, grid, block, lds, E.stream, e, ra, g, RollMembers{});
+      };
+      if (E.faults())
+        launch(ks_rollout_kernel<T, ENG, false, NoiseScale, true>, ks_rollout_kernel<T, ENG, true, T, true>,
+               ks_rollout_kernel<T, ENG, false, T, true>, make_dev_faults<T>(E));
+      else
+        launch(ks_rollout_kernel<T, ENG, false, NoiseScale>, ks_rollout_kernel<T, ENG, true>, ks_rollout_kernel<T, ENG, false>, make_dev<T>(E));
     });
   });
   PDEC_HIP(hipGetLastError());

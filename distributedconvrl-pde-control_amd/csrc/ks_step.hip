@@ -23,8 +23,12 @@ namespace pdec {
 // MU (pdec_env_set_disturbance): the disturbance amplitude per trajectory -- likewise instantiations of their own: in the one code
 // path for both cases the register form of <float, FftWave256> took 98 VGPRs instead of 96 and its SIMD-sharing form spilled 20
 // instead of 15, and those two budgets are what lets the step run beside the update passes
-template <class T, class ENG, bool FUSED, bool SHARE = false, bool SYNC = false, bool MU = false>
-__global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kernel(EnvDev<T> e, const T* __restrict__ y_in, const T* __restrict__ p_in,
+// FLT (pdec_env_set_faults; FUSED only): actuator gains and sensor faults per trajectory -- instantiations of their own for the
+// same reason, with the three arrays behind the EnvDev argument (EnvDevF), so that the others keep their kernel arguments too.
+// No LDS of its own: the applied action gain * action is staged in `act` for the actuation and the commanded action read again
+// for the reward; the dots featurize reads stand in `part`, which is free behind sense_dots
+template <class T, class ENG, bool FUSED, bool SHARE = false, bool SYNC = false, bool MU = false, bool FLT = false>
+__global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kernel(EnvArg<T, FLT> e, const T* __restrict__ y_in, const T* __restrict__ p_in,
                                    const T* __restrict__ action, const T* __restrict__ action_prev,
                                    const T* __restrict__ state_prev, T* __restrict__ y_out,
                                    T* __restrict__ p_out, T* __restrict__ state_out,
@@ -68,6 +72,10 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
       act[e.A + a] = has1 ? action[(size_t)b1 * e.A + a] : (T)0;
       actp[a] = action_prev[(size_t)b0 * e.A + a];
       actp[e.A + a] = has1 ? action_prev[(size_t)b1 * e.A + a] : (T)0;
+      if constexpr (FLT) {
+        act[a] = fault_action<T>(e.flt, b0, e.A, a, act[a]);
+        if (has1) act[e.A + a] = fault_action<T>(e.flt, b1, e.A, a, act[e.A + a]);
+      }
     }
   }
   __syncthreads();
@@ -95,6 +103,13 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
       }
     } else {
       actuate_cells<T, KS_MPT>(e, act, act + e.A, n4, pa4, pb4);
+    }
+    if constexpr (FLT) {      // the forcing is made: back to the commanded action, which the reward punishes
+      __syncthreads();
+      for (int a = tid; a < e.A; a += nt) {
+        act[a] = action[(size_t)b0 * e.A + a];
+        if (has1) act[e.A + a] = action[(size_t)b1 * e.A + a];
+      }
     }
   }
 #pragma unroll
@@ -238,16 +253,23 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
   const int rw = e.mono ? 1 : e.A;             // reward entries per trajectory
   const int sw = e.mono ? e.S : e.A * e.ns;    // state entries per trajectory
   T rmine;
+  const T* fd = dots;          // what featurize reads
+  if constexpr (FLT) {
+    fault_dots<T>(e.flt, b0, e.S, dots, part, tid, nt);
+    if (has1) fault_dots<T>(e.flt, b1, e.S, dots + e.S, part + e.S, tid, nt);
+    __syncthreads();
+    fd = part;
+  }
   if (e.fmap && !e.mono) {     // both trajectories in one pass each
     rmine = reward_pair<T>(e, dots, dots + e.S, act, act + e.A, actp, actp + e.A, reward_out + (size_t)b0 * rw,
                            has1 ? reward_out + (size_t)b1 * rw : nullptr, tid, nt);
-    featurize_pair<T>(e, dots, dots + e.S, state_out + (size_t)b0 * sw, has1 ? state_out + (size_t)b1 * sw : nullptr, tid, nt);
+    featurize_pair<T>(e, fd, fd + e.S, state_out + (size_t)b0 * sw, has1 ? state_out + (size_t)b1 * sw : nullptr, tid, nt);
   } else {
     rmine = reward_traj<T>(e, dots, act, actp, reward_out + (size_t)b0 * rw, tid, nt);
-    featurize_traj<T>(e, dots, state_prev ? state_prev + (size_t)b0 * sw : nullptr, state_out + (size_t)b0 * sw, tid, nt);
+    featurize_traj<T>(e, fd, state_prev ? state_prev + (size_t)b0 * sw : nullptr, state_out + (size_t)b0 * sw, tid, nt);
     if (has1) {
       rmine += reward_traj<T>(e, dots + e.S, act + e.A, actp + e.A, reward_out + (size_t)b1 * rw, tid, nt);
-      featurize_traj<T>(e, dots + e.S, state_prev ? state_prev + (size_t)b1 * sw : nullptr,
+      featurize_traj<T>(e, fd + e.S, state_prev ? state_prev + (size_t)b1 * sw : nullptr,
                         state_out + (size_t)b1 * sw, tid, nt);
     }
   }
@@ -291,37 +313,53 @@ size_t ks_lds_bytes(const pdec_env_cfg& c, KsEngine k) {      // the engine's bu
   return (fft * 2 + 4 * (size_t)c.A + 2 * c.S + 16 * c.S + 16) * dtype_size(c.dtype);
 }
 
+// The instantiation a launch takes.  FLT (pdec_env_set_faults) is a template argument -- its kernels take EnvDevF -- and exists for
+// the fused forms only; SHARE: the 64-VGPR form (fp32 single-wave engine); SYNC: fp64 fixed plans (launch_step has checked the rest)
+template <class T, class ENG, KsEngine KIND, bool FLT>
+auto ks_step_kernel_for(bool fused, bool share, bool synced, bool mu) {
+  auto kern = mu ? ks_env_step_kernel<T, ENG, true, false, false, true, FLT> : ks_env_step_kernel<T, ENG, true, false, false, false, FLT>;
+  if constexpr (!FLT)
+    if (!fused) kern = mu ? ks_env_step_kernel<T, ENG, false, false, false, true> : ks_env_step_kernel<T, ENG, false>;
+  if constexpr (sizeof(T) == 4 && ks_is_single_wave(KIND))
+    if (share) kern = mu ? ks_env_step_kernel<T, ENG, true, true, false, true, FLT> : ks_env_step_kernel<T, ENG, true, true, false, false, FLT>;
+  if constexpr (!FLT && sizeof(T) == 8 && ks_is_fixed_plan(KIND))
+    if (synced) kern = mu ? ks_env_step_kernel<T, ENG, true, false, true, true> : ks_env_step_kernel<T, ENG, true, false, true>;
+  return kern;
+}
+
 int ks_launch_step(Env& E, bool fused, const StepArgs& a, const LaunchSync& sync) {
   const pdec_env_cfg& c = E.cfg;
   const dim3 grid(E.member ? c.B : (c.B + 1) / 2), block(E.nthreads);
   const bool synced = sync.wait || sync.done;
+  const bool mu = E.mu_b != nullptr;          // pdec_env_set_disturbance: the MU instantiation of whichever form is launched
+  // SHARE: the 64-VGPR form + its lane-private constant slots (8 float4 per lane, 16-byte aligned)
+  const bool share = fused && E.share_simd && c.dtype == PDEC_F32 && ks_is_single_wave(E.engine);
+  const size_t lds = E.lds_bytes + (share ? 16 + 8 * 16 * 64 : 0);
   // the training pipeline's form of the step, profiled in the pipeline (one launch per event pair): timed by the dispatch's own
   // timestamps (PDEC_TIMED_LAUNCH) so that the measurement puts no packets around the kernel
   const bool timed = c.dtype == PDEC_F32 && ks_is_single_wave(E.engine) && fused && E.prof && E.prof_reps == 1;
   by_dtype(c.dtype, [&](auto t) {
     using T = decltype(t);
-    EnvDev<T> e = make_dev<T>(E);
-    e.sync = sync;
     with_ks_engine<T>(E.engine, [&](auto tag) {
       using ENG = typename decltype(tag)::type;
-      const bool mu = E.mu_b != nullptr;      // pdec_env_set_disturbance: the MU instantiation of whichever form is launched
-      auto kern = fused ? (mu ? ks_env_step_kernel<T, ENG, true, false, false, true> : ks_env_step_kernel<T, ENG, true>)
-                        : (mu ? ks_env_step_kernel<T, ENG, false, false, false, true> : ks_env_step_kernel<T, ENG, false>);
-      size_t lds = E.lds_bytes;
-      if constexpr (sizeof(T) == 4 && ks_is_single_wave(decltype(tag)::kind))   // SHARE: the 64-VGPR form + its lane-private
-        if (fused && E.share_simd) {                                           // constant slots (8 float4 per lane, 16-byte aligned)
-          kern = mu ? ks_env_step_kernel<T, ENG, true, true, false, true> : ks_env_step_kernel<T, ENG, true, true>;
-          lds += 16 + 8 * 16 * 64;
+      constexpr KsEngine KIND = decltype(tag)::kind;
+      // one launch tail for the healthy and the fault-carrying kernels (their first argument differs: EnvDev / EnvDevF)
+      auto launch = [&](auto kern, const auto& e) {
+        if (timed) {
+          PDEC_TIMED_LAUNCH(&E, "ks_env_step", kern, grid, block, lds, PDEC_STEP_KERNEL_ARGS(T, e, a));
+          return;
         }
-      if constexpr (sizeof(T) == 8 && ks_is_fixed_plan(decltype(tag)::kind))    // SYNC (launch_step has checked the rest)
-        if (synced) kern = mu ? ks_env_step_kernel<T, ENG, true, false, true, true> : ks_env_step_kernel<T, ENG, true, false, true>;
-      if (timed) {
-        PDEC_TIMED_LAUNCH(&E, "ks_env_step", kern, grid, block, lds, PDEC_STEP_KERNEL_ARGS(T, e, a));
-        return;
+        // replay is safe when the step does not run in place (y_out != y_in)
+        ProfScope ps(&E, fused ? "ks_env_step" : "ks_pde_step", !synced && a.y_out != a.y_in && a.state_out != a.state_prev);
+        for (int rep = 0; rep < ps.reps; ++rep) hipLaunchKernelGGL(kern, grid, block, lds, E.stream, PDEC_STEP_KERNEL_ARGS(T, e, a));
+      };
+      if (fused && E.faults()) {              // pdec_env_set_faults (the integrator alone has neither side; a sync is refused before)
+        launch(ks_step_kernel_for<T, ENG, KIND, true>(fused, share, synced, mu), make_dev_faults<T>(E));
+      } else {
+        EnvDev<T> e = make_dev<T>(E);
+        e.sync = sync;
+        launch(ks_step_kernel_for<T, ENG, KIND, false>(fused, share, synced, mu), e);
       }
-      // replay is safe when the step does not run in place (y_out != y_in)
-      ProfScope ps(&E, fused ? "ks_env_step" : "ks_pde_step", !synced && a.y_out != a.y_in && a.state_out != a.state_prev);
-      for (int rep = 0; rep < ps.reps; ++rep) hipLaunchKernelGGL(kern, grid, block, lds, E.stream, PDEC_STEP_KERNEL_ARGS(T, e, a));
     });
   });
   PDEC_HIP(hipGetLastError());

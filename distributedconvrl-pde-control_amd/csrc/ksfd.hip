@@ -51,8 +51,11 @@ __device__ __forceinline__ void ksfd_reward_partial(const EnvDev<T>& e, T rmine,
   }
 }
 
-template <class T, int MODE>  // MODE 0: fused env step, 1: integrate only, 2: rhs only
-__global__ void ksfd_env_step_kernel(EnvDev<T> e, const T* __restrict__ y_in, const T* __restrict__ p_in,
+// FLT (pdec_env_set_faults; MODE 0): per-trajectory actuator gains and sensor faults, instantiations of their own whose argument
+// carries the three arrays (EnvDevF).  As in ks_step.hip: the applied action is staged in `act` for the actuation and the commanded
+// one read again for the reward; featurize reads its dots from `part`
+template <class T, int MODE, bool FLT = false>  // MODE 0: fused env step, 1: integrate only, 2: rhs only
+__global__ void ksfd_env_step_kernel(EnvArg<T, FLT> e, const T* __restrict__ y_in, const T* __restrict__ p_in,
                                      const T* __restrict__ action, const T* __restrict__ action_prev,
                                      const T* __restrict__ state_prev, T* __restrict__ y_out, T* __restrict__ p_out,
                                      T* __restrict__ state_out, T* __restrict__ reward_out, int32_t* __restrict__ done) {
@@ -72,12 +75,17 @@ __global__ void ksfd_env_step_kernel(EnvDev<T> e, const T* __restrict__ y_in, co
   if (MODE == 0) {
     for (int a = tid; a < e.A; a += nt) {
       act[a] = action[(size_t)b * e.A + a];
+      if constexpr (FLT) act[a] = fault_action<T>(e.flt, b, e.A, a, act[a]);
       actp[a] = action_prev[(size_t)b * e.A + a];
     }
     __syncthreads();
     if (live) {
       p = actuate_cell<T>(e, act, n);
       if (p_out) p_out[yo + n] = p;
+    }
+    if constexpr (FLT) {
+      __syncthreads();
+      for (int a = tid; a < e.A; a += nt) act[a] = action[(size_t)b * e.A + a];
     }
   } else if (live) {
     p = p_in[yo + n];
@@ -121,7 +129,13 @@ __global__ void ksfd_env_step_kernel(EnvDev<T> e, const T* __restrict__ y_in, co
   const int rw = e.mono ? 1 : e.A;
   const size_t sw = e.mono ? (size_t)e.S : (size_t)e.A * e.ns;
   const T rmine = reward_traj<T>(e, dots, act, actp, reward_out + (size_t)b * rw, tid, nt);
-  featurize_traj<T>(e, dots, state_prev ? state_prev + b * sw : nullptr, state_out + b * sw, tid, nt);
+  const T* fd = dots;
+  if constexpr (FLT) {
+    fault_dots<T>(e.flt, b, e.S, dots, part, tid, nt);
+    __syncthreads();
+    fd = part;
+  }
+  featurize_traj<T>(e, fd, state_prev ? state_prev + b * sw : nullptr, state_out + b * sw, tid, nt);
   if (e.rsum_out) ksfd_reward_partial<T>(e, rmine, red, tid, nt);
   if (done && e.check_max == 2) {
     __syncthreads();
@@ -176,8 +190,8 @@ __device__ __forceinline__ void ksfd_rhs_wave(const T (&w)[CPL], const T (&force
   }
 }
 
-template <class T, int CPL>
-__global__ void __launch_bounds__(64) ksfd_wave_step_kernel(EnvDev<T> e, const T* __restrict__ y_in, const T* __restrict__ action,
+template <class T, int CPL, bool FLT = false>
+__global__ void __launch_bounds__(64) ksfd_wave_step_kernel(EnvArg<T, FLT> e, const T* __restrict__ y_in, const T* __restrict__ action,
                                                             const T* __restrict__ action_prev, const T* __restrict__ state_prev,
                                                             T* __restrict__ y_out, T* __restrict__ p_out, T* __restrict__ state_out,
                                                             T* __restrict__ reward_out, int32_t* __restrict__ done) {
@@ -197,6 +211,7 @@ __global__ void __launch_bounds__(64) ksfd_wave_step_kernel(EnvDev<T> e, const T
   for (int c = 0; c < CPL; ++c) u[c] = y_in[yo + n0 + c];
   for (int a = tid; a < e.A; a += nt) {
     act[a] = action[(size_t)b * e.A + a];
+    if constexpr (FLT) act[a] = fault_action<T>(e.flt, b, e.A, a, act[a]);
     actp[a] = action_prev[(size_t)b * e.A + a];
   }
   __syncthreads();
@@ -208,6 +223,10 @@ __global__ void __launch_bounds__(64) ksfd_wave_step_kernel(EnvDev<T> e, const T
     if (p_out) p_out[yo + n] = p;
     // forcing = actuation + disturbance mu cos(2 + pi + x/(Lx/2)), x = dx (n+1)   (KSSetup.jl:36,155)
     force[c] = p + mu * (T)cos(2.0 + 3.14159265358979323846 + (double)e.dx * (n + 1) / ((double)e.dx * N / 2));
+  }
+  if constexpr (FLT) {
+    __syncthreads();
+    for (int a = tid; a < e.A; a += nt) act[a] = action[(size_t)b * e.A + a];
   }
   const T i2dx = (T)0.5 / e.dx, idx2 = (T)1 / (e.dx * e.dx), idx4 = idx2 * idx2, h = e.hstep;
   for (int it = 0; it < e.K; ++it) {
@@ -252,7 +271,13 @@ __global__ void __launch_bounds__(64) ksfd_wave_step_kernel(EnvDev<T> e, const T
   const int rw = e.mono ? 1 : e.A;
   const size_t sw = e.mono ? (size_t)e.S : (size_t)e.A * e.ns;
   const T rmine = reward_traj<T>(e, dots, act, actp, reward_out + (size_t)b * rw, tid, nt);
-  featurize_traj<T>(e, dots, state_prev ? state_prev + b * sw : nullptr, state_out + b * sw, tid, nt);
+  const T* fd = dots;
+  if constexpr (FLT) {
+    fault_dots<T>(e.flt, b, e.S, dots, part, tid, nt);
+    __syncthreads();
+    fd = part;
+  }
+  featurize_traj<T>(e, fd, state_prev ? state_prev + b * sw : nullptr, state_out + b * sw, tid, nt);
   if (e.rsum_out) ksfd_reward_partial<T>(e, rmine, red, tid, nt);
   if (done && e.check_max == 2) {
     __syncthreads();
@@ -277,13 +302,19 @@ int ksfd_launch_step(Env& E, int mode, const StepArgs& a) {
   const bool wave = mode == 0 && c.N == 256 && getenv("PDEC_KSFD_LDS") == nullptr;
   by_dtype(c.dtype, [&](auto t) {
     using T = decltype(t);
-    const EnvDev<T> e = make_dev<T>(E);
-    const auto kern = mode == 0 ? ksfd_env_step_kernel<T, 0> : (mode == 1 ? ksfd_env_step_kernel<T, 1> : ksfd_env_step_kernel<T, 2>);
-    if (wave)
-      hipLaunchKernelGGL((ksfd_wave_step_kernel<T, 4>), dim3(c.B), dim3(64), E.lds_bytes, E.stream, e, (const T*)a.y_in, (const T*)a.action,
-                         (const T*)a.action_prev, (const T*)a.state_prev, (T*)a.y_out, (T*)a.p_out, (T*)a.state_out, (T*)a.reward_out, a.done);
+    // one launch tail for the healthy and the fault-carrying kernels (pdec_env_set_faults: FLT, fused step only, argument EnvDevF)
+    auto launch = [&](auto wave_kern, auto kern, const auto& e) {
+      if (wave)
+        hipLaunchKernelGGL(wave_kern, dim3(c.B), dim3(64), E.lds_bytes, E.stream, e, (const T*)a.y_in, (const T*)a.action,
+                           (const T*)a.action_prev, (const T*)a.state_prev, (T*)a.y_out, (T*)a.p_out, (T*)a.state_out, (T*)a.reward_out, a.done);
+      else
+        hipLaunchKernelGGL(kern, dim3(c.B), dim3(E.nthreads), E.lds_bytes, E.stream, PDEC_STEP_KERNEL_ARGS(T, e, a));
+    };
+    if (mode == 0 && E.faults())
+      launch(ksfd_wave_step_kernel<T, 4, true>, ksfd_env_step_kernel<T, 0, true>, make_dev_faults<T>(E));
     else
-      hipLaunchKernelGGL(kern, dim3(c.B), dim3(E.nthreads), E.lds_bytes, E.stream, PDEC_STEP_KERNEL_ARGS(T, e, a));
+      launch(ksfd_wave_step_kernel<T, 4>, mode == 0 ? ksfd_env_step_kernel<T, 0> : (mode == 1 ? ksfd_env_step_kernel<T, 1> : ksfd_env_step_kernel<T, 2>),
+             make_dev<T>(E));
   });
   PDEC_HIP(hipGetLastError());
   return PDEC_OK;

@@ -141,6 +141,7 @@ class PDEenv:
         self._state0 = torch.empty(self._sshape, **kw)
         self.mu = None                  # set_disturbance: the per-trajectory amplitudes the library reads (kept alive here)
         self._control_from = 0
+        self.actuator_gain = self.sensor_gain = self.sensor_bias = None     # set_faults: kept alive here, read by the library
         self.reset()
 
     # ---- helpers
@@ -409,6 +410,37 @@ class PDEenv:
             t = t.to(device=self.device, dtype=self.dtype).contiguous().clone()
         _lib.check(self.lib.pdec_env_set_disturbance(self._h, _lib.ptr(t)))
         self.mu = t
+
+    def set_faults(self, actuator_gain=None, sensor_gain=None, sensor_bias=None):
+        """Per-trajectory actuator and sensor faults (pdec_env_set_faults; KS setups, per-actuator agents, memory_size = 0).
+        actuator_gain [B, A]: the forcing of trajectory b is synthesised from actuator_gain[b, a] * action[b, a] (0 dead, 0.5
+        weak, -1 reversed); the commanded action stays what the reward punishes, what the agent stores and what env.action
+        holds, env.p is the forcing applied.  sensor_gain, sensor_bias [B, S]: featurize writes
+        (sensor_gain[b, s] * dot_s + sensor_bias[b, s]) * sensor_scale for sensor s (the bias in units of the field); the reward
+        keeps the true dots.  Arrays or tensors, converted once to the environment's dtype and device on its stream and kept
+        alive as env.actuator_gain / env.sensor_gain / env.sensor_bias: writing into them changes what later launches read,
+        recorded steps and captured graphs included.  Each may be None (healthy); all None returns to the healthy environment.
+        They belong to the batch slot: resets and autoreset leave them alone.  The reset image is refreshed from y0 through the
+        new sensors, so a per-trajectory reset restores a state seen through them; y, state and action are not touched."""
+        names = ("actuator_gain", "sensor_gain", "sensor_bias")
+        before = [getattr(self, k) for k in names]
+        kept = []
+        with _on_stream(self.stream):
+            for v in (actuator_gain, sensor_gain, sensor_bias):
+                t = v if v is None or isinstance(v, torch.Tensor) else torch.as_tensor(np.array(v, dtype=np.float64, copy=True))
+                kept.append(None if t is None else t.to(device=self.device, dtype=self.dtype).contiguous().clone())
+        # the library first: it stores the pointers and reads nothing, and an environment it does not serve is refused by ITS name
+        # whatever the arrays look like; then the shapes, by name, with the pointers of before put back where one is wrong
+        _lib.check(self.lib.pdec_env_set_faults(self._h, *[_lib.ptr(t) for t in kept]))
+        want = (getattr(self.setup, "n_actuators", None), getattr(self.setup, "n_sensors", None), getattr(self.setup, "n_sensors", None))
+        for name, t, n in zip(names, kept, want):
+            if t is not None and tuple(t.shape) != (self.B, n):
+                _lib.check(self.lib.pdec_env_set_faults(self._h, *[_lib.ptr(t0) for t0 in before]))
+                raise _lib.PdecError(f"PDEenv.set_faults: {name} has shape {tuple(t.shape)}, expected ({self.B}, {n})")
+        self.actuator_gain, self.sensor_gain, self.sensor_bias = kept
+        if any(t is not None for t in kept + before):      # (healthy before and after: the reset image stands)
+            with _on_stream(self.stream):
+                _lib.check(self.lib.pdec_featurize(self._h, _lib.ptr(self.y0), None, _lib.ptr(self._state0)))
 
     # ---- T control steps without returning to the host (SURVEY.md §8f row F2)
     def rollout(self, actor, T, act_noise=0.0, act_limit=1.0, learning=False, seed=0, offset=0, log=False, control_from=0,

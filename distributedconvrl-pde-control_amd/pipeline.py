@@ -192,6 +192,14 @@ class TrainPipeline:
         noise_scale = [B] (host array or device tensor): trajectory b explores at noise_scale[b] in the place of the policy's
         act_noise -- see set_noise_scale.  None: the policy's scalar.
 
+        An environment that holds fault arrays (PDEenv.set_faults, called before the pipeline is made) needs no argument here:
+        the arrays are read by the kernels, so eager steps, recorded calls and captured graphs all step through them, writing
+        new values into them between two run() calls keeps the recorded steps and the graphs, the reset image of the episode
+        start is featurized through them and the per-trajectory episode clock re-featurizes a restarted trajectory through its
+        own sensor faults.  The evaluation environment (eval_every) is this pipeline's own and stays healthy.  (The flag-synchronised
+        single-trajectory step of run(..., device_episodes) has no fault-carrying form; run() orders such an environment's streams
+        with events.)
+
         episodes = "per_trajectory": every trajectory keeps its own episode clock on the device (csrc/episode_clock.hip;
         DESIGN.md 3.5).  One boundary call behind every env step ends the episode of trajectory b IN that step when its blow-up
         flag is raised or its clock reaches episode_steps: the row's transition is terminal, its return is logged, and the

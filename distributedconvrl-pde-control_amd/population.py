@@ -230,8 +230,21 @@ def act_members_tiles(C, maxw, itemsize):
     return tc, -(-int(C) // tc)
 
 
+FAULT_KEYS = ("actuator_gain", "sensor_gain", "sensor_bias")
+
+
+def fault_arrays(setup, scenario, index=0):
+    """one scenario of evaluate_actors(faults=...) as float64 arrays [A], [S], [S], missing keys healthy; shapes refused by name"""
+    if not hasattr(setup, "fault_scenario"):
+        raise _lib.PdecError(f"evaluate_actors(faults=...): {type(setup).__name__} has no actuator / sensor faults (KS setups only)")
+    extra = set(scenario) - set(FAULT_KEYS)
+    if extra:
+        raise _lib.PdecError(f"evaluate_actors: faults[{index}] has unknown keys {sorted(extra)}; a scenario holds {FAULT_KEYS}")
+    return setup.fault_scenario(**{k: scenario[k] for k in FAULT_KEYS if scenario.get(k) is not None})
+
+
 def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, dtype=torch.float64, stream=None, act_limit=1.0,
-                    log=False, device="cuda:0", mu=None, control_from=0):
+                    log=False, device="cuda:0", mu=None, control_from=0, faults=None):
     """One greedy evaluation episode of each of M actors (HipMLPs or approximators of ONE shape) from the same K initial fields:
     `y0` [K, ...] in the environment's memory layout, or -- None -- n_inits fields drawn once with env.random_init from the
     Philox stream (init_seed, 0).  `steps` defaults to one episode (te / dt + 1, as testrun).  The environment of
@@ -253,7 +266,14 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
     amplitude) -- and `control_from` = n0 leaves the first n0 steps uncontrolled and unrewarded (PDEenv.rollout).  The result
     then carries episode_reward [M, n_mu, K], reward_sum [M, n_mu, K, A], done_step [M, n_mu, K], score [M, n_mu] (the NaN rule
     per (member, amplitude)), mu (numpy) and order by the mean of score over the amplitudes (NaN if any of them is NaN); the
-    log rows are [T, M, n_mu, K, ...].  mu=None: the shapes above, setup.mu everywhere."""
+    log rows are [T, M, n_mu, K, ...].  mu=None: the shapes above, setup.mu everywhere.
+    Fault tolerance (KS setups): `faults`, a sequence of n_f scenarios as KSSetup.fault_scenario makes them (dicts of
+    actuator_gain [A], sensor_gain [S], sensor_bias [S]), evaluates every actor under every scenario on the same K fields, laid
+    out exactly as `mu` is: B = M * n_f * K, each (member, scenario) block its own entry of the actor table (PDEenv.set_faults on
+    the one environment, whose initial state is sensed through the faults).  The result carries episode_reward [M, n_f, K],
+    reward_sum [M, n_f, K, A], done_step [M, n_f, K], score [M, n_f], faults (the scenarios) and order by the mean score over the
+    scenarios with the NaN rule of the mu form; a block is bit for bit the call with that single scenario.  `faults` together
+    with `mu` is refused."""
     members = [_model(a) for a in actors]
     M = len(members)
     if M < 1:
@@ -261,7 +281,14 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
     mus = None if mu is None else [float(x) for x in np.asarray(mu, dtype=np.float64).reshape(-1)]
     if mus is not None and not mus:
         raise _lib.PdecError("evaluate_actors: mu is empty")
-    n_mu = 1 if mus is None else len(mus)
+    if faults is not None and mus is not None:
+        raise _lib.PdecError("evaluate_actors: faults together with mu is not served (one sweep per call)")
+    scen = None
+    if faults is not None:
+        scen = [fault_arrays(setup, f, i) for i, f in enumerate(faults)]
+        if not scen:
+            raise _lib.PdecError("evaluate_actors: faults is empty")
+    n_mu = len(scen) if scen is not None else (1 if mus is None else len(mus))      # blocks per member: amplitudes or scenarios
     control_from = int(control_from)
     models = [md for md in members for _ in range(n_mu)]       # one entry per (member, amplitude) block of K trajectories
     M_members, M = M, M * n_mu
@@ -288,6 +315,10 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
                          autoreset=False)
             if mus is not None:
                 env.set_disturbance(torch.tensor(mus, dtype=torch.float64).repeat_interleave(K).repeat(M_members))
+            if scen is not None:    # trajectory (m, f, k) carries scenario f; the initial state is sensed through it
+                env.set_faults(**{k: torch.as_tensor(np.stack([sc[k] for sc in scen])).repeat_interleave(K, dim=0).repeat(M_members, 1)
+                                  for k in FAULT_KEYS})
+                env.reset()
             if control_from:
                 _lib.check(env.lib.pdec_env_set_control_from(env.handle, control_from))
     B = M * K
@@ -334,6 +365,8 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
                 actor = md if (md.dtype == small.dtype and md.max_cols >= cols) else md.clone(dtype=small.dtype, max_cols=cols)
             if mus is not None:
                 small.set_disturbance(torch.full((K,), mus[v % n_mu], dtype=torch.float64))
+            if scen is not None:
+                small.set_faults(**{k: torch.as_tensor(scen[v % n_mu][k]).unsqueeze(0).repeat(K, 1) for k in FAULT_KEYS})
             small.reset()
             parts.append(small.rollout(actor, T, act_limit=act_limit, learning=False, log=log, control_from=control_from))
         with _on_stream(stream):
@@ -347,7 +380,7 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
                 res[k] = out[k].view((T, M, K) + tuple(out[k].shape[2:]))
         host = (res["episode_reward"].double().cpu().numpy(), res["done_step"].cpu().numpy())     # (waits for the stream)
     res["score"], res["order"] = score_members(*host)
-    if mus is not None:
+    if mus is not None or scen is not None:
         with _on_stream(stream):
             for k in ("reward_sum", "done_step", "episode_reward"):
                 res[k] = res[k].view((M_members, n_mu) + tuple(res[k].shape[1:]))
@@ -355,7 +388,10 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
                 if k in res:
                     res[k] = res[k].view((T, M_members, n_mu) + tuple(res[k].shape[2:]))
         res["score"] = res["score"].reshape(M_members, n_mu)
-        res["mu"] = np.asarray(mus, dtype=np.float64)
+        if mus is not None:
+            res["mu"] = np.asarray(mus, dtype=np.float64)
+        else:
+            res["faults"] = scen
         mean = res["score"].mean(axis=1)                  # NaN if any amplitude's score is
         res["order"] = sorted(range(M_members), key=lambda m: (bool(np.isnan(mean[m])), -mean[m] if not np.isnan(mean[m]) else 0.0, m))
     res["one_launch"], res["batched"] = one, batched

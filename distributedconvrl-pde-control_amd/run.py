@@ -260,10 +260,12 @@ def _episode_schedule(start, T, cols, na, capacity, stride, update_after, update
 
 
 def _launch_sync_ok(env):
-    """the fused fp64 KS step of one trajectory with 192 / 240 / 600 cells: the launch that honours pdec_set_launch_sync"""
+    """the fused fp64 KS step of one trajectory with 192 / 240 / 600 cells: the launch that honours pdec_set_launch_sync (its
+    fault-carrying form, PDEenv.set_faults, does not: such an environment hands over between the streams with events)"""
     s = env.setup
+    faults = any(getattr(env, k, None) is not None for k in ("actuator_gain", "sensor_gain", "sensor_bias"))
     return (getattr(s, "integrator", None) == "cnab2" and getattr(s, "nx", 0) in (192, 240, 600) and env.B == 1
-            and env.dtype == torch.float64 and not getattr(s, "memory_size", 0))
+            and env.dtype == torch.float64 and not getattr(s, "memory_size", 0) and not faults)
 
 
 def _step_glue(lib, pol, tr, env, logs, t, cols, A, acting, pending_rt, done_event=None):

@@ -171,6 +171,30 @@ class KSSetup:
         c.action_punish, c.delta_action_punish = self.action_punish, self.delta_action_punish
         return c
 
+    def fault_scenario(self, dead_actuators=(), dead_sensors=(), actuator_gain=None, sensor_gain=None, sensor_bias=None):
+        """One actuator / sensor fault scenario for PDEenv.set_faults and evaluate_actors(faults=[...]): a dict of float64 arrays
+        actuator_gain [A], sensor_gain [S], sensor_bias [S], healthy (1, 1, 0) where nothing is said.  The arrays given are the
+        base; dead_actuators / dead_sensors then zero the gains of the listed actuators / sensors, numbered from 1 as in
+        actuators_to_sensors (KSSetup.jl:113).  A dead sensor reads 0 + its bias."""
+        A, S = self.n_actuators, self.n_sensors
+        out = {}
+        for name, given, n, fill in (("actuator_gain", actuator_gain, A, 1.0), ("sensor_gain", sensor_gain, S, 1.0),
+                                     ("sensor_bias", sensor_bias, S, 0.0)):
+            if given is None:
+                out[name] = np.full(n, fill)
+                continue
+            a = np.array(given, dtype=np.float64, copy=True)
+            if a.shape != (n,):
+                raise _lib.PdecError(f"KSSetup.fault_scenario: {name} has shape {a.shape}, expected ({n},)")
+            out[name] = a
+        for name, dead, n, what in (("actuator_gain", dead_actuators, A, "dead_actuators"), ("sensor_gain", dead_sensors, S, "dead_sensors")):
+            idx = np.asarray(list(dead), dtype=np.int64).reshape(-1)
+            bad = idx[(idx < 1) | (idx > n)]
+            if len(bad):
+                raise _lib.PdecError(f"KSSetup.fault_scenario: {what} entry {int(bad[0])} is outside 1..{n} (numbered from 1)")
+            out[name][idx - 1] = 0.0
+        return out
+
     def tables(self):
         return (np.ascontiguousarray(self.gaussians, dtype=np.float64),
                 np.ascontiguousarray(self.gaussians_actuators, dtype=np.float64),

@@ -578,6 +578,26 @@ int pdec_env_set_member_layout(pdec_handle env, int on);
  * (KSglobalSetup.jl:167 has no such term), for 1-D and 2-D Keller-Segel and for the fluid.  The acting-only closures
  * (pdec_actuate, pdec_featurize, pdec_reward) do not depend on it. */
 int pdec_env_set_disturbance(pdec_handle env, const void* mu_per_trajectory);
+/* Fault-tolerance runs: per-trajectory actuator and sensor faults of the KS environments, read by the kernels the way the
+ * disturbance amplitude is.  Modifies the closures prepare_action and featurize (KSSetup.jl:190-245); reward_function and the
+ * blow-up test stay what they are.  Three device arrays of the environment's dtype, owned by the caller; each may be NULL
+ * (healthy), all NULL returns to the healthy environment.  The call stores the pointers and neither copies nor synchronises, so
+ * launches recorded or captured afterwards follow later writes to the arrays.
+ *   actuator_gain [B][A]: the forcing of trajectory b is synthesised from gain[b][a] * action[b][a] (0: dead, -1: reversed).
+ *     The commanded action is unchanged everywhere else: the reward's action_punish / delta_action_punish terms, action_prev,
+ *     the rollouts' action logs.  p_out and the p logs hold the forcing actually applied.
+ *   sensor_gain, sensor_bias [B][S]: featurize writes (gain[b][s] * dot_s + bias[b][s]) * sensor_scale for sensor s -- indexed
+ *     by the sensor, so a window row that reads a neighbouring sensor takes that sensor's fault; the bias is in units of the
+ *     field.  Rows copied from the previous state (temporal_steps > 1) keep their values.  The reward reads the true dots.
+ * The arrays belong to the batch slot, not to the episode: resets and the episode clock leave them alone, and the clock
+ * re-featurizes a restarted trajectory through its own sensor faults.  Ones and zeros give, bit for bit, the healthy run (on
+ * fields that are not identically zero: -0 * 1 + 0 is +0).
+ * Served for PDEC_PDE_KS_CNAB2 (fused step in both forms, member layout, persistent rollouts, with or without a disturbance
+ * array) and PDEC_PDE_KS_RK4_FD (both integrators), pdec_actuate and pdec_featurize, with per-actuator agents and
+ * memory_size = 0.  Refused for the global/mono agent, memory_size > 0, 1-D and 2-D Keller-Segel and the fluid.  The fault-carrying
+ * step has no synchronised form: pdec_env_step with a launch sync pending (pdec_set_launch_sync) and arrays set is refused by name;
+ * a caller that hands over between streams by device flags uses events for such an environment (run.py does). */
+int pdec_env_set_faults(pdec_handle env, const void* actuator_gain, const void* sensor_gain, const void* sensor_bias);
 /* Delayed control (src/plotting.jl:55-60, plot_heat(p_t_action = ...): uncontrolled until t = p_t_action, then the actor
  * engages), a sticky setting read by pdec_rollout and pdec_rollout_members in all their forms; n0 = 0 (the default) is off.
  * For the steps t < n0 the action is exactly zero -- no actor evaluation, no exploration noise -- and reward_sum adds only the

@@ -179,6 +179,12 @@ end
 function set_disturbance(h::UInt64, mu::Ptr{Cvoid})
     check(ccall((:pdec_env_set_disturbance, LIB), Cint, (UInt64, Ptr{Cvoid}), h, mu))
 end
+# per-trajectory actuator and sensor faults (pdec_env_set_faults): device arrays of the environment's dtype that the caller keeps
+# alive -- actuator_gain [B][A], sensor_gain [B][S], sensor_bias [B][S] -- each may be C_NULL (healthy), all C_NULL returns to the
+# healthy environment; the forcing comes from gain .* action, featurize writes (gain * dot + bias) * sensor_scale
+function set_faults(h::UInt64, actuator_gain::Ptr{Cvoid}, sensor_gain::Ptr{Cvoid}, sensor_bias::Ptr{Cvoid})
+    check(ccall((:pdec_env_set_faults, LIB), Cint, (UInt64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), h, actuator_gain, sensor_gain, sensor_bias))
+end
 function set_control_from(h::UInt64, n0::Integer)
     check(ccall((:pdec_env_set_control_from, LIB), Cint, (UInt64, Cint), h, n0))
 end
