@@ -131,6 +131,8 @@ SIGNATURES = {
     "pdec_ledger_eval_best_params": [Handle, Handle],
     "pdec_epclock_create": [C.POINTER(Handle), Handle, _i, _i, _i, _u64, _i, _i], "pdec_epclock_set": [Handle, _vp],
     "pdec_epclock_step": [Handle] + [_vp] * 9, "pdec_epclock_read": [Handle, _vp, _vp, _vp, _vp, _vp],
+    "pdec_nstep_create": [C.POINTER(Handle), _i, _i, _i, _i, _i],
+    "pdec_nstep_step": [Handle, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp], "pdec_nstep_read": [Handle, C.POINTER(_i64)] + [_vp] * 4,
     "pdec_capture_begin": [Handle], "pdec_capture_end": [Handle, C.POINTER(Handle)],
     "pdec_graph_launch": [Handle, _vp], "pdec_graph_num_nodes": [Handle, C.POINTER(_i)],
     "pdec_event_create": [C.POINTER(Handle)], "pdec_event_record": [Handle, _vp], "pdec_stream_wait_event": [_vp, Handle], "pdec_mlp_set_stop_event": [Handle, Handle], "pdec_mlp_flush_stop_event": [Handle],

@@ -390,12 +390,15 @@ class CustomDDPGPolicy:
             self._noise_off += (cols * na + 3) // 4
 
     # ---- update!(policy, batch) (src/PDEagent.jl:363-418), fused on the device
-    def update(self, batch, before_actor_half=None, interleave=1):
+    def update(self, batch, before_actor_half=None, interleave=1, gamma=None):
         """batch: dict(state [Bu,ns], action [Bu,na], reward [Bu], terminal [Bu], next_state [Bu,ns]).
         before_actor_half: optional callable run between the critic half and the actor half of the update
         (e.g. a stream wait on the event of a concurrent acting kernel that still reads the actor).
         interleave: the L of the reward groups (set_reward_interleave) -- A when the batch holds B trajectories x A
-        actuators as columns b A + a, 1 for a sampled minibatch."""
+        actuators as columns b A + a, 1 for a sampled minibatch.
+        gamma: the discount of this batch's bootstrap term in the place of self.y (None) -- the caller's product of n
+        factors self.y for a batch of n-step transitions (TrainPipeline.gamma_n)."""
+        y = float(self.y if gamma is None else gamma)
         self.set_reward_interleave(interleave)
         A, Cn, At, Ct = (self.behavior_actor.model, self.behavior_critic.model, self.target_actor.model,
                          self.target_critic.model)
@@ -410,18 +413,18 @@ class CustomDDPGPolicy:
             if before_actor_half is None:
                 _lib.check(self.lib.pdec_ddpg_update_async(
                     A.handle, Cn.handle, At.handle, Ct.handle, _lib.ptr(s), _lib.ptr(a), _lib.ptr(r), _lib.ptr(t),
-                    _lib.ptr(sn), Bu, float(self.y), self.rho_effective, int(self.quirk), float(oa.eta), float(oc.eta),
+                    _lib.ptr(sn), Bu, y, self.rho_effective, int(self.quirk), float(oa.eta), float(oc.eta),
                     C.c_void_p(L.data_ptr())))
                 return
             _lib.check(self.lib.pdec_ddpg_update_critic_async(
                 A.handle, Cn.handle, At.handle, Ct.handle, _lib.ptr(s), _lib.ptr(a), _lib.ptr(r), _lib.ptr(t),
-                _lib.ptr(sn), Bu, float(self.y), self.rho_effective, int(self.quirk), float(oc.eta), C.c_void_p(L.data_ptr())))
+                _lib.ptr(sn), Bu, y, self.rho_effective, int(self.quirk), float(oc.eta), C.c_void_p(L.data_ptr())))
             before_actor_half()
             _lib.check(self.lib.pdec_ddpg_update_actor_async(
                 A.handle, Cn.handle, At.handle, Ct.handle, _lib.ptr(s), Bu, self.rho_effective, float(oa.eta),
                 C.c_void_p(L.data_ptr())))
             return
-        self.update_critic_half(batch, interleave)
+        self.update_critic_half(batch, interleave, gamma)
         if before_actor_half is not None:
             before_actor_half()
         self.actor_grads(batch)
@@ -436,9 +439,10 @@ class CustomDDPGPolicy:
         self._batch_keepalive = arrs
         return arrs
 
-    def update_critic_half(self, batch, interleave=1):
+    def update_critic_half(self, batch, interleave=1, gamma=None):
         """critic pass + ADAM(C) + Polyak(Ct) (src/PDEagent.jl:385-400, :415-417 for the critic pair): the local fused form when
-        only the policy gradient is exchanged, gradient pass -> all-reduce -> apply launch otherwise"""
+        only the policy gradient is exchanged, gradient pass -> all-reduce -> apply launch otherwise.  gamma: as in update()"""
+        y = float(self.y if gamma is None else gamma)
         self.set_reward_interleave(interleave)
         A, Cn, At, Ct = (self.behavior_actor.model, self.behavior_critic.model, self.target_actor.model,
                          self.target_critic.model)
@@ -448,10 +452,10 @@ class CustomDDPGPolicy:
             # policy-gradient-only exchange: the critic half is the local fused form (no all-reduce)
             _lib.check(self.lib.pdec_ddpg_update_critic_async(
                 A.handle, Cn.handle, At.handle, Ct.handle, _lib.ptr(s), _lib.ptr(a), _lib.ptr(r), _lib.ptr(t),
-                _lib.ptr(sn), Bu, float(self.y), self.rho_effective, int(self.quirk), float(oc.eta), C.c_void_p(L.data_ptr())))
+                _lib.ptr(sn), Bu, y, self.rho_effective, int(self.quirk), float(oc.eta), C.c_void_p(L.data_ptr())))
             return
         _lib.check(self.lib.pdec_ddpg_critic_grads(A.handle, Cn.handle, At.handle, Ct.handle, _lib.ptr(s), _lib.ptr(a),
-                                                   _lib.ptr(r), _lib.ptr(t), _lib.ptr(sn), Bu, float(self.y),
+                                                   _lib.ptr(r), _lib.ptr(t), _lib.ptr(sn), Bu, y,
                                                    int(self.quirk), 1.0 / self.reducer.world_size, C.c_void_p(L.data_ptr())))
         self.reducer.all_reduce(Cn)
         # update!(critic) :400 fused with the critic's Polyak step :415-417 (independent of the actor)

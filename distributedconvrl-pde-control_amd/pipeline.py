@@ -57,7 +57,17 @@ sring[(k+1) % 6] -- ends the episode of every trajectory whose blow-up flag is r
 episode_steps, in that step: terminal row, log entry, restart field and its features, zero action_prev (a ring of two buffers the
 clock writes and the next env step reads).  The host schedules as for episode_steps = 0: only step 0 is a first step, there is no
 last step, every other step is interior -- the same launch sequence, recorded and captured.  The batch-mean reward of the reward
-broadcast is taken by pdec_reward_mean behind the clock, on the rows it has sanitised; the env step's reward partials are not armed."""
+broadcast is taken by pdec_reward_mean behind the clock, on the rows it has sanitised; the env step's reward partials are not armed.
+
+n-step transitions (opt-in, n_step = n > 1; csrc/nstep.hip): one more launch on the env stream, pdec_nstep_step, behind everything
+that writes the rows of step k -- pdec_env_step, the clock call, the ledger call, the last step's time-out fill -- and in front of
+pdec_reward_mean.  It stores (s_k, a_k, r_k, t_k) in a device ring of depth n and writes nbatch[k % 3]: per column the transition that
+starts at step u = k - n + 1 -- s_u, a_u, R = sum_{i <= m} gamma^i r_{u+i} up to the first terminal step u + m (m <= n - 1), T = 1 where
+there was one.  update_k trains on nbatch[(k - LAG) % 3] with next_state = sring[(k - LAG + 1) % 6] and the scalar gamma_n; a cut
+window has T = 1 and does not bootstrap, so one discount serves every column.  Every step emits cols transitions, each start once;
+transitions that start before the last restart are not consumed: the first update is at k - LAG >= _first_tick + n - 1.  pdec_reward_mean
+runs on the assembled reward and the env step's reward partials are not armed.  The ring position is a device counter, so recorded steps
+and graphs carry the call."""
 import ctypes as C
 import os
 
@@ -117,6 +127,21 @@ class _Clock:
             pass
 
 
+class _NStep:
+    """the n-step object of a pipeline (pdec_nstep_create) on the env stream, released with it"""
+
+    def __init__(self, lib, n, cols, ns, na, dtype, stream):
+        self.lib, self.h = lib, _lib.Handle()
+        _lib.check(lib.pdec_nstep_create(C.byref(self.h), int(n), int(cols), int(ns), int(na), _lib.dtype_code(dtype)))
+        _lib.check(lib.pdec_set_stream(self.h, C.c_void_p(stream.cuda_stream)))
+
+    def __del__(self):
+        try:
+            self.lib.pdec_destroy(self.h)
+        except Exception:
+            pass
+
+
 class _Ledger:
     """the episode ledger of a pipeline (pdec_ledger_create), released with it"""
 
@@ -153,7 +178,7 @@ class TrainPipeline:
                  chunks=(24, 6, 1), use_replay=False, noise_seed=1234, kick_env_after_critic=None, stream_ar=None,
                  ar_off_chain=None, log_episodes=0, min_best_episode=0, random_init=False, init_seed=0, init_rng=None,
                  init_rank=(0, 1), eval_every=0, eval_inits=8, eval_seed=0, eval_y0=None, eval_capacity=64, eval_stream=None,
-                 best_by="train", noise_scale=None, episodes="lockstep", stagger=False):
+                 best_by="train", noise_scale=None, episodes="lockstep", stagger=False, n_step=1):
         """env: PDEenv on `stream_env`; agent: create_agent(..., stream=stream_upd).  lag: the update of step k trains on
         the transition of step k - lag (>= 1).  episode_steps: lock-stepped episodes of that many control steps (0: one
         endless episode): the last transition is terminal (done = time >= te, src/PDEenv.jl:227) and the next step starts
@@ -213,7 +238,19 @@ class TrainPipeline:
         (finished_episodes(), episodes_finished); episode_returns() / rewards belong to the lock-stepped mode.  reset_from()
         sets every clock back to its initial value and drops the running returns.  The 1-D environments with per-actuator
         agents and memory_size = 0 only; not with use_replay, an active reducer, evaluations or best-actor tracking (score
-        actors with population.evaluate_actors between run() calls)."""
+        actors with population.evaluate_actors between run() calls).
+
+        n_step = n > 1 (1 .. 32): the update trains on n-step transitions assembled on the device (module docstring;
+        csrc/nstep.hip).  Step k emits, per column, the transition that starts at step k - n + 1: its state and action, the
+        discounted sum of the rewards up to its first terminal step (at most n of them), terminal = 1 where the window was cut by
+        one; the next state is the one-step batch's, sring[(k + 1) % 6].  update_k trains on the batch assembled at step k - lag
+        with gamma_n (policy.y multiplied n times) in the place of policy.y, so the first update after a restart is n - 1 steps
+        later than with n = 1.  pipe.n_step, pipe.gamma_n; pipe.nstep_batch(j): the batch assembled at step j.  Both episode
+        modes, every environment, the ledger, evaluations, noise_scale and a reducer are served; use_replay=True is refused
+        (the replay route pushes one-step rows).  n_step is run state of the pipeline: checkpoints do not store it.  n_step = 1
+        builds nothing and issues the launches it always did."""
+        self._check_n_step(n_step, use_replay)
+        self.n_step = int(n_step)
         # pdec_policy_act_rng_dev reads the state ring in the actor's type: a fluid environment of another dtype cannot step.
         # Refused by name at the first run() / capture(), not here: an object of that combination may be constructed and asked
         # for its episode-start draw (tests/test_gpu_pipeline_episodes.py::test_random_inits_fluid does).
@@ -279,6 +316,13 @@ class TrainPipeline:
             # per-trajectory episodes: action_prev of step k, written by the clock of step k - 1 (the action ring slot is the
             # transition's action and keeps its values where a trajectory restarts)
             self.aprev = [torch.zeros(env._ashape, **kw) for _ in range(2)] if self.per_traj else None
+            # n-step transitions: the batch assembled behind env step k (state, action, reward, terminal of the window that
+            # starts at step k - n + 1), a ring of three like the one-step rows it replaces in the update
+            self.nstep, self.nbatch = None, None
+            if self.n_step > 1:
+                self.nstep = _NStep(self.lib, self.n_step, self.cols, self.ns, self.na, dt, self.s_env)
+                self.nbatch = [dict(state=torch.zeros((self.cols, self.ns), **kw), action=torch.zeros((self.cols, self.na), **kw),
+                                    reward=torch.zeros(self.cols, **kw), terminal=torch.zeros(self.cols, **kw)) for _ in range(3)]
         # the reference's reward broadcast (quirk) needs the batch-mean reward: reduced on the env stream
         # right behind the env step instead of by every workgroup of the critic pass
         # (not with reward groups: the critic call reduces the group means itself, CustomDDPGPolicy.reward_group)
@@ -289,9 +333,10 @@ class TrainPipeline:
         # ... and for the fused KS step + 3-layer fused critic without any extra launch: the env step leaves one reward sum
         # per workgroup, the critic pass adds them
         # (per-trajectory episodes: the partials are summed before the clock sanitises the rows of blown-up trajectories and
-        # cannot be corrected afterwards -- the mean is taken by pdec_reward_mean behind the clock)
+        # cannot be corrected afterwards -- the mean is taken by pdec_reward_mean behind the clock; n-step transitions: the
+        # reward of the batch is the assembled one, whose mean pdec_reward_mean takes behind the n-step call)
         self.rpart, self.n_rpart = None, 0
-        if self.pre_rbar and not self.per_traj:
+        if self.pre_rbar and not self.per_traj and self.n_step == 1:
             npart = C.c_int()
             probe = torch.zeros(B, dtype=torch.float32, device=dev)
             ok = self.lib.pdec_env_set_reward_partials_out(env.handle, _lib.ptr(probe), C.byref(npart)) == 0
@@ -372,6 +417,15 @@ class TrainPipeline:
         self._setup_eval(eval_every, eval_inits, eval_seed, eval_y0, eval_capacity, eval_stream, best_by, Ev)
         self.reset_from(env.y0)
         self._keep_y0 = False
+
+    @staticmethod
+    def _check_n_step(n_step, use_replay):
+        """the refusals of n_step, by name, before anything is allocated"""
+        if isinstance(n_step, bool) or not isinstance(n_step, (int, np.integer)) or not 1 <= int(n_step) <= 32:
+            raise _lib.PdecError(f"TrainPipeline(n_step={n_step!r}): an integer from 1 to 32")
+        if int(n_step) > 1 and use_replay:
+            raise _lib.PdecError(f"TrainPipeline(n_step={int(n_step)}): use_replay=True is not covered (the replay route pushes "
+                                 "one-step rows)")
 
     @staticmethod
     def _check_episode_mode(env, agent, episodes, stagger, episode_steps, use_replay, eval_every, min_best_episode, best_by):
@@ -687,7 +741,7 @@ class TrainPipeline:
         # one stream + the collective off the chain: act_k needs ADAM(actor)_{k-1}, which waits for the all-reduce on the side
         # stream -- so the critic half of update_k, which needs neither, goes first and hides it (two streams: the critic half is
         # on the other stream anyway)
-        late_env = self.serial and self.ar_off_chain and j >= self._first_tick and not self.use_replay
+        late_env = self.serial and self.ar_off_chain and j >= self._first_update and not self.use_replay
         if not late_env:
             act_part()
 
@@ -712,8 +766,15 @@ class TrainPipeline:
                         L.check(lib.pdec_ledger_close(self.ledger.h, self.n_episodes, self.min_best_episode,
                                                       int(self.track_best)))
                         self.n_episodes += 1
+                rew_batch = rew
+                if self.nstep is not None:
+                    # the transition that starts at step k - n + 1, from the rows as the calls above have left them
+                    nb = self.nbatch[k % 3]
+                    rew_batch = nb["reward"]
+                    L.check(lib.pdec_nstep_step(self.nstep.h, L.ptr(s_in), L.ptr(act), L.ptr(rew), L.ptr(term), float(pol.y),
+                                                L.ptr(nb["state"]), L.ptr(nb["action"]), L.ptr(rew_batch), L.ptr(nb["terminal"])))
                 if self.pre_rbar and self.rpart is None:
-                    L.check(lib.pdec_reward_mean(env.handle, L.ptr(rew), self.cols, L.ptr(self.rbar[k % 3])))
+                    L.check(lib.pdec_reward_mean(env.handle, L.ptr(rew_batch), self.cols, L.ptr(self.rbar[k % 3])))
                 if self.use_replay:
                     # a host function with step-dependent ring positions: re-evaluated, not replayed verbatim (_Lib.note)
                     lib.note(self._replay_push, self.ev_push[k % 2], s_in, act, rew, term, s_out, first, last)
@@ -729,11 +790,13 @@ class TrainPipeline:
                 torch.cuda.synchronize()
 
         batch = None
-        if j >= self._first_tick:
+        if j >= self._first_update:
             if self.use_replay:
                 with torch.cuda.stream(self.s_upd):
                     lib.note(self._replay_sample, self.ev_push[(k - 1) % 2] if (not self.serial and k > 0) else None)
                 batch = self._batch_cur
+            elif self.nstep is not None:
+                batch = dict(self.nbatch[j % 3], next_state=self.sring[(j + 1) % PERIOD].view(self.cols, self.ns))
             else:
                 batch = dict(state=self.sring[j % PERIOD].view(self.cols, self.ns), action=self.aring[j % 3].view(self.cols, self.na),
                              reward=self.rring[j % 3].view(self.cols), terminal=self.tring[j % 3].view(self.cols),
@@ -789,9 +852,9 @@ class TrainPipeline:
                 if self.ar_off_chain:
                     self._update_ar_off_chain(k, batch, between_halves, use_stop)
                 elif kick or (self.act_in_place and not self.serial):
-                    pol.update(batch, before_actor_half=between_halves, interleave=self.reward_interleave)
+                    pol.update(batch, before_actor_half=between_halves, interleave=self.reward_interleave, gamma=self._gamma_arg)
                 else:
-                    pol.update(batch, interleave=self.reward_interleave)
+                    pol.update(batch, interleave=self.reward_interleave, gamma=self._gamma_arg)
             if self.ar_off_chain and batch is not None:
                 pass                                    # (the completion event was recorded on the side stream)
             elif use_stop:
@@ -809,7 +872,7 @@ class TrainPipeline:
         next acting kernel (env stream) and the next actor pass (update stream) wait for."""
         pol, lib, L = self.policy, self.lib, _lib
         A, At = pol.behavior_actor.model, pol.target_actor.model
-        pol.update_critic_half(batch, self.reward_interleave)
+        pol.update_critic_half(batch, self.reward_interleave, self._gamma_arg)
         between_halves()
         red_on_launch = use_stop and lib.pdec_mlp_set_reduce_event(A.handle, self.ev_red.h) == 0
         pol.actor_grads(batch)                                      # (records a reduce event its launches did not carry)
@@ -834,6 +897,36 @@ class TrainPipeline:
     _mid_wait_prev = False    # update_{k-1} waited for env_{k-2} between its halves (so step k needs no wait at its top)
     drain_between = False
     per_traj = False          # episodes="per_trajectory"
+    n_step = 1
+    nstep = None              # the n-step object (n_step > 1)
+
+    @property
+    def _first_update(self):
+        """the first transition after the last restart that an update may train on: the n-step window that ends at step j starts
+        at j - n + 1, which must not precede the restart"""
+        return self._first_tick + self.n_step - 1
+
+    @property
+    def gamma_n(self):
+        """w_n of w_0 = 1, w_{i+1} = w_i policy.y: the discount of a full n-step window's bootstrap term, the product the
+        assembling kernel forms"""
+        w = 1.0
+        for _ in range(self.n_step):
+            w = w * float(self.policy.y)
+        return w
+
+    @property
+    def _gamma_arg(self):
+        return None if self.n_step == 1 else self.gamma_n
+
+    def nstep_batch(self, j):
+        """(state [cols, ns], action [cols, na], reward [cols], terminal [cols], next_state [cols, ns]) of the batch assembled at
+        step j -- the transitions that start at step j - n_step + 1 -- as the device holds them (the ring of three: valid until
+        step j + 3 is issued; the caller synchronises).  For tests and probes."""
+        if self.nstep is None:
+            raise _lib.PdecError("TrainPipeline.nstep_batch: n_step = 1 assembles nothing (the update reads the ring slots)")
+        nb = self.nbatch[j % 3]
+        return nb["state"], nb["action"], nb["reward"], nb["terminal"], self.sring[(j + 1) % PERIOD].view(self.cols, self.ns)
 
     @property
     def _E_host(self):
@@ -913,7 +1006,7 @@ class TrainPipeline:
         if self._E_host > 0:
             assert self.E > 2 * PERIOD, "episodes must be longer than two graph periods"
             self.chunks = tuple(c for c in self.chunks if c <= self.E - 2)
-        while self.tick - self.LAG < self._first_tick + 2:      # lazily created buffers / first-use uploads happen eagerly
+        while self.tick - self.LAG < self._first_update + 2:      # lazily created buffers / first-use uploads happen eagerly
             self._eager()
         self._key = self._scalar_key()
         for c in self.chunks:
@@ -946,7 +1039,7 @@ class TrainPipeline:
         E = self._E_host
         if E <= 0:
             return True
-        t0 = max(self.tick, self._first_tick + self.LAG)
+        t0 = max(self.tick, self._first_update + self.LAG)
         return any(t % PERIOD == pos and self._interior(t, c) for t in range(t0, t0 + PERIOD * E + PERIOD))
 
     def set_noise_scale(self, values):
@@ -994,7 +1087,7 @@ class TrainPipeline:
 
     def _interior(self, k, n):
         """steps k .. k+n-1 are neither the first nor the last of an episode (those run eagerly)"""
-        if k - self.LAG < self._first_tick:
+        if k - self.LAG < self._first_update:
             return False
         e, E = k - self.ep_start, self._E_host
         if E <= 0:

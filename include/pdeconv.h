@@ -766,6 +766,33 @@ int pdec_epclock_step(pdec_handle clock, void* reward, const int32_t* flags, voi
  * bit and the 1-based number of the pdec_epclock_step call that ended it */
 int pdec_epclock_read(pdec_handle clock, int64_t* counts, double* returns, int32_t* lengths, int32_t* blew_up, int64_t* end_steps);
 
+/* ---------------------------------------------------------------- n-step transitions, assembled on the device */
+/* An object that keeps the last n_step rows of a batched control loop -- state [cols][ns], action [cols][na], reward [cols],
+ * terminal [cols] in `dtype` (PDEC_F32 / PDEC_F64) -- on its own stream (pdec_set_stream).  1 <= n_step <= 32.  It knows no
+ * environment: it reads the rows it is handed.  Released with pdec_destroy. */
+int pdec_nstep_create(pdec_handle* nstep, int n_step, int cols, int ns, int na, int dtype);
+/* Call number k (0-based) stores the row (s_in, action, reward, terminal) of step k and emits, per column c, the transition
+ * that STARTS at step u = k - n + 1 (n = n_step):
+ *   m             = the smallest i in [0, n-1] with terminal_{u+i}[c] != 0, or n - 1 if there is none
+ *   reward_out[c] = sum_{i=0..m} w_i reward_{u+i}[c],  w_0 = 1, w_{i+1} = w_i gamma: in double, summed in index order without
+ *                   FMA contraction, rounded once to dtype
+ *   terminal_out[c] = 1 if terminal_{u+m}[c] != 0 else 0
+ *   state_out[c]  = s_in_u[c],  action_out[c] = action_u[c]
+ * The next state of that transition is the caller's own: the state that followed step k.  A window cut short by a terminal has
+ * terminal_out = 1, so its bootstrap term gamma (1 - terminal) q' vanishes whatever the discount; every window that bootstraps
+ * is full, and the update of the emitted batch takes the scalar w_n (the same repeated product) in the place of gamma for every
+ * column.  Every call emits cols transitions, each transition start exactly once; the first n - 1 calls emit windows that reach
+ * back before call 0 (rows of zeros) and are the caller's to ignore.  A non-finite reward reaches exactly the windows that hold
+ * it at an index <= m.
+ * One launch on the object's stream, one thread per element, every access coalesced along the columns; the ring position is a
+ * device counter (read by pdec_nstep_read), so the arguments do not depend on k and the call can be part of a recorded step or a
+ * captured graph.  No output may alias an input. */
+int pdec_nstep_step(pdec_handle nstep, const void* s_in, const void* action, const void* reward, const void* terminal, double gamma,
+                    void* state_out, void* action_out, void* reward_out, void* terminal_out);
+/* host accessor (synchronises the object's stream; any pointer may be NULL): position = calls so far -- call k wrote ring slot
+ * k mod n_step --, and the rings states [n_step][cols][ns], actions [n_step][cols][na], rewards / terminals [n_step][cols] */
+int pdec_nstep_read(pdec_handle nstep, int64_t* position, void* states, void* actions, void* rewards, void* terminals);
+
 /* ---------------------------------------------------------------- HIP graphs -- */
 /* Record everything enqueued on the stream of `origin` (pdec_set_stream; not the null stream) -- library calls, and any
  * other stream that forks from it and joins it again through events -- between _begin and _end into one HIP graph;
