@@ -133,6 +133,9 @@ SIGNATURES = {
     "pdec_epclock_step": [Handle] + [_vp] * 9, "pdec_epclock_read": [Handle, _vp, _vp, _vp, _vp, _vp],
     "pdec_nstep_create": [C.POINTER(Handle), _i, _i, _i, _i, _i],
     "pdec_nstep_step": [Handle, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp], "pdec_nstep_read": [Handle, C.POINTER(_i64)] + [_vp] * 4,
+    "pdec_telemetry_create": [C.POINTER(Handle), _i, _i, _i, _i, _i, _i, Handle, Handle],
+    "pdec_telemetry_step": [Handle, _vp, _vp, _vp, _vp, _vp, _d], "pdec_telemetry_update": [Handle] * 5 + [_vp],
+    "pdec_telemetry_read": [Handle, _vp, C.POINTER(_i64), _vp, C.POINTER(_i64), _vp], "pdec_telemetry_reset": [Handle],
     "pdec_capture_begin": [Handle], "pdec_capture_end": [Handle, C.POINTER(Handle)],
     "pdec_graph_launch": [Handle, _vp], "pdec_graph_num_nodes": [Handle, C.POINTER(_i)],
     "pdec_event_create": [C.POINTER(Handle)], "pdec_event_record": [Handle, _vp], "pdec_stream_wait_event": [_vp, Handle], "pdec_mlp_set_stop_event": [Handle, Handle], "pdec_mlp_flush_stop_event": [Handle],

@@ -38,7 +38,7 @@ void set_error(const char* fmt, ...);
     }                                  \
   } while (0)
 
-enum class Kind { Env, Mlp, Comm, Graph, Event, Ledger, Population, EpisodeClock, NStep };
+enum class Kind { Env, Mlp, Comm, Graph, Event, Ledger, Population, EpisodeClock, NStep, Telemetry };
 
 struct ProfEntry {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;

@@ -67,7 +67,19 @@ there was one.  update_k trains on nbatch[(k - LAG) % 3] with next_state = sring
 window has T = 1 and does not bootstrap, so one discount serves every column.  Every step emits cols transitions, each start once;
 transitions that start before the last restart are not consumed: the first update is at k - LAG >= _first_tick + n - 1.  pdec_reward_mean
 runs on the assembled reward and the env step's reward partials are not armed.  The ring position is a device counter, so recorded steps
-and graphs carry the call."""
+and graphs carry the call.
+
+Telemetry (opt-in, telemetry = N > 0; csrc/telemetry.hip): two more launches, each reducing what its stream has just written to one row
+of doubles in a device ring of N rows.  pdec_telemetry_step sits on the env stream behind the n-step call -- behind everything step k
+puts there -- and reads sring[(k+1) % 6], aring / rring / tring / fring[k % 3] as those calls leave them: reward mean / min / max,
+action mean and saturation, the largest state entry, blown-up and terminal counts, non-finite counts.  pdec_telemetry_update sits on
+the update stream behind the last launch of update_k (in front of the event act_{k+1} waits for where that event is a record; where it
+rides on the update's own launch, an event of its own behind the telemetry launch orders it before the next chunk graph)
+and reads the four networks' flat parameters and the loss pair: both losses, sum theta^2, the squared distance to the targets and to
+the parameters at the previous call, the largest entry, non-finite counts.  It is issued at the updating steps with k % telemetry_every
+== 0; telemetry_every divides the ring period, so a ring phase always holds the same calls.  The row counters live on the device and
+are advanced by the one thread that writes the row, so no argument depends on the step and recorded steps and graphs carry both calls.
+Nothing is read back until pipe.telemetry()."""
 import ctypes as C
 import os
 
@@ -142,6 +154,30 @@ class _NStep:
             pass
 
 
+class _Telemetry:
+    """the telemetry object of a pipeline (pdec_telemetry_create), its step launch on the env stream, released with it"""
+
+    def __init__(self, lib, capacity, B, cols, ns, na, dtype, actor_handle, critic_handle, stream):
+        self.lib, self.h = lib, _lib.Handle()
+        _lib.check(lib.pdec_telemetry_create(C.byref(self.h), int(capacity), int(B), int(cols), int(ns), int(na),
+                                             _lib.dtype_code(dtype), actor_handle, critic_handle))
+        _lib.check(lib.pdec_set_stream(self.h, C.c_void_p(stream.cuda_stream)))
+
+    def __del__(self):
+        try:
+            self.lib.pdec_destroy(self.h)
+        except Exception:
+            pass
+
+
+# the columns of a telemetry row, in the device's order (csrc/telemetry.hip)
+TELEMETRY_STEP_COLUMNS = ("step", "reward_mean", "reward_min", "reward_max", "reward_nonfinite", "action_mean", "action_abs_mean",
+                          "action_saturated", "state_abs_max", "state_nonfinite", "blown_up", "terminal")
+TELEMETRY_UPDATE_COLUMNS = ("update", "critic_loss", "actor_loss", "actor_norm2", "critic_norm2", "actor_target_dist2",
+                            "critic_target_dist2", "actor_step2", "critic_step2", "actor_abs_max", "critic_abs_max",
+                            "actor_nonfinite", "critic_nonfinite")
+
+
 class _Ledger:
     """the episode ledger of a pipeline (pdec_ledger_create), released with it"""
 
@@ -178,7 +214,8 @@ class TrainPipeline:
                  chunks=(24, 6, 1), use_replay=False, noise_seed=1234, kick_env_after_critic=None, stream_ar=None,
                  ar_off_chain=None, log_episodes=0, min_best_episode=0, random_init=False, init_seed=0, init_rng=None,
                  init_rank=(0, 1), eval_every=0, eval_inits=8, eval_seed=0, eval_y0=None, eval_capacity=64, eval_stream=None,
-                 best_by="train", noise_scale=None, episodes="lockstep", stagger=False, n_step=1):
+                 best_by="train", noise_scale=None, episodes="lockstep", stagger=False, n_step=1,
+                 telemetry=0, telemetry_every=1):
         """env: PDEenv on `stream_env`; agent: create_agent(..., stream=stream_upd).  lag: the update of step k trains on
         the transition of step k - lag (>= 1).  episode_steps: lock-stepped episodes of that many control steps (0: one
         endless episode): the last transition is terminal (done = time >= te, src/PDEenv.jl:227) and the next step starts
@@ -248,9 +285,26 @@ class TrainPipeline:
         later than with n = 1.  pipe.n_step, pipe.gamma_n; pipe.nstep_batch(j): the batch assembled at step j.  Both episode
         modes, every environment, the ledger, evaluations, noise_scale and a reducer are served; use_replay=True is refused
         (the replay route pushes one-step rows).  n_step is run state of the pipeline: checkpoints do not store it.  n_step = 1
-        builds nothing and issues the launches it always did."""
+        builds nothing and issues the launches it always did.
+
+        telemetry = N > 0: per-step training telemetry kept on the device (module docstring; csrc/telemetry.hip), the last N rows
+        of each of two rings.  One row per control step -- step, reward_mean / _min / _max over the finite rewards and
+        reward_nonfinite, action_mean / action_abs_mean over the driving row of every action column and action_saturated (columns
+        with |a| >= policy.act_limit), state_abs_max, state_nonfinite, blown_up (trajectories), terminal (columns) -- and one row
+        per recorded update -- update, critic_loss, actor_loss (- mean Q), and per network norm2 = sum theta^2, target_dist2 =
+        sum (theta - theta_target)^2, step2 = sum (theta - theta_prev)^2, abs_max, nonfinite.  telemetry_every = m in {1, 2, 3, 6}:
+        the update row is written at the updating steps k with k % m == 0 only (the update stream is the critical chain of the
+        two-stream step); theta_prev is the parameters at the previous RECORDED update, so *_step2 then spans m updates (0 in the
+        first row).  The step row is written at every step.  pipe.telemetry() synchronises and returns the rows;
+        pipe.telemetry_reset() clears them; reset_from() leaves them alone and `step` keeps counting control steps.  Both episode
+        modes, every environment, n_step, noise_scale, the ledger, evaluations and use_replay are served.  An active reducer is
+        refused: the actor's apply runs on a side stream beside the next critic half there, and no point of one stream sees a
+        consistent parameter set.  It is run state of the pipeline: checkpoints do not store it.  telemetry = 0 builds nothing and
+        issues the launches it always did."""
         self._check_n_step(n_step, use_replay)
         self.n_step = int(n_step)
+        self._check_telemetry(telemetry, telemetry_every, agent.policy.reducer)
+        self.telemetry_capacity, self.telemetry_every = int(telemetry), int(telemetry_every)
         # pdec_policy_act_rng_dev reads the state ring in the actor's type: a fluid environment of another dtype cannot step.
         # Refused by name at the first run() / capture(), not here: an object of that combination may be constructed and asked
         # for its episode-start draw (tests/test_gpu_pipeline_episodes.py::test_random_inits_fluid does).
@@ -323,6 +377,13 @@ class TrainPipeline:
                 self.nstep = _NStep(self.lib, self.n_step, self.cols, self.ns, self.na, dt, self.s_env)
                 self.nbatch = [dict(state=torch.zeros((self.cols, self.ns), **kw), action=torch.zeros((self.cols, self.na), **kw),
                                     reward=torch.zeros(self.cols, **kw), terminal=torch.zeros(self.cols, **kw)) for _ in range(3)]
+            self._telem = None
+            if self.telemetry_capacity > 0:
+                pol = self.policy
+                self._telem = _Telemetry(self.lib, self.telemetry_capacity, B, self.cols, self.ns, self.na, dt,
+                                         pol.behavior_actor.model.handle, pol.behavior_critic.model.handle, self.s_env)
+                self._telem_nets = tuple(n.model.handle for n in (pol.behavior_actor, pol.behavior_critic, pol.target_actor,
+                                                                  pol.target_critic))
         # the reference's reward broadcast (quirk) needs the batch-mean reward: reduced on the env stream
         # right behind the env step instead of by every workgroup of the critic pass
         # (not with reward groups: the critic call reduces the group means itself, CustomDDPGPolicy.reward_group)
@@ -358,6 +419,7 @@ class TrainPipeline:
         self.ev_samp = Ev(self.lib)                                 # replay sample of update_k done (update stream)
         self.ev_red = Ev(self.lib)                                  # actor gradient of update_k reduced (update stream) -> side stream
         self.ev_env = [Ev(self.lib), Ev(self.lib)]                  # env_k done (env stream; collective off the chain only)
+        self.ev_tel = Ev(self.lib)                                  # telemetry launch behind update_k done (update stream, see _issue)
         # collective off the chain, two streams, LAG >= 2: both cross-stream waits of the update stream sit between the halves
         # of an update (between_halves) instead of one there and one at the top of the step
         self._mid_waits = self.ar_off_chain and not self.serial and self.LAG >= 2 and not self.use_replay
@@ -426,6 +488,21 @@ class TrainPipeline:
         if int(n_step) > 1 and use_replay:
             raise _lib.PdecError(f"TrainPipeline(n_step={int(n_step)}): use_replay=True is not covered (the replay route pushes "
                                  "one-step rows)")
+
+    @staticmethod
+    def _check_telemetry(telemetry, telemetry_every, reducer):
+        """the refusals of telemetry / telemetry_every, by name, before anything is allocated"""
+        def integer(v):
+            return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+        if not integer(telemetry) or int(telemetry) < 0:
+            raise _lib.PdecError(f"TrainPipeline(telemetry={telemetry!r}): an integer >= 0, the ring capacity in rows")
+        if not integer(telemetry_every) or int(telemetry_every) not in (1, 2, 3, 6):
+            raise _lib.PdecError(f"TrainPipeline(telemetry_every={telemetry_every!r}): one of 1, 2, 3, 6 (a divisor of the ring "
+                                 "period, so that a ring phase always holds the same calls)")
+        if int(telemetry) > 0 and reducer is not None and reducer.active:
+            raise _lib.PdecError(f"TrainPipeline(telemetry={int(telemetry)}): not available with an active reducer (the actor's "
+                                 "apply may run on a side stream beside the next critic half: no point of one stream sees a "
+                                 "consistent parameter set)")
 
     @staticmethod
     def _check_episode_mode(env, agent, episodes, stagger, episode_steps, use_replay, eval_every, min_best_episode, best_by):
@@ -773,6 +850,10 @@ class TrainPipeline:
                     rew_batch = nb["reward"]
                     L.check(lib.pdec_nstep_step(self.nstep.h, L.ptr(s_in), L.ptr(act), L.ptr(rew), L.ptr(term), float(pol.y),
                                                 L.ptr(nb["state"]), L.ptr(nb["action"]), L.ptr(rew_batch), L.ptr(nb["terminal"])))
+                if self._telem is not None:
+                    # one row of facts about step k's own rows (not the assembled batch), as the calls above have left them
+                    L.check(lib.pdec_telemetry_step(self._telem.h, L.ptr(s_out), L.ptr(act), L.ptr(rew), L.ptr(term), L.ptr(flags),
+                                                    float(pol.act_limit)))
                 if self.pre_rbar and self.rpart is None:
                     L.check(lib.pdec_reward_mean(env.handle, L.ptr(rew_batch), self.cols, L.ptr(self.rbar[k % 3])))
                 if self.use_replay:
@@ -855,6 +936,15 @@ class TrainPipeline:
                     pol.update(batch, before_actor_half=between_halves, interleave=self.reward_interleave, gamma=self._gamma_arg)
                 else:
                     pol.update(batch, interleave=self.reward_interleave, gamma=self._gamma_arg)
+                if self._telem is not None and k % self.telemetry_every == 0:
+                    # behind the last launch of update_k: the parameters and losses it leaves (a captured chunk joins through the
+                    # event recorded below, so the call stays in front of it)
+                    L.check(lib.pdec_telemetry_update(self._telem.h, *self._telem_nets, L.ptr(pol._losses)))
+                    if use_stop:
+                        # ev_upd[k % 2] rides on the update's own last launch and does not cover this one: a chunk graph launched
+                        # on the env stream next -- whose update branch rewrites what this launch reads and shares its ticket,
+                        # partials and counter -- waits for this event as well (_sync_streams_for_graph)
+                        self.ev_tel.record(self.s_upd)
             if self.ar_off_chain and batch is not None:
                 pass                                    # (the completion event was recorded on the side stream)
             elif use_stop:
@@ -899,6 +989,8 @@ class TrainPipeline:
     per_traj = False          # episodes="per_trajectory"
     n_step = 1
     nstep = None              # the n-step object (n_step > 1)
+    telemetry_capacity, telemetry_every = 0, 1
+    _telem = None             # the telemetry object (telemetry > 0)
 
     @property
     def _first_update(self):
@@ -1126,6 +1218,10 @@ class TrainPipeline:
         """a graph runs wholly on the env stream: order the eager update still queued on the update stream before it"""
         if not self.serial and not self._after_graph and self.tick > 0:
             self.ev_upd[(self.tick - 1) % 2].wait(self.s_env)
+            if self._telem is not None and self.stop_events:
+                # the last telemetry launch behind an eager update is not covered by ev_upd where that event rode on the update's
+                # own launch (a wait for an event never recorded, or recorded steps ago, is satisfied at once)
+                self.ev_tel.wait(self.s_env)
 
     def _launch(self, h):
         _lib.check(self.lib.pdec_graph_launch(h, self._sp_env))
@@ -1288,6 +1384,43 @@ class TrainPipeline:
             _lib.check(self.lib.pdec_ledger_best_params(self.ledger.h, out.handle))
         import copy
         return CustomNeuralNetworkApproximator(out, copy.copy(A.optimizer))
+
+    # ------------------------------------------------------------------ telemetry (host accessors: synchronise)
+    @staticmethod
+    def _telemetry_rows(rows, calls, columns):
+        """(name -> column of the last min(calls, N) rows of a ring of N, oldest first; how many earlier rows were overwritten)"""
+        N = rows.shape[0]
+        n = min(int(calls), N)
+        order = [c % N for c in range(int(calls) - n, int(calls))]
+        kept = rows[order]
+        return {name: kept[:, i].copy() for i, name in enumerate(columns)}, int(calls) - n
+
+    def telemetry(self):
+        """the telemetry rings (TrainPipeline(telemetry=N)) as a dict: step and update -- name -> float64 array, the last
+        min(calls, N) rows oldest first, columns TELEMETRY_STEP_COLUMNS / TELEMETRY_UPDATE_COLUMNS, counts as doubles; step also holds
+        action_saturated_fraction = action_saturated / columns, divided here on the host --, dropped_steps / dropped_updates: rows
+        the rings have overwritten, first_nonfinite_step / first_nonfinite_update: the `step` / `update` value of the first row
+        with a non-finite reward or state entry / loss or parameter since construction or telemetry_reset(), None when there was
+        none (sticky: later clean rows do not clear it).  Synchronises the env and the update stream."""
+        if self._telem is None:
+            raise _lib.PdecError("TrainPipeline.telemetry: telemetry is off (telemetry=0)")
+        N = self.telemetry_capacity
+        srows, urows = np.empty((N, len(TELEMETRY_STEP_COLUMNS))), np.empty((N, len(TELEMETRY_UPDATE_COLUMNS)))
+        ns, nu, sent = C.c_int64(), C.c_int64(), np.empty(2, dtype=np.int64)
+        _lib.check(self.lib.pdec_telemetry_read(self._telem.h, _lib.ptr(srows), C.byref(ns), _lib.ptr(urows), C.byref(nu),
+                                                _lib.ptr(sent)))
+        step, ds = self._telemetry_rows(srows, ns.value, TELEMETRY_STEP_COLUMNS)
+        upd, du = self._telemetry_rows(urows, nu.value, TELEMETRY_UPDATE_COLUMNS)
+        step["action_saturated_fraction"] = step["action_saturated"] / float(self.cols)
+        return dict(step=step, update=upd, dropped_steps=ds, dropped_updates=du,
+                    first_nonfinite_step=None if sent[0] < 0 else int(sent[0]),
+                    first_nonfinite_update=None if sent[1] < 0 else int(sent[1]))
+
+    def telemetry_reset(self):
+        """clear the telemetry rings, their counters, the sentinel and theta_prev (synchronises the env and the update stream)"""
+        if self._telem is None:
+            raise _lib.PdecError("TrainPipeline.telemetry_reset: telemetry is off (telemetry=0)")
+        _lib.check(self.lib.pdec_telemetry_reset(self._telem.h))
 
     def sync(self):
         self.s_env.synchronize()

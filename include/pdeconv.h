@@ -793,6 +793,42 @@ int pdec_nstep_step(pdec_handle nstep, const void* s_in, const void* action, con
  * k mod n_step --, and the rings states [n_step][cols][ns], actions [n_step][cols][na], rewards / terminals [n_step][cols] */
 int pdec_nstep_read(pdec_handle nstep, int64_t* position, void* states, void* actions, void* rewards, void* terminals);
 
+/* ---------------------------------------------------------------- per-step training telemetry, kept on the device */
+/* An object with two rings of `capacity` rows of doubles -- one row per control step, one per update -- and a sticky pair
+ * (first_nonfinite_step, first_nonfinite_update).  It is made for rows of B trajectories and cols >= B columns -- state
+ * [cols][ns], action [cols][na], reward / terminal [cols] in env_dtype, flags [B] -- and for an actor and a critic (mlp handles of
+ * one dtype) whose flat parameter counts it keeps a copy of.  Nothing is read back until pdec_telemetry_read.  Every value is
+ * promoted to double (exact); squares and sums are formed in double without FMA contraction; an entry that is not finite is left
+ * out of sums and maxima and counted; partial sums are combined in an order that depends on the shapes only (no floating-point
+ * atomics), so two runs of one program give bit-equal rows.  The row counters live on the device and no argument depends on the
+ * call number, so both calls can be part of a recorded step or a captured graph.  Released with pdec_destroy. */
+int pdec_telemetry_create(pdec_handle* telemetry, int capacity, int B, int cols, int ns, int na, int env_dtype, pdec_handle actor,
+                          pdec_handle critic);
+/* One launch on the object's stream (pdec_set_stream) writes step row n mod capacity, n the number of earlier step calls:
+ *   step | reward_mean reward_min reward_max (over the finite rewards; NaN when there is none) reward_nonfinite |
+ *   action_mean action_abs_mean (row 0 of every action column) action_saturated (columns with |a[c][0]| >= act_limit) |
+ *   state_abs_max (over the finite entries, 0 when there is none) state_nonfinite | blown_up (flags[b] != 0) |
+ *   terminal (terminal[c] != 0)                                                          -- 12 columns, counts as doubles.
+ * first_nonfinite_step <- n when it is still -1 and reward_nonfinite + state_nonfinite > 0. */
+int pdec_telemetry_step(pdec_handle telemetry, const void* s_out, const void* action, const void* reward, const void* terminal,
+                        const int32_t* flags, double act_limit);
+/* One launch on the stream of `critic` writes update row n mod capacity, n the number of earlier update calls, from the flat
+ * parameters of the four networks (sizes and dtype as at creation) and losses = [critic, actor] in the networks' dtype:
+ *   update | critic_loss actor_loss | actor_norm2 critic_norm2 (sum theta^2) | actor_target_dist2 critic_target_dist2
+ *   (sum (theta - theta_target)^2) | actor_step2 critic_step2 (sum (theta - theta_prev)^2) | actor_abs_max critic_abs_max |
+ *   actor_nonfinite critic_nonfinite                                                     -- 13 columns.
+ * theta_prev is the object's copy of the parameters at the previous call, rewritten by this launch; step2 = 0 for the first call
+ * after creation or reset.  A difference is left out when either entry is not finite.  first_nonfinite_update <- n when it is
+ * still -1 and a loss or a parameter is not finite. */
+int pdec_telemetry_update(pdec_handle telemetry, pdec_handle actor, pdec_handle critic, pdec_handle actor_target,
+                          pdec_handle critic_target, const void* losses);
+/* host accessor (synchronises both streams; any pointer may be NULL): the rings [capacity][12] and [capacity][13] -- call n sits
+ * in row n mod capacity --, the numbers of calls so far, and sentinel[2] = (first_nonfinite_step, first_nonfinite_update) */
+int pdec_telemetry_read(pdec_handle telemetry, double* step_rows, int64_t* n_step_calls, double* update_rows, int64_t* n_update_calls,
+                        int64_t* sentinel);
+/* rings, counters, the sentinel and theta_prev back to their state at creation.  Synchronises both streams. */
+int pdec_telemetry_reset(pdec_handle telemetry);
+
 /* ---------------------------------------------------------------- HIP graphs -- */
 /* Record everything enqueued on the stream of `origin` (pdec_set_stream; not the null stream) -- library calls, and any
  * other stream that forks from it and joins it again through events -- between _begin and _end into one HIP graph;
