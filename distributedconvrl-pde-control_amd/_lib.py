@@ -237,6 +237,27 @@ def check(rc):
         raise PdecError(f"libpdeconv error {rc}: {load().pdec_last_error().decode(errors='replace')}")
 
 
+class Owned:
+    """a Python object that owns one library object: `lib`, the handle `h` its constructor fills, released with it"""
+
+    def __init__(self, lib):
+        self.lib, self.h = lib, Handle()
+
+    def __del__(self):
+        try:
+            self.lib.pdec_destroy(self.h)
+        except Exception:
+            pass
+
+
+def ring_rows(count, N):
+    """(rows, dropped) of a device ring of N rows in which entry c sits in row c mod N: the rows of the last min(count, N) entries,
+    oldest first, and how many earlier entries the ring has overwritten"""
+    count = int(count)
+    n = min(count, N)
+    return [c % N for c in range(count - n, count)], count - n
+
+
 _inited = set()
 
 

@@ -24,6 +24,7 @@ from .agent import Agent, PRE_EXPERIMENT_STAGE, PRE_EPISODE_STAGE, POST_EPISODE_
 from .env import PDEenv, _on_stream
 from .hook import PDEhook
 from .pipeline import _Event
+from .pipeline_eval import held_out_fields
 from .run import (StopAfterEpisode, StopAfterEpisodeWithMinSteps, _EpisodeLogs, _add_episode_reward, _episode_schedule,
                   _episode_steps, _episode_time, _executed_steps, _join, _stop_fired, device_episodes_ok)
 
@@ -301,12 +302,7 @@ def evaluate_actors(setup, actors, y0=None, n_inits=8, init_seed=0, steps=None, 
     T = int(round((setup.te - setup.t0) / setup.dt)) + 1 if steps is None else int(steps)
     with _on_stream(stream):    # (the environments' own tensors are made on their stream as well)
         if y0 is None:
-            small = PDEenv(setup, B=int(n_inits), dtype=dtype, device=device, stream=stream, autoreset=False)
-            if getattr(setup, "is_fluid", False):   # the fluid's own initialiser: vortex tables from numpy's default_rng(init_seed)
-                y0 = setup.random_init_device(small, np.random.default_rng(int(init_seed)))
-            else:
-                y0 = torch.empty_like(small.y)
-                small.random_init(int(init_seed), 0, out=y0)
+            small, y0 = held_out_fields(setup, n_inits, init_seed, dtype, device, stream)   # (the draw of TrainPipeline(eval_every=...))
         y0 = (y0 if isinstance(y0, torch.Tensor) else torch.as_tensor(np.array(y0, copy=True))).to(device=dev, dtype=dtype).contiguous()
         K = int(y0.shape[0])
         env = None              # without a persistent rollout or a batched step loop no B = M K environment is built to hear it

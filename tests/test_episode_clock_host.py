@@ -147,5 +147,5 @@ def test_rank_offsets_are_one_stream(W, B, nc):
         assert split == whole
         # ... and consecutive episodes do not overlap: a draw takes W B nblk counters
         assert init_offset(n + 1, 0, W, B, nc) - init_offset(n, 0, W, B, nc) == W * B * nblk
-    # the lock-stepped pipeline's _draw_init: off = (e W + r) n with n = B ceil(nc / 4)
+    # the lock-stepped pipeline's Inits.draw: off = (e W + r) n with n = B ceil(nc / 4)
     assert init_offset(5, 1, 3, 8, 8) == (5 * 3 + 1) * (8 * 2)

@@ -286,7 +286,7 @@ def test_restarts_draw_the_lockstep_fields(pkg, dtype, rank):
         y, s = rows(n)
         return y[b], s[b]
 
-    # (step 0 is the host's: episode 0 through _draw_init)
+    # (step 0 is the host's: episode 0 through Inits.draw)
     _drained(p, 1, model, restart)
     y, _ = rows(0)
     assert torch.equal(p.env.y0, y) and p.init_offsets == [init_offset(0, rank[0], rank[1], B, 8)]
