@@ -1,0 +1,115 @@
+"""The case table of test_gpu_population_update.py (population_update_cases.py) against what it claims.  Runs without a GPU:
+every kernel name the small-update dispatch can return has a member case (a new instantiation without one fails here), every
+member sits on the trigger edge its role names, the updating members draw different minibatches, the wrapped member's state and
+reward slots differ, and no member that samples has an empty range to draw from."""
+import os
+import re
+
+import numpy as np
+
+import population_update_cases as pc
+from oracle import rng as orng
+from test_gpu_small_update import _kernel_names_of_the_dispatch
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "distributedconvrl-pde-control_amd", "csrc")
+
+
+def test_every_kernel_of_the_dispatch_has_a_member_case():
+    assert {pc.kernel_of(c) for c in pc.CASES} == _kernel_names_of_the_dispatch()
+
+
+def test_bounded_names_are_the_ones_the_library_refuses_member_hyper_for():
+    """small_serves_member_hyper (csrc/mlp_small.hip) names the ids it refuses; their reported names are the table's BOUNDED"""
+    src = open(os.path.join(CSRC, "mlp_small.hip")).read()
+    body = re.search(r"static bool small_serves_member_hyper\(const SmallPlan& pl\) \{(.*?)\n\}", src, re.S).group(1)
+    ids = re.findall(r"pl\.id == SK_(\w+)", body)
+    names = dict(re.findall(r'X\((\w+), "([^"]+)"', src))
+    assert sorted(names[i] for i in ids) == sorted(pc.BOUNDED) and len(ids) == 4
+    assert any(pc.serves_member_hyper(c) for c in pc.CASES) and not all(pc.serves_member_hyper(c) for c in pc.CASES)
+    for k in pc.BOUNDED:
+        assert any(pc.kernel_of(c) == k for c in pc.CASES), k
+
+
+def test_row_slots_are_the_library_s():
+    """enum PopSlot / PopHyperSlot of csrc/population.hpp in the table's order, 16 slots with the last one free"""
+    src = open(os.path.join(CSRC, "population.hpp")).read()
+    slot = re.search(r"enum PopSlot \{(.*?)\};", src, re.S).group(1)
+    hyp = re.search(r"enum PopHyperSlot \{(.*?)\};", src, re.S).group(1)
+    names = re.findall(r"^\s*POP_(\w+)", slot, re.M) + re.findall(r"^\s*POP_(\w+)", hyp, re.M)
+    assert names == ["USTEP", "NSA", "NRT", "NOISE", "SAMPLE", "HALT", "ACTIVE", "BPA", "BPC", "NOISE_AMP", "LIMIT", "GAMMA", "RHO",
+                     "ETA_A", "ETA_C"]
+    assert [getattr(pc, n) for n in names] == list(range(15)) and pc.SPARE == 15 and pc.ROW == 16
+    assert "POP_GAMMA = 11" in hyp and "#define POP_ROW 16" in src
+
+
+def test_members_sit_on_the_edges_their_roles_name():
+    for case in pc.CASES:
+        mbs = pc.members(case)
+        assert len(mbs) == pc.M == 6
+        assert [pc.fires(mb) for mb in mbs] == [mb.updates for mb in mbs] == [True, True, False, False, False, True], case
+        m0, m1, m2, m3, m4, m5 = mbs
+        # member 0: the first row count that fires, one more than member 2's, which is `after` exactly
+        assert pc.n_valid(m0) == pc.AFTER_ROWS + 1 and pc.n_valid(m2) == pc.AFTER_ROWS and m0.ustep % pc.FREQ == 0 == m2.ustep % pc.FREQ
+        assert not m0.halt and not m2.halt and not m0.aged
+        # member 1: wrapped, a sample offset past 2^32, aged
+        assert m1.n_rt == pc.CAP + 23 and pc.n_valid(m1) == pc.CAP and m1.offset > 2 ** 32 and m1.aged
+        # members 3 and 4 are due but for the one condition their role names
+        assert m3.ustep % pc.FREQ == 1 and pc.fires(m3._replace(ustep=m3.ustep + 1))
+        assert m4.halt == 1 and pc.fires(m4._replace(halt=0))
+        # member 5: member 0's seed and counters, another offset whose draws do not overlap member 0's two launches
+        assert (m5.seed, m5.n_rt) == (m0.seed, m0.n_rt) and m5.offset >= m0.offset + 2 * pc.dsample(case) and m5.ustep % pc.FREQ == 0
+        assert len({mb.seed for mb in mbs}) == pc.M - 1
+        for mb in mbs:
+            if mb.updates:                      # nothing here asks a kernel to draw from an empty range
+                assert pc.n_valid(mb) - pc.STRIDE >= 1, (case, mb.role)
+
+
+def test_updating_members_draw_different_minibatches():
+    for case in pc.CASES:
+        Bu = pc.CASES[case][5]
+        assert pc.dsample(case) == -(-pc.LOOPS * Bu // 4)
+        upd = [mb for mb in pc.members(case) if mb.updates]
+        for launch in (0, 1):
+            tabs = [pc.slots(case, mb, launch) for mb in upd]
+            for t in tabs:
+                assert t.shape == (3, pc.LOOPS, Bu) and t.min() >= 0 and t[1].max() < pc.CAP and t[[0, 2]].max() < pc.CAP + pc.STRIDE
+            for i in range(len(tabs)):
+                for j in range(i + 1, len(tabs)):
+                    assert not np.array_equal(tabs[i], tabs[j]), (case, launch, upd[i].role, upd[j].role)
+        for mb in upd:                          # the second launch draws other slots than the first
+            assert not np.array_equal(pc.slots(case, mb, 0), pc.slots(case, mb, 1)), (case, mb.role)
+        m1 = pc.members(case)[1]
+        wrapped = pc.slots(case, m1, 0)
+        assert (wrapped[0] != wrapped[1]).any(), case         # state rows and reward rows of a wrapped ring differ
+        # what a prologue that dropped the ring's base, or the high half of POP_SAMPLE, would draw is something else
+        n = pc.LOOPS * Bu
+        no_base = orng.sample_slots(m1.seed, m1.offset, n, pc.n_valid(m1), pc.n_valid(m1), pc.CAP, pc.STRIDE)
+        low_half = orng.sample_slots(m1.seed, m1.offset & 0xFFFFFFFF, n, pc.n_valid(m1), m1.n_rt, pc.CAP, pc.STRIDE)
+        assert not np.array_equal(no_base.reshape(wrapped.shape), wrapped), case
+        assert not np.array_equal(low_half.reshape(wrapped.shape), wrapped), case
+
+
+def test_rows_and_their_expected_successors():
+    for case in pc.CASES:
+        for hyper in (False, True):
+            r = pc.rows(case, hyper)
+            assert r.shape == (pc.M, pc.ROW) and r.dtype == np.int64
+            h = r[:, pc.GAMMA:pc.ETA_C + 1].view(np.float64)
+            if hyper:
+                hy = pc.hyper(case)
+                assert np.array_equal(h, hy)
+                upd = [m for m, mb in enumerate(pc.members(case)) if mb.updates]
+                for k in range(4):
+                    frozen_rho = k == 1 and np.float32(pc.CASES[case][6]) == np.float32(1.0)
+                    assert len({hy[m, k] for m in upd}) == (1 if frozen_rho else len(upd)), (case, k)
+                assert (hy[:, 1] == 1.0).all() if np.float32(pc.CASES[case][6]) == np.float32(1.0) else (hy[:, 1] < 1.0).all()
+                assert hy[1, 2] == 0.0 == hy[1, 3] and (hy[[0, 5], 2:] > 0).all()
+                assert np.array_equal(hy[0], [pc.GAMMA0, pc.CASES[case][6], pc.ETA_A0, pc.ETA_C0])    # member 0's create the population
+            else:
+                assert np.isnan(h).all() and len(set(r[:, pc.GAMMA:pc.ETA_C + 1].reshape(-1).tolist())) == 4 * pc.M
+            a1, a2 = pc.rows_after(case, r), pc.rows_after(case, r, 2)
+            for m, mb in enumerate(pc.members(case)):
+                moved = np.flatnonzero(a1[m] != r[m]).tolist()
+                assert moved == (sorted(pc.MOVES) if mb.updates else []), (case, m)
+                assert a2[m, pc.SAMPLE] - r[m, pc.SAMPLE] == (2 * pc.dsample(case) if mb.updates else 0)
+                assert np.array_equal(a2[m, [pc.BPA, pc.BPC]], r[m, [pc.BPA, pc.BPC]])
