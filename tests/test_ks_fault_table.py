@@ -267,7 +267,7 @@ class _Stop(Exception):
 def test_evaluate_actors_lays_the_scenarios_out_as_mu_is(pkg, monkeypatch):
     """B = M n_f K, member m's block [n_f][K]: trajectory (m, f, k) carries scenario f -- seen on a stub environment, no GPU"""
     import types
-    pop = __import__(pkg.__name__ + ".population", fromlist=["x"])
+    pop = __import__(pkg.__name__ + ".population_eval", fromlist=["x"])     # (the module whose names evaluate_actors reads)
     torch = pytest.importorskip("torch")
     setup, _ = kc.build(pkg, ks, "perm_oddA_256")
     A, S = fc.sizes("perm_oddA_256")
