@@ -1,6 +1,7 @@
 // population.hip -- the population object (include/pdeconv.h, population.py): its creation from M learners' networks, traces and
 // counter rows, the members' beta-power slots, the hooks' actor snapshots and exploit by clone.  Its per-step launches are
-// pdec_population_glue (act.hip) and the members' update (mlp_small.hip), its episode boundary pop_book.hip.
+// pdec_population_glue (act.hip) and the members' update (pdec_population_update in mlp_small.hip, the kernels in small_generic.hpp /
+// small2.hpp / small2f.hpp), its episode boundary pop_book.hip.
 #include "common.hpp"
 #include "population.hpp"
 

@@ -1,5 +1,6 @@
 // population.hpp -- the device tables of a population and the object behind its handle, for the files that build, serve or read
-// them: population.hip, act.hip (pdec_population_glue), mlp_small.hip (the members' update), pop_book.hip (the episode boundary)
+// them: population.hip, act.hip (pdec_population_glue), mlp_small.hip with small_args.hpp (the members' update: pdec_population_update
+// and the kernels' member prologue sm_member_begin), pop_book.hip (the episode boundary)
 #pragma once
 #include "mlp.hpp"
 

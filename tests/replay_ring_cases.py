@@ -1,6 +1,6 @@
 """The case table of test_gpu_replay_ring.py: the trajectory glue of csrc/replay.hip (replay_push2_kernel, replay_push_rt_kernel,
 replay_sample_kernel, autoreset_kernel), the same pushes inside csrc/act.hip's step_glue_kernel and the slot table of
-csrc/mlp_small.hip, at the seams of the two rings -- away from the one geometry the shipped runs use (ns = na = 1, stride = A = 8,
+csrc/small_args.hpp, at the seams of the two rings -- away from the one geometry the shipped runs use (ns = na = 1, stride = A = 8,
 a capacity that is a multiple of the push).  Imports neither torch nor numpy (numpy only inside the functions that draw data), so
 test_replay_ring_table.py can hold the table against its claims on a machine without a GPU.
 
@@ -137,7 +137,7 @@ ACCEPTED = {          # the same calls one step inside the bound: they succeed
     "sample_one_valid": ("sample", dict(cap=12, stride=3, n_valid=4, n_rt=4)),
 }
 
-# ring states of the in-kernel sampler (csrc/mlp_small.hip, pdec_ddpg_update_small_rng) for a setup of A columns a step and a
+# ring states of the in-kernel sampler (csrc/small_args.hpp, pdec_ddpg_update_small_rng) for a setup of A columns a step and a
 # trajectory of 5 A rows: name -> (full control steps, further reward columns, seed, offset).  One loop of SMALL_BU columns.
 SMALL_BU, SMALL_STEPS_CAP = 6, 5
 SMALL_STATES = {

@@ -1,5 +1,5 @@
 """A plain model of the device replay (csrc/replay.hip: replay_push2_kernel, replay_push_rt_kernel, replay_sample_kernel; the same
-pushes inside csrc/act.hip's step_glue_kernel; the slot table of csrc/mlp_small.hip) that holds NO ring.  numpy only.
+pushes inside csrc/act.hip's step_glue_kernel; the slot table of csrc/small_args.hpp) that holds NO ring.  numpy only.
 
 Four lists indexed by LOGICAL entry number -- state, action (one entry per pushed row) and reward, terminal -- and two counters,
 n_sa and n_rt, that move as the host's do (agent.py: CircularArraySARTTrajectory).  What a physical trace must hold is derived

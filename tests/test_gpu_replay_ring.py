@@ -1,5 +1,5 @@
 """GPU tests of the trajectory glue at its seams: csrc/replay.hip (replay_push2_kernel, replay_push_rt_kernel, replay_sample_kernel,
-autoreset_kernel), the pushes of csrc/act.hip's step_glue_kernel and the slot table of csrc/mlp_small.hip, every row of
+autoreset_kernel), the pushes of csrc/act.hip's step_glue_kernel and the slot table of csrc/small_args.hpp, every row of
 replay_ring_cases.py against the plain model of replay_ring_ref.py.  These kernels copy, cast fp64 -> fp32 and do integer
 arithmetic, so every comparison is exact (np.array_equal; NaN positions by mask where NaNs are planted).
 test_replay_ring_table.py holds the table's claims and shows that each comparison rejects the mistake it is there for."""
@@ -198,7 +198,7 @@ def _fill(tr, steps, extra, A, ns, g):
 @pytest.mark.parametrize("state", list(rc.SMALL_STATES))
 @pytest.mark.parametrize("which", ["two_layer_register_kernel", "three_layer_generic_kernel"])
 def test_in_kernel_sampler_at_the_ring_states(pkg, which, state):
-    """pdec_ddpg_update_small_rng (the slot table of csrc/mlp_small.hip) at the table's ring states: ONE update of SMALL_BU columns
+    """pdec_ddpg_update_small_rng (the slot table of csrc/small_args.hpp) at the table's ring states: ONE update of SMALL_BU columns
     == pdec_ddpg_update_small fed the oracle's slots of the same stream, bit for bit"""
     setup = pkg.KSSetup.KS22() if which.startswith("two") else pkg.KSSetup.bench_C2(256)
     ns, A = setup.state_shape

@@ -1,4 +1,4 @@
-"""Every kernel of the small DDPG update (pdec_ddpg_update_small / _rng, csrc/mlp_small.hip) against the fp64 oracle.
+"""Every kernel of the small DDPG update (pdec_ddpg_update_small / _rng, csrc/mlp_small.hip; the kernels in small_generic.hpp, small2.hpp, small2f.hpp) against the fp64 oracle.
 
 Each case names the instantiation it must reach and asserts it through pdec_debug_small_update_kernel; together the cases
 reach every name the dispatch can return (test_cases_reach_every_kernel_of_the_dispatch).  Per case:

@@ -39,7 +39,7 @@ def test_hyper_slots_equal_the_device_enum(pop):
     assert pop.ROW == 16 == int(re.search(r"#define POP_ROW (\d+)", hpp).group(1))
     assert max(hyper.values()) < pop.ROW - 1          # slot 15 stays free
     # the kernels' prologue reads exactly these names
-    small = open(os.path.join(ROOT, "distributedconvrl-pde-control_amd", "csrc", "mlp_small.hip")).read()
+    small = open(os.path.join(ROOT, "distributedconvrl-pde-control_amd", "csrc", "small_args.hpp")).read()   # sm_member_begin
     for k in hyper:
         assert re.search(r"\b%s\b" % k, small), k
 

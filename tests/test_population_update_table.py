@@ -19,11 +19,16 @@ def test_every_kernel_of_the_dispatch_has_a_member_case():
 
 
 def test_bounded_names_are_the_ones_the_library_refuses_member_hyper_for():
-    """small_serves_member_hyper (csrc/mlp_small.hip) names the ids it refuses; their reported names are the table's BOUNDED"""
+    """small_serves_member_hyper (csrc/mlp_small.hip) refuses the rows of SMALL2_KERNELS whose EXACT column is false; their
+    reported names are the table's BOUNDED"""
     src = open(os.path.join(CSRC, "mlp_small.hip")).read()
     body = re.search(r"static bool small_serves_member_hyper\(const SmallPlan& pl\) \{(.*?)\n\}", src, re.S).group(1)
-    ids = re.findall(r"pl\.id == SK_(\w+)", body)
+    assert "small2_rows" in body and "return r.exact;" in body
+    # the EXACT column by its position: X(ID, "name", NS, BU, OS, EXACT, NWC, kernel).  Every row must spell it true or false
+    rows = re.findall(r'X\((\w+), "[^"]+", ([^,]+), ([^,]+), ([^,]+), ([^,]+),', src)
     names = dict(re.findall(r'X\((\w+), "([^"]+)"', src))
+    assert len(rows) == len(names) and all(r[4] in ("true", "false") for r in rows), rows
+    ids = [r[0] for r in rows if r[4] == "false"]
     assert sorted(names[i] for i in ids) == sorted(pc.BOUNDED) and len(ids) == 4
     assert any(pc.serves_member_hyper(c) for c in pc.CASES) and not all(pc.serves_member_hyper(c) for c in pc.CASES)
     for k in pc.BOUNDED:
