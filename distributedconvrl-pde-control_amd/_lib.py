@@ -87,6 +87,7 @@ SIGNATURES = {
     "pdec_ddpg_update_small": [Handle] * 4 + [_vp] * 7 + [_i, _i, _d, _d, _i, _d, _d, _vp],
     "pdec_ddpg_update_critic_async": [Handle] * 4 + [_vp] * 5 + [_i, _d, _d, _i, _d, _vp],
     "pdec_ddpg_update_actor_async": [Handle] * 4 + [_vp, _i, _d, _d, _vp],
+    "pdec_ddpg_defer_actor_finish": [Handle, _i, _d, C.POINTER(_i)], "pdec_ddpg_flush_actor_finish": [Handle],
     "pdec_policy_act": [Handle, _vp, _vp, _i, _d, _d, _vp],
     "pdec_rollout": [Handle, Handle, _i, _vp, _vp, _vp, _d, _d, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pdec_rollout_members": [Handle, _vp, _i, _i, _i, _vp, _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i)],
@@ -154,6 +155,7 @@ DEBUG_SIGNATURES = {
     "pdec_debug_wave_fft": [_vp, _vp, _i, _i, _i],
     "pdec_debug_wave_fft_f32": [_vp, _vp, _i, _i, _i],
     "pdec_debug_critic_stamps": [Handle, _i, _pd],
+    "pdec_debug_fused_image": [Handle, _i, _vp] + [C.POINTER(_i)] * 4,
     "pdec_debug_kseg2d_probe": [Handle, _i, _i, _i, _pd],
     "pdec_debug_spin_us": [_vp, _d],
     "pdec_debug_small_update_kernel": [Handle, Handle, Handle, Handle, _i, _i, _d, _i, C.c_char_p, _i, C.POINTER(_i64)],

@@ -440,6 +440,26 @@ int pdec_ddpg_update_actor_async(pdec_handle hA, pdec_handle hC, pdec_handle hAt
                             losses_dev);
 }
 
+int pdec_ddpg_defer_actor_finish(pdec_handle hA, int on, double rho, int* armed) {
+  GET_MLP(A, hA);
+  // the fused 3-layer family only (its finish launch is what is deferred), and frozen targets only: with moving targets the
+  // next critic pass reads the target actor that the actor's finish writes
+  const bool ok = on && (&fused3_family)->net_ok(A) && (float)rho == 1.0f;
+  if (!ok) {                           // switched off, or declined: nothing stays pending
+    A->defer_finish = false;
+    if (int rc = fused_flush_pending(A)) return rc;
+  } else {
+    A->defer_finish = true;
+  }
+  if (armed) *armed = ok ? 1 : 0;
+  return PDEC_OK;
+}
+
+int pdec_ddpg_flush_actor_finish(pdec_handle hA) {
+  GET_MLP(A, hA);
+  return fused_flush_pending(A);
+}
+
 int pdec_debug_batched_update_route(pdec_handle hA, pdec_handle hC, pdec_handle hAt, pdec_handle hCt, int Bu, int which, char* name,
                                     int name_len, int64_t* lds_bytes) {
   PDEC_REQUIRE(name && name_len > 0 && lds_bytes, "pdec_debug_batched_update_route: null argument");
@@ -472,6 +492,23 @@ int pdec_debug_batched_update_route(pdec_handle hA, pdec_handle hC, pdec_handle 
   if (which >= 2 && rt && !update_applies_in_finish(full, Bu)) {
     const size_t n = strlen(name);
     snprintf(name + n, (size_t)name_len > n ? name_len - n : 0, "/adam_apart");
+  }
+  return PDEC_OK;
+}
+
+int pdec_debug_fused_image(pdec_handle mlp, int which, float* out_host, int* nfloats, int* pub, int* pending, int* paired) {
+  GET_MLP(M, mlp);
+  PDEC_REQUIRE(which >= 0 && which <= 2, "pdec_debug_fused_image: which = %d", which);
+  PDEC_REQUIRE(fused_net_supported(M), "pdec_debug_fused_image: not a fused 3-layer network");
+  const DevBuf& img = which == 0 ? M->fw : M->fw_pub[which - 1];
+  if (nfloats) *nfloats = (int)(img.bytes / 4);
+  if (pub) *pub = M->pub;
+  if (pending) *pending = M->pend.on ? 1 : 0;
+  if (paired) *paired = M->n_paired;
+  if (out_host) {
+    PDEC_REQUIRE(img.bytes > 0, "pdec_debug_fused_image: the network has no image yet (no fused pass or acting call has run)");
+    PDEC_HIP(hipStreamSynchronize(M->stream));
+    PDEC_HIP(hipMemcpy(out_host, img.p, img.bytes, hipMemcpyDeviceToHost));
   }
   return PDEC_OK;
 }

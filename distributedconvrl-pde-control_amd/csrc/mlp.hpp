@@ -11,6 +11,22 @@
 
 namespace pdec {
 
+struct AdamPolyak {
+  double eta, b1, b2, eps, rho;
+};
+
+// The finish launch of a fused 3-layer actor pass that has not been issued yet (pdec_ddpg_defer_actor_finish): what
+// launch_finish needs to issue it later, alone (pdec_ddpg_flush_actor_finish) or as extra blocks of the next critic finish
+struct PendingFinish {
+  bool on = false;
+  const float* slabs = nullptr;      // the actor's slab buffer as the pass left it
+  int nslab = 0, mta = 0, Bu = 0;
+  double scale = 1.0;
+  void* loss = nullptr;
+  AdamPolyak ap{};
+  hipEvent_t stop = nullptr;         // the one-shot stop event that was set on the net when its pass was launched
+};
+
 struct Mlp : Object {
   int dtype = PDEC_F32, L = 0, max_cols = 0, nparams = 0;
   std::vector<int> dims, acts;
@@ -51,6 +67,9 @@ struct Mlp : Object {
   bool fw_dirty = true;
   DevBuf fw_pub[2];                  // published copies of the image for concurrent acting kernels
   int pub = 0;
+  bool defer_finish = false;         // pdec_ddpg_defer_actor_finish: armed (actor nets of the fused 3-layer family)
+  PendingFinish pend;
+  int n_paired = 0;                  // finish launches of this net that were blocks of a critic's finish launch (tests)
 
   Mlp() : Object(Kind::Mlp) {}
   int init(int dtype, int L, const int32_t* dims, const int32_t* acts, int max_cols);
@@ -177,9 +196,6 @@ int reward_group_route(Mlp* C, const void* r, int Bu, int quirk, CriticRoute* ou
 template <int N>
 using tile_c = std::integral_constant<int, N>;
 
-struct AdamPolyak {
-  double eta, b1, b2, eps, rho;
-};
 // ---- a fused DDPG kernel family: fp32 MFMA passes, apply and acting kernels for one class of actor / critic pairs.  Two exist:
 // fused3_family (mlp_mfma.hip: 3-layer pairs on padded weight images) and fused2_family (mlp_mfma2.hip: the reference-shaped
 // 2-layer nets [ns, h, 1] / [ns+1, H, 1] on the flat parameters).  ddpg.hip and act.hip pick one through the selectors below and
@@ -218,6 +234,12 @@ inline bool act_route_is_fused(const Mlp* M, int cols) { return fused_family_of_
 // the flat parameters of the published image the next acting kernel reads (fw_pub[pub]), enqueued on `stream`
 bool fused_net_supported(const Mlp* M);
 int fused_unpack_published(Mlp* A, float* flat_out, hipStream_t stream);
+// the pending finish of A as a launch of its own on A's stream (no-op when nothing is pending)
+int fused_flush_pending(Mlp* A);
+// an entry that reads what a pending finish has yet to write (the actor's image, its published copy, its parameters)
+#define PDEC_REQUIRE_NO_PENDING(M, who)                                                                                     \
+  PDEC_REQUIRE(!(M)->pend.on, "%s: the actor's finish launch is still pending (pdec_ddpg_defer_actor_finish): flush it first " \
+                              "(pdec_ddpg_flush_actor_finish)", who)
 // mean of r[0..n) in a fixed order, one block; *out = device scalar owned by C (mlp_mfma2.hip)
 int launch_rmean(Mlp* C, const float* r, int n, float** out);
 

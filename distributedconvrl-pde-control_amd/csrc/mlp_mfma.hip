@@ -896,13 +896,14 @@ __global__ __launch_bounds__(1024) void fused_finish_ref_kernel(FinishArgs g_in)
 //   * all blocks are co-resident (792 blocks x 2 waves = 6 waves per CU), so no second round of blocks waits for the first.
 // grid: nslab > 0 -> 8 * slab_tiles(MT) blocks; nslab == 0 -> ceil(n / 128) blocks (apply from the gradient buffer).
 #define FIN_THREADS 128
-__global__ __launch_bounds__(FIN_THREADS) void fused_finish_kernel(FinishArgs g_in) {
+// the work of block `bx` of a finish grid with the launch arguments g_in
+__device__ __forceinline__ void finish_block(const FinishArgs& g_in, const unsigned bx) {
   FinishArgs g = g_in;
   set_wave_prio(g.prio);
   if (g.apply) {      // the beta powers come from device memory; one thread of the grid writes the advanced pair
     g.omb1p = 1.0 - g.bp.cur[0];
     g.omb2p = 1.0 - g.bp.cur[1];
-    if (blockIdx.x == 0 && threadIdx.x == 0) bp_advance(g.bp, g.b1, g.b2);
+    if (bx == 0 && threadIdx.x == 0) bp_advance(g.bp, g.b1, g.b2);
   }
   __shared__ float part[16][36];
   const int tid = threadIdx.x;
@@ -910,7 +911,7 @@ __global__ __launch_bounds__(FIN_THREADS) void fused_finish_kernel(FinishArgs g_
   const int n = H * K0 + H + H * H + H + H + 1;
   const int offb1 = H * K0, offW2 = offb1 + H, offb2 = offW2 + H * H, offW3 = offb2 + H, offb3 = offW3 + H;
   if (g.nslab > 0) {
-    const int c = blockIdx.x >> 1, half = blockIdx.x & 1, T = c >> 2, r = c & 3;
+    const int c = bx >> 1, half = bx & 1, T = c >> 2, r = c & 3;
     int i = -1;   // flat parameter index of the chunk element this thread finishes (threads 0..31; -1: padding)
     if (tid < 32) {
       const int l = 32 * half + tid, q = l >> 4, lr = l & 15;
@@ -959,10 +960,10 @@ __global__ __launch_bounds__(FIN_THREADS) void fused_finish_kernel(FinishArgs g_
       }
     }
   } else {
-    const int i = blockIdx.x * FIN_THREADS + tid;
+    const int i = bx * FIN_THREADS + tid;
     if (i < n && g.apply) finish_param(g, i, g.grads[i], g.p[i], g.m[i], g.v[i], g.pt ? g.pt[i] : 0.f);
   }
-  if (blockIdx.x == 0 && g.loss_out && g.nslab > 0) {   // block 0 also finalises the loss (fixed-order tree -> deterministic)
+  if (bx == 0 && g.loss_out && g.nslab > 0) {   // block 0 also finalises the loss (fixed-order tree -> deterministic)
     // the round-2 tree: 256 strided partial sums, pairwise tree 128, 64, ..., 1 -- thread t owns partials t and t + 128
     // and starts with their sum (= the tree's first level)
     __shared__ double red[5][FIN_THREADS];
@@ -987,6 +988,19 @@ __global__ __launch_bounds__(FIN_THREADS) void fused_finish_kernel(FinishArgs g_
         *g.loss_out = (float)(-red[0][0] * inv);
     }
   }
+}
+
+__global__ __launch_bounds__(FIN_THREADS) void fused_finish_kernel(FinishArgs g_in) {
+  finish_block(g_in, blockIdx.x);
+}
+
+// Two finish grids in one launch: blocks [0, nc) are the grid of c, blocks [nc, gridDim.x) the grid of a, each block doing
+// what it does in a launch of its own (block 0 of either grid finalises that grid's loss), so both nets end bit-identical to
+// two launches.  For the critic's finish of update k + 1 and the actor's of update k under frozen targets, which touch
+// disjoint memory.
+__global__ __launch_bounds__(FIN_THREADS) void fused_finish_pair_kernel(FinishArgs c_in, FinishArgs a_in, int nc) {
+  if ((int)blockIdx.x < nc) finish_block(c_in, blockIdx.x);
+  else finish_block(a_in, blockIdx.x - nc);
 }
 
 // ------------------------------------------------------------------ fused policy act
@@ -1249,10 +1263,10 @@ static int ensure_slab(Mlp* M, size_t floats) {
   return PDEC_OK;
 }
 
-// Slab reduction (nslab > 0) and/or the parameter update (apply): ADAM on M with M->adam_* hyper-parameters,
-// Polyak into Mt, refresh of both padded images.  One launch.
-static int launch_finish(Mlp* M, Mlp* Mt, const float* slabs, int nslab, int MT, double grad_scale, int mode,
-                         int Bu, int quirk, void* loss_dev, const AdamPolyak* ap, const void* loss_add = nullptr) {
+// The arguments of a finish launch on M: slab reduction (nslab > 0) and/or the parameter update (ap): ADAM on M, Polyak into
+// Mt, refresh of both padded images.  Takes the beta-power slots of M; finish_issued() follows the launch.
+static int finish_args(Mlp* M, Mlp* Mt, const float* slabs, int nslab, int MT, double grad_scale, int mode, int Bu, int quirk,
+                       void* loss_dev, const AdamPolyak* ap, const void* loss_add, FinishArgs* out) {
   FinishArgs g{};
   g.slabs = slabs; g.nslab = nslab; g.K0 = M->dims[0]; g.H = M->dims[1]; g.MT = MT;
   g.grads = M->grads.as<float>(); g.scale = (float)grad_scale; g.mode = mode; g.Bu = Bu; g.quirk = quirk;
@@ -1277,6 +1291,22 @@ static int launch_finish(Mlp* M, Mlp* Mt, const float* slabs, int nslab, int MT,
       g.rho = r; g.omr = 1.0f - r;
     }
   }
+  *out = g;
+  return PDEC_OK;
+}
+// the host's half of a finish launch that applied the update: the selectors of the beta powers and of the published image
+static void finish_issued(Mlp* M, const AdamPolyak* ap) {
+  if (ap) {
+    bp_done(M);
+    flip(M->pub);
+  }
+}
+
+// One finish launch on M's stream.
+static int launch_finish(Mlp* M, Mlp* Mt, const float* slabs, int nslab, int MT, double grad_scale, int mode,
+                         int Bu, int quirk, void* loss_dev, const AdamPolyak* ap, const void* loss_add = nullptr) {
+  FinishArgs g;
+  if (int rc = finish_args(M, Mt, slabs, nslab, MT, grad_scale, mode, Bu, quirk, loss_dev, ap, loss_add, &g)) return rc;
   const int n = M->nparams;
   {
     const char* label = ap ? (nslab > 0 ? "fused_finish" : "fused_apply") : "fused_reduce";
@@ -1305,15 +1335,56 @@ static int launch_finish(Mlp* M, Mlp* Mt, const float* slabs, int nslab, int MT,
     slot = nullptr;     // consumed (the stop event only by a launch that applies the update, the reduce event only by a reduce-only one)
   }
   PDEC_HIP(hipGetLastError());
-  if (ap) {
-    bp_done(M);
-    flip(M->pub);
+  finish_issued(M, ap);
+  return PDEC_OK;
+}
+
+// ---- the deferred actor finish (pdec_ddpg_defer_actor_finish).  With frozen targets the critic half of update k + 1 reads
+// nothing the actor's finish of update k writes, so that finish need not be a launch of the update chain: the actor pass leaves
+// it pending, and the critic's finish launch of the next update takes its blocks along (fused_finish_pair_kernel).
+int fused_flush_pending(Mlp* A) {
+  PendingFinish& P = A->pend;
+  if (!P.on) return PDEC_OK;
+  P.on = false;
+  if (P.stop) A->stop_event = P.stop;       // the plain launch carries it, as the launch it replaces would have
+  P.stop = nullptr;
+  return launch_finish(A, nullptr, P.slabs, P.nslab, P.mta, P.scale, 1, P.Bu, 0, P.loss, &P.ap);
+}
+
+// The critic's finish (always with its update: ap) and the pending finish of A in one launch on C's stream.  The launch carries
+// C's stop event; a stop event that was set on A is recorded behind it.
+static int launch_finish_pair(Mlp* C, Mlp* Ct, const float* slabs, int nslab, int MT, double grad_scale, int Bu, int quirk,
+                              void* loss_dev, const AdamPolyak* ap, const void* loss_add, Mlp* A) {
+  PendingFinish& P = A->pend;
+  // the round-2 reference kernel, a profiled launch and nets on two streams keep the two launches
+  if (getenv("PDEC_FINISH_REF") != nullptr || C->prof || A->prof || A->stream != C->stream) {
+    if (int rc = fused_flush_pending(A)) return rc;
+    return launch_finish(C, Ct, slabs, nslab, MT, grad_scale, 0, Bu, quirk, loss_dev, ap, loss_add);
   }
+  FinishArgs gc, ga;
+  int rc;
+  if ((rc = finish_args(C, Ct, slabs, nslab, MT, grad_scale, 0, Bu, quirk, loss_dev, ap, loss_add, &gc))) return rc;
+  if ((rc = finish_args(A, nullptr, P.slabs, P.nslab, P.mta, P.scale, 1, P.Bu, 0, P.loss, &P.ap, nullptr, &ga))) return rc;
+  const int nc = 8 * slab_tiles(MT), na = 8 * slab_tiles(P.mta);
+  const hipEvent_t ev = C->stop_event, eva = P.stop;
+  if (ev)
+    hipExtLaunchKernelGGL(fused_finish_pair_kernel, dim3(nc + na), dim3(FIN_THREADS), 0, C->stream, nullptr, ev, 0, gc, ga, nc);
+  else
+    hipLaunchKernelGGL(fused_finish_pair_kernel, dim3(nc + na), dim3(FIN_THREADS), 0, C->stream, gc, ga, nc);
+  C->stop_event = nullptr;
+  P.on = false;
+  P.stop = nullptr;
+  ++A->n_paired;
+  PDEC_HIP(hipGetLastError());
+  if (eva) PDEC_HIP(hipEventRecord(eva, C->stream));
+  finish_issued(C, ap);
+  finish_issued(A, &P.ap);
   return PDEC_OK;
 }
 
 int fused_unpack_published(Mlp* A, float* flat_out, hipStream_t stream) {
   PDEC_REQUIRE(fused_net_supported(A), "fused_unpack_published: not a fused 3-layer network");
+  PDEC_REQUIRE_NO_PENDING(A, "fused_unpack_published");
   int rc = ensure_prepped(A);
   if (rc) return rc;
   FNet f = make_fnet_layout(A->dims[0], A->dims[1]);
@@ -1342,6 +1413,7 @@ static int fused_act_plan(const Mlp* A, int* mta, size_t* lds) {
 
 static int fused_policy_act(Mlp* A, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
                             uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc) {
+  PDEC_REQUIRE_NO_PENDING(A, "fused act");
   int rc = ensure_prepped(A);
   if (rc) return rc;
   FNet f = fnet_of(A);
@@ -1388,6 +1460,7 @@ static int fused_act_describe(const Mlp* A, char* name, int name_len, int64_t* l
 // ADAM(M) + Polyak(Mt <- M) + image refresh from the gradient buffer (after an external all-reduce)
 static int fused_adam_polyak(Mlp* M, Mlp* Mt, const AdamPolyak& ap) {
   int rc;
+  PDEC_REQUIRE_NO_PENDING(M, "fused apply");
   if ((rc = ensure_prepped(M)) || (Mt && (rc = ensure_prepped(Mt)))) return rc;
   return launch_finish(M, Mt, nullptr, 0, mt_of(M->dims[1]), 1.0, 0, 1, 0, nullptr, &ap);
 }
@@ -1422,6 +1495,11 @@ static int fused_critic_grads(Mlp* A, Mlp* C, Mlp* At, Mlp* Ct, const void* s, c
     return launch_critic<decltype(MT)::value, decltype(MTA)::value>(C, g, grid);
   });
   if (rc) return rc;
+  if (A->pend.on) {
+    // (a reduce-only critic finish has no place for the actor's update: the pending finish goes first, as a launch of its own)
+    if (apply) return launch_finish_pair(C, Ct, C->fslab.as<float>(), grid, mt, grad_scale, Bu, quirk, loss_dev, apply, loss_add, A);
+    if ((rc = fused_flush_pending(A))) return rc;
+  }
   return launch_finish(C, apply ? Ct : nullptr, C->fslab.as<float>(), grid, mt, grad_scale, 0, Bu, quirk, loss_dev, apply,
                        loss_add);
 }
@@ -1441,6 +1519,7 @@ static int fused_describe(const Mlp* A, const Mlp* C, bool actor_pass, char* nam
 static int fused_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, double grad_scale, void* loss_dev,
                              const AdamPolyak* apply) {
   int rc;
+  PDEC_REQUIRE_NO_PENDING(A, "fused actor pass");
   if ((rc = ensure_prepped(C)) || (rc = ensure_prepped(A)) || (apply && At && (rc = ensure_prepped(At)))) return rc;
   const int mt = mt_of(C->dims[1]), mta = mt_of(A->dims[1]);
   const int grid = (Bu + FCOLS - 1) / FCOLS;
@@ -1458,6 +1537,16 @@ static int fused_actor_grads(Mlp* A, Mlp* C, Mlp* At, const void* s, int Bu, dou
   });
   if (rc) return rc;
   (void)C;
+  // armed (pdec_ddpg_defer_actor_finish) and the targets frozen: the finish stays pending for the next critic finish launch.
+  // (Moving targets: that critic pass reads the target actor this finish writes, so the launch is made here as ever.)
+  if (A->defer_finish && apply && (float)apply->rho == 1.0f) {
+    PendingFinish& P = A->pend;
+    P.on = true;
+    P.slabs = A->fslab.as<float>(); P.nslab = grid; P.mta = mta; P.Bu = Bu; P.scale = grad_scale; P.loss = loss_dev; P.ap = *apply;
+    P.stop = A->stop_event;
+    A->stop_event = nullptr;
+    return PDEC_OK;
+  }
   return launch_finish(A, apply ? At : nullptr, A->fslab.as<float>(), grid, mta, grad_scale, 1, Bu, 0, loss_dev, apply);
 }
 

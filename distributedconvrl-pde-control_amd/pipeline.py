@@ -12,6 +12,16 @@ back to back behind update_{k-1} beside act_k / env_k; act_{k+1} follows update_
 `update!` in the run loop.  (update_k must follow act_{k-1}, the last reader of the image its actor half republishes;
 env_{k-LAG}, its batch, precedes act_{k-1} on the env stream.)
 
+Frozen target networks, one rank, inside run(): the finish launch of the actor half of update_k (slab reduction, ADAM, image
+refresh) is not a launch of its own -- the critic half of update_{k+1} reads nothing it writes, so its blocks ride in the
+critic's finish launch of update_{k+1} (pdec_ddpg_defer_actor_finish):
+
+    update stream:  wait act_{k-1} -> critic pass_k -> [critic finish_k + actor finish_{k-1}] -> actor pass_k
+    env stream:                                         wait that launch -> act_k -> env_k
+
+Three launches on the update chain instead of four and one cross-stream wait fewer; the same bits.  run() flushes the last
+finish before it returns, so nothing is pending outside it (PDEC_DEFER_ACTOR_FINISH=0: the four-launch step).
+
 Data-parallel runs (N > 1, policy-gradient-only exchange, frozen target networks): the all-reduce of the actor's gradient and
 the ADAM launch that consumes it leave the update stream (`stream_ar`):
 
@@ -316,7 +326,7 @@ class TrainPipeline:
             _lib.check(self.lib.pdec_env_set_simd_sharing(env.handle, 1, C.byref(eff)))
             self.simd_sharing = bool(eff.value)
         self.graphs = {}          # (chunk, pos) -> graph handle
-        self._progs = {}          # ring phase -> recorded library calls of an interior eager step
+        self._progs = {}          # (ring phase, armed) -> recorded library calls of an interior eager step (_eager)
         # the recorded-call replay re-issues LIBRARY calls only: with torch events (PDEC_TORCH_EVENTS=1) the cross-stream
         # records / waits are torch calls it would not see, so it is off for that event type
         # N > 1: the gradient all-reduce is one more recorded call (a library call with NativeGradReducer, a noted torch call
@@ -336,6 +346,14 @@ class TrainPipeline:
                                                              init_rank)
         self.evals = (Evaluation(self, eval_every, eval_inits, eval_seed, eval_y0, eval_capacity, eval_stream)
                       if self.eval_every > 0 else None)
+        # Frozen targets: the actor's finish launch of update_k rides in the critic's finish launch of update_{k+1} (module
+        # docstring; pdec_ddpg_defer_actor_finish) -- inside run(), in the eager two-stream step that kicks env_k behind the critic
+        # half and carries its events on the launches, on fresh transitions, one rank, no telemetry (its update row reads the
+        # actor behind the update).  PDEC_DEFER_ACTOR_FINISH=0: the four-launch sequence (A/B runs).
+        self.defer_actor_finish = (self.stop_events and self.kick_env_after_critic and not self.serial and not self.act_in_place
+                                   and not self.use_replay and not self.multi_rank and not self.ar_off_chain
+                                   and self._telem is None and os.environ.get("PDEC_DEFER_ACTOR_FINISH", "1") != "0")
+        self._armed = self._pending = False   # armed: inside run() with the library armed; pending: the last step left a finish
         self.reset_from(env.y0)
         self.inits.keep_y0 = False
 
@@ -434,7 +452,31 @@ class TrainPipeline:
         st.late_env = self.serial and self.ar_off_chain and st.updating and fresh
         st.kick = self.kick_env_after_critic and st.updating and not self.serial and not st.capturing
         st.use_stop = self.stop_events and st.updating and not st.capturing and not self.serial
+        st.defer = self._armed and st.kick and st.use_stop and fresh
         return st
+
+    # ------------------------------------------------------------------ the deferred actor finish (frozen targets)
+    def _arm_deferral(self, on):
+        """run() entry / exit: arm the library (declined with moving targets: the steps are then the four-launch ones), or
+        disarm it behind a flush -- outside run() nothing is pending, and every host reader sees what it always saw"""
+        if not self.defer_actor_finish:
+            return
+        if not on:
+            self._flush_actor_finish()
+        armed = C.c_int()
+        _lib.check(self.lib.pdec_ddpg_defer_actor_finish(self.actor.handle, int(on), float(self.policy.rho_effective),
+                                                         C.byref(armed)))
+        self._armed = bool(armed.value)
+
+    def _flush_actor_finish(self):
+        """the pending finish of update_{tick-1} as a launch of its own carrying ev_upd, what that update's last launch always
+        carried (recorded behind the update where the library had nothing pending)"""
+        if self._pending:
+            h = self.actor.handle
+            _lib.check(self.lib.pdec_mlp_set_stop_event(h, self.ev_upd[(self.tick - 1) % 2].h))
+            _lib.check(self.lib.pdec_ddpg_flush_actor_finish(h))
+            _lib.check(self.lib.pdec_mlp_flush_stop_event(h))
+            self._pending = False
 
     def _issue(self, k, chunk_first=False, chunk_last=False):
         """enqueue control step k.  chunk_first / chunk_last: first / last step of a chunk being CAPTURED (fork / join of
@@ -443,6 +485,8 @@ class TrainPipeline:
         st = self._plan(k, chunk_first, chunk_last)
         # 1. the waits at the top of the step
         mid_wait_prev, self._mid_wait_prev = self._mid_wait_prev, False
+        if self._pending and not st.defer:        # a step of the four-launch sequence behind a deferred one
+            self._flush_actor_finish()
         if not self.serial:
             if chunk_first:                       # fork: everything before this chunk is ordered before it on the env stream
                 self.ev_fork.record(self.s_env)
@@ -458,9 +502,12 @@ class TrainPipeline:
                     # (collective off the chain: update_{k-1} waited for env_{k-2} between its halves, see _between_halves)
                     if not mid_wait_prev:
                         self.ev_act[st.prev].wait(self.s_upd)
-                    self.ev_upd[st.prev].wait(self.s_env)
-        # 2. act_k and env_k, unless they go between the halves of update_k (late_env: both; kick: env_k)
-        if not st.late_env:
+                    # (deferred: everything step k puts on the env stream waits for ev_mid of update_k, which the update
+                    # stream reaches behind update_{k-1} -- whose actor finish, if pending, is part of that very launch)
+                    if not st.defer:
+                        self.ev_upd[st.prev].wait(self.s_env)
+        # 2. act_k and env_k, unless they go between the halves of update_k (late_env: both; kick: env_k; deferred: both)
+        if not st.late_env and not st.defer:
             self._act(st)
         if st.sample:
             # the replay route: a host function with step-dependent ring positions, re-evaluated, not replayed verbatim (_Lib.note)
@@ -473,7 +520,8 @@ class TrainPipeline:
         if st.use_stop:
             if st.kick:
                 L.check(lib.pdec_mlp_set_stop_event(pol.behavior_critic.model.handle, self.ev_mid.h))
-            L.check(lib.pdec_mlp_set_stop_event(pol.behavior_actor.model.handle, self.ev_upd[st.cur].h))
+            if not st.defer:        # (deferred: ev_upd is carried by the flush, if this finish is ever one: _flush_actor_finish)
+                L.check(lib.pdec_mlp_set_stop_event(pol.behavior_actor.model.handle, self.ev_upd[st.cur].h))
         with torch.cuda.stream(self.s_upd):
             # 4. update_k
             if st.batch is not None:
@@ -493,6 +541,8 @@ class TrainPipeline:
             # 5. its completion event
             if self.ar_off_chain and st.batch is not None:
                 pass                                    # (the completion event was recorded on the side stream)
+            elif st.defer:
+                self._pending = True                    # (its last launch is yet to come)
             elif st.use_stop:
                 L.check(lib.pdec_mlp_flush_stop_event(pol.behavior_actor.model.handle))          # no-op when consumed
             elif not self.serial:
@@ -578,6 +628,10 @@ class TrainPipeline:
             else:
                 self.ev_mid.record(self.s_upd)
             self.ev_mid.wait(self.s_env)
+            if st.defer:
+                # act_k reads the actor of update_{k-1}, whose finish was part of the launch ev_mid rode on (or a launch in
+                # front of the critic pass); the host has issued that launch, so the published copy is the new one
+                self._act(st)
             self._env(st)
         if self.act_in_place and not self.serial:
             self.ev_act[st.cur].wait(self.s_upd)
@@ -699,8 +753,14 @@ class TrainPipeline:
         if self._E_host > 0:
             assert self.E > 2 * PERIOD, "episodes must be longer than two graph periods"
             self.chunks = tuple(c for c in self.chunks if c <= self.E - 2)
-        while self.tick - self.LAG < self._first_update + 2:      # lazily created buffers / first-use uploads happen eagerly
-            self._eager()
+        # (every eager step of this method is one of run()'s -- one kind of recorded step per pipeline --, and a captured step is
+        # a four-launch one: the library is armed around the eager steps and disarmed while a chunk records)
+        self._arm_deferral(True)
+        try:
+            while self.tick - self.LAG < self._first_update + 2:  # lazily created buffers / first-use uploads happen eagerly
+                self._eager()
+        finally:
+            self._arm_deferral(False)
         self._key = self._scalar_key()
         for c in self.chunks:
             for pos in range(PERIOD):
@@ -708,8 +768,12 @@ class TrainPipeline:
                     # e.g. chunk 24 with 26-step episodes: the interior offsets 1 .. E-1-c never meet this ring phase
                     # (the search below would issue eager steps for ever); run() falls back to a smaller chunk
                     continue
-                while not (self.tick % PERIOD == pos and self._interior(self.tick, c)):
-                    self._eager()
+                self._arm_deferral(True)
+                try:
+                    while not (self.tick % PERIOD == pos and self._interior(self.tick, c)):
+                        self._eager()
+                finally:
+                    self._arm_deferral(False)
                 self._sync_streams_for_graph()
                 _lib.check(self.lib.pdec_capture_begin(self.env.handle))
                 self._capturing = True
@@ -798,7 +862,12 @@ class TrainPipeline:
         k = self.tick
         fast = (self.fast_eager and not self.drain_between and not self._after_graph and k > 0
                 and self._interior(k, 1) and self._interior(k - 1, 1))
-        prog = self._progs.get(k % PERIOD) if fast else None
+        # armed (run() with the actor's finish deferred): an interior step is a deferred one, another list of calls than the
+        # four-launch step's; the lists are those of steps that FOUND a finish pending -- not of the first step of a run() or
+        # of the step behind a flush, whose top differs
+        fast = fast and (self._pending or not self._armed)
+        key = (k % PERIOD, self._armed)
+        prog = self._progs.get(key) if fast else None
         if prog is not None:
             for f, a in prog:
                 rc = f(*a)
@@ -811,7 +880,7 @@ class TrainPipeline:
                 self._issue(k)
             finally:
                 self.lib.record_into(None)
-            self._progs[k % PERIOD] = calls
+            self._progs[key] = calls
         else:
             self._issue(k)
         self.tick += 1
@@ -819,6 +888,7 @@ class TrainPipeline:
 
     def _sync_streams_for_graph(self):
         """a graph runs wholly on the env stream: order the eager update still queued on the update stream before it"""
+        self._flush_actor_finish()            # (a graph's steps are the four-launch ones; the flush carries ev_upd)
         if not self.serial and not self._after_graph and self.tick > 0:
             self.ev_upd[(self.tick - 1) % 2].wait(self.s_env)
             if self._telem is not None and self.stop_events:
@@ -836,22 +906,26 @@ class TrainPipeline:
         if self._dtype_refusal:
             raise _lib.PdecError(self._dtype_refusal)
         self._check_key()
-        while n > 0:
-            k = self.tick
-            done = False
-            if self._captured:
-                for c in self.chunks:
-                    if c <= n and (c, k % PERIOD) in self.graphs and self._interior(k, c):
-                        self._sync_streams_for_graph()
-                        self._launch(self.graphs[(c, k % PERIOD)])
-                        self.tick += c
-                        n -= c
-                        self.n_graph_launches += 1
-                        done = True
-                        break
-            if not done:
-                self._eager()
-                n -= 1
+        self._arm_deferral(True)
+        try:
+            while n > 0:
+                k = self.tick
+                done = False
+                if self._captured:
+                    for c in self.chunks:
+                        if c <= n and (c, k % PERIOD) in self.graphs and self._interior(k, c):
+                            self._sync_streams_for_graph()
+                            self._launch(self.graphs[(c, k % PERIOD)])
+                            self.tick += c
+                            n -= c
+                            self.n_graph_launches += 1
+                            done = True
+                            break
+                if not done:
+                    self._eager()
+                    n -= 1
+        finally:
+            self._arm_deferral(False)
 
     def step(self):
         self.run(1)
@@ -938,6 +1012,7 @@ class TrainPipeline:
         self._on("_telem", "TrainPipeline.telemetry_reset: telemetry is off (telemetry=0)").reset()
 
     def sync(self):
+        self._flush_actor_finish()
         for s in (self.s_env, self.s_upd, self.s_ar, self.s_eval):
             if s is not None:
                 s.synchronize()

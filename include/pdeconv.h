@@ -514,6 +514,18 @@ int pdec_ddpg_update_critic_async(pdec_handle A, pdec_handle C, pdec_handle At, 
                                   int Bu, double gamma, double rho, int quirk, double eta_critic, void* losses_dev);
 int pdec_ddpg_update_actor_async(pdec_handle A, pdec_handle C, pdec_handle At, pdec_handle Ct,
                                  const void* s, int Bu, double rho, double eta_actor, void* losses_dev);
+/* Frozen targets (rho == 1), fused 3-layer family: the finish launch of the actor half (slab reduction + ADAM + image
+ * refresh) need not be a launch of its own.  While armed, pdec_ddpg_update_actor_async(.., rho = 1, ..) launches the pass and
+ * leaves the finish PENDING, and the next pdec_ddpg_update_critic_async issues it as extra blocks of the critic's own finish
+ * launch (the critic half reads nothing it writes): three launches per update instead of four, the same bits in every buffer.
+ * While a finish is pending, calls that read what it writes (acting, another actor pass, pdec_adam_polyak_step on the actor)
+ * are refused; the caller keeps the order critic half -> acting.  on = 0 disarms and flushes.  *armed: 1 when armed; 0 when
+ * declined (another family, rho != 1) -- then, as with a later call that passes rho != 1, the sequence is the plain one.
+ * A stop event set on the actor (pdec_mlp_set_stop_event) stays with the pending finish: a flush carries it on its launch,
+ * the paired launch records it behind itself (and carries the critic's). */
+int pdec_ddpg_defer_actor_finish(pdec_handle A, int on, double rho, int* armed);
+/* the pending finish as a launch of its own on the actor's stream; no-op when nothing is pending */
+int pdec_ddpg_flush_actor_finish(pdec_handle A);
 
 /* ---------------------------------------------------------------- replay ---- */
 /* The trajectory glue of src/PDEagent.jl:237-340 on device-resident traces (fp32, as RL.jl keeps them, :112-117):

@@ -60,6 +60,13 @@ int pdec_debug_small_update_kernel(pdec_handle actor, pdec_handle critic, pdec_h
 int pdec_debug_batched_update_route(pdec_handle actor, pdec_handle critic, pdec_handle target_actor, pdec_handle target_critic,
                                     int Bu, int which, char* name, int name_len, int64_t* lds_bytes);
 
+/* Unit-test entry (no reference counterpart): the padded weight images of a fused 3-layer network as the device holds them.
+ * which = 0: the image the update passes stage from, 1 / 2: the two published copies acting kernels read.  *nfloats = floats of
+ * one image (out_host may be null to ask for it), *pub = the copy the next acting kernel reads (0 / 1), *pending = 1 while a
+ * deferred finish of this net has not been issued (pdec_ddpg_defer_actor_finish), *paired = how many of its finish launches so
+ * far were blocks of a critic's finish launch.  Any out pointer may be null.  Copying an image synchronises the net's stream. */
+int pdec_debug_fused_image(pdec_handle mlp, int which, float* out_host, int* nfloats, int* pub, int* pending, int* paired);
+
 /* Unit-test entry (no reference counterpart): the tile plan of pdec_policy_act_members for an actor of this shape under states of
  * `state_dtype` with cols_per_member columns per member -- launches nothing.  *tile_cols = columns per workgroup (the largest
  * multiple of 64 whose two activation buffers [widest layer][tile_cols] fit 48 KB, capped at cols_per_member rounded up to 64;
