@@ -1,8 +1,8 @@
-// mfma_blocks.hpp -- device building blocks shared by the fused fp32 MFMA DDPG passes (mlp_mfma.hip: 3-layer nets,
-// mlp_mfma2.hip: 2-layer nets).  v_mfma_f32_16x16x4_f32 tiles: an output tile D[16 rows][16 cols] lives in 4 VGPRs
-// per lane (col = lane & 15, row = 4 * (lane >> 4) + r).
+// mfma_blocks.hpp -- device building blocks shared by the fused fp32 MFMA DDPG passes (mlp_mfma.hip and its fused3_*.hpp
+// headers: 3-layer nets, mlp_mfma2.hip: 2-layer nets).  v_mfma_f32_16x16x4_f32 tiles: an output tile D[16 rows][16 cols]
+// lives in 4 VGPRs per lane (col = lane & 15, row = 4 * (lane >> 4) + r).
 #pragma once
-// gradient slab accesses: non-temporal by default (round 2); -DPDEC_SLAB_NT=0 / -DPDEC_SLAB_NT_LOAD=0 build the plain forms (A/B builds)
+// gradient slab accesses: non-temporal by default; -DPDEC_SLAB_NT=0 / -DPDEC_SLAB_NT_LOAD=0 build the plain forms (A/B builds)
 #ifndef PDEC_SLAB_NT
 #define PDEC_SLAB_NT 1
 #endif
@@ -35,6 +35,34 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+// the four-MFMA step: c += sum_k a[k] * b[k] over the four k a lane holds of both operands, k = 0 .. 3 in order.  (Operands
+// by value: taken by reference the passes' instruction streams change)
+__device__ __forceinline__ f32x4 mfma4x4(f32x4 a, f32x4 b, f32x4 c) {
+  c = mfma4(a[0], b[0], c);
+  c = mfma4(a[1], b[1], c);
+  c = mfma4(a[2], b[2], c);
+  c = mfma4(a[3], b[3], c);
+  return c;
+}
+// two such steps with their MFMAs alternating: consecutive MFMAs of the wave are independent
+__device__ __forceinline__ void mfma4x4_pair(f32x4 a0, f32x4 b0, f32x4& c0, f32x4 a1, f32x4 b1, f32x4& c1) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    c0 = mfma4(a0[k], b0[k], c0);
+    c1 = mfma4(a1[k], b1[k], c1);
+  }
+}
+// a += sum over 16 * NT staged columns l[c] * r[c]: one accumulation chain (l, r: this lane's operand rows)
+template <int NT>
+__device__ __forceinline__ f32x4 tile_chain(f32x4 a, const float* l, const float* r) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const f32x4 av = *reinterpret_cast<const f32x4*>(l + 16 * t);
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(r + 16 * t);
+    a = mfma4x4(av, bv, a);
+  }
+  return a;
 }
 
 template <int MT>
@@ -95,17 +123,7 @@ __device__ __forceinline__ void gemm_pass(f32x4 (&acc)[NACC], const float* L, co
       const int ti = p / nR, tk = p - ti * nR;
       const float* lrow = L + (16 * ti + lr) * LDP + 4 * q;
       const float* rrow = R + (16 * tk + lr) * LDP + 4 * q;
-      f32x4 a = acc[pp];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const f32x4 av = *reinterpret_cast<const f32x4*>(lrow + 16 * t);
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(rrow + 16 * t);
-        a = mfma4(av[0], bv[0], a);
-        a = mfma4(av[1], bv[1], a);
-        a = mfma4(av[2], bv[2], a);
-        a = mfma4(av[3], bv[3], a);
-      }
-      acc[pp] = a;
+      acc[pp] = tile_chain<4>(acc[pp], lrow, rrow);
     }
     // keep the scheduler from hoisting the next tiles' operand loads over this tile (register pressure: the
     // whole dz2 / h1 / dz1 activation set is live here); the partner wave on the SIMD hides the LDS latency
@@ -137,29 +155,12 @@ __device__ __forceinline__ void gemm_pass_paired(f32x4 (&acc)[NACC], const float
           const f32x4 bv0 = *reinterpret_cast<const f32x4*>(r0 + 16 * t);
           const f32x4 av1 = *reinterpret_cast<const f32x4*>(l1 + 16 * t);
           const f32x4 bv1 = *reinterpret_cast<const f32x4*>(r1 + 16 * t);
-          a0 = mfma4(av0[0], bv0[0], a0);
-          a1 = mfma4(av1[0], bv1[0], a1);
-          a0 = mfma4(av0[1], bv0[1], a0);
-          a1 = mfma4(av1[1], bv1[1], a1);
-          a0 = mfma4(av0[2], bv0[2], a0);
-          a1 = mfma4(av1[2], bv1[2], a1);
-          a0 = mfma4(av0[3], bv0[3], a0);
-          a1 = mfma4(av1[3], bv1[3], a1);
+          mfma4x4_pair(av0, bv0, a0, av1, bv1, a1);
         }
         acc[pp] = a0;
         acc[pp + 1 < NACC ? pp + 1 : pp] = a1;
       } else {
-        f32x4 a0 = acc[pp];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          const f32x4 av = *reinterpret_cast<const f32x4*>(l0 + 16 * t);
-          const f32x4 bv = *reinterpret_cast<const f32x4*>(r0 + 16 * t);
-          a0 = mfma4(av[0], bv[0], a0);
-          a0 = mfma4(av[1], bv[1], a0);
-          a0 = mfma4(av[2], bv[2], a0);
-          a0 = mfma4(av[3], bv[3], a0);
-        }
-        acc[pp] = a0;
+        acc[pp] = tile_chain<NT>(acc[pp], l0, r0);
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -190,25 +191,10 @@ __device__ __forceinline__ void gemm_pass_paired_store(f32x4 (&acc)[NACC], const
           const f32x4 bv0 = *reinterpret_cast<const f32x4*>(r0 + 16 * t);
           const f32x4 av1 = *reinterpret_cast<const f32x4*>(l1 + 16 * t);
           const f32x4 bv1 = *reinterpret_cast<const f32x4*>(r1 + 16 * t);
-          a0 = mfma4(av0[0], bv0[0], a0);
-          a1 = mfma4(av1[0], bv1[0], a1);
-          a0 = mfma4(av0[1], bv0[1], a0);
-          a1 = mfma4(av1[1], bv1[1], a1);
-          a0 = mfma4(av0[2], bv0[2], a0);
-          a1 = mfma4(av1[2], bv1[2], a1);
-          a0 = mfma4(av0[3], bv0[3], a0);
-          a1 = mfma4(av1[3], bv1[3], a1);
+          mfma4x4_pair(av0, bv0, a0, av1, bv1, a1);
         }
       } else {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          const f32x4 av = *reinterpret_cast<const f32x4*>(l0 + 16 * t);
-          const f32x4 bv = *reinterpret_cast<const f32x4*>(r0 + 16 * t);
-          a0 = mfma4(av[0], bv[0], a0);
-          a0 = mfma4(av[1], bv[1], a0);
-          a0 = mfma4(av[2], bv[2], a0);
-          a0 = mfma4(av[3], bv[3], a0);
-        }
+        a0 = tile_chain<NT>(a0, l0, r0);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -273,6 +259,5 @@ __device__ __forceinline__ float block_sum(float v, float* red, int tid) {
   __syncthreads();
   return r;
 }
-
 
 }  // namespace pdec

@@ -1,6 +1,6 @@
 // mlp.hpp -- the MLP object, what every acting path and every ADAM kernel share (activations, the exploration-noise stream, the
 // beta powers) and the table of a fused DDPG kernel family.  For every file that holds an Mlp*: mlp.hip (generic path), ddpg.hip
-// (DDPG passes and their routing), act.hip (acting), mlp_mfma.hip / mlp_mfma2.hip (the two fused families), and the rollout,
+// (DDPG passes and their routing), act.hip (acting), mlp_mfma.hip with fused3_*.hpp / mlp_mfma2.hip (the two fused families), and the rollout,
 // replay, ledger, communicator and population files
 #pragma once
 #include <algorithm>
@@ -197,7 +197,7 @@ template <int N>
 using tile_c = std::integral_constant<int, N>;
 
 // ---- a fused DDPG kernel family: fp32 MFMA passes, apply and acting kernels for one class of actor / critic pairs.  Two exist:
-// fused3_family (mlp_mfma.hip: 3-layer pairs on padded weight images) and fused2_family (mlp_mfma2.hip: the reference-shaped
+// fused3_family (mlp_mfma.hip, kernels in fused3_*.hpp: 3-layer pairs on padded weight images) and fused2_family (mlp_mfma2.hip: the reference-shaped
 // 2-layer nets [ns, h, 1] / [ns+1, H, 1] on the flat parameters).  ddpg.hip and act.hip pick one through the selectors below and
 // call through the table; null = the generic path.
 struct FusedFamily {
@@ -230,7 +230,7 @@ const FusedFamily* fused_family_of_act(const Mlp* M, int cols);
 // small_act_kernel / gemm_kernel do.
 inline bool act_route_is_fused(const Mlp* M, int cols) { return fused_family_of_act(M, cols) != nullptr; }
 
-// features of the 3-layer image, not of "a family" (mlp_mfma.hip): the net predicate (stop / reduce events, reward partials) and
+// features of the 3-layer image, not of "a family" (mlp_mfma.hip, fused3_image.hpp): the net predicate (stop / reduce events, reward partials) and
 // the flat parameters of the published image the next acting kernel reads (fw_pub[pub]), enqueued on `stream`
 bool fused_net_supported(const Mlp* M);
 int fused_unpack_published(Mlp* A, float* flat_out, hipStream_t stream);

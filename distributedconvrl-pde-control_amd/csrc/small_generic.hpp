@@ -9,7 +9,7 @@
 // critic forward/backward + ADAM, actor forward/backward through the updated critic + ADAM, Polyak -- with workgroup
 // barriers between dependent layers.  Parameters, moments and gradients stay in global memory (L2-hot; a workgroup's
 // waves share the CU's L1, so a barrier orders them), activations in LDS.  fp32 like the reference's networks, ADAM
-// arithmetic in fp64 like Flux (see finish_param in mlp_mfma.hip).
+// arithmetic in fp64 like Flux (see finish_param in fused3_finish.hpp).
 #pragma once
 #include "small_args.hpp"
 

@@ -1,5 +1,5 @@
 """The case table of test_gpu_fused_shapes.py and a plain-Python restatement of the shape rules of the fused MFMA DDPG passes
-(csrc/mlp_mfma.hip: 3-layer pairs, csrc/mlp_mfma2.hip: 2-layer pairs).  Imports neither torch nor the library, so
+(csrc/mlp_mfma.hip + fused3_*.hpp: 3-layer pairs, csrc/mlp_mfma2.hip: 2-layer pairs).  Imports neither torch nor the library, so
 test_fused_shape_table.py can hold the table against the rules on a machine without a GPU.
 
 A row: (layers, ns, actor hidden, critic hidden, Bu, grad_scale, pair, act)

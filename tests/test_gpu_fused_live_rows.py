@@ -1,4 +1,4 @@
-"""The fused 3-layer DDPG passes issue no MFMA on a k-step or a tile whose operands are zero by construction (csrc/mlp_mfma.hip,
+"""The fused 3-layer DDPG passes issue no MFMA on a k-step or a tile whose operands are zero by construction (csrc/fused3_layers.hpp,
 LiveRows): the first layers run ceil(K0 / 4) of their four k-steps, and a last hidden tile that holds only the bias row of the
 gradient image (H a multiple of 16) is zero without a product.  Every skipped instruction added exact zeros, so nothing may move:
 

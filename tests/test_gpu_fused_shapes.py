@@ -1,6 +1,6 @@
 """Every instantiation of the fused MFMA DDPG passes at its width, row and batch edges, against the fp64 oracle.
 
-The passes are templates over padded tile counts (csrc/mlp_mfma.hip, csrc/mlp_mfma2.hip); a shape inside a tile is served by
+The passes are templates over padded tile counts (csrc/mlp_mfma.hip with fused3_*.hpp, csrc/mlp_mfma2.hip); a shape inside a tile is served by
 zero padding, and the lines that pad are only exercised where a shape sits ON a tile edge.  The rows of fused_shape_cases.CASES
 sit on those edges; each names the instantiation it must reach, asserted through pdec_debug_batched_update_route BEFORE anything is
 launched, and together they reach every name the dispatch can produce (test_fused_shape_table.py, on the CPU).  Per row and target
