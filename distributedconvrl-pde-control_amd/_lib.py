@@ -58,6 +58,7 @@ SIGNATURES = {
     "pdec_pde_step": [Handle, _vp, _vp, _vp, _vp],
     "pdec_featurize": [Handle, _vp, _vp, _vp], "pdec_featurize_action": [Handle, _vp, _vp, _vp, _vp], "pdec_mlp_set_noise_rows": [Handle, _i],
     "pdec_mlp_set_noise_scale": [Handle, _vp, _i64, _i],
+    "pdec_mlp_set_noise_color": [Handle, _vp, _vp, _i64, _i],
     "pdec_reward": [Handle, _vp, _vp, _vp, _vp],
     "pdec_env_step": [Handle] + [_vp] * 9,
     "pdec_rhs_eval": [Handle, _vp, _vp, _vp],

@@ -8,6 +8,7 @@ CircularArraySARTTrajectory and samples `batch_size` of them per update
 the next-state of column i sits at i + B*A (the reference's `inds .+ number_actuators`)."""
 import contextlib
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -237,6 +238,30 @@ def noise_scale_buffer(scale, n, device, who, out=None, stream=None):
     return out
 
 
+def corr_from_time(tau, dt):
+    """the step-to-step correlation exp(-dt / tau) of an Ornstein-Uhlenbeck process of correlation time tau sampled every dt
+    (the control interval): what set_noise_corr takes"""
+    tau, dt = float(tau), float(dt)
+    if not (tau > 0 and dt >= 0):
+        raise ValueError(f"corr_from_time: tau > 0 and dt >= 0 (got tau = {tau!r}, dt = {dt!r})")
+    return math.exp(-dt / tau)
+
+
+def noise_corr_ab(corr, n, who):
+    """the host array [n, 2] of {a, b = sqrt(1 - a^2)} (fp64) of a noise correlation: `corr` a scalar or n values in [0, 1)
+    (n = None: as many as given)"""
+    a = np.array(corr.cpu() if isinstance(corr, torch.Tensor) else corr, dtype=np.float64, copy=True)
+    if a.ndim == 0:
+        a = np.full(1 if n is None else n, float(a))
+    if a.ndim != 1 or a.shape[0] < 1 or (n is not None and a.shape[0] != n):
+        raise ValueError(f"{who}: expected a scalar or {'>= 1' if n is None else n} correlations in a 1-D array, got shape {a.shape}")
+    bad = np.flatnonzero(~((a >= 0) & (a < 1)))
+    if bad.size:
+        raise ValueError(f"{who}: correlations must lie in [0, 1); entry {int(bad[0])} is {float(a[bad[0]])!r}"
+                         f" ({bad.size} of {a.shape[0]} entries do not)")
+    return np.ascontiguousarray(np.stack([a, np.sqrt(1.0 - a * a)], axis=1))
+
+
 class CustomDDPGPolicy:
     """src/PDEagent.jl:121-209, 342-418"""
 
@@ -290,6 +315,8 @@ class CustomDDPGPolicy:
         self._noise = None
         self._actions = None
         self.noise_scale = None                           # set_noise_scale: float64 device tensor [n] of per-entry amplitudes
+        self.noise_corr = None                            # set_noise_corr: what was asked for (scalar or host array)
+        self.noise_ab = self.noise_state = None           # its float64 device tensors [n, 2] and [n * cols_per_entry * outputs]
         self._set_noise_rows(m)
 
     def set_reward_interleave(self, interleave):
@@ -329,6 +356,57 @@ class CustomDDPGPolicy:
         for model in [m] + list(self._acting.values()):
             model.set_noise_scale(self.noise_scale, self._noise_scale_cpe)
 
+    def set_noise_corr(self, corr, cols_per_entry=None):
+        """Temporally correlated exploration noise (pdec_mlp_set_noise_color): `corr` the step-to-step correlation a in [0, 1),
+        a scalar or n values (entry e serves cols_per_entry consecutive columns; number_actuators by default, so entry b is
+        trajectory b), or None for white noise.  Every acting call with learning then adds x * amplitude with
+        x = a x + sqrt(1 - a^2) randn kept per action element, in the place of randn * amplitude: the stationary variance is 1, so
+        act_noise and set_noise_scale mean what they meant, and corr = 0 is the white run bit for bit (corr_from_time(tau, dt)
+        gives a from a correlation time).  The policy owns the float64 device tensors self.noise_ab [n, 2] (b computed in fp64
+        on the host) and self.noise_state (zeroed here; reset_noise_state() at an episode's start) and applies them to every
+        acting clone.  With a scalar the tensors are made at the first acting call, for its number of columns.  Run state:
+        checkpoints do not store it."""
+        m = self.behavior_actor.model
+        self.noise_ab = self.noise_state = None
+        for model in [m] + list(self._acting.values()):
+            model.set_noise_color(None)
+        if corr is None:
+            self.noise_corr = None
+            return
+        cpe = self.number_actuators if cols_per_entry is None else cols_per_entry
+        if int(cpe) != cpe or int(cpe) < 1:
+            raise ValueError(f"set_noise_corr: cols_per_entry must be an integer >= 1 (got {cols_per_entry!r})")
+        ab = noise_corr_ab(corr, None, "CustomDDPGPolicy.set_noise_corr")
+        self.noise_corr = float(ab[0, 0]) if np.ndim(corr) == 0 else ab[:, 0].copy()
+        self._noise_color_cpe = int(cpe)
+        if np.ndim(corr) != 0:
+            self._noise_color_build(ab)
+
+    def _noise_color_build(self, ab):
+        m = self.behavior_actor.model
+        with self._acting_stream():
+            self.noise_ab = torch.from_numpy(ab).to(m.device)
+            self.noise_state = torch.zeros(ab.shape[0] * self._noise_color_cpe * m.dims[-1], dtype=torch.float64, device=m.device)
+        for model in [m] + list(self._acting.values()):
+            model.set_noise_color(self.noise_state, self.noise_ab, self._noise_color_cpe)
+
+    def size_noise_state(self, cols):
+        """a scalar correlation is sized by the first acting call, or by the episode start in front of it"""
+        if self.noise_corr is not None and self.noise_state is None:
+            if cols % self._noise_color_cpe:
+                raise ValueError(f"set_noise_corr: {cols} columns are no multiple of cols_per_entry = {self._noise_color_cpe}")
+            self._noise_color_build(noise_corr_ab(self.noise_corr, cols // self._noise_color_cpe, "CustomDDPGPolicy.set_noise_corr"))
+
+    def _acting_stream(self):
+        s = self.behavior_actor.model.stream
+        return torch.cuda.stream(s) if s is not None else contextlib.nullcontext()
+
+    def reset_noise_state(self):
+        """zero the AR(1) states of set_noise_corr on the acting stream (an episode's start); nothing to do without them"""
+        if self.noise_state is not None:
+            with self._acting_stream():
+                self.noise_state.zero_()
+
     @property
     def rho_effective(self):
         """the Polyak factor the update kernels receive (see quirk_frozen_targets)"""
@@ -345,6 +423,8 @@ class CustomDDPGPolicy:
             self._set_noise_rows(self._acting[key])
             if self.noise_scale is not None:
                 self._acting[key].set_noise_scale(self.noise_scale, self._noise_scale_cpe)
+            if self.noise_state is not None:
+                self._acting[key].set_noise_color(self.noise_state, self.noise_ab, self._noise_color_cpe)
         else:
             _lib.check(self.lib.pdec_mlp_copy(self._acting[key].handle, m.handle))
         return self._acting[key]
@@ -375,6 +455,8 @@ class CustomDDPGPolicy:
         m = self.behavior_actor.model
         na = m.dims[-1]
         served = False
+        if learning:
+            self.size_noise_state(cols)
         if dtype != m.dtype:
             flag = C.c_int(0)
             _lib.check(self.lib.pdec_policy_act_rng_as(m.handle, _lib.dtype_code(dtype), _lib.ptr(state), cols, float(self.act_noise),
@@ -543,6 +625,9 @@ class Agent:
         if stage == PRE_EPISODE_STAGE:        # :237-252 pop the dummy (s, a) of the previous episode
             if len(tr) > 0 and tr.n_sa > tr.n_rt:
                 tr.pop_sa(tr.stride)
+            if getattr(p, "noise_corr", None) is not None:      # set_noise_corr: an episode starts from zero noise states
+                p.size_noise_state(env.state.shape[0] * env.state.shape[1])
+                p.reset_noise_state()
         elif stage == PRE_ACT_STAGE:          # :254-274 push, then :342-361 update
             action = args[2]
             s = env.state.reshape(-1, env.state.shape[-1])

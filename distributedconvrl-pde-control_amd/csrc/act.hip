@@ -14,8 +14,8 @@ using namespace pdec;
 // the activation -- the order of gemm_kernel's epilogue --, the Philox / Box-Muller draw of randn_kernel for element
 // column * outputs + row, then v += noise * act_noise and the clamp of act_noise_clamp_kernel.
 // (SMALL_ACT_MAXL: mlp.hpp)
-// AN: what carries the amplitude -- the launch scalar, or NoiseScale (pdec_mlp_set_noise_scale; a kernel family of its own, so
-// that the scalar kernels keep their arguments and their code)
+// AN: what carries the amplitude -- the launch scalar, NoiseScale (pdec_mlp_set_noise_scale; a kernel family of its own, so
+// that the scalar kernels keep their arguments and their code) or NoiseColor (pdec_mlp_set_noise_color; likewise)
 template <class AN>
 struct SmallActArgsT {
   int L, cols, maxw, learning, nrows;
@@ -65,7 +65,7 @@ __device__ __forceinline__ T* small_act_body(const SmallActArgsT<AN>& g, const T
     T* t = xin; xin = xout; xout = t;
   }
   const int no = g.dims[g.L];
-  constexpr bool NS = std::is_same<AN, NoiseScale>::value;
+  constexpr bool NS = noise_per_column<AN>;
   T an = 0;
   if constexpr (!NS) an = (T)g.act_noise;
   const T lim = (T)g.lim;
@@ -73,7 +73,7 @@ __device__ __forceinline__ T* small_act_body(const SmallActArgsT<AN>& g, const T
     const int c = i / no, f = i - c * no;
     T v = xin[f * cols + c];
     if (g.learning && f < g.nrows) {
-      const T z = (T)noise_normal(g.seed, offset, i);
+      const T z = noise_draw<T>(g.act_noise, noise_normal(g.seed, offset, i), c, i);
       if constexpr (NS) an = noise_amp<T>(g.act_noise, c);
       v += z * an;
     }
@@ -251,6 +251,9 @@ static int small_act_launch(Mlp* M, int dtype, const void* state, int cols, AN a
 }
 static int small_act(Mlp* M, int dtype, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
                      uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc) {
+  if (learning && M->noise_color)
+    return small_act_launch(M, dtype, state, cols, noise_color_of(M, act_noise), act_limit, learning, seed, offset, actions_out,
+                            ctr_cur, ctr_next, ctr_inc);
   if (M->noise_scale)
     return small_act_launch(M, dtype, state, cols, noise_scale_of(M), act_limit, learning, seed, offset, actions_out, ctr_cur,
                             ctr_next, ctr_inc);
@@ -284,14 +287,15 @@ static int policy_act_rng_impl(pdec_handle actor, Mlp* M, const void* state, int
     return small_act(M, M->dtype, state, cols, act_noise, act_limit, learning, seed, offset, actions_out, ctr_cur, ctr_next, ctr_inc);
   void* noise = nullptr;
   const size_t n = (size_t)cols * M->dims[M->L];
+  const int zdtype = learning && M->noise_color ? PDEC_F64 : M->dtype;   // (the recurrence takes z as the double it is drawn as)
   if (learning || ctr_cur) {
-    if (M->noise.bytes < n * dtype_size(M->dtype)) PDEC_HIP(M->noise.alloc(n * dtype_size(M->dtype)));
+    if (M->noise.bytes < n * dtype_size(zdtype)) PDEC_HIP(M->noise.alloc(n * dtype_size(zdtype)));
     ProfScope ps(M, "randn");
-    int rc = launch_randn(M, M->noise.p, n, M->dtype, seed, offset, ctr_cur, ctr_next, ctr_inc);
+    int rc = launch_randn(M, M->noise.p, n, zdtype, seed, offset, ctr_cur, ctr_next, ctr_inc);
     if (rc) return rc;
     if (learning) noise = M->noise.p;
   }
-  return pdec_policy_act(actor, state, noise, cols, act_noise, act_limit, actions_out);
+  return policy_act_noise(M, state, noise, zdtype, cols, act_noise, act_limit, actions_out, "pdec_policy_act_rng");
 }
 
 int pdec_policy_act_rng(pdec_handle actor, const void* state, int cols, double act_noise, double act_limit,
@@ -360,7 +364,7 @@ int pdec_step_glue(pdec_handle actor, pdec_handle trajectory_handle, int dtype, 
   }
   *served = 1;
   ProfScope ps(M, "step_glue");
-  // by what carries the amplitude: the call's scalar, or the array set on the actor (a kernel family of its own)
+  // by what carries the amplitude: the call's scalar, or the arrays set on the actor (each a kernel family of its own)
   auto launch = [&](auto amp) -> int {
     using AN = decltype(amp);
     StepGlueArgsT<AN> g{};
@@ -382,6 +386,7 @@ int pdec_step_glue(pdec_handle actor, pdec_handle trajectory_handle, int dtype, 
     PDEC_HIP(hipGetLastError());
     return PDEC_OK;
   };
+  if (act_mode == 1 && M->noise_color) return launch(noise_color_of(M, act_noise));
   return act_mode == 1 && M->noise_scale ? launch(noise_scale_of(M)) : launch(act_noise);
 }
 
@@ -449,6 +454,20 @@ int pdec_mlp_set_noise_scale(pdec_handle actor, const double* scale_dev, int64_t
   PDEC_REQUIRE(n >= 1 && cols_per_entry >= 1 && n * cols_per_entry <= INT32_MAX, "pdec_mlp_set_noise_scale: %lld entries x %d columns",
                (long long)n, cols_per_entry);
   M->noise_scale = scale_dev; M->noise_scale_n = n; M->noise_scale_cpe = cols_per_entry;
+  return PDEC_OK;
+}
+
+int pdec_mlp_set_noise_color(pdec_handle actor, double* state_dev, const double* ab_dev, int64_t n, int cols_per_entry) {
+  GET_MLP(M, actor);
+  if (!state_dev) {
+    M->noise_color = nullptr; M->noise_color_ab = nullptr; M->noise_color_n = 0; M->noise_color_cpe = 1;
+    return PDEC_OK;
+  }
+  PDEC_REQUIRE(n >= 1 && cols_per_entry >= 1 && n <= INT32_MAX / cols_per_entry &&
+                   n * cols_per_entry <= INT32_MAX / M->dims[M->L],
+               "pdec_mlp_set_noise_color: %lld entries x %d columns x %d outputs", (long long)n, cols_per_entry, M->dims[M->L]);
+  PDEC_REQUIRE(ab_dev, "pdec_mlp_set_noise_color: null {a, b} array with a state array set");
+  M->noise_color = state_dev; M->noise_color_ab = ab_dev; M->noise_color_n = n; M->noise_color_cpe = cols_per_entry;
   return PDEC_OK;
 }
 

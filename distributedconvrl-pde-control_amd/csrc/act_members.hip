@@ -135,6 +135,7 @@ extern "C" int pdec_policy_act_members(pdec_handle henv, const pdec_handle* acto
   for (int m = 0; m < M; ++m) {
     nets[m] = lookup_as<Mlp>(actors[m], Kind::Mlp);
     if (!nets[m]) { set_error("pdec_policy_act_members: bad actor handle (member %d)", m); return PDEC_E_HANDLE; }
+    PDEC_REFUSE_NOISE_COLOR(nets[m], "pdec_policy_act_members", "the member forms do not serve it");
   }
   if (!act_members_served(E->cfg.dtype, nets, cols_per_member)) return PDEC_OK;
   const int rc = act_members_launch(*E, nets, state, cols_per_member, act_limit, actions_out);

@@ -15,7 +15,8 @@ struct ActLds {
 // actions = clamp(actor(state) + randn * act_noise, +-act_limit)  (src/PDEagent.jl:183-207) in ONE launch on the
 // same MFMA building blocks as the update passes (16 columns per wave, layer outputs chained as B operands);
 // exploration noise from the same Philox counter stream as pdec_randn (element index = column), so both
-// paths draw identical numbers.  AN: what carries the amplitude -- the launch scalar, or NoiseScale (pdec_mlp_set_noise_scale).
+// paths draw identical numbers.  AN: what carries the amplitude -- the launch scalar, NoiseScale (pdec_mlp_set_noise_scale) or NoiseColor
+// (pdec_mlp_set_noise_color).
 #define ACT_THREADS 256
 template <int MTA, class AN = float>
 __global__ __launch_bounds__(ACT_THREADS) void policy_act_fused_kernel(FNet f, const float* __restrict__ state, int cols, int ns,
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(ACT_THREADS) void policy_act_fused_kernel(FNet f, c
   if (!valid || q != 0) return;
   if (tanh_out) o = tanhf(o);
   if (learning) {
-    const float z = (float)noise_normal(seed, offset, c);
+    const float z = noise_draw<float>(act_noise, noise_normal(seed, offset, c), c, c);
     o += z * noise_amp<float>(act_noise, c);
   }
   out[c] = fminf(fmaxf(o, -lim), lim);

@@ -198,15 +198,18 @@ __global__ void cast_copy_kernel(TD* __restrict__ dst, const TS* __restrict__ sr
 
 // actions[c][f] = clamp(H[f][c] + noise[c][f]*act_noise, +-lim)
 // (noise on the first nrows outputs only: the action-memory rows stay noise-free, src/PDEagent.jl:201)
-// AN: what carries the amplitude -- the launch scalar, or NoiseScale (pdec_mlp_set_noise_scale)
+// AN: what carries the amplitude -- the launch scalar, NoiseScale (pdec_mlp_set_noise_scale) or NoiseColor
+// (pdec_mlp_set_noise_color: the kernel advances the state of element c n + f with z = noise[c n + f], and `noise` then points
+// to DOUBLES whatever T is -- z as it is drawn; the parameter keeps its type so that the other instantiations keep their names)
 template <class T, class AN = T>
 __global__ void act_noise_clamp_kernel(const T* __restrict__ H, const T* __restrict__ noise, int cols, int n, int nrows,
                                        AN act_noise, T lim, T* __restrict__ out) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= cols) return;
+  const noise_elem_t<T, AN>* z = reinterpret_cast<const noise_elem_t<T, AN>*>(noise);
   for (int f = 0; f < n; ++f) {
     T v = H[(size_t)f * cols + c];
-    if (noise && f < nrows) v += noise[(size_t)c * n + f] * noise_amp<T>(act_noise, c);
+    if (noise && f < nrows) v += noise_draw<T>(act_noise, z[(size_t)c * n + f], c, (size_t)c * n + f) * noise_amp<T>(act_noise, c);
     v = v < -lim ? -lim : (v > lim ? lim : v);
     out[(size_t)c * n + f] = v;
   }
@@ -444,6 +447,48 @@ static int get_flat(Mlp* M, const DevBuf& buf, void* host) {
   return PDEC_OK;
 }
 
+// pdec_policy_act, with the noise in `noise_dtype` (mlp.hpp)
+int pdec::policy_act_noise(Mlp* M, const void* state, const void* noise, int noise_dtype, int cols, double act_noise,
+                           double act_limit, void* actions_out, const char* who) {
+  PDEC_REQUIRE(state && actions_out, "%s: null", who);
+  if (noise) PDEC_REQUIRE_NOISE_COLS(M, cols, who);
+  PDEC_REQUIRE(noise_dtype == M->dtype || (noise && M->noise_color && noise_dtype == PDEC_F64), "%s: noise of dtype %d", who, noise_dtype);
+  if (noise && M->noise_color && noise_dtype != PDEC_F64) {   // a caller's fp32 noise: the recurrence reads z as doubles
+    const size_t nz = (size_t)cols * M->dims[M->L];
+    if (M->noise.bytes < nz * sizeof(double)) PDEC_HIP(M->noise.alloc(nz * sizeof(double)));
+    hipLaunchKernelGGL((cast_copy_kernel<double, float>), dim3(cdiv((long)nz, 256)), dim3(256), 0, M->stream, M->noise.as<double>(),
+                       (const float*)noise, (int)nz);
+    noise = M->noise.p;
+  }
+  int rc = M->pack(state, M->dims[0], 0, nullptr, 0, 0, cols);
+  if (rc) return rc;
+  rc = M->forward(cols);
+  if (rc) return rc;
+  const int no = M->dims[M->L], nrows = M->noise_rows < 0 ? no : M->noise_rows;
+  dim3 grid(cdiv(cols, 256)), block(256);
+  ProfScope ps(M, "act_noise_clamp");
+  if (noise && M->noise_color && M->dtype == PDEC_F64)
+    hipLaunchKernelGGL((act_noise_clamp_kernel<double, NoiseColor>), grid, block, 0, M->stream, M->H[M->L].as<double>(),
+                       (const double*)noise, cols, no, nrows, noise_color_of(M, act_noise), act_limit, (double*)actions_out);
+  else if (noise && M->noise_color)
+    hipLaunchKernelGGL((act_noise_clamp_kernel<float, NoiseColor>), grid, block, 0, M->stream, M->H[M->L].as<float>(),
+                       (const float*)noise, cols, no, nrows, noise_color_of(M, act_noise), (float)act_limit, (float*)actions_out);
+  else if (noise && M->noise_scale && M->dtype == PDEC_F64)
+    hipLaunchKernelGGL((act_noise_clamp_kernel<double, NoiseScale>), grid, block, 0, M->stream, M->H[M->L].as<double>(),
+                       (const double*)noise, cols, no, nrows, noise_scale_of(M), act_limit, (double*)actions_out);
+  else if (noise && M->noise_scale)
+    hipLaunchKernelGGL((act_noise_clamp_kernel<float, NoiseScale>), grid, block, 0, M->stream, M->H[M->L].as<float>(),
+                       (const float*)noise, cols, no, nrows, noise_scale_of(M), (float)act_limit, (float*)actions_out);
+  else if (M->dtype == PDEC_F64)
+    hipLaunchKernelGGL((act_noise_clamp_kernel<double>), grid, block, 0, M->stream, M->H[M->L].as<double>(), (const double*)noise,
+                       cols, no, nrows, act_noise, act_limit, (double*)actions_out);
+  else
+    hipLaunchKernelGGL((act_noise_clamp_kernel<float>), grid, block, 0, M->stream, M->H[M->L].as<float>(), (const float*)noise, cols,
+                       no, nrows, (float)act_noise, (float)act_limit, (float*)actions_out);
+  PDEC_HIP(hipGetLastError());
+  return PDEC_OK;
+}
+
 extern "C" {
 
 int pdec_mlp_create(pdec_handle* h, int dtype, int n_layers, const int32_t* dims, const int32_t* acts,
@@ -638,29 +683,7 @@ int pdec_polyak(pdec_handle dst, pdec_handle src, double rho) {
 int pdec_policy_act(pdec_handle actor, const void* state, const void* noise, int cols, double act_noise,
                     double act_limit, void* actions_out) {
   GET_MLP(M, actor);
-  PDEC_REQUIRE(state && actions_out, "pdec_policy_act: null");
-  if (noise) PDEC_REQUIRE_NOISE_COLS(M, cols, "pdec_policy_act");
-  int rc = M->pack(state, M->dims[0], 0, nullptr, 0, 0, cols);
-  if (rc) return rc;
-  rc = M->forward(cols);
-  if (rc) return rc;
-  const int no = M->dims[M->L], nrows = M->noise_rows < 0 ? no : M->noise_rows;
-  dim3 grid(cdiv(cols, 256)), block(256);
-  ProfScope ps(M, "act_noise_clamp");
-  if (noise && M->noise_scale && M->dtype == PDEC_F64)
-    hipLaunchKernelGGL((act_noise_clamp_kernel<double, NoiseScale>), grid, block, 0, M->stream, M->H[M->L].as<double>(),
-                       (const double*)noise, cols, no, nrows, noise_scale_of(M), act_limit, (double*)actions_out);
-  else if (noise && M->noise_scale)
-    hipLaunchKernelGGL((act_noise_clamp_kernel<float, NoiseScale>), grid, block, 0, M->stream, M->H[M->L].as<float>(),
-                       (const float*)noise, cols, no, nrows, noise_scale_of(M), (float)act_limit, (float*)actions_out);
-  else if (M->dtype == PDEC_F64)
-    hipLaunchKernelGGL((act_noise_clamp_kernel<double>), grid, block, 0, M->stream, M->H[M->L].as<double>(), (const double*)noise,
-                       cols, no, nrows, act_noise, act_limit, (double*)actions_out);
-  else
-    hipLaunchKernelGGL((act_noise_clamp_kernel<float>), grid, block, 0, M->stream, M->H[M->L].as<float>(), (const float*)noise, cols,
-                       no, nrows, (float)act_noise, (float)act_limit, (float*)actions_out);
-  PDEC_HIP(hipGetLastError());
-  return PDEC_OK;
+  return policy_act_noise(M, state, noise, M->dtype, cols, act_noise, act_limit, actions_out, "pdec_policy_act");
 }
 
 int pdec_randn(pdec_handle any_handle, void* dst, size_t n, int dtype, uint64_t seed, uint64_t offset) {

@@ -53,6 +53,10 @@ struct Mlp : Object {
   const double* noise_scale = nullptr;   // pdec_mlp_set_noise_scale: the caller's device array of amplitudes (null: the call's scalar)
   int64_t noise_scale_n = 0;             // its entries; an acting call then has noise_scale_n * noise_scale_cpe columns
   int noise_scale_cpe = 1;
+  double* noise_color = nullptr;         // pdec_mlp_set_noise_color: the caller's device array of AR(1) states (null: white noise)
+  const double* noise_color_ab = nullptr;  // its {a, b} per entry
+  int64_t noise_color_n = 0;             // entries; an acting call then has noise_color_n * noise_color_cpe columns
+  int noise_color_cpe = 1;
   std::vector<DevBuf> H;             // activations, feature-major [dims[l]][cols]
   DevBuf dz[2];                      // ping-pong dL/dz buffers [maxdim][cols]
   DevBuf dy;                         // dL/dy of the output layer [dims[L]][cols]
@@ -108,6 +112,10 @@ ActRoute act_route(const Mlp* M, int cols);
 // counter of pdec_policy_act_rng_dev, see FusedFamily::policy_act
 int launch_randn(Object* o, void* dst, size_t n, int dtype, uint64_t seed, uint64_t offset, const uint64_t* ctr_cur,
                  uint64_t* ctr_next, uint64_t ctr_inc);
+// pdec_policy_act with the noise in `noise_dtype` (mlp.hip).  A state array set on M (pdec_mlp_set_noise_color) is advanced with
+// noise[] as z, read as doubles: pdec_policy_act_rng draws them so, a caller's fp32 noise is converted first
+int policy_act_noise(Mlp* M, const void* state, const void* noise, int noise_dtype, int cols, double act_noise,
+                     double act_limit, void* actions_out, const char* who);
 
 // Philox4x32-10 counter-based generator (the exploration noise that replaces randn(rng), src/PDEagent.jl:201)
 __device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t k1) {
@@ -157,11 +165,58 @@ __device__ __forceinline__ T noise_amp(S a, I) { return (T)a; }
 template <class T, class I>
 __device__ __forceinline__ T noise_amp(NoiseScale s, I c) { return (T)s.scale[c / s.cols_per_entry]; }
 inline NoiseScale noise_scale_of(const Mlp* M) { return NoiseScale{M->noise_scale, M->noise_scale_cpe}; }
-// an acting call of `cols` columns against the array set on M (none set: fine)
-#define PDEC_REQUIRE_NOISE_COLS(M, cols, who)                                                                                  \
-  PDEC_REQUIRE(!(M)->noise_scale || (long long)(cols) == (long long)(M)->noise_scale_n * (M)->noise_scale_cpe,                 \
-               "%s: %d columns, but the noise scale set on the actor serves %lld entries x %d columns = %lld", who, (int)(cols), \
-               (long long)(M)->noise_scale_n, (M)->noise_scale_cpe, (long long)(M)->noise_scale_n * (M)->noise_scale_cpe)
+// the number a kernel multiplies by the amplitude: the normal z of element i, converted to the kernel's type
+template <class T, class S, class Z, class I, class J>
+__device__ __forceinline__ T noise_draw(S, Z z, I, J) { return (T)z; }
+
+// ---- temporally correlated noise (pdec_mlp_set_noise_color): the third carrier.  Element i = column * outputs + row keeps an
+// AR(1) state x[i] in the caller's device array, a double whatever the kernel's type; a learning call advances it with the normal
+// z the white call draws for that element, x = a_e x + b_e z (e = column / cols_per_entry), stores it, and adds (T)x times the
+// amplitude -- entry e of the scale array where one is set too, the call's scalar otherwise (chosen at run time: ONE
+// instantiation per kernel).  The lane that draws z owns x[i], so the load and the store need no synchronisation.  a = 0, b = 1
+// gives x = z exactly, and such a call is the white call bit for bit.
+struct NoiseColor {
+  double* state;
+  const double* ab;
+  int cols_per_entry;
+  const double* scale;
+  double amp;
+};
+template <class T, class I>
+__device__ __forceinline__ T noise_amp(const NoiseColor& k, I c) { return (T)(k.scale ? k.scale[c / k.cols_per_entry] : k.amp); }
+template <class T, class Z, class I, class J>
+__device__ __forceinline__ T noise_draw(const NoiseColor& k, Z z, I c, J i) {
+  const double* ab = k.ab + 2 * (size_t)(c / k.cols_per_entry);
+  const double x = ab[0] * k.state[i] + ab[1] * (double)z;
+  k.state[i] = x;
+  return (T)x;
+}
+// the element type of the noise[] an acting sequence hands to its last kernel: the kernel's own, or z as it is drawn
+template <class T, class AN>
+using noise_elem_t = std::conditional_t<std::is_same<AN, NoiseColor>::value, double, T>;
+inline NoiseColor noise_color_of(const Mlp* M, double act_noise) {
+  return NoiseColor{M->noise_color, M->noise_color_ab, M->noise_color_cpe, M->noise_scale, act_noise};
+}
+// is AN one of the carriers that hold an amplitude per column?
+template <class AN>
+inline constexpr bool noise_per_column = std::is_same<AN, NoiseScale>::value || std::is_same<AN, NoiseColor>::value;
+
+// an acting call of `cols` columns against the arrays set on M (none set: fine)
+#define PDEC_REQUIRE_NOISE_COLS(M, cols, who)                                                                                    \
+  do {                                                                                                                           \
+    PDEC_REQUIRE(!(M)->noise_scale || (long long)(cols) == (long long)(M)->noise_scale_n * (M)->noise_scale_cpe,                 \
+                 "%s: %d columns, but the noise scale set on the actor serves %lld entries x %d columns = %lld", who, (int)(cols), \
+                 (long long)(M)->noise_scale_n, (M)->noise_scale_cpe, (long long)(M)->noise_scale_n * (M)->noise_scale_cpe);     \
+    PDEC_REQUIRE(!(M)->noise_color || (long long)(cols) == (long long)(M)->noise_color_n * (M)->noise_color_cpe,                 \
+                 "%s: %d columns, but the noise color set on the actor serves %lld entries x %d columns = %lld", who, (int)(cols), \
+                 (long long)(M)->noise_color_n, (M)->noise_color_cpe, (long long)(M)->noise_color_n * (M)->noise_color_cpe);     \
+    PDEC_REQUIRE(!(M)->noise_color || !(M)->noise_scale || (M)->noise_color_cpe == (M)->noise_scale_cpe,                         \
+                 "%s: the noise color set on the actor has %d columns per entry, its noise scale %d: they must be equal", who,   \
+                 (M)->noise_color_cpe, (M)->noise_scale_cpe);                                                                    \
+  } while (0)
+// an entry that explores, or runs members, and has no AR(1) state to advance
+#define PDEC_REFUSE_NOISE_COLOR(M, who, why)                                                                            \
+  PDEC_REQUIRE(!(M)->noise_color, "%s: a noise color is set on the actor (pdec_mlp_set_noise_color); %s", who, why)
 
 // kernel-side view of the beta powers: read `cur` (every thread that needs it), one thread of the grid writes `next`
 struct BpArgs {
@@ -214,7 +269,8 @@ struct FusedFamily {
                      const AdamPolyak* apply);
   int (*adam_polyak)(Mlp* M, Mlp* Mt, const AdamPolyak& ap);
   // ctr_cur != null: the noise offset is *ctr_cur (+ offset) and one thread writes *ctr_next = that + ctr_inc.  With an array set
-  // on A (pdec_mlp_set_noise_scale) the launch takes the kernel's NoiseScale instantiation and act_noise is not read
+  // on A (pdec_mlp_set_noise_scale) the launch takes the kernel's NoiseScale instantiation and act_noise is not read; with a
+  // state array set (pdec_mlp_set_noise_color) and learning != 0 its NoiseColor instantiation
   int (*policy_act)(Mlp* A, const void* state, int cols, double act_noise, double act_limit, int learning, uint64_t seed,
                     uint64_t offset, void* actions_out, const uint64_t* ctr_cur, uint64_t* ctr_next, uint64_t ctr_inc);
   // kernel name and dynamic LDS bytes of the pass / acting launch the functions above would make (nothing is launched)

@@ -379,7 +379,8 @@ static int fused_policy_act(Mlp* A, const void* state, int cols, double act_nois
       if (A->prof) PDEC_TIMED_LAUNCH(A, "policy_act_fused", kern, grid, block, lds, ACT_ARGS(an));
       else hipLaunchKernelGGL(kern, grid, block, lds, A->stream, ACT_ARGS(an));
     };
-    if (A->noise_scale) go(policy_act_fused_kernel<decltype(MTA)::value, NoiseScale>, noise_scale_of(A));
+    if (learning && A->noise_color) go(policy_act_fused_kernel<decltype(MTA)::value, NoiseColor>, noise_color_of(A, act_noise));
+    else if (A->noise_scale) go(policy_act_fused_kernel<decltype(MTA)::value, NoiseScale>, noise_scale_of(A));
     else go(policy_act_fused_kernel<decltype(MTA)::value>, (float)act_noise);
 #undef ACT_ARGS
     return (int)PDEC_OK;

@@ -686,7 +686,7 @@ __global__ void apply2_kernel(Finish2Args g_in, int n) {
 // actions = clamp(actor(state) + randn * act_noise, +-act_limit)   (src/PDEagent.jl:183-207) in ONE launch: first layer
 // on MFMA out of the padded LDS image, output row + tanh, exploration noise from the Philox stream of pdec_randn
 // (element index = column: both paths draw identical numbers), clamp.  256 threads = 4 waves x 16 columns.  AN: what carries
-// the amplitude -- the launch scalar, or NoiseScale (pdec_mlp_set_noise_scale).
+// the amplitude -- the launch scalar, NoiseScale (pdec_mlp_set_noise_scale) or NoiseColor (pdec_mlp_set_noise_color).
 template <int MTA, int KB, class AN = float>
 __global__ __launch_bounds__(256) void policy_act2_kernel(Net2 n, const float* __restrict__ state, int cols, AN act_noise,
                                                           float lim, int learning, int tanh_out, uint64_t seed, uint64_t offset,
@@ -719,7 +719,7 @@ __global__ __launch_bounds__(256) void policy_act2_kernel(Net2 n, const float* _
   if (!valid || q != 0) return;
   if (tanh_out) o = tanhf(o);
   if (learning) {
-    const float z = (float)noise_normal(seed, offset, c);
+    const float z = noise_draw<float>(act_noise, noise_normal(seed, offset, c), c, c);
     o += z * noise_amp<float>(act_noise, c);
   }
   out[c] = fminf(fmaxf(o, -lim), lim);
@@ -919,7 +919,11 @@ static int fused2_policy_act(Mlp* A, const void* state, int cols, double act_noi
   int rc = visit2_act(n.kb, mta, [&](auto MTA, auto KB) {
     constexpr int mta_ = decltype(MTA)::value, kb_ = decltype(KB)::value;
     const size_t lds = act2_lds<mta_, kb_>();
-    if (A->noise_scale)
+    if (learning && A->noise_color)
+      hipLaunchKernelGGL((policy_act2_kernel<mta_, kb_, NoiseColor>), grid, block, lds, A->stream, n, (const float*)state, cols,
+                         noise_color_of(A, act_noise), (float)act_limit, learning, tanh_out, seed, offset, (float*)actions_out,
+                         ctr_cur, ctr_next, ctr_inc);
+    else if (A->noise_scale)
       hipLaunchKernelGGL((policy_act2_kernel<mta_, kb_, NoiseScale>), grid, block, lds, A->stream, n, (const float*)state, cols,
                          noise_scale_of(A), (float)act_limit, learning, tanh_out, seed, offset, (float*)actions_out, ctr_cur,
                          ctr_next, ctr_inc);

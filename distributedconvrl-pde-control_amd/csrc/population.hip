@@ -48,6 +48,8 @@ int pdec_population_create(pdec_handle* out, int M, const pdec_handle* actors, c
     PDEC_REQUIRE(!A->halt && !C->halt, "pdec_population_create: member %d: an episode halt flag is attached", m);
     PDEC_REQUIRE(!A->noise_scale, "pdec_population_create: member %d: a noise scale array is set on its actor "
                                   "(pdec_mlp_set_noise_scale); a member's amplitude is the act_noise of its row", m);
+    PDEC_REQUIRE(!A->noise_color, "pdec_population_create: member %d: a noise color is set on its actor "
+                                  "(pdec_mlp_set_noise_color); the member glue does not serve it", m);
     BpArgs bp{};
     int rc;
     if ((rc = bp_begin(A, 0.9, 0.999, &bp)) || (rc = bp_begin(C, 0.9, 0.999, &bp))) return rc;   // (uploads the powers once)

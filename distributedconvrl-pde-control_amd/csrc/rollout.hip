@@ -104,6 +104,7 @@ extern "C" int pdec_rollout(pdec_handle henv, pdec_handle hactor, int T, void* y
   const int ns = env_ns(c), cols = c.B * (c.mono ? 1 : c.A), na = A->dims[A->L];
   PDEC_REQUIRE(A->dims[0] == (c.mono ? c.S : ns) && cols * na == c.B * c.A * env_na(c),
                "pdec_rollout: actor shape %d -> %d does not match the state/action matrices", A->dims[0], na);
+  if (learning) PDEC_REFUSE_NOISE_COLOR(A, "pdec_rollout", "an exploring rollout does not advance its state: act step by step");
   const bool ntab = learning && A->noise_scale;
   if (ntab) PDEC_REQUIRE_NOISE_COLS(A, cols, "pdec_rollout");
   const RollSpec spec{T, learning, act_noise, act_limit, seed, offset, E->control_from, ntab ? A->noise_scale : nullptr, A->noise_scale_cpe};
@@ -140,6 +141,7 @@ extern "C" int pdec_rollout_members(pdec_handle henv, const pdec_handle* actors,
   for (int m = 0; m < M; ++m) {
     nets[m] = lookup_as<Mlp>(actors[m], Kind::Mlp);
     if (!nets[m]) { set_error("pdec_rollout_members: bad actor handle (member %d)", m); return PDEC_E_HANDLE; }
+    PDEC_REFUSE_NOISE_COLOR(nets[m], "pdec_rollout_members", "the member forms do not serve it");
   }
   for (int m = 1; m < M; ++m)
     if (nets[m]->dims != nets[0]->dims || nets[m]->acts != nets[0]->acts || nets[m]->dtype != nets[0]->dtype)

@@ -44,6 +44,7 @@ class HipMLP:
                                             self.max_cols))
         self.stream = stream
         self.noise_scale = None
+        self.noise_color = None
         if stream is not None:
             _lib.check(self.lib.pdec_set_stream(self._h, C.c_void_p(stream.cuda_stream)))
         if params is not None:
@@ -127,6 +128,25 @@ class HipMLP:
             raise _lib.PdecError("HipMLP.set_noise_scale: a contiguous float64 device tensor [n]")
         _lib.check(self.lib.pdec_mlp_set_noise_scale(self._h, _lib.ptr(scale), int(scale.shape[0]), int(cols_per_entry)))
         self.noise_scale = (scale, int(cols_per_entry))
+
+    def set_noise_color(self, state, ab=None, cols_per_entry=1):
+        """pdec_mlp_set_noise_color: `state` a contiguous float64 device tensor of n * cols_per_entry * outputs AR(1) states and
+        `ab` one [n, 2] of {a, b} per entry, both kept alive by this object (a learning call advances
+        state[c * outputs + f] = a state + b z and adds it times the amplitude in the place of z), or state = None for white noise.
+        self.noise_color: (state, ab, cols_per_entry) or None."""
+        if state is None:
+            _lib.check(self.lib.pdec_mlp_set_noise_color(self._h, None, None, 0, 1))
+            self.noise_color = None
+            return
+        ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+        if not (ok(state) and ok(ab) and ab.dim() == 2 and ab.shape[1] == 2):
+            raise _lib.PdecError("HipMLP.set_noise_color: contiguous float64 device tensors, state [n * cols_per_entry * outputs] and ab [n, 2]")
+        n, cpe = int(ab.shape[0]), int(cols_per_entry)
+        if state.numel() != n * cpe * self.dims[-1]:
+            raise _lib.PdecError(f"HipMLP.set_noise_color: {state.numel()} states, but {n} entries x {cpe} columns x "
+                                 f"{self.dims[-1]} outputs = {n * cpe * self.dims[-1]}")
+        _lib.check(self.lib.pdec_mlp_set_noise_color(self._h, _lib.ptr(state), _lib.ptr(ab), n, cpe))
+        self.noise_color = (state, ab, cpe)
 
     def clone(self, dtype=None, max_cols=None):
         m = HipMLP(self.dims, self.acts, None, dtype or self.dtype, self.device, max_cols or self.max_cols, self.stream)

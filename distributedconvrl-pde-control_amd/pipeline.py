@@ -105,13 +105,17 @@ _LEDGER_OFF, _EVAL_OFF = ("TrainPipeline: the episode ledger is off (log_episode
                           "TrainPipeline: evaluations are off (eval_every=0)")
 
 
+_NOISE_CORR_PER_TRAJ = ("TrainPipeline(noise_corr=...) belongs to lock-stepped episodes: with episodes='per_trajectory' a "
+                        "restarted trajectory would have to zero its noise states inside the boundary launch")
+
+
 class TrainPipeline:
     def __init__(self, env, agent, lag=2, episode_steps=51, stream_env=None, stream_upd=None, use_graphs=True,
                  chunks=(24, 6, 1), use_replay=False, noise_seed=1234, kick_env_after_critic=None, stream_ar=None,
                  ar_off_chain=None, log_episodes=0, min_best_episode=0, random_init=False, init_seed=0, init_rng=None,
                  init_rank=(0, 1), eval_every=0, eval_inits=8, eval_seed=0, eval_y0=None, eval_capacity=64, eval_stream=None,
                  best_by="train", noise_scale=None, episodes="lockstep", stagger=False, n_step=1,
-                 telemetry=0, telemetry_every=1):
+                 telemetry=0, telemetry_every=1, noise_corr=None):
         """env: PDEenv on `stream_env`; agent: create_agent(..., stream=stream_upd).  lag: the update of step k trains on
         the transition of step k - lag (>= 1).  episode_steps: lock-stepped episodes of that many control steps (0: one
         endless episode): the last transition is terminal (done = time >= te, src/PDEenv.jl:227) and the next step starts
@@ -149,6 +153,14 @@ class TrainPipeline:
 
         noise_scale = [B] (host array or device tensor): trajectory b explores at noise_scale[b] in the place of the policy's
         act_noise -- see set_noise_scale.  None: the policy's scalar.
+
+        noise_corr = a scalar or [B] (host array or device tensor) in [0, 1): temporally correlated exploration noise, trajectory b's
+        step-to-step correlation -- see set_noise_corr.  pipe.noise_state [B A na] holds the AR(1) states; it is zeroed on the env
+        stream ahead of an episode's first acting launch (a first step is always issued eagerly, so the eager, the recorded and the
+        captured forms all see it) and by reset_from().  Lock-stepped episodes only; n_step, telemetry, the ledger, evaluations
+        (greedy: they touch nothing), noise_scale, use_replay and a reducer (each rank has its own states) are served.  It is run
+        state of the pipeline: checkpoints do not store it.  noise_corr = None builds nothing and issues the launches it always
+        did.
 
         An environment that holds fault arrays (PDEenv.set_faults, called before the pipeline is made) needs no argument here:
         the arrays are read by the kernels, so eager steps, recorded calls and captured graphs all step through them, writing
@@ -210,6 +222,11 @@ class TrainPipeline:
                                "the environment's state ring in the actor's type") if mixed else None
         check_episode_mode(env, agent, episodes, stagger, episode_steps, use_replay, eval_every, min_best_episode, best_by)
         self.per_traj, self.stagger = episodes == "per_trajectory", bool(stagger)
+        if noise_corr is not None and self.per_traj:
+            raise _lib.PdecError(_NOISE_CORR_PER_TRAJ)
+        if getattr(agent.policy, "noise_corr", None) is not None:
+            raise _lib.PdecError("TrainPipeline: a noise correlation is set on the policy (set_noise_corr); the pipeline zeroes the "
+                                 "states it owns at its episode starts: unset it and pass noise_corr= here")
         self.env, self.agent, self.policy = env, agent, agent.policy
         self.s_env = stream_env if stream_env is not None else env.stream
         self.s_upd = stream_upd if stream_upd is not None else self.policy.behavior_critic.model.stream
@@ -338,6 +355,8 @@ class TrainPipeline:
         self.n_graph_launches = self.n_eager_steps = 0
         self.noise_scale = None   # set_noise_scale: float64 [B] on the device, read by every acting launch
         self.set_noise_scale(noise_scale)
+        self.noise_ab = self.noise_state = None   # set_noise_corr: float64 [B, 2] and [B A na] on the device
+        self.set_noise_corr(noise_corr)
         # the opt-in features: each object owns its buffers and launches, and is None -- nothing built, nothing issued -- when off
         self.nstep = NStep(self) if self.n_step > 1 else None
         self._telem = Telemetry(self) if self.telemetry_capacity > 0 else None
@@ -387,6 +406,8 @@ class TrainPipeline:
         if self.clock is not None:
             self.clock.reset()
         with torch.cuda.stream(self.s_env):
+            if self.noise_state is not None:
+                self.noise_state.zero_()
             if y0.data_ptr() != env.y0.data_ptr():
                 env.y0.copy_(y0)
             _lib.check(self.lib.pdec_featurize(env.handle, _lib.ptr(env.y0), None, _lib.ptr(self.state0)))
@@ -564,6 +585,8 @@ class TrainPipeline:
                 self.inits.keep_y0 = False
                 st.y_in.copy_(env.y0)
                 st.s_in.copy_(self.state0)
+                if self.noise_state is not None:           # the AR(1) states of set_noise_corr start an episode at zero
+                    self.noise_state.zero_()
             L.check(lib.pdec_set_stream(self.actor.handle, self._sp_env))
             L.check(lib.pdec_policy_act_rng_dev(self.actor.handle, L.ptr(st.s_in), self.cols, float(pol.act_noise),
                                                 float(pol.act_limit), 1, self.noise_seed, L.ptr(st.act)))
@@ -820,6 +843,42 @@ class TrainPipeline:
             self.actor.set_noise_scale(buf, self.cols // self.env.B)
             self.noise_scale = buf
 
+    def set_noise_corr(self, values):
+        """Temporally correlated exploration noise (CustomDDPGPolicy.set_noise_corr, pdec_mlp_set_noise_color): `values` the
+        step-to-step correlation in [0, 1), a scalar or [B] as a host array (checked) or a [B] device tensor (copied device to
+        device, b = sqrt(1 - a^2) taken on the device, no host wait), or None for white noise.  They are written on the env stream
+        INTO the [B, 2] buffer the pipeline owns (self.noise_ab), whose pointer the acting launches hold beside that of
+        self.noise_state: a schedule between episodes keeps the recorded steps and the captured graphs; turning it on or off
+        changes the key (_check_key).  Setting it does not touch the states: they are zeroed at the next episode's first step."""
+        if values is None:
+            if self.noise_state is not None:
+                self.actor.set_noise_color(None)
+                self.noise_ab = self.noise_state = None
+            return
+        if self.per_traj:
+            raise _lib.PdecError(_NOISE_CORR_PER_TRAJ)
+        B, dev = self.env.B, self.env.device
+        if isinstance(values, torch.Tensor) and values.is_cuda:
+            if values.dim() != 1 or int(values.shape[0]) != B:
+                raise ValueError(f"TrainPipeline.set_noise_corr: expected {B} correlations in a 1-D array, got shape {tuple(values.shape)}")
+            src = None
+        else:
+            from .agent import noise_corr_ab
+            src = torch.from_numpy(noise_corr_ab(values, B, "TrainPipeline.set_noise_corr"))
+        with torch.cuda.stream(self.s_env):
+            ab = self.noise_ab if self.noise_ab is not None else torch.empty((B, 2), dtype=torch.float64, device=dev)
+            if src is not None:
+                ab.copy_(src)
+            else:
+                a = values.to(torch.float64)
+                ab[:, 0].copy_(a)
+                ab[:, 1].copy_(torch.sqrt(1.0 - a * a))
+            if self.noise_state is None:
+                self.noise_state = torch.zeros(self.cols * self.na, dtype=torch.float64, device=dev)
+        if self.noise_ab is None:
+            self.noise_ab = ab
+            self.actor.set_noise_color(self.noise_state, ab, self.cols // B)
+
     def _scalar_key(self):
         """the per-step scalars that a recorded step / a captured graph holds as frozen launch arguments (with a noise scale
         array set, a fixed marker in the place of act_noise: the launches hold the array's pointer, not its values)"""
@@ -827,6 +886,7 @@ class TrainPipeline:
         return ("noise_scale" if self.noise_scale is not None else float(pol.act_noise), float(pol.act_limit), float(pol.behavior_actor.optimizer.eta),
                 float(pol.behavior_critic.optimizer.eta), float(pol.y), float(pol.rho_effective), int(bool(pol.quirk)),
                 pol.reward_group, bool(self.kick_env_after_critic), int(self.noise_seed)) + (
+                    ("noise_corr",) if self.noise_state is not None else ()) + (
                     (self.env.y0.data_ptr(),) if self.per_traj else ())     # (the clock's launch holds the pointer of env.y0)
 
     def _drop_graphs(self):

@@ -63,6 +63,8 @@ def _not_of_this_setup(setup, ag):
         (getattr(pol.behavior_actor.model, "noise_scale", None) is not None,
          "a noise scale array is set on its actor (set_noise_scale); a member explores at its own act_noise, which may differ from "
          "member to member"),
+        (getattr(pol, "noise_corr", None) is not None or getattr(pol.behavior_actor.model, "noise_color", None) is not None,
+         "a noise correlation is set on its policy (set_noise_corr); the member glue draws white noise only"),
         (per_actuator and (rows != ns or stride != A),
          f"its actor reads {rows} state rows and its replay takes {stride} columns per step, but {name} has {ns} state rows and {A} "
          "actuators: the member was not made for this setup"),

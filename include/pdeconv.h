@@ -354,6 +354,28 @@ int pdec_mlp_set_noise_rows(pdec_handle actor, int rows);
  * pdec_population_create refuses a member whose actor has an array set (members carry their amplitude in the row table); the
  * member forms (pdec_rollout_members, pdec_policy_act_members) are greedy and do not read it. */
 int pdec_mlp_set_noise_scale(pdec_handle actor, const double* scale_dev, int64_t n, int cols_per_entry);
+/* temporally correlated (Ornstein-Uhlenbeck / AR(1)) exploration noise in the place of the white draw (src/PDEagent.jl:201 adds
+ * randn * act_noise, fresh at every control step; an integrator low-pass filters that away within a few steps).  Every noise
+ * element i = column * outputs + row keeps a state x[i], a double whatever the kernel's type.  An acting call with learning = 1
+ * draws z = the normal the white call draws for element i (stream numbering and the device counter unchanged) and computes, in
+ * double,  x[i] = a_e x[i] + b_e z  with e = column / cols_per_entry, stores it back, and adds (T)x[i] * amp_c where the white
+ * call added (T)z * amp_c; amp_c is the call's act_noise, or entry e of the array of pdec_mlp_set_noise_scale when one is set
+ * (the two cols_per_entry must then be equal: refused by the acting call otherwise).  a_e in [0, 1) is the step-to-step
+ * correlation and b_e = sqrt(1 - a_e^2) keeps the stationary variance at 1, so act_noise and the scale array mean what they
+ * meant; a = 0, b = 1 gives x = z exactly and the white call bit for bit.  Rows >= the noise rows are neither read nor written,
+ * and a call with learning = 0 touches nothing.
+ *   state_dev [n * cols_per_entry * outputs] doubles, ab_dev [n][2] doubles {a, b}: device arrays the caller keeps alive and
+ * zeroes (or fills) at an episode's start.  The pointers are stored, nothing is copied or synchronised: values written into
+ * either array on the acting stream between launches serve the next launch, a recorded call and a captured graph alike.
+ * state_dev = NULL switches it off.  Refused (PDEC_E_INVALID): n < 1, cols_per_entry < 1, a product n * cols_per_entry * outputs
+ * beyond 2^31 - 1, ab_dev NULL with a state set; and by every acting call, a column count that is not n * cols_per_entry.
+ *   Served by pdec_policy_act (with noise: the caller's noise[] is z), pdec_policy_act_rng, _rng_as, _rng_dev and pdec_step_glue,
+ * on every kernel these reach; which kernel a shape reaches does not depend on it (pdec_debug_batched_update_route).  Refused
+ * by name while a state is set: pdec_rollout with learning = 1 (the persistent and the host-enqueued exploring rollouts), the
+ * member forms pdec_policy_act_members and pdec_rollout_members, and pdec_population_create, hence the member glue
+ * (pdec_population_glue).  In Python, Population refuses such a member and TrainPipeline(episodes="per_trajectory") the option:
+ * a restarted trajectory would have to zero its rows inside the boundary launch. */
+int pdec_mlp_set_noise_color(pdec_handle actor, double* state_dev, const double* ab_dev, int64_t n, int cols_per_entry);
 int pdec_policy_act_rng(pdec_handle actor, const void* state, int cols, double act_noise, double act_limit,
                         int learning, uint64_t seed, uint64_t offset, void* actions_out);
 /* agent(env) where the environment computes in `state_dtype` and the actor keeps parameters of another type -- the reference's
