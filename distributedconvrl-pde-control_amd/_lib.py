@@ -143,6 +143,7 @@ SIGNATURES = {
     "pdec_event_create": [C.POINTER(Handle)], "pdec_event_record": [Handle, _vp], "pdec_stream_wait_event": [_vp, Handle], "pdec_mlp_set_stop_event": [Handle, Handle], "pdec_mlp_flush_stop_event": [Handle],
     "pdec_mlp_set_reduce_event": [Handle, Handle],
     "pdec_env_set_simd_sharing": [Handle, C.c_int, C.POINTER(C.c_int)],
+    "pdec_env_set_two_wave_step": [Handle, C.c_int, C.POINTER(C.c_int)],
     "pdec_ddpg_critic_grads": [Handle] * 4 + [_vp] * 5 + [_i, _d, _i, _d, _vp],
     "pdec_ddpg_actor_grads": [Handle, Handle, _vp, _i, _d, _vp],
     "pdec_ddpg_update": [Handle] * 4 + [_vp] * 5 + [_i, _d, _d, _i, _d, _d, _pd, _pd],

@@ -331,6 +331,13 @@ int pdec_env_set_simd_sharing(pdec_handle h, int on, int* effective) {
   return PDEC_OK;
 }
 
+int pdec_env_set_two_wave_step(pdec_handle h, int on, int* effective) {
+  GET_ENV(E, h);
+  E->two_wave = on != 0;
+  if (effective) *effective = ks_step_engine(*E, true) == KsEngine::Wave256x2 ? 1 : 0;
+  return PDEC_OK;
+}
+
 // Population (population.py): every trajectory of the batch is an independent member; the KS step runs one trajectory per
 // workgroup instead of two per complex FFT, so each member's result is bit for bit its B = 1 step and a blown-up member's
 // NaNs stay in its own workgroup.  The other 1-D kinds already run one trajectory per workgroup.

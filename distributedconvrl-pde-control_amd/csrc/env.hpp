@@ -60,6 +60,7 @@ enum class KsEngine {
   Fixed240,
   Fixed600,
   Generic,      // any N = 2^a 3^b 5^c: mixed-radix Stockham through LDS (FftGeneric); every N under PDEC_KS_GENERIC_FFT=1
+  Wave256x2,    // N = 256, fp32: the Wave256 transform over two waves (FftWave256x2); never Env::engine, see ks_step_engine
 };
 constexpr bool ks_is_single_wave(KsEngine k) { return k == KsEngine::Wave256; }
 constexpr bool ks_is_fixed_plan(KsEngine k) { return k == KsEngine::Fixed192 || k == KsEngine::Fixed240 || k == KsEngine::Fixed600; }
@@ -91,6 +92,7 @@ struct Env : Object {
   void* term_out = nullptr;
   float* rsum_out = nullptr;
   bool share_simd = false;   // pdec_env_set_simd_sharing: launch the 64-VGPR form of the fused KS step
+  bool two_wave = false;     // pdec_env_set_two_wave_step: the fused fp32 N = 256 step on two waves per trajectory pair (ks_step_engine)
   bool member = false;       // pdec_env_set_member_layout: one KS trajectory per workgroup, the B = 1 launch's arithmetic
   const void* mu_b = nullptr;   // pdec_env_set_disturbance: caller-owned device array [B] of the environment's dtype
   int control_from = 0;         // pdec_env_set_control_from: the rollouts act from this step on (zero action before it)
@@ -115,6 +117,15 @@ struct Env : Object {
   virtual int rhs_eval(const void* y, const void* p, void* out);
   virtual int env_step(const StepArgs& a);
 };
+
+// The engine a step launch takes: Env::engine, except that the fused step of an fp32 N = 256 CNAB2 environment with nothing
+// opt-in set (no disturbance array, no faults, not the SIMD-sharing form, not the member layout) runs FftWave256x2 once pdec_env_set_two_wave_step asked
+// for it.  The ONE statement of that rule: the launch (ks_launch_step) and the setter's `effective` both read it.
+inline KsEngine ks_step_engine(const Env& E, bool fused) {
+  const bool two = E.two_wave && fused && E.cfg.pde_kind == PDEC_PDE_KS_CNAB2 && E.engine == KsEngine::Wave256 &&
+                   E.cfg.dtype == PDEC_F32 && !E.share_simd && !E.member && !E.mu_b && !E.faults();
+  return two ? KsEngine::Wave256x2 : E.engine;
+}
 
 // ---- host pieces shared by the translation units of the 1-D environments: the kernels' view of an Env, the dtype dispatch
 // and the step launches of the three PDEs

@@ -6,6 +6,11 @@
 namespace pdec {
 
 // ------------------------------------------------------------------ shared device pieces
+// sense_dots, reward_traj and reward_pair may be called with tid = SUM_IDLE_TID by threads that take no part in the sums (the
+// second wave of the two-wave KS step, ks_step.hip): such a thread must do nothing but meet the barriers.  So in these three
+// `tid` is only ever the start of a `for (i = tid; i < bound; i += nt)` loop or compared with 0 -- never scaled, never an index
+// outside such a loop (the value leaves room for bounds up to 2^28 and for `tid + nt` without overflow).
+constexpr int SUM_IDLE_TID = 1 << 28;
 
 // dots[r][s] = sum_j Gs[j][s] * y_r[(sn0[s]+j) mod N] for r in {0,1}; yf(r,n) reads LDS.  Threads
 // are split into groups that each cover a slice of the window; partials are combined via `part`.

@@ -350,6 +350,175 @@ struct FftWave256 {
   }
 };
 
+// ---- N = 256 over TWO waves (fp32; the fused step beside the update passes, pdec_env_set_two_wave_step): 128 lanes x 2 points,
+// bit for bit the one-wave engine on 0.6 of its vector instructions per wave.  Every radix-4 DIF butterfly of FftWave256 is
+// run as its two radix-2 levels -- level 1 over the high bit of the digit (s02, d02 | s13, d13), level 2 over the low bit with
+// the inner -+i as a swap and a negation of d13 in the lanes that hold the d pair -- and the twiddles multiply where they
+// multiply there, so every element sees the same floating-point operations in the same order.  Between two levels the ONE
+// register bit is exchanged with one bit of the thread id: bits 5 and 4 by v_permlane32/16_swap, bits 3..0 by the DPP select
+// steps of PDEC_XSTEP on one register pair, the wave bit through LDS (1 KB per exchange, two halves alternating, one raw
+// barrier).  Index bits, forward: thread tid owns n = tid + 128 r (r: register); at the end wave = k0 & 1, lane bits
+// 5..0 = k0 >> 1, k1 & 1, k1 >> 1, k2 & 1, k2 >> 1, k3 & 1 and r = k3 >> 1 of mode k0 + 4 k1 + 16 k2 + 64 k3.
+__device__ __forceinline__ void wave_pair_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+#define PDEC_XSTEP2(CA, CB, MASK, P0, Q0, P1, Q1)                                                          \
+  {                                                                                                        \
+    float n0_, n1_;                                                                                        \
+    asm("s_nop 1\n\t"                                                                                      \
+        "s_mov_b64 vcc, %6\n\t"                                                                            \
+        "v_cndmask_b32_dpp %4, %0, %1, vcc " CA " row_mask:0xf bank_mask:0xf\n\t"                           \
+        "v_cndmask_b32_dpp %5, %2, %3, vcc " CA " row_mask:0xf bank_mask:0xf\n\t"                           \
+        "s_mov_b64 vcc, %7\n\t"                                                                            \
+        "v_cndmask_b32_dpp %0, %1, %0, vcc " CB " row_mask:0xf bank_mask:0xf\n\t"                           \
+        "v_cndmask_b32_dpp %2, %3, %2, vcc " CB " row_mask:0xf bank_mask:0xf"                                \
+        : "+v"(P0), "+v"(Q0), "+v"(P1), "+v"(Q1), "=&v"(n0_), "=&v"(n1_)                                   \
+        : "s"(MASK), "s"(~(MASK))                                                                          \
+        : "vcc");                                                                                          \
+    Q0 = n0_; Q1 = n1_;                                                                                    \
+  }
+// a * w (SGN < 0) or a * conj(w) (SGN > 0) in the lanes of `mask`, a in the others: pk_cmul's two instructions under EXEC
+template <int SGN>
+__device__ __forceinline__ pkf2 pk_cmul_lanes(pkf2 a, pkf2 w, unsigned long long mask) {
+  pkf2 t;
+  unsigned long long sv;
+  if (SGN < 0)
+    asm("s_and_saveexec_b64 %2, %4\n\t"
+        "v_pk_mul_f32 %1, %0, %3 op_sel_hi:[1,0]\n\t"
+        "v_pk_fma_f32 %0, %0, %3, %1 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]\n\t"
+        "s_mov_b64 exec, %2"
+        : "+v"(a), "=&v"(t), "=&s"(sv) : "v"(w), "s"(mask) : "scc");
+  else
+    asm("s_and_saveexec_b64 %2, %4\n\t"
+        "v_pk_mul_f32 %1, %0, %3 op_sel_hi:[1,0]\n\t"
+        "v_pk_fma_f32 %0, %0, %3, %1 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[0,1,0]\n\t"
+        "s_mov_b64 exec, %2"
+        : "+v"(a), "=&v"(t), "=&s"(sv) : "v"(w), "s"(mask) : "scc");
+  return a;
+}
+
+struct FftWave256x2 {
+  static constexpr int kThreads = 128;
+  static constexpr int kMpt = 2;            // points per lane (the kernels' KS_MPT for this engine)
+  static constexpr int kSumThreads = 64;    // the step's sums (sensor dots, reward partial) keep the one-wave engine's tree: wave 0 does them
+  static constexpr int N = 256, NT = 128;
+  C2<float>* buf;      // [2][128]: the halves of the cross-wave exchange; [256]: publish()
+  pkf2 w0[3], w1[3];   // twiddles of the three inner stages for register 0 (digit k = kl; unused where kl = 0) and 1 (k = kl + 2)
+  int tid, lane, wv, par;
+  __device__ __forceinline__ void init(unsigned char* smem, const EnvDev<float>& e, int tid_, int) {
+    tid = tid_; lane = tid & 63; par = 0;
+    wv = __builtin_amdgcn_readfirstlane(tid >> 6);     // uniform: the wave's own branches are scalar
+    buf = reinterpret_cast<C2<float>*>(smem);
+    const int kl[3] = {wv, (lane >> 4) & 1, (lane >> 2) & 1};               // low bit of the stage's output digit
+    const int low[3] = {lane, 4 * (lane & 15), 16 * (lane & 3)};            // as in FftWave256
+#pragma unroll
+    for (int st = 0; st < 3; ++st) {
+      w0[st] = __builtin_bit_cast(pkf2, e.tw[(kl[st] * low[st]) & 255]);
+      w1[st] = __builtin_bit_cast(pkf2, e.tw[((kl[st] + 2) * low[st]) & 255]);
+    }
+  }
+  static __host__ __device__ size_t lds_complex(int) { return (size_t)N; }
+  __device__ __forceinline__ int mode_index(int j) const {
+    const int k0 = wv + 2 * (lane >> 5), k1 = ((lane >> 4) & 1) + 2 * ((lane >> 3) & 1);
+    const int k2 = ((lane >> 2) & 1) + 2 * ((lane >> 1) & 1), k3 = (lane & 1) + 2 * j;
+    return k0 + 4 * k1 + 16 * k2 + 64 * k3;
+  }
+  __device__ __forceinline__ int phys_index(int j) const { return tid + NT * j; }
+
+  // level 1 of a radix-4 butterfly: (v0, v2) -> (s02, d02) or (v1, v3) -> (s13, d13)
+  static __device__ __forceinline__ void level1(C2<float> (&a)[2]) {
+    const pkf2 p = __builtin_bit_cast(pkf2, a[0]), q = __builtin_bit_cast(pkf2, a[1]);
+    a[0] = __builtin_bit_cast(C2<float>, p + q);
+    a[1] = __builtin_bit_cast(C2<float>, p - q);
+  }
+  // level 2 in lanes: (s02, s13) -> (v0, v2) where d is clear, (d02, d13) -> (v1, v3) = d02 +- (-+i) d13 where it is set
+  template <int SGN>
+  static __device__ __forceinline__ void level2(C2<float> (&a)[2], bool d) {
+    const C2<float> b = a[1];
+    pkf2 r;
+    if (SGN < 0) { r.x = d ? b.y : b.x; r.y = d ? -b.x : b.y; }      // -i b = (b.y, -b.x)
+    else { r.x = d ? -b.y : b.x; r.y = d ? b.x : b.y; }              // +i b = (-b.y, b.x)
+    const pkf2 p = __builtin_bit_cast(pkf2, a[0]);
+    a[0] = __builtin_bit_cast(C2<float>, p + r);
+    a[1] = __builtin_bit_cast(C2<float>, p - r);
+  }
+  // level 2 where the wave bit says which pair a wave holds (wave 1: the d pair)
+  template <int SGN>
+  __device__ __forceinline__ void level2_wave(C2<float> (&a)[2]) const {
+    const pkf2 p = __builtin_bit_cast(pkf2, a[0]), q = __builtin_bit_cast(pkf2, a[1]);
+    if (wv) {
+      a[0] = __builtin_bit_cast(C2<float>, SGN < 0 ? pk_add_mi(p, q) : pk_add_pi(p, q));
+      a[1] = __builtin_bit_cast(C2<float>, SGN < 0 ? pk_add_pi(p, q) : pk_add_mi(p, q));
+    } else {
+      a[0] = __builtin_bit_cast(C2<float>, p + q);
+      a[1] = __builtin_bit_cast(C2<float>, p - q);
+    }
+  }
+  // twiddles of stage ST: register 1 always (digit 2 or 3), register 0 where the digit's low bit is set (digit 1)
+  template <int ST, int SGN>
+  __device__ __forceinline__ void twiddle(C2<float> (&a)[2]) const {
+    a[1] = __builtin_bit_cast(C2<float>, pk_cmul<SGN>(__builtin_bit_cast(pkf2, a[1]), w1[ST]));
+    if (ST == 0) {
+      if (wv) a[0] = __builtin_bit_cast(C2<float>, pk_cmul<SGN>(__builtin_bit_cast(pkf2, a[0]), w0[0]));
+    } else {
+      a[0] = __builtin_bit_cast(C2<float>, pk_cmul_lanes<SGN>(__builtin_bit_cast(pkf2, a[0]), w0[ST],
+                                                              ST == 1 ? 0xFFFF0000FFFF0000ull : 0xF0F0F0F0F0F0F0F0ull));
+    }
+  }
+  // exchange the register bit with lane bit BIT
+  template <int BIT>
+  static __device__ __forceinline__ void xch(C2<float> (&a)[2]) {
+    if (BIT == 5) {
+      asm("s_nop 1\n\t"
+          "v_permlane32_swap_b32 %0, %2\n\t"
+          "v_permlane32_swap_b32 %1, %3"
+          : "+v"(a[0].x), "+v"(a[0].y), "+v"(a[1].x), "+v"(a[1].y));
+    } else if (BIT == 4) {
+      asm("s_nop 1\n\t"
+          "v_permlane16_swap_b32 %0, %2\n\t"
+          "v_permlane16_swap_b32 %1, %3"
+          : "+v"(a[0].x), "+v"(a[0].y), "+v"(a[1].x), "+v"(a[1].y));
+    } else if (BIT == 3) {
+      PDEC_XSTEP2("row_ror:8", "row_ror:8", 0xFF00FF00FF00FF00ull, a[0].x, a[1].x, a[0].y, a[1].y)
+    } else if (BIT == 2) {
+      PDEC_XSTEP2("row_ror:12", "row_ror:4", 0xF0F0F0F0F0F0F0F0ull, a[0].x, a[1].x, a[0].y, a[1].y)
+    } else if (BIT == 1) {
+      PDEC_XSTEP2("quad_perm:[2,3,0,1]", "quad_perm:[2,3,0,1]", 0xCCCCCCCCCCCCCCCCull, a[0].x, a[1].x, a[0].y, a[1].y)
+    } else {
+      PDEC_XSTEP2("quad_perm:[1,0,3,2]", "quad_perm:[1,0,3,2]", 0xAAAAAAAAAAAAAAAAull, a[0].x, a[1].x, a[0].y, a[1].y)
+    }
+  }
+  // ... with the wave bit: wave 0 hands its register 1 to wave 1's register 0 and takes that one.  The halves alternate, so
+  // the writes of the next exchange need no second barrier (the one after it lies behind this one's reads)
+  __device__ __forceinline__ void xch_wave(C2<float> (&a)[2]) {
+    C2<float>* X = buf + 128 * par;
+    par ^= 1;
+    if (wv) X[tid] = a[0]; else X[tid] = a[1];
+    wave_pair_barrier();
+    if (wv) a[0] = X[tid ^ 64]; else a[1] = X[tid ^ 64];
+  }
+  template <int SGN>
+  __device__ __forceinline__ void run(C2<float> (&a)[2]) {
+    const bool d4 = (lane & 16) != 0, d2 = (lane & 4) != 0, d0 = (lane & 1) != 0;
+    if (SGN < 0) {   // forward: natural -> digit-reversed
+      level1(a); xch_wave(a); level2_wave<-1>(a); twiddle<0, -1>(a);
+      xch<5>(a); level1(a); xch<4>(a); level2<-1>(a, d4); twiddle<1, -1>(a);
+      xch<3>(a); level1(a); xch<2>(a); level2<-1>(a, d2); twiddle<2, -1>(a);
+      xch<1>(a); level1(a); xch<0>(a); level2<-1>(a, d0);
+    } else {         // inverse: digit-reversed -> natural (unnormalised)
+      level1(a); xch<0>(a); level2<+1>(a, d0);
+      xch<1>(a); twiddle<2, +1>(a); level1(a); xch<2>(a); level2<+1>(a, d2);
+      xch<3>(a); twiddle<1, +1>(a); level1(a); xch<4>(a); level2<+1>(a, d4);
+      xch<5>(a); twiddle<0, +1>(a); level1(a); xch_wave(a); level2_wave<+1>(a);
+    }
+  }
+  __device__ __forceinline__ C2<float>* publish(const C2<float> (&a)[2]) {
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 2; ++j) buf[tid + NT * j] = a[j];
+    __syncthreads();
+    return buf;
+  }
+};
+
 // ---- N = 1024 (BASELINE configs[2]) on four waves: ONE cross-wave radix-4 stage + the single-wave 256-point engine (round 4).
 // Thread tid of 256 owns x[tid + 256 j], j = 0..3 -- exactly the inputs of the first radix-4 DIF butterfly.  After that
 // butterfly and its twiddle W_1024^(tid k2), slot k2 holds element n1 = tid of the length-256 sub-sequence k2; one LDS round
@@ -523,12 +692,21 @@ template <class T> using FftFixed192 = FftFixed<T, 192, 4, 4, 4, 3, 4, 1>;
 template <class T> using FftFixed240 = FftFixed<T, 240, 4, 4, 5, 3, 4, 1>;
 template <class T> using FftFixed600 = FftFixed<T, 600, 5, 4, 5, 5, 2, 3>;
 
+// modes / cells per thread of an engine (KS_MPT unless it says otherwise) and the threads that do the step's sums (0: all)
+template <class ENG, class = void> struct KsMpt { static constexpr int value = KS_MPT; };
+template <class ENG> struct KsMpt<ENG, std::void_t<decltype(ENG::kMpt)>> { static constexpr int value = ENG::kMpt; };
+template <class ENG, class = void> struct KsSumThreads { static constexpr int value = 0; };
+template <class ENG> struct KsSumThreads<ENG, std::void_t<decltype(ENG::kSumThreads)>> { static constexpr int value = ENG::kSumThreads; };
+
 // ---- the list of engines: calls f with a tag that names the engine type of `k` at precision T (tag.kind: the enumerator,
 // decltype(tag)::type: the engine).  Every launch ladder, the LDS footprint (ENG::lds_complex) and the workgroup sizes
 // (ENG::kThreads) go through here; guard with `if constexpr` on the tag where only some engines have an instantiation.
+// STEP: the list of ks_step.hip, which alone has the two-wave form of the N = 256 step (fp32)
 template <KsEngine K, class ENG> struct KsEngineTag { static constexpr KsEngine kind = K; using type = ENG; };
-template <class T, class F>
+template <class T, bool STEP = false, class F>
 auto with_ks_engine(KsEngine k, F&& f) {
+  if constexpr (STEP && sizeof(T) == 4)
+    if (k == KsEngine::Wave256x2) return f(KsEngineTag<KsEngine::Wave256x2, FftWave256x2>{});
   switch (k) {
     case KsEngine::Wave256: return f(KsEngineTag<KsEngine::Wave256, FftWave256<T>>{});
     case KsEngine::Wave1024: return f(KsEngineTag<KsEngine::Wave1024, FftWave1024<T>>{});

@@ -35,6 +35,12 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
                                    T* __restrict__ reward_out, int32_t* __restrict__ done) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int N = e.N, tid = threadIdx.x, nt = blockDim.x;
+  constexpr int MPT = KsMpt<ENG>::value;        // modes / cells per thread: KS_MPT, two in the two-wave N = 256 engine
+  // the sums (sensor dots: a window is split over nt / S groups; reward partial) keep the tree of the engine's one-wave form
+  // where an engine names the threads that do them; the others take SUM_IDLE_TID (env_sense.hpp), pass the loops by and meet
+  // the barriers
+  constexpr int SUMT = KsSumThreads<ENG>::value;
+  const int stid = SUMT ? (tid < SUMT ? tid : SUM_IDLE_TID) : tid, snt = SUMT ? SUMT : nt;
   if constexpr (SYNC) launch_sync_wait(e.sync);
   // This kernel is a long dependent chain (63 FFTs) issued by very few waves.  Beside the f32-MFMA update passes (which
   // execute on the vector unit) each of its instructions waits for an MFMA to drain (~2.7x slower), and their eight waves
@@ -86,23 +92,23 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
   constexpr bool LDSC = SHARE;
   typedef T T4v __attribute__((ext_vector_type(4)));
   T4v* cst = reinterpret_cast<T4v*>(smem_raw + ((size_t)(reinterpret_cast<unsigned char*>(red + 16) - smem_raw + 15) & ~(size_t)15));
-  C2<T> U[KS_MPT], Nn[KS_MPT], Ck[KS_MPT], v[KS_MPT];
-  T kc1[KS_MPT], kc2[KS_MPT], kc3[KS_MPT], kg[KS_MPT];
+  C2<T> U[MPT], Nn[MPT], Ck[MPT], v[MPT];
+  T kc1[MPT], kc2[MPT], kc3[MPT], kg[MPT];
   // forcing p (packed pair) -> spectrum -> constant term of the CNAB2 update
-  T pa4[KS_MPT], pb4[KS_MPT];
+  T pa4[MPT], pb4[MPT];
   if (FUSED) {
-    int n4[KS_MPT];
+    int n4[MPT];
 #pragma unroll
-    for (int j = 0; j < KS_MPT; ++j) n4[j] = eng.phys_index(j);
+    for (int j = 0; j < MPT; ++j) n4[j] = eng.phys_index(j);
     if ((N & 3) == 0 && 2 * N <= 16 * e.S) {     // `part` ([8][2][S], free until the sensor dots) holds the [2][N] scratch
       actuate_consecutive<T>(e, act, act + e.A, part, tid, nt);
 #pragma unroll
-      for (int j = 0; j < KS_MPT; ++j) {
+      for (int j = 0; j < MPT; ++j) {
         pa4[j] = n4[j] < N ? part[n4[j]] : (T)0;
         pb4[j] = n4[j] < N ? part[N + n4[j]] : (T)0;
       }
     } else {
-      actuate_cells<T, KS_MPT>(e, act, act + e.A, n4, pa4, pb4);
+      actuate_cells<T, MPT>(e, act, act + e.A, n4, pa4, pb4);
     }
     if constexpr (FLT) {      // the forcing is made: back to the commanded action, which the reward punishes
       __syncthreads();
@@ -113,7 +119,7 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
     }
   }
 #pragma unroll
-  for (int j = 0; j < KS_MPT; ++j) {
+  for (int j = 0; j < MPT; ++j) {
     const int n = eng.phys_index(j);
     T pa = 0, pb = 0;
     if (n < N) {
@@ -133,7 +139,7 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
   }
   eng.template run<-1>(v);
 #pragma unroll
-  for (int j = 0; j < KS_MPT; ++j) {
+  for (int j = 0; j < MPT; ++j) {
     const int k = eng.mode_index(j);
     if (k < N) {
       const C2<T> d = dtab[k];
@@ -157,14 +163,14 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
   }
   // Nn = G * fft(u^2);  u_hat = fft(u)
 #pragma unroll
-  for (int j = 0; j < KS_MPT; ++j) {
+  for (int j = 0; j < MPT; ++j) {
     const int n = eng.phys_index(j);
     U[j] = n < N ? mk<T>(y_in[o0 + n], has1 ? y_in[o1 + n] : (T)0) : mk<T>(0, 0);
     v[j] = mk<T>(U[j].x * U[j].x, U[j].y * U[j].y);
   }
   eng.template run<-1>(v);
 #pragma unroll
-  for (int j = 0; j < KS_MPT; ++j) Nn[j] = cscale(mul_i<+1, T>(v[j]), kg[j]);   // G = i * (-alpha/2)
+  for (int j = 0; j < MPT; ++j) Nn[j] = cscale(mul_i<+1, T>(v[j]), kg[j]);   // G = i * (-alpha/2)
   if constexpr (LDSC) {
     cst[6 * nt + tid] = T4v{Nn[0].x, Nn[0].y, Nn[1].x, Nn[1].y};
     cst[7 * nt + tid] = T4v{Nn[2].x, Nn[2].y, Nn[3].x, Nn[3].y};
@@ -174,10 +180,10 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
   if constexpr (LDSC) {
     for (int it = 0; it < e.K; ++it) {
 #pragma unroll
-      for (int j = 0; j < KS_MPT; ++j) v[j] = U[j];
+      for (int j = 0; j < MPT; ++j) v[j] = U[j];
       eng.template run<+1>(v);
 #pragma unroll
-      for (int j = 0; j < KS_MPT; ++j) {
+      for (int j = 0; j < MPT; ++j) {
         const T wr = v[j].x * invN, wi = v[j].y * invN;
         v[j] = mk<T>(wr * wr, wi * wi);
       }
@@ -201,16 +207,16 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
   } else {
     for (int it = 0; it < e.K; ++it) {
 #pragma unroll
-      for (int j = 0; j < KS_MPT; ++j) v[j] = U[j];
+      for (int j = 0; j < MPT; ++j) v[j] = U[j];
       eng.template run<+1>(v);
 #pragma unroll
-      for (int j = 0; j < KS_MPT; ++j) {
+      for (int j = 0; j < MPT; ++j) {
         const T wr = v[j].x * invN, wi = v[j].y * invN;
         v[j] = mk<T>(wr * wr, wi * wi);
       }
       eng.template run<-1>(v);
 #pragma unroll
-      for (int j = 0; j < KS_MPT; ++j) {
+      for (int j = 0; j < MPT; ++j) {
         const C2<T> nn1 = Nn[j];
         Nn[j] = cscale(mul_i<+1, T>(v[j]), kg[j]);
         U[j] = mk<T>(kc1[j] * U[j].x + kc2[j] * Nn[j].x - kc3[j] * nn1.x + Ck[j].x,
@@ -222,7 +228,7 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
   eng.template run<+1>(U);
   T mx0 = 0, mx1 = 0;
 #pragma unroll
-  for (int j = 0; j < KS_MPT; ++j) {
+  for (int j = 0; j < MPT; ++j) {
     const int n = eng.phys_index(j);
     U[j] = mk<T>(U[j].x * invN, U[j].y * invN);
     if (n < N) {
@@ -249,7 +255,7 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
   }
   if (!FUSED) return;
   const T* Rt = reinterpret_cast<const T*>(eng.publish(U));
-  sense_dots<T>(e, [&](int r, int n) { return Rt[2 * n + r]; }, dots, part, tid, nt);
+  sense_dots<T>(e, [&](int r, int n) { return Rt[2 * n + r]; }, dots, part, stid, snt);
   const int rw = e.mono ? 1 : e.A;             // reward entries per trajectory
   const int sw = e.mono ? e.S : e.A * e.ns;    // state entries per trajectory
   T rmine;
@@ -262,13 +268,13 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
   }
   if (e.fmap && !e.mono) {     // both trajectories in one pass each
     rmine = reward_pair<T>(e, dots, dots + e.S, act, act + e.A, actp, actp + e.A, reward_out + (size_t)b0 * rw,
-                           has1 ? reward_out + (size_t)b1 * rw : nullptr, tid, nt);
+                           has1 ? reward_out + (size_t)b1 * rw : nullptr, stid, snt);
     featurize_pair<T>(e, fd, fd + e.S, state_out + (size_t)b0 * sw, has1 ? state_out + (size_t)b1 * sw : nullptr, tid, nt);
   } else {
-    rmine = reward_traj<T>(e, dots, act, actp, reward_out + (size_t)b0 * rw, tid, nt);
+    rmine = reward_traj<T>(e, dots, act, actp, reward_out + (size_t)b0 * rw, stid, snt);
     featurize_traj<T>(e, fd, state_prev ? state_prev + (size_t)b0 * sw : nullptr, state_out + (size_t)b0 * sw, tid, nt);
     if (has1) {
-      rmine += reward_traj<T>(e, dots + e.S, act + e.A, actp + e.A, reward_out + (size_t)b1 * rw, tid, nt);
+      rmine += reward_traj<T>(e, dots + e.S, act + e.A, actp + e.A, reward_out + (size_t)b1 * rw, stid, snt);
       featurize_traj<T>(e, fd + e.S, state_prev ? state_prev + (size_t)b1 * sw : nullptr,
                         state_out + (size_t)b1 * sw, tid, nt);
     }
@@ -306,10 +312,10 @@ __global__ void __launch_bounds__(ENG::kThreads, SHARE ? 8 : 1) ks_env_step_kern
 
 // ------------------------------------------------------------------ host side
 int ks_engine_threads(KsEngine k) {
-  return with_ks_engine<float>(k, [](auto tag) { return (int)decltype(tag)::type::kThreads; });
+  return with_ks_engine<float, true>(k, [](auto tag) { return (int)decltype(tag)::type::kThreads; });
 }
 size_t ks_lds_bytes(const pdec_env_cfg& c, KsEngine k) {      // the engine's buffers + act | actp | dots | part | red
-  const size_t fft = with_ks_engine<float>(k, [&](auto tag) { return decltype(tag)::type::lds_complex(c.N); });
+  const size_t fft = with_ks_engine<float, true>(k, [&](auto tag) { return decltype(tag)::type::lds_complex(c.N); });
   return (fft * 2 + 4 * (size_t)c.A + 2 * c.S + 16 * c.S + 16) * dtype_size(c.dtype);
 }
 
@@ -329,18 +335,21 @@ auto ks_step_kernel_for(bool fused, bool share, bool synced, bool mu) {
 
 int ks_launch_step(Env& E, bool fused, const StepArgs& a, const LaunchSync& sync) {
   const pdec_env_cfg& c = E.cfg;
-  const dim3 grid(E.member ? c.B : (c.B + 1) / 2), block(E.nthreads);
+  // pdec_env_set_two_wave_step: the engine of THIS launch (Env::engine, nthreads and lds_bytes stay those of the one-wave form)
+  const KsEngine engine = ks_step_engine(E, fused);
+  const bool two = engine != E.engine;
+  const dim3 grid(E.member ? c.B : (c.B + 1) / 2), block(two ? ks_engine_threads(engine) : E.nthreads);
   const bool synced = sync.wait || sync.done;
   const bool mu = E.mu_b != nullptr;          // pdec_env_set_disturbance: the MU instantiation of whichever form is launched
   // SHARE: the 64-VGPR form + its lane-private constant slots (8 float4 per lane, 16-byte aligned)
   const bool share = fused && E.share_simd && c.dtype == PDEC_F32 && ks_is_single_wave(E.engine);
-  const size_t lds = E.lds_bytes + (share ? 16 + 8 * 16 * 64 : 0);
+  const size_t lds = (two ? ks_lds_bytes(c, engine) : E.lds_bytes) + (share ? 16 + 8 * 16 * 64 : 0);
   // the training pipeline's form of the step, profiled in the pipeline (one launch per event pair): timed by the dispatch's own
   // timestamps (PDEC_TIMED_LAUNCH) so that the measurement puts no packets around the kernel
   const bool timed = c.dtype == PDEC_F32 && ks_is_single_wave(E.engine) && fused && E.prof && E.prof_reps == 1;
   by_dtype(c.dtype, [&](auto t) {
     using T = decltype(t);
-    with_ks_engine<T>(E.engine, [&](auto tag) {
+    with_ks_engine<T, true>(engine, [&](auto tag) {
       using ENG = typename decltype(tag)::type;
       constexpr KsEngine KIND = decltype(tag)::kind;
       // one launch tail for the healthy and the fault-carrying kernels (their first argument differs: EnvDev / EnvDevF)
@@ -353,7 +362,11 @@ int ks_launch_step(Env& E, bool fused, const StepArgs& a, const LaunchSync& sync
         ProfScope ps(&E, fused ? "ks_env_step" : "ks_pde_step", !synced && a.y_out != a.y_in && a.state_out != a.state_prev);
         for (int rep = 0; rep < ps.reps; ++rep) hipLaunchKernelGGL(kern, grid, block, lds, E.stream, PDEC_STEP_KERNEL_ARGS(T, e, a));
       };
-      if (fused && E.faults()) {              // pdec_env_set_faults (the integrator alone has neither side; a sync is refused before)
+      if constexpr (KIND == KsEngine::Wave256x2) {      // ks_step_engine: fused, nothing opt-in set -- the one instantiation
+        EnvDev<T> e = make_dev<T>(E);
+        e.sync = sync;
+        launch(ks_env_step_kernel<T, ENG, true>, e);
+      } else if (fused && E.faults()) {              // pdec_env_set_faults (the integrator alone has neither side; a sync is refused before)
         launch(ks_step_kernel_for<T, ENG, KIND, true>(fused, share, synced, mu), make_dev_faults<T>(E));
       } else {
         EnvDev<T> e = make_dev<T>(E);

@@ -392,6 +392,16 @@ class PDEenv:
         _lib.check(self.lib.pdec_env_set_simd_sharing(self.handle, 1 if on else 0, C.byref(eff)))
         return bool(eff.value)
 
+    def set_two_wave_step(self, on=True):
+        """Launch the fused KS step with one trajectory pair spread over two waves (pdec_env_set_two_wave_step): bit for bit the
+        one-wave step, on 0.6 of its vector instructions per wave -- for callers that run the step beside the update passes
+        on a second stream (TrainPipeline does).  Returns True when the next fused step takes that form (KS CNAB2, N = 256,
+        fp32, no disturbance array, no faults, not the SIMD-sharing form)."""
+        import ctypes as C
+        eff = C.c_int()
+        _lib.check(self.lib.pdec_env_set_two_wave_step(self.handle, 1 if on else 0, C.byref(eff)))
+        return bool(eff.value)
+
     def set_disturbance(self, mu):
         """Per-trajectory amplitude of the KS disturbance mu cos(2 + pi + x / (Lx / 2)) (KSSetup.jl:155) in the place of the
         setup's scalar mu (pdec_env_set_disturbance): `mu` a tensor or array [B], converted once to the environment's dtype and

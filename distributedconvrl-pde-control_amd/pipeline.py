@@ -342,6 +342,15 @@ class TrainPipeline:
             eff = C.c_int()
             _lib.check(self.lib.pdec_env_set_simd_sharing(env.handle, 1, C.byref(eff)))
             self.simd_sharing = bool(eff.value)
+        # The same step over two waves per trajectory pair (csrc/ks_engines.hpp, FftWave256x2): 0.6 of the vector instructions
+        # per wave, bit for bit the one-wave step.  Measured: the C2 step 1.9 % shorter, although the passes' own durations do
+        # not show why.  PDEC_TWO_WAVE=0 keeps the one-wave kernel.
+        self.two_wave = False
+        if (not self.serial and self.rpart is not None and not self.simd_sharing
+                and os.environ.get("PDEC_TWO_WAVE", "1") != "0"):
+            eff = C.c_int()
+            _lib.check(self.lib.pdec_env_set_two_wave_step(env.handle, 1, C.byref(eff)))
+            self.two_wave = bool(eff.value)
         self.graphs = {}          # (chunk, pos) -> graph handle
         self._progs = {}          # (ring phase, armed) -> recorded library calls of an interior eager step (_eager)
         # the recorded-call replay re-issues LIBRARY calls only: with torch events (PDEC_TORCH_EVENTS=1) the cross-stream
@@ -1083,4 +1092,7 @@ class TrainPipeline:
         if getattr(self, "simd_sharing", False):
             self.lib.pdec_env_set_simd_sharing(self.env.handle, 0, None)
             self.simd_sharing = False
+        if getattr(self, "two_wave", False):
+            self.lib.pdec_env_set_two_wave_step(self.env.handle, 0, None)
+            self.two_wave = False
         self._drop_graphs()

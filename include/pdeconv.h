@@ -479,6 +479,12 @@ int pdec_reward_mean(pdec_handle any_handle, const void* r, int n, void* mean_ou
  * (and being excluded by it) per CU; that form also runs at wave priority 3.  Alone it is slower (37 vs 29 us at C2), so
  * it is off by default.  *effective = 1 when the environment has such a form (KS CNAB2, N = 256, fp32), else 0. */
 int pdec_env_set_simd_sharing(pdec_handle env, int on, int* effective);
+/* For the same callers: launch the fused KS step with one trajectory pair spread over TWO waves (128-thread workgroups, two
+ * points per lane, FftWave256x2), which puts 0.6 of the one-wave step's vector instructions on each SIMD it touches; the results are bit
+ * for bit those of the one-wave step.  *effective = 1 when the next fused step takes that form (KS CNAB2, N = 256, fp32,
+ * register-resident engine, no disturbance array, no faults, not the SIMD-sharing form, not the member layout), else 0; the launch re-reads the rule,
+ * so an array set later returns the step to its one-wave kernel.  Off by default: alone it is 1.3 us slower; beside the update passes the training step measured 1.9 % shorter. */
+int pdec_env_set_two_wave_step(pdec_handle env, int on, int* effective);
 /* the same without any extra launch for the fused KS steps + 3-layer fused critic: every later pdec_env_step also writes the
  * sum of the rewards of each of its workgroups (CNAB2: two trajectories each, RK4 + FD: one) to partial_sums [*n_partials]
  * (fp32; NULL switches it off), and pdec_ddpg_set_reward_partials hands them to the next critic pass, which adds them in a
