@@ -1,8 +1,10 @@
 // ddpg.hip -- the DDPG update of an actor / critic pair (RLBase.update!(policy, batch), src/PDEagent.jl:363-418): the generic
 // critic and actor passes on the Mlp methods with their loss kernels, reward groups, and the routing of every pass, apply and
-// report to the fused family that serves it (FusedFamily, mlp.hpp) or to the generic path.
+// report to the fused family that serves it (FusedFamily, mlp.hpp) or to the generic path.  Also the batch-mean reward as a
+// launch of its own (rmean_kernel), which both fused families and the producer of r use.
 #include "common.hpp"
 #include "mlp.hpp"
+#include "mfma_blocks.hpp"     // f32x4
 
 namespace pdec {
 
@@ -77,6 +79,33 @@ __global__ void fill_kernel(T* __restrict__ p, int n, T v) {
 }
 template <class T>
 __global__ void neg_copy_kernel(T* __restrict__ dst, const T* __restrict__ src) { *dst = -*src; }
+
+// mean of r in a fixed order (one block): the batch-mean reward of the reference's (1xBu).+(Bu) broadcast
+__global__ __launch_bounds__(1024) void rmean_kernel(const float* __restrict__ r, int n, float* __restrict__ out) {
+  __builtin_amdgcn_s_setprio(3);      // one short block; beside the update passes (priority 2) it would otherwise starve
+  __shared__ float part[1024];
+  const int tid = threadIdx.x;
+  float acc = 0.f;
+  const int n4 = ((reinterpret_cast<uintptr_t>(r) & 15) == 0) ? n / 4 : 0;
+  const f32x4* r4 = reinterpret_cast<const f32x4*>(r);
+  int i = tid;
+  for (; i + 7 * 1024 < n4; i += 8 * 1024) {
+    f32x4 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = r4[i + u * 1024];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc += (v[u][0] + v[u][1]) + (v[u][2] + v[u][3]);
+  }
+  for (; i < n4; i += 1024) { const f32x4 v = r4[i]; acc += (v[0] + v[1]) + (v[2] + v[3]); }
+  for (int k = 4 * n4 + tid; k < n; k += 1024) acc += r[k];
+  part[tid] = acc;
+  __syncthreads();
+  for (int sft = 512; sft > 0; sft >>= 1) {
+    if (tid < sft) part[tid] += part[tid + sft];
+    __syncthreads();
+  }
+  if (tid == 0) out[0] = part[0] / (float)n;
+}
 
 }  // namespace pdec
 
@@ -169,6 +198,15 @@ int pdec::reward_group_route(Mlp* C, const void* r, int Bu, int quirk, CriticRou
   out->r = C->rg_vals.p;
   out->quirk = 0;
   out->loss_add = C->rg_vals.as<char>() + (size_t)Bu * ts;
+  return PDEC_OK;
+}
+
+int pdec::launch_rmean(Mlp* C, const float* r, int n, float** out) {
+  float* rb = C->scratch.as<float>() + 40;      // device scalar behind the generic path's statistics and losses
+  ProfScope ps(C, "ddpg_rmean");
+  hipLaunchKernelGGL(rmean_kernel, dim3(1), dim3(1024), 0, C->stream, r, n, rb);
+  PDEC_HIP(hipGetLastError());
+  *out = rb;
   return PDEC_OK;
 }
 
@@ -303,6 +341,36 @@ int pdec_ddpg_set_reward_groups(pdec_handle critic, int g, int L) {
   PDEC_REQUIRE(g >= 0 && L >= 1, "pdec_ddpg_set_reward_groups: needs g >= 0 (0: off) and L >= 1 (got g = %d, L = %d)", g, L);
   C->rg_g = g;
   C->rg_L = g ? L : 1;
+  return PDEC_OK;
+}
+
+// batch-mean reward as its own (fixed-order, one block) reduction on the caller's stream: the producer of r -- the env
+// step -- reduces it beside the update, which then reads one scalar instead of every workgroup summing all of r
+int pdec_reward_mean(pdec_handle any_handle, const void* r, int n, void* mean_out) {
+  Object* o = lookup(any_handle);
+  if (!o) { set_error("pdec_reward_mean: bad handle"); return PDEC_E_HANDLE; }
+  PDEC_REQUIRE(r && mean_out && n >= 1, "pdec_reward_mean: null/empty");
+  ProfScope ps(o, "ddpg_rmean");
+  hipLaunchKernelGGL(rmean_kernel, dim3(1), dim3(1024), 0, o->stream, (const float*)r, n, (float*)mean_out);
+  PDEC_HIP(hipGetLastError());
+  return PDEC_OK;
+}
+
+int pdec_ddpg_set_reward_partials(pdec_handle critic, const void* partial_sums, int n) {
+  Mlp* C = lookup_as<Mlp>(critic, Kind::Mlp);
+  if (!C) { set_error("pdec_ddpg_set_reward_partials: bad handle"); return PDEC_E_HANDLE; }
+  PDEC_REQUIRE(C->dtype == PDEC_F32 && n >= 0, "pdec_ddpg_set_reward_partials: fp32 critics only");
+  PDEC_REQUIRE(partial_sums == nullptr || fused_net_supported(C), "pdec_ddpg_set_reward_partials: 3-layer fused critics only");
+  C->rpart_ext = (const float*)partial_sums;
+  C->rpart_n = n;
+  return PDEC_OK;
+}
+
+int pdec_ddpg_set_reward_mean(pdec_handle critic, const void* mean_dev) {
+  Mlp* C = lookup_as<Mlp>(critic, Kind::Mlp);
+  if (!C) { set_error("pdec_ddpg_set_reward_mean: bad handle"); return PDEC_E_HANDLE; }
+  PDEC_REQUIRE(C->dtype == PDEC_F32, "pdec_ddpg_set_reward_mean: fp32 critics only");
+  C->rbar_ext = mean_dev;
   return PDEC_OK;
 }
 

@@ -1,5 +1,5 @@
 // mfma_blocks.hpp -- device building blocks shared by the fused fp32 MFMA DDPG passes (mlp_mfma.hip and its fused3_*.hpp
-// headers: 3-layer nets, mlp_mfma2.hip: 2-layer nets).  v_mfma_f32_16x16x4_f32 tiles: an output tile D[16 rows][16 cols]
+// headers: 3-layer nets, mlp_mfma2.hip and its fused2_*.hpp headers: 2-layer nets; ddpg.hip takes f32x4 from here).  v_mfma_f32_16x16x4_f32 tiles: an output tile D[16 rows][16 cols]
 // lives in 4 VGPRs per lane (col = lane & 15, row = 4 * (lane >> 4) + r).
 #pragma once
 // gradient slab accesses: non-temporal by default; -DPDEC_SLAB_NT=0 / -DPDEC_SLAB_NT_LOAD=0 build the plain forms (A/B builds)
@@ -112,28 +112,10 @@ __device__ __forceinline__ void stage_rows(float* img, const f32x4 (&v)[MT], int
     }
 }
 
-// D[i][k] += sum over the 64 staged columns L[i][c] * R[k][c]; wave w takes tile pairs w, w+8, ...
-template <int NACC>
-__device__ __forceinline__ void gemm_pass(f32x4 (&acc)[NACC], const float* L, const float* R, int nL, int nR, int w,
-                                          int lr, int q) {
-#pragma unroll
-  for (int pp = 0; pp < NACC; ++pp) {
-    const int p = w + 8 * pp;
-    if (p < nL * nR) {
-      const int ti = p / nR, tk = p - ti * nR;
-      const float* lrow = L + (16 * ti + lr) * LDP + 4 * q;
-      const float* rrow = R + (16 * tk + lr) * LDP + 4 * q;
-      acc[pp] = tile_chain<4>(acc[pp], lrow, rrow);
-    }
-    // keep the scheduler from hoisting the next tiles' operand loads over this tile (register pressure: the
-    // whole dz2 / h1 / dz1 activation set is live here); the partner wave on the SIMD hides the LDS latency
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-// the same product with the tiles of a wave taken in PAIRS whose MFMAs alternate: two independent accumulation chains
-// per wave, so consecutive MFMAs never wait for the 40-cycle dependent latency of v_mfma_f32_16x16x4_f32 (issue
-// interval 32).  ldp = leading dimension of both images (8 mod 16 floats: conflict-free ds_read_b128), NT = staged
-// columns / 16.
+// D[i][k] += sum over the staged columns L[i][c] * R[k][c]; wave w takes the tiles w, w+8, ... in PAIRS whose MFMAs alternate:
+// two independent accumulation chains per wave, so consecutive MFMAs never wait for the 40-cycle dependent latency of
+// v_mfma_f32_16x16x4_f32 (issue interval 32).  ldp = leading dimension of both images (8 mod 16 floats: conflict-free
+// ds_read_b128), NT = staged columns / 16.  (One tile at a time: gemm_cols, fused2_layers.hpp.)
 template <int NACC, int NT>
 __device__ __forceinline__ void gemm_pass_paired(f32x4 (&acc)[NACC], const float* L, const float* R, int ldp, int nL, int nR,
                                                  int w, int lr, int q) {

@@ -16,7 +16,7 @@
 // Polyak, the counter-based normals and the generic acting sequence, with the Mlp methods and
 // the pdec_mlp_* / pdec_adam_* / pdec_polyak / pdec_policy_act / pdec_randn entry points.
 // The DDPG passes and their routing live in ddpg.hip, acting for few columns and the step glue
-// in act.hip, the fp32 MFMA families in mlp_mfma.hip (+ fused3_*.hpp) / mlp_mfma2.hip.
+// in act.hip, the fp32 MFMA families in mlp_mfma.hip (+ fused3_*.hpp) / mlp_mfma2.hip (+ fused2_*.hpp).
 #include "common.hpp"
 #include "mlp.hpp"
 

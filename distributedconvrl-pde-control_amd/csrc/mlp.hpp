@@ -1,6 +1,6 @@
 // mlp.hpp -- the MLP object, what every acting path and every ADAM kernel share (activations, the exploration-noise stream, the
 // beta powers) and the table of a fused DDPG kernel family.  For every file that holds an Mlp*: mlp.hip (generic path), ddpg.hip
-// (DDPG passes and their routing), act.hip (acting), mlp_mfma.hip with fused3_*.hpp / mlp_mfma2.hip (the two fused families), and the rollout,
+// (DDPG passes and their routing), act.hip (acting), mlp_mfma.hip with fused3_*.hpp / mlp_mfma2.hip with fused2_*.hpp (the two fused families), and the rollout,
 // replay, ledger, communicator and population files
 #pragma once
 #include <algorithm>
@@ -252,8 +252,8 @@ template <int N>
 using tile_c = std::integral_constant<int, N>;
 
 // ---- a fused DDPG kernel family: fp32 MFMA passes, apply and acting kernels for one class of actor / critic pairs.  Two exist:
-// fused3_family (mlp_mfma.hip, kernels in fused3_*.hpp: 3-layer pairs on padded weight images) and fused2_family (mlp_mfma2.hip: the reference-shaped
-// 2-layer nets [ns, h, 1] / [ns+1, H, 1] on the flat parameters).  ddpg.hip and act.hip pick one through the selectors below and
+// fused3_family (mlp_mfma.hip, kernels in fused3_*.hpp: 3-layer pairs on padded weight images) and fused2_family (mlp_mfma2.hip,
+// kernels in fused2_*.hpp: the reference-shaped 2-layer nets [ns, h, 1] / [ns+1, H, 1] on the flat parameters).  ddpg.hip and act.hip pick one through the selectors below and
 // call through the table; null = the generic path.
 struct FusedFamily {
   bool (*pair_ok)(const Mlp* A, const Mlp* C);   // the passes serve this actor / critic pair
@@ -296,7 +296,7 @@ int fused_flush_pending(Mlp* A);
 #define PDEC_REQUIRE_NO_PENDING(M, who)                                                                                     \
   PDEC_REQUIRE(!(M)->pend.on, "%s: the actor's finish launch is still pending (pdec_ddpg_defer_actor_finish): flush it first " \
                               "(pdec_ddpg_flush_actor_finish)", who)
-// mean of r[0..n) in a fixed order, one block; *out = device scalar owned by C (mlp_mfma2.hip)
+// mean of r[0..n) in a fixed order, one block; *out = device scalar owned by C (ddpg.hip; both fused families call it)
 int launch_rmean(Mlp* C, const float* r, int n, float** out);
 
 }  // namespace pdec

@@ -56,7 +56,7 @@ int pdec_debug_small_update_kernel(pdec_handle actor, pdec_handle critic, pdec_h
  * dynamic LDS bytes of that launch (0 for the last two) to *lds_bytes; or returns the error the call would return.  For which = 2 / 3
  * the name carries the suffix "/adam_apart" where the update runs a fused pass but ADAM and Polyak as launches of their own
  * (2-layer pairs below 64 columns).  Computed by the host code that dispatches (the family selectors of csrc/ddpg.hip, act_route of
- * csrc/act.hip, the visitors and LDS layouts of csrc/mlp_mfma.hip / fused3_*.hpp and csrc/mlp_mfma2.hip). */
+ * csrc/act.hip, the visitors and LDS layouts of csrc/mlp_mfma.hip / fused3_*.hpp and csrc/mlp_mfma2.hip / fused2_*.hpp). */
 int pdec_debug_batched_update_route(pdec_handle actor, pdec_handle critic, pdec_handle target_actor, pdec_handle target_critic,
                                     int Bu, int which, char* name, int name_len, int64_t* lds_bytes);
 

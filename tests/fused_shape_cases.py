@@ -1,5 +1,5 @@
 """The case table of test_gpu_fused_shapes.py and a plain-Python restatement of the shape rules of the fused MFMA DDPG passes
-(csrc/mlp_mfma.hip + fused3_*.hpp: 3-layer pairs, csrc/mlp_mfma2.hip: 2-layer pairs).  Imports neither torch nor the library, so
+(csrc/mlp_mfma.hip + fused3_*.hpp: 3-layer pairs, csrc/mlp_mfma2.hip + fused2_*.hpp: 2-layer pairs).  Imports neither torch nor the library, so
 test_fused_shape_table.py can hold the table against the rules on a machine without a GPU.
 
 A row: (layers, ns, actor hidden, critic hidden, Bu, grad_scale, pair, act)
@@ -88,6 +88,7 @@ def read_constants(csrc=CSRC):
     m3 = open(os.path.join(csrc, "mlp_mfma.hip")).read()
     m2 = open(os.path.join(csrc, "mlp_mfma2.hip")).read()
     blocks = open(os.path.join(csrc, "mfma_blocks.hpp")).read()
+    layers2 = open(os.path.join(csrc, "fused2_layers.hpp")).read()
 
     def define(src, name):
         return int(re.search(rf"^#define {name} (\d+)\b", src, flags=re.M).group(1))
@@ -102,6 +103,7 @@ def read_constants(csrc=CSRC):
     k["ACT2_MIN_COLS"] = int(re.search(r"bool fused2_act_supported\(.*?cols < (\d+)\)", m2, flags=re.S).group(1))
     k["APPLY2_MIN_BU"] = define(m2, "FUSED2_APPLY_MIN_BU")
     k["ACT3_MAX_H"] = define(m3, "FUSED3_ACT_MAX_H")
+    k["LDP"], k["LDQ"] = define(blocks, "LDP"), define(layers2, "LDQ")      # leading dims of the 64- / 32-column staging images
     return k
 
 
@@ -149,3 +151,22 @@ def grid2_rule(Bu, k):
         tpw = -(-nt // g0)
         grid = -(-nt // tpw)
     return grid, tpw, nt - (grid - 1) * tpw, Bu - 16 * (nt - 1)
+
+
+def lds2_rule(ns, ha, hc, k):
+    """(critic pass, actor pass, acting kernel) dynamic LDS bytes of a 2-layer pair [ns, ha, 1] / [ns + 1, hc, 1]: the byte counts
+    of lds2_bytes / act2_lds as they stood before the layouts moved into Critic2Lds / Actor2Lds / Act2Lds (fused2_*.hpp), restated
+    so that a drifted layout fails here.  img: a weight image [HP][8 KB + 4] with b1 [HP], w2 [HP], b2 [4].  nR: 16-row staging tiles
+    of the inputs and the ones row, nr_of(K0) = (K0 + 1 + 15) // 16 -- 1 up to ns = 14 and 2 from ns = 15 on for the critic
+    (K0 = ns + 1), one row later for the actor (K0 = ns), the edges the table's head comment names.  KB of both passes comes from
+    the critic's ns + 1 rows, the acting kernel's from the actor's ns."""
+    def kb_of(K0):
+        return next(v for v in k["KB2"] if -(-K0 // 8) <= v)
+
+    def img(HP, KB):
+        return HP * (8 * KB + 4) + 2 * HP + 4
+    HP, HPa, KB = 16 * tiles_of(hc), 16 * tiles_of(ha), kb_of(ns + 1)
+    nR, nRa = (ns + 1 + 1 + 15) // 16, (ns + 1 + 15) // 16
+    critic = img(HP, KB) + max(HP * k["LDQ"] + 16 * nR * k["LDQ"], 8 * HP) + img(HPa, KB) + HP
+    actor = img(HP, KB) + img(HPa, KB) + HPa * k["LDP"] + 16 * nRa * k["LDP"] + 8 * HPa + HPa + 8
+    return 4 * critic, 4 * actor, 4 * img(HPa, kb_of(ns))

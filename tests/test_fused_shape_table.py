@@ -18,6 +18,7 @@ def test_constants_are_the_ones_the_table_was_written_for(k):
     assert k["T3"] == [(9, 2), (9, 1), (2, 2), (2, 1)] and k["A3"] == [2, 1]
     assert k["T2"] == [(22, 2), (22, 1), (9, 2), (9, 1)] and k["A2"] == [2, 1] and k["KB2"] == [2, 5, 6]
     assert (k["ACT2_MIN_COLS"], k["APPLY2_MIN_BU"], k["ACT3_MAX_H"]) == (256, 64, 31)
+    assert (k["LDP"], k["LDQ"]) == (72, 40)
 
 
 def test_table_imports_without_torch_or_the_library():
@@ -74,3 +75,21 @@ def test_batch_edges_of_both_grid_rules(k):
     assert fc.grid2_rule(32835, k) == (229, 9, 1, 3)
     assert fc.grid2_rule(65536, k) == (256, 16, 16, 16)
     assert fc.grid2_rule(100352, k) == (251, 25, 22, 16)          # config C4 (test_gpu_grads.py)
+
+
+def test_lds_rule_of_the_two_layer_passes(k):
+    """the dynamic LDS of every 2-layer row stays within the 160 KiB of a CU (64 KiB for the acting kernel's launch), and the
+    rule reproduces the bytes that pdec_debug_batched_update_route reported for the corner row before the layouts became
+    Critic2Lds / Actor2Lds / Act2Lds: ddpg2_critic_kernel<22,2,6> 148 384, ddpg2_actor_kernel<22,2,6> 107 200,
+    policy_act2_kernel<2,6> 6 928"""
+    for case, (layers, ns, ha, hc, _, _, pair, act) in fc.CASES.items():
+        if layers != 2:
+            continue
+        if pair is not None:
+            critic, actor, _ = fc.lds2_rule(ns, ha, hc, k)
+            assert 0 < critic <= 160 * 1024 and 0 < actor <= 160 * 1024, (case, critic, actor)
+        if act is not None:
+            assert 0 < fc.lds2_rule(ns, ha, hc, k)[2] <= 64 * 1024, case
+    for case in ("l2_ns46_a31_c351_bu32789", "l2_ns46_a31_c351_bu65536"):
+        _, ns, ha, hc = fc.CASES[case][:4]
+        assert fc.lds2_rule(ns, ha, hc, k) == (148384, 107200, 6928)

@@ -1,6 +1,6 @@
 """Every instantiation of the fused MFMA DDPG passes at its width, row and batch edges, against the fp64 oracle.
 
-The passes are templates over padded tile counts (csrc/mlp_mfma.hip with fused3_*.hpp, csrc/mlp_mfma2.hip); a shape inside a tile is served by
+The passes are templates over padded tile counts (csrc/mlp_mfma.hip with fused3_*.hpp, csrc/mlp_mfma2.hip with fused2_*.hpp); a shape inside a tile is served by
 zero padding, and the lines that pad are only exercised where a shape sits ON a tile edge.  The rows of fused_shape_cases.CASES
 sit on those edges; each names the instantiation it must reach, asserted through pdec_debug_batched_update_route BEFORE anything is
 launched, and together they reach every name the dispatch can produce (test_fused_shape_table.py, on the CPU).  Per row and target
@@ -83,9 +83,11 @@ class Rig:
         return buf.value.decode(), lds.value
 
     def assert_routes(self):
-        """the passes and the acting kernel this row must reach -- nothing is launched"""
+        """the passes and the acting kernel this row must reach, and for a 2-layer row the dynamic LDS bytes of
+        fused_shape_cases.lds2_rule -- nothing is launched"""
         crit, actor, acting = fc.kernel_names(self.case)
-        layers = fc.CASES[self.case][0]
+        layers, ns, ha, hc = fc.CASES[self.case][:4]
+        lds2 = fc.lds2_rule(ns, ha, hc, fc.read_constants()) if layers == 2 else None
         apart = "/adam_apart" if crit and layers == 2 and self.Bu < 64 else ""
         want = {CRITIC_GRADS: crit or "generic", ACTOR_GRADS: actor or "generic", UPDATE_CRITIC: (crit or "generic") + apart,
                 UPDATE_ACTOR: (actor or "generic") + apart}
@@ -93,9 +95,13 @@ class Rig:
             got, lds = self.route(which)
             assert got == name, (self.case, which, got, name)
             assert (0 < lds <= 160 * 1024) if name != "generic" else lds == 0, (self.case, which, lds)
+            if lds2 and name != "generic":
+                assert lds == lds2[which in (ACTOR_GRADS, UPDATE_ACTOR)], (self.case, which, lds, lds2)
         got, lds = self.route(ACT, fc.ACT_COLS)
         if acting:
             assert got == acting and 0 < lds <= 64 * 1024, (self.case, got, acting, lds)
+            if lds2:
+                assert lds == lds2[2], (self.case, lds, lds2)
         else:
             assert got in ("generic", "small_act_kernel") and lds == 0, (self.case, got)
 
